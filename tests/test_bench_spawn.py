@@ -52,7 +52,7 @@ def test_a_world_size_other_than_gpus_is_refused(world):
 @pytest.mark.gpu
 def test_plain_bench_gpus_2_prints_a_two_rank_line():
     out = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--backend", "gloo", "--share", "1024", "--batch", "2", "--pipeline", "2",
-                          "--steps", "2", "--warmup", "1", "--roofline-reps", "2", "--no-cpu", "--no-legs", "--no-config4"],
+                          "--steps", "2", "--warmup", "1", "--roofline-reps", "2", "--no-cpu", "--no-legs", "--no-config4", "--full"],
                          env=_clean_env(), capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     line = _json_line(out.stdout)

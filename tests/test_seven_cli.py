@@ -53,11 +53,10 @@ def test_to_7_normalises_like_xpng_store(tmp_path):
         assert got.shape == want.shape and np.array_equal(got, want), case
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/images"), reason="reference corpus not present (container-only test)")
 def test_to_7_on_the_reference_corpus_gives_the_pinned_md5s():
     """SURVEY 8(c) / DESIGN 8: `seven --to_7` (host/seven_cli.c, the libpng16 runtime bound by dlopen) on the reference's own
-    images/*.png (test.rb:28-30 feeds exactly these) produces the .7 files whose md5 the manifest pins as `seven_md5` - the
-    inputs every corpus golden was generated from (reference 7/seven.c:39-79)."""
+    images/*.png (test.rb:28-30 feeds exactly these; stored unchanged in tests/golden/corpus_png/) produces the .7 files whose
+    md5 the manifest pins as `seven_md5` - the inputs every corpus golden was generated from (reference 7/seven.c:39-79)."""
     import hashlib
     import json
     import tempfile
@@ -67,7 +66,7 @@ def test_to_7_on_the_reference_corpus_gives_the_pinned_md5s():
     with tempfile.TemporaryDirectory() as td:
         for name, ent in corpus_entries(man):
             stem = name.split("_", 1)[1]
-            png = os.path.join("/root/reference/images", stem + ".png")
+            png = os.path.join(GOLD, "corpus_png", stem + ".png")
             assert os.path.exists(png), png
             out = os.path.join(td, "o.7")
             assert subprocess.run([SEVEN, "--to_7", png, out]).returncode == 0

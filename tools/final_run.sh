@@ -1,13 +1,14 @@
 #!/bin/bash
-# end-of-round evidence run (GPU box): plain default bench (timed), rocprofv3 kernel stats + digest of the same command, whole-step HBM traffic
+# end-of-round evidence run (on an MI355X): bench.py --full (timed), rocprofv3 kernel stats + digest of the same command, whole-step HBM traffic
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
+F=bench_out/final_bench_full; mkdir -p bench_out
 t0=$(date +%s)
-timeout -k 10 600 python bench.py > gpurun_out/final_bench_plain.json 2> gpurun_out/final_bench_plain.err || { echo "bench failed"; tail -5 gpurun_out/final_bench_plain.err; exit 1; }
-echo "default bench wall: $(( $(date +%s) - t0 )) s"
+timeout -k 10 600 python bench.py --full > $F.json 2> $F.err || { echo "bench failed"; tail -5 $F.err; exit 1; }
+echo "bench --full wall: $(( $(date +%s) - t0 )) s"
 python3 -c "
 import json
-d=json.loads(open('gpurun_out/final_bench_plain.json').read().strip().splitlines()[-1])
+d=json.loads(open('$F.json').read().strip().splitlines()[-1])
 print('value',d['value'],'ms',d['ms_per_step'],'roof',d['roofline']['frac'],'GB',d['config']['hbm_in_use_gb'])
 print('single',d['single_image'])
 print('legs',{k:(v.get('value'),v.get('hbm_in_use_gb')) for k,v in d.get('legs',{}).items()})
