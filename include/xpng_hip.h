@@ -162,6 +162,31 @@ int xpnghip_decode_device_batch(xpnghip_ctx *ctx, int mode, const void *const *d
  * was rejected (its pixels are left untouched), -1 on a HIP error.  xpnghip_decode_tiles checks it for you. */
 int xpnghip_ctx_decode_status(xpnghip_ctx *ctx, void *stream);
 
+/* ---- region decode: only the tiles a crop rectangle touches (INTEGRATION.md "Region decode") ----------
+ * A rectangle rect = {x, y, w, h} (pixels) is valid when w > 0, h > 0, x + w <= image width and y + h <= image height.  An
+ * invalid rectangle is rejected before any device work: the call fails, xpnghip_last_error() says why, nothing is written.
+ * Each tile is coded independently, so a crop is decoded from the tiles it intersects and nothing else.  The selected tiles are
+ * reconstructed into a per-context staging raster (allocated on first use, grown on demand: nimg x the largest tile-aligned
+ * bounding box of the selected tiles of a call), and the rectangle is copied from there into the caller's buffer.
+ *
+ * host-only (needs no device): the tiles of a w x h image that rect intersects, ascending; returns their count, -1 on an empty /
+ * out-of-image rect or when cap is too small */
+int xpnghip_region_tiles(uint64_t w, uint64_t h, const uint64_t rect[4], uint32_t *tiles, int cap);
+/* Host buffers, one device (T and XPNG_GPUS do not apply).  blobs = the file body after the 8-byte header; the tile sizes are
+ * walked on the host and only the bytes from the first selected tile's blob to the end of the last one are uploaded.
+ * out = rect[2] * rect[3] * pxsz bytes, rows back to back. */
+int xpnghip_decode_region(int mode, const uint8_t *blobs, uint64_t blobs_len, uint64_t w, uint64_t h, int pxsz,
+                          const uint64_t rect[4], uint8_t *out);
+/* Device-resident batch on a context created over the whole tile table: rects = nimg * 4 (one rectangle PER IMAGE);
+ * d_outs[i] receives image i's crop, rect[2] * pxsz bytes per row at row pitch out_bpr (>= rect[2] * pxsz): bytes of a row
+ * beyond rect[2] * pxsz and everything behind the last row are not written.  tile_off == NULL: the size walk runs on the device;
+ * otherwise it holds nimg * N offsets (the FULL tile table of every image, image-major, relative to each image's blob buffer;
+ * entries of tiles outside the rectangle are not read).  Tile headers are validated as in xpnghip_decode_device_batch, and
+ * xpnghip_ctx_decode_status reports on this launch (a rejected tile leaves its part of the crop undefined). */
+int xpnghip_decode_region_device_batch(xpnghip_ctx *ctx, int mode, const void *const *d_blobs, const uint64_t *blobs_len,
+                                       uint32_t nimg, const uint64_t *tile_off, const uint64_t *rects,
+                                       void *const *d_outs, uint64_t out_bpr, void *stream);
+
 /* Stage-only run for BASELINE config 2: predictor chooser + per-pixel transform (libxpng.c:92-140 and
  * the arithmetic of 497-519) over tiles [t0, t1); symbol planes stay in the context's workspace. */
 int xpnghip_m1_transform_device(xpnghip_ctx *ctx, const void *d_raster, uint64_t t0, uint64_t t1, void *stream);

@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 import subprocess
 
@@ -26,9 +27,12 @@ HIP_SYMBOLS = [
     "xpnghip_image_begin", "xpnghip_image_single_colour", "xpnghip_image_encode", "xpnghip_image_fetch", "xpnghip_image_end",
     "xpnghip_normalize_device", "xpnghip_encode_tiles_T", "xpnghip_decode_tiles_T", "xpnghip_image_encode_T", "xpnghip_devices_for",
     "xpnghip_shard_ranges", "xpnghip_shutdown", "xpnghip_probes_built",
+    "xpnghip_region_tiles", "xpnghip_decode_region", "xpnghip_decode_region_device_batch",
 ]
 HOST_SYMBOLS = ["xpng_store", "xpng_load", "xpng_from_jpg", "xpng_store_T", "xpng_load_T", "xpng_from_jpg_T",
                 "store_7", "load_7"]
+# libxpng.so's own additions beyond the reference's surface (include/xpng_region.h)
+HOST_EXT_SYMBOLS = ["xpng_load_region"]
 
 
 class XpngError(RuntimeError):
@@ -126,6 +130,13 @@ def _bind_hip(path):
         L.xpnghip_image_fetch.argtypes = [vp, vp]
         L.xpnghip_image_end.restype = None
         L.xpnghip_image_end.argtypes = [vp]
+        L.xpnghip_region_tiles.restype = C.c_int
+        L.xpnghip_region_tiles.argtypes = [u64, u64, C.POINTER(u64), C.POINTER(C.c_uint32), C.c_int]
+        L.xpnghip_decode_region.restype = C.c_int
+        L.xpnghip_decode_region.argtypes = [C.c_int, vp, u64, u64, u64, C.c_int, C.POINTER(u64), vp]
+        L.xpnghip_decode_region_device_batch.restype = C.c_int
+        L.xpnghip_decode_region_device_batch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64), C.c_uint32, C.POINTER(u64),
+                                                         C.POINTER(u64), C.POINTER(vp), u64, vp]
     return L
 
 
@@ -174,6 +185,8 @@ def host_lib():
         L.xpng_store_T.argtypes = [C.c_uint64, C.c_uint64, C.POINTER(XpngT), C.c_char_p]
         L.xpng_load_T.argtypes = [C.c_uint64, C.c_char_p, C.POINTER(XpngT)]
         L.store_7.argtypes = [C.POINTER(XpngT), C.c_char_p]
+        L.xpng_load_region.restype = C.c_bool
+        L.xpng_load_region.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(XpngT)]
         L.load_7.argtypes = [C.c_char_p, C.POINTER(XpngT)]
         _host = L
     return _host
@@ -299,6 +312,45 @@ def load(path: str, T: int = None) -> np.ndarray:
     return out
 
 
+@functools.lru_cache(maxsize=64)
+def _tile_count(w: int, h: int) -> int:
+    from .shard import tile_table
+    return len(tile_table(w, h))
+
+
+def region_tiles(w: int, h: int, rect) -> list:
+    """Tiles of a w x h image that rect = (x, y, w, h) intersects, ascending (xpnghip_region_tiles; host-only, needs no GPU).
+    Raises XpngError on an empty or out-of-image rect."""
+    cap = _tile_count(w, h) if 0 < w <= 1 << 24 and 0 < h <= 1 << 24 else 1
+    arr, r = (C.c_uint32 * cap)(), (C.c_uint64 * 4)(*rect)
+    n = hip_lib().xpnghip_region_tiles(w, h, r, arr, cap)
+    if n < 0:
+        raise XpngError(f"region_tiles: bad rect {tuple(rect)} for a {w} x {h} image")
+    return list(arr[:n])
+
+
+def decode_region(mode: int, blobs: bytes, w: int, h: int, pxsz: int, rect, lib=None) -> np.ndarray:
+    """The rect = (x, y, w, h) crop of a tile body (the file after its 8-byte header) -> (rect h, rect w, pxsz) uint8
+    (xpnghip_decode_region: only the tiles the rect touches are uploaded and decoded)."""
+    out = np.zeros((max(int(rect[3]), 0), max(int(rect[2]), 0), pxsz), dtype=np.uint8)
+    buf = np.frombuffer(blobs, dtype=np.uint8)
+    lib = lib or hip_lib()
+    if lib.xpnghip_decode_region(mode, buf.ctypes.data_as(C.c_void_p), len(blobs), w, h, pxsz, (C.c_uint64 * 4)(*rect),
+                                 out.ctypes.data_as(C.c_void_p)):
+        raise XpngError("xpnghip_decode_region: " + lib.xpnghip_last_error().decode(errors="replace"))
+    return out
+
+
+def load_region(path: str, x: int, y: int, w: int, h: int) -> np.ndarray:
+    """xpng_load_region (include/xpng_region.h): the (h, w, 3|4) crop at (x, y) of an .xpng file."""
+    pm = XpngT()
+    if host_lib().xpng_load_region(path.encode(), x, y, w, h, C.byref(pm)):
+        raise XpngError("xpng_load_region failed")
+    out = np.ctypeslib.as_array(pm.p, shape=(pm.h, pm.w, 3 + int(pm.A))).copy()
+    _libc.free(pm.p)
+    return out
+
+
 def normalize_device(d_rgba: int, npx: int, d_out: int, stream=0):
     """normalize_RGBA (libxpng.c:688-721) on a device-resident RGBA raster -> (bytes per pixel, rewritten into d_out?)."""
     pxsz, rew = C.c_int(0), C.c_int(0)
@@ -385,6 +437,23 @@ class Context:
         ins, outs, lens = (C.c_void_p * k)(*d_blobs), (C.c_void_p * k)(*d_rasters), (C.c_uint64 * k)(*blob_lens)
         if hip_lib().xpnghip_decode_device_batch(self._h, mode, ins, lens, k, off_arr, t0, t1, outs, stream):
             raise XpngError("xpnghip_decode_device_batch: " + _err())
+
+    def decode_region_batch(self, mode, d_blobs, blob_lens, rects, d_outs, out_bpr, tile_offs=None, stream=0):
+        """One region decode launch (xpnghip_decode_region_device_batch): image i's rects[i] = (x, y, w, h) crop goes to
+        d_outs[i] at row pitch out_bpr.  tile_offs None: the size walk runs on the device; else per image the blob offsets of
+        ALL its tiles."""
+        k = len(d_blobs)
+        assert len(blob_lens) == k and len(rects) == k and len(d_outs) == k
+        off_arr = None
+        if tile_offs is not None:
+            flat = [o for offs in tile_offs for o in offs]
+            assert len(flat) == k * self.n_tiles
+            off_arr = (C.c_uint64 * len(flat))(*flat)
+        flat_r = [int(v) for r in rects for v in r]
+        ins, outs, lens = (C.c_void_p * k)(*d_blobs), (C.c_void_p * k)(*d_outs), (C.c_uint64 * k)(*blob_lens)
+        if hip_lib().xpnghip_decode_region_device_batch(self._h, mode, ins, lens, k, off_arr, (C.c_uint64 * (4 * k))(*flat_r),
+                                                        outs, out_bpr, stream):
+            raise XpngError("xpnghip_decode_region_device_batch: " + _err())
 
     def last_blobs_len(self) -> int:
         return hip_lib().xpnghip_ctx_last_blobs_len(self._h)

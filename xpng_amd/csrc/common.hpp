@@ -170,12 +170,21 @@ struct TileDesc {
 //                      image j % nimg.  Neighbouring work items then have chains of equal length (the wide kernels put
 //                      32-64 of them in one wavefront, which runs for its longest), and the biggest tiles come first.
 // Per-tile outputs that the host sees per image (sizes, offsets) are indexed by imglin() = image * cnt + (tile - t0).
-struct TileSel { uint32_t t0, cnt, N, nimg; const uint32_t *order; };
+// A region decode (xpnghip_decode_region_device_batch) selects a different set of tiles in every image: an explicit work list
+//   list != nullptr  : work item j decodes virtual tile list[j] (image * N + tile), for j < cnt; t0 and order are not used, and
+//                      the per-image arrays are full tables (nimg * N entries): imglin() is the virtual tile itself.
+// The test is one scalar branch per work item (every kernel resolves its tile once, never per pixel).
+struct TileSel { uint32_t t0, cnt, N, nimg; const uint32_t *order; const uint32_t *list = nullptr; };
 __host__ __device__ inline uint32_t vtile(const TileSel &s, uint32_t j) {
+    if (s.list) return s.list[j];
     if (s.order) { const uint32_t r = j / s.nimg; return (j - r * s.nimg) * s.N + s.order[r]; }
     return (j / s.cnt) * s.N + s.t0 + (j % s.cnt);
 }
-__host__ __device__ inline uint32_t imglin(const TileSel &s, uint32_t vt) { const uint32_t img = vt / s.N; return img * s.cnt + (vt - img * s.N - s.t0); }
+__host__ __device__ inline uint32_t imglin(const TileSel &s, uint32_t vt) {
+    if (s.list) return vt;
+    const uint32_t img = vt / s.N;
+    return img * s.cnt + (vt - img * s.N - s.t0);
+}
 
 // Stream-scratch layout of one tile, all offsets relative to TileDesc::sbase:
 //   [k bit stream: 8*pxsz bits + <= 24 bits/pixel][alpha block][nine context streams, back to back][nine context blocks, back to back]

@@ -11,6 +11,7 @@
  */
 #include "../../../include/xpng.h"
 #include "../../../include/xpng_hip.h"
+#include "../../../include/xpng_region.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -164,19 +165,28 @@ _Bool xpng_store_T(uint64_t T, uint64_t mode, const xpng_t *pm, const char *fn) 
 
 _Bool xpng_store(uint64_t mode, const xpng_t *pm, const char *fn) { return xpng_store_T(0, mode, pm, fn); }
 
-_Bool xpng_load_T(uint64_t T, const char *fn, xpng_t *pm) {
-    if (!fn || !pm) return 1;
+/* whole file -> malloc()ed buffer with 16 zero bytes behind it; NULL when it cannot be read or is shorter than a header */
+static uint8_t *read_file(const char *fn, uint64_t *len) {
     FILE *f = fopen(fn, "rb");
-    if (!f) return 1;
-    if (fseek(f, 0, SEEK_END)) { fclose(f); return 1; }
+    if (!f) return NULL;
+    if (fseek(f, 0, SEEK_END)) { fclose(f); return NULL; }
     const long fl = ftell(f);
-    if (fl < 8 || fseek(f, 0, SEEK_SET)) { fclose(f); return 1; }
+    if (fl < 8 || fseek(f, 0, SEEK_SET)) { fclose(f); return NULL; }
     const uint64_t flen = (uint64_t)fl;
     uint8_t *buf = malloc(flen + 16);
-    if (!buf) { fclose(f); return 1; }
-    if (fread(buf, 1, flen, f) != flen) { fclose(f); free(buf); return 1; }
+    if (!buf) { fclose(f); return NULL; }
+    if (fread(buf, 1, flen, f) != flen) { fclose(f); free(buf); return NULL; }
     fclose(f);
     memset(buf + flen, 0, 16);
+    *len = flen;
+    return buf;
+}
+
+_Bool xpng_load_T(uint64_t T, const char *fn, xpng_t *pm) {
+    if (!fn || !pm) return 1;
+    uint64_t flen = 0;
+    uint8_t *buf = read_file(fn, &flen);
+    if (!buf) return 1;
     const uint64_t t_start = now_ns(); /* file read is not timed, libxpng.c:967 */
     const uint32_t h0 = get_u32(buf), h1 = get_u32(buf + 4);
     const uint64_t mode = h0 >> 24;
@@ -203,6 +213,42 @@ _Bool xpng_load_T(uint64_t T, const char *fn, xpng_t *pm) {
 }
 
 _Bool xpng_load(const char *fn, xpng_t *pm) { return xpng_load_T(0, fn, pm); }
+
+/* include/xpng_region.h: the rectangle {x, y, w, h} of the image.  The header and the two host-only forms are those of
+ * xpng_load_T; levels 1 and 2 decode only the tiles the rectangle touches (xpnghip_decode_region). */
+_Bool xpng_load_region(const char *fn, uint64_t x, uint64_t y, uint64_t w, uint64_t h, xpng_t *pm) {
+    if (!fn || !pm) return 1;
+    uint64_t flen = 0;
+    uint8_t *buf = read_file(fn, &flen);
+    if (!buf) return 1;
+    const uint32_t h0 = get_u32(buf), h1 = get_u32(buf + 4);
+    const uint64_t mode = h0 >> 24, W = (h0 & 0xFFFFFF) + 1, H = (h1 & 0xFFFFFF) + 1;
+    const _Bool A = (h1 >> 24) & 1;
+    const int pxsz = 3 + A;
+    if (!(mode == 1 || mode == 2 || mode == 7) || !w || !h || x > W || w > W - x || y > H || h > H - y) { free(buf); return 1; }
+    uint8_t *p = malloc(w * h * (uint64_t)pxsz);
+    if (!p) { free(buf); return 1; }
+    const uint64_t row = w * (uint64_t)pxsz;
+    _Bool rc = 1;
+    if (mode == 7) {
+        if (flen >= 8 + W * H * (uint64_t)pxsz) {
+            for (uint64_t r = 0; r < h; r++) memcpy(p + r * row, buf + 8 + ((y + r) * W + x) * (uint64_t)pxsz, row);
+            rc = 0;
+        }
+    } else if (flen == 11u + A && (buf[7] & 2)) { /* whole-image single colour, libxpng.c:976-980 */
+        for (uint64_t i = 0; i < w * h; i++) memcpy(p + i * (uint64_t)pxsz, buf + 8, (size_t)pxsz);
+        rc = 0;
+    } else {
+        const uint64_t rect[4] = {x, y, w, h};
+        if (xpnghip_decode_region((int)mode, buf + 8, flen - 8, W, H, pxsz, rect, p))
+            fprintf(stderr, "xpng: GPU region decode failed: %s\n", xpnghip_last_error());
+        else rc = 0;
+    }
+    free(buf);
+    if (rc) { free(p); return 1; }
+    pm->p = p; pm->w = w; pm->h = h; pm->A = A; pm->s = w * h * (uint64_t)pxsz;
+    return 0;
+}
 
 /* libxpng.c:1004-1014: the reference ships this entry point as a stub */
 _Bool xpng_from_jpg_T(uint64_t T, const char *jpg, const char *xpng) {

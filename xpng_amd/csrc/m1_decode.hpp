@@ -1697,16 +1697,19 @@ inline int decode_m1_launch(DecodeWs &ws, uint32_t B, uint64_t n_tiles, uint64_t
                             uint32_t max_w, uint32_t max_h, int pxsz, const uint8_t *const *d_blob_ptrs, const uint64_t *d_blob_len,
                             uint32_t *d_status, const uint64_t *tile_off, uint32_t t0, uint32_t t1,
                             uint8_t *const *d_raster_ptrs, hipStream_t s, std::string &err, uint64_t *dbg = nullptr,
-                            const uint32_t *d_order = nullptr, uint32_t n_big = 0, uint32_t min_w = 0) {
-    const uint32_t cnt = t1 - t0, total = B * cnt, spt = pxsz == 4 ? 10 : 9;
+                            const uint32_t *d_order = nullptr, uint32_t n_big = 0, uint32_t min_w = 0,
+                            const uint32_t *d_list = nullptr, uint32_t list_n = 0) {
+    // d_list: the tiles of a region decode (TileSel::list, list_n work items; tile_off then holds B * n_tiles full-table offsets).
+    // A list launch runs unsplit (the caller passes no d_order): DESIGN.md 12.
+    const uint32_t cnt = d_list ? list_n : t1 - t0, total = d_list ? list_n : B * cnt, spt = pxsz == 4 ? 10 : 9;
     // RGBA: the residual kernel rebuilds alpha from its symbols itself (k_dec_resid FOLD) when every tile is at least 4 pixels wide -
     // every tile of a file the reference can write (RGBA narrower than 4 px is stored at level 7); otherwise k_dec_alpha makes the plane
     const bool fold = pxsz == 4 && min_w >= 4 && !probe_env("XPNG_NO_ALPHA_FOLD");
-    const TileSel sel{t0, cnt, (uint32_t)n_tiles, B, d_order};
+    const TileSel sel{t0, cnt, (uint32_t)n_tiles, B, d_list ? nullptr : d_order, d_list};
     const uint64_t plane = plane_total;
     auto bad = [&](const char *m) { err = m; return 1; };
     dbg_count_sequence();
-    if (decode_ws_prepare(ws, B, n_tiles, plane, tile_off, t0, total, s, err, d_blob_ptrs, d_blob_len)) return 1;
+    if (decode_ws_prepare(ws, B, n_tiles, plane, tile_off, t0, d_list ? B * (uint32_t)n_tiles : total, s, err, d_blob_ptrs, d_blob_len)) return 1;
     // (a null workspace pointer handed to a kernel is a GPU fault, i.e. abort(): refuse to launch instead)
     if (!ws.d_info || !ws.d_off || !ws.d_wdec || !ws.d_dtab || !ws.d_ctxsym || !ws.d_asym || !ws.d_alpha || !ws.d_nlseq || !ws.d_resid || !d_tiles || !d_blob_ptrs || !d_raster_ptrs)
         return bad("internal error: a decode workspace buffer was never allocated");
@@ -1755,7 +1758,7 @@ inline int decode_m1_launch(DecodeWs &ws, uint32_t B, uint64_t n_tiles, uint64_t
     // the encode's and the decode's alpha branch and no third stream, 64 x 6 reads 43 where 64 x 4 reads 39 (profiles/r04_experiments.txt).
     // (probe builds: XPNG_SPLIT3=1 = the three-stream form.)
     const bool band = wide && max_w <= RB_MAXW && !probe_env("XPNG_WAVEFRONT_RECON");
-    const bool split = band && d_order && n_big > 0 && n_big < cnt && !probe_env("XPNG_NARROW_WALK") && !getenv("XPNG_NO_SPLIT");
+    const bool split = band && sel.order && n_big > 0 && n_big < cnt && !probe_env("XPNG_NARROW_WALK") && !getenv("XPNG_NO_SPLIT");
     const bool split3 = split && probe_env("XPNG_SPLIT3");
     const uint32_t jb = split ? n_big * B : 0;
     const uint32_t nostore = probe_env("XPNG_DBG_NOSTORE") ? 1u : 0u;

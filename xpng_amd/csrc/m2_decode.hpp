@@ -47,8 +47,9 @@ __global__ void k_m2_dec_parse(const uint8_t *const *__restrict__ blobs, const u
     const uint32_t tile = vtile(sel, j);
     const TileDesc t = tiles[tile];
     M2DecTile d{};
-    d.blob = blobs[j / cnt] + off[j];
-    const uint64_t avail = blob_len[j / cnt] > off[j] ? blob_len[j / cnt] - off[j] : 0;
+    const uint32_t il = imglin(sel, tile);  // off[] is image-major (host order); = j for a tile range
+    d.blob = blobs[t.img] + off[il];
+    const uint64_t avail = blob_len[t.img] > off[il] ? blob_len[t.img] - off[il] : 0;
     bool ok = avail >= 4;
     const uint32_t h0 = ok ? ld32u(d.blob) : 0, ty = h0 >> 24, L = h0 & 0xFFFFFF;
     ok = ok && L <= avail && L >= 8;
@@ -497,16 +498,18 @@ inline int m2_wide_decode(DecodeWs &ws, uint32_t B, uint64_t n_tiles, uint32_t t
                           TileSel sel, const M2Blk *d_blk2, const uint16_t *d_tabs2, uint8_t *d_scratch2, const uint64_t *d_sbase2,
                           const uint32_t *d_stream_n2, hipStream_t s, std::string &err);  // rans1_wide_dec.hpp
 
-// Launch the mode-2 decode of tiles [t0, t1) of every image of the batch (RGB only).
+// Launch the mode-2 decode of tiles [t0, t1) of every image of the batch, or of the tiles of d_list (RGB only).
 inline int decode_m2_launch(DecodeWs &ws, uint32_t B, uint64_t n_tiles, uint64_t plane_total, const TileDesc *d_tiles, uint64_t W,
                             uint32_t max_w, uint32_t max_h,
                             const uint8_t *const *d_blob_ptrs, const uint64_t *d_blob_len, uint32_t *d_status,
                             const uint64_t *tile_off, uint32_t t0, uint32_t t1,
                             uint8_t *const *d_raster_ptrs, M2DecTile *d_info2, M2Blk *d_blk2, uint16_t *d_tabs2, uint8_t *d_scratch2,
-                            const uint64_t *d_sbase2, uint32_t *d_stream_n2, hipStream_t s, std::string &err) {
-    const uint32_t cnt = t1 - t0, total = B * cnt;
-    const TileSel sel{t0, cnt, (uint32_t)n_tiles, B, nullptr};
-    if (decode_ws_prepare(ws, B, n_tiles, plane_total, tile_off, t0, total, s, err, d_blob_ptrs, d_blob_len)) return 1;
+                            const uint64_t *d_sbase2, uint32_t *d_stream_n2, hipStream_t s, std::string &err,
+                            const uint32_t *d_list = nullptr, uint32_t list_n = 0) {
+    // d_list: the tiles of a region decode (TileSel::list, list_n work items; tile_off then holds B * n_tiles full-table offsets)
+    const uint32_t cnt = d_list ? list_n : t1 - t0, total = d_list ? list_n : B * cnt;
+    const TileSel sel{t0, cnt, (uint32_t)n_tiles, B, nullptr, d_list};
+    if (decode_ws_prepare(ws, B, n_tiles, plane_total, tile_off, t0, d_list ? B * (uint32_t)n_tiles : total, s, err, d_blob_ptrs, d_blob_len)) return 1;
     if (!ws.d_off || !ws.d_nlseq || !ws.d_resid || !d_info2 || !d_blk2 || !d_tabs2 || !d_scratch2 || !d_sbase2 || !d_stream_n2 || !d_tiles || !d_blob_ptrs || !d_raster_ptrs) {
         err = "internal error: a mode-2 decode workspace buffer was never allocated";  // (a null pointer in a kernel is a GPU fault = abort())
         return 1;

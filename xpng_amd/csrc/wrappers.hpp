@@ -529,6 +529,52 @@ static int decode_tiles_impl(uint64_t T, int mode, const uint8_t *blobs, uint64_
     return 0;
 }
 
+// Region of a file body on one device: the sizes are walked on the host (libxpng.c:982), and only the byte span from the first
+// selected tile's blob to the end of the last one travels to the device; the crop comes back tight (rect[2] * pxsz per row).
+static int decode_region_impl(int mode, const uint8_t *blobs, uint64_t blobs_len, uint64_t w, uint64_t h, int pxsz, const uint64_t *rect, uint8_t *out) {
+    if (!blobs || !rect || !out) return fail("null argument");
+    if (!w || !h || w > (1u << 24) || h > (1u << 24) || (pxsz != 3 && pxsz != 4)) return fail("bad raster geometry");
+    if (!region_valid(w, h, rect)) return fail("bad region: empty, or it leaves the image");
+    if (mode != 1 && mode != 2) return fail("tile mode must be 1 or 2");
+    if (mode == 2 && pxsz != 3) return fail("mode 2 codes RGB only");
+    if (check_geometry(w, h, pxsz)) return 1;
+    std::vector<TileDesc> tiles;
+    build_tiles(w, h, tiles);
+    const uint64_t N = tiles.size();
+    if (blobs_len / 4 < N) return fail("truncated file: shorter than its tile table");
+    std::vector<uint32_t> sel;
+    region_select(tiles, rect, sel);
+    std::vector<uint64_t> off(N + 1);
+    uint64_t o = 0;
+    for (uint64_t i = 0; i < N; i++) {  // serial size walk, libxpng.c:982
+        if (o + 4 > blobs_len) return fail("truncated file: tile table runs past the end");
+        uint32_t h0; memcpy(&h0, blobs + o, 4);
+        off[i] = o; o += h0 & 0xFFFFFF;
+    }
+    if (o > blobs_len) return fail("truncated file: last tile runs past the end");
+    off[N] = o;
+    const uint64_t first = off[sel.front()], span = off[sel.back() + 1] - first;
+    std::vector<uint64_t> rel(N, 0);  // full-table offsets into the span (tiles outside the selection are never read)
+    for (uint32_t t : sel) rel[t] = off[t] - first;
+    DevGuard guard;
+    HIPCHK(hipSetDevice(base_device()));
+    CtxLease lease(ctx_checkout(base_device(), w, h, pxsz));
+    xpnghip_ctx *c = lease.c;
+    if (!c) return 1;
+    const uint64_t crop = rect[2] * rect[3] * (uint64_t)pxsz;
+    if (ensure_buf(c->d_raster, c->cap_raster, crop) || ensure_buf(c->d_blob_in, c->cap_blob_in, span)) return 1;
+    HIPCHK(hipMemcpyAsync(c->d_blob_in, blobs + first, span, hipMemcpyHostToDevice, ctx_stream(c)));
+    const void *bp = c->d_blob_in;
+    void *op = c->d_raster;
+    if (xpnghip_decode_region_device_batch(c, mode, &bp, &span, 1, rel.data(), rect, &op, rect[2] * (uint64_t)pxsz, nullptr)) return 1;
+    const int st = xpnghip_ctx_decode_status(c, nullptr);
+    if (st == 1) return fail("corrupt file: a tile header is inconsistent with the tile table");
+    if (st != 0) return fail("decode failed");
+    HIPCHK(hipMemcpyAsync(out, c->d_raster, crop, hipMemcpyDeviceToHost, ctx_stream(c)));
+    HIPCHK(hipStreamSynchronize(ctx_stream(c)));
+    return 0;
+}
+
 // extern "C" must not leak C++ exceptions (std::bad_alloc from a header that claims an absurd geometry)
 #define XPNG_GUARDED(expr)                                               \
     try { return (expr); }                                               \
@@ -546,6 +592,10 @@ extern "C" int xpnghip_decode_tiles_T(uint64_t T, int mode, const uint8_t *blobs
 }
 extern "C" int xpnghip_decode_tiles(int mode, const uint8_t *blobs, uint64_t blobs_len, uint64_t w, uint64_t h, int pxsz, uint8_t *raster) {
     XPNG_GUARDED(decode_tiles_impl(1, mode, blobs, blobs_len, w, h, pxsz, raster))
+}
+extern "C" int xpnghip_decode_region(int mode, const uint8_t *blobs, uint64_t blobs_len, uint64_t w, uint64_t h, int pxsz,
+                                     const uint64_t rect[4], uint8_t *out) {
+    XPNG_GUARDED(decode_region_impl(mode, blobs, blobs_len, w, h, pxsz, rect, out))
 }
 
 // ---- normalize_RGBA and the single-colour test on the device ---------------------------------------------------

@@ -26,6 +26,7 @@
 #include "rans1_wide.hpp"
 #include "rans1_wide_dec.hpp"
 #include "tile_container.hpp"
+#include "region.hpp"
 
 using namespace xpng;
 
@@ -161,6 +162,12 @@ struct xpnghip_ctx {
     uint64_t cap_stage = 0;
     uint64_t call = 0;  // id of the last host-wrapper call that used this context (wrappers.hpp: never evicted mid-call)
     DecodeWs dec;
+    // region decode (region.hpp), allocated on first use: the staging raster (nimg x the largest tile-aligned bounding box of a
+    // call; grown on demand), and one buffer with the work list (B * N entries) followed by B RegionCopy records
+    uint8_t *d_region_stage = nullptr;
+    uint64_t cap_region_stage = 0;
+    uint8_t *d_region_meta = nullptr;
+    std::vector<uint8_t> h_region_meta;  // what d_region_meta holds (skip the upload when unchanged)
 };
 
 // the context's own stream, created when a call first needs it (the `stream == NULL` form of the device-resident entry points,
@@ -181,7 +188,7 @@ extern "C" void xpnghip_ctx_destroy(xpnghip_ctx *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void *ptrs[] = {c->d_tiles, c->d_planes, c->d_scratch, c->d_sums, c->d_nlh, c->d_ctx_n, c->d_k_n, c->d_blk_sz, c->d_tile_sz,
                     c->d_tile_hdr, c->d_off, c->d_totals, c->d_raster, c->d_blobs, c->d_blob_in, c->d_dbg, (void *)c->d_in_ptrs, (void *)c->d_out_ptrs, (void *)c->d_dec_in_ptrs, (void *)c->d_dec_out_ptrs, (void *)c->d_order,
-                    c->d_wprep, c->d_wtab, c->d_wF, c->d_blob_len, c->d_status, c->d_scratch2, c->d_sbase2, c->d_flags2, c->d_stream_n2, c->d_blk2, c->d_mt2, c->d_info2, c->d_tabs2, c->d_w1prep, c->d_w1tab, c->d_w1F};
+                    c->d_wprep, c->d_wtab, c->d_wF, c->d_blob_len, c->d_status, c->d_scratch2, c->d_sbase2, c->d_flags2, c->d_stream_n2, c->d_blk2, c->d_mt2, c->d_info2, c->d_tabs2, c->d_w1prep, c->d_w1tab, c->d_w1F, c->d_region_stage, c->d_region_meta};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->enc_side) (void)hipStreamDestroy(c->enc_side);
     if (c->enc_side2) (void)hipStreamDestroy(c->enc_side2);
@@ -601,13 +608,9 @@ extern "C" int xpnghip_encode_device(xpnghip_ctx *c, int mode, const void *d_ras
 extern "C" uint64_t xpnghip_ctx_last_blobs_len(xpnghip_ctx *c) { return c ? c->h_total[0] : 0; }
 extern "C" uint64_t xpnghip_ctx_last_blobs_len_at(xpnghip_ctx *c, uint32_t img) { return c && img < c->B ? c->h_total[img] : 0; }
 
-extern "C" int xpnghip_decode_device_batch(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
-                                           const uint64_t *tile_off, uint64_t t0, uint64_t t1, void *const *d_rasters, void *stream) {
-    if (check_range(c, t0, t1)) return 1;
-    if (mode != 1 && mode != 2) return fail("tile mode must be 1 or 2");
-    if (mode == 2 && c->pxsz != 3) return fail("mode 2 codes RGB only");
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(c);
+// What every decode launch sequence does before its kernels: pointer tables, blob lengths, status word, workspaces.
+static int dec_prepare(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
+                       void *const *d_rasters, hipStream_t s) {
     if (set_ptrs(c, d_blobs, d_rasters, nimg, s, true)) return 1;
     if (!blobs_len) return fail("blob lengths are required (tile headers are validated against them)");
     if (c->h_blob_len.size() != nimg || memcmp(c->h_blob_len.data(), blobs_len, (size_t)nimg * 8) != 0) {
@@ -616,8 +619,6 @@ extern "C" int xpnghip_decode_device_batch(xpnghip_ctx *c, int mode, const void 
         c->h_blob_len.assign(blobs_len, blobs_len + nimg);
     }
     HIPCHK(hipMemsetAsync(c->d_status, 0, 4, s));
-    uint32_t max_w = 0, max_h = 0, min_w = ~0u;
-    for (uint64_t i = t0; i < t1; i++) { max_w = c->tiles[i].w > max_w ? c->tiles[i].w : max_w; max_h = c->tiles[i].h > max_h ? c->tiles[i].h : max_h; min_w = c->tiles[i].w < min_w ? c->tiles[i].w : min_w; }
     if (ensure_arena(c)) return 1;
     if (!c->dec.side) {  // (also after decode_ws_prepare rebuilt the workspace: it forgets the loan)
         if (!c->enc_side) HIPCHK(chain_stream_create(&c->enc_side));
@@ -628,9 +629,23 @@ extern "C" int xpnghip_decode_device_batch(xpnghip_ctx *c, int mode, const void 
     if (mode == 2) {
         if (ensure_m2(c)) return 1;
         XPNG_REQUIRE(c->d_info2, c->d_blk2, c->d_tabs2, c->d_scratch2, c->d_sbase2, c->d_stream_n2);
+    }
+    return 0;
+}
+
+extern "C" int xpnghip_decode_device_batch(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
+                                           const uint64_t *tile_off, uint64_t t0, uint64_t t1, void *const *d_rasters, void *stream) {
+    if (check_range(c, t0, t1)) return 1;
+    if (mode != 1 && mode != 2) return fail("tile mode must be 1 or 2");
+    if (mode == 2 && c->pxsz != 3) return fail("mode 2 codes RGB only");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(c);
+    if (dec_prepare(c, mode, d_blobs, blobs_len, nimg, d_rasters, s)) return 1;
+    uint32_t max_w = 0, max_h = 0, min_w = ~0u;
+    for (uint64_t i = t0; i < t1; i++) { max_w = c->tiles[i].w > max_w ? c->tiles[i].w : max_w; max_h = c->tiles[i].h > max_h ? c->tiles[i].h : max_h; min_w = c->tiles[i].w < min_w ? c->tiles[i].w : min_w; }
+    if (mode == 2)
         return decode_m2_launch(c->dec, nimg, c->tiles.size(), c->plane_stride, c->d_tiles, c->W, max_w, max_h, c->d_dec_in_ptrs, c->d_blob_len, c->d_status, tile_off, (uint32_t)t0,
                                 (uint32_t)t1, c->d_dec_out_ptrs, c->d_info2, c->d_blk2, c->d_tabs2, c->d_scratch2, c->d_sbase2, c->d_stream_n2, s, g_err);
-    }
     return decode_m1_launch(c->dec, nimg, c->tiles.size(), c->plane_stride, c->d_tiles, c->W, max_w, max_h, c->pxsz, c->d_dec_in_ptrs, c->d_blob_len, c->d_status, tile_off,
                             (uint32_t)t0, (uint32_t)t1, c->d_dec_out_ptrs, s, g_err, c->stamps ? c->d_dbg + c->tiles.size() * c->B * 80 : nullptr,
                             order_for(c, (uint32_t)t0, (uint32_t)t1), order_for(c, (uint32_t)t0, (uint32_t)t1) ? c->n_big : 0u, min_w);
@@ -639,6 +654,123 @@ extern "C" int xpnghip_decode_device(xpnghip_ctx *c, int mode, const void *d_blo
                                      const uint64_t *tile_off, uint64_t t0, uint64_t t1, void *d_raster, void *stream) {
     return xpnghip_decode_device_batch(c, mode, &d_blobs, &blobs_len, 1, tile_off, t0, t1, &d_raster, stream);
 }
+// ---- region decode (region.hpp) ----------------------------------------------------------------
+extern "C" int xpnghip_region_tiles(uint64_t w, uint64_t h, const uint64_t rect[4], uint32_t *tiles, int cap) {
+    try {
+        if (!w || !h || w > (1u << 24) || h > (1u << 24) || !rect || !region_valid(w, h, rect)) return -1;
+        std::vector<TileDesc> all;
+        build_tiles(w, h, all);
+        std::vector<uint32_t> sel;
+        region_select(all, rect, sel);
+        if (cap < 0 || sel.size() > (size_t)cap || (!tiles && !sel.empty())) return -1;
+        std::copy(sel.begin(), sel.end(), tiles);
+        return (int)sel.size();
+    } catch (...) { return -1; }
+}
+
+static int region_batch_impl(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
+                             const uint64_t *tile_off, const uint64_t *rects, void *const *d_outs, uint64_t out_bpr, void *stream) {
+    // every argument is checked before anything reaches the device: a rejected call writes nothing
+    if (!c) return fail("null context");
+    if (mode != 1 && mode != 2) return fail("tile mode must be 1 or 2");
+    if (mode == 2 && c->pxsz != 3) return fail("mode 2 codes RGB only");
+    if (nimg < 1 || nimg > c->B) return fail("batch size exceeds the context's batch");
+    if (c->r0 != 0 || c->r1 != c->tiles.size()) return fail("region decode needs a context over the whole tile table");
+    if (!d_blobs || !blobs_len || !rects || !d_outs) return fail("null argument");
+    const uint64_t N = c->tiles.size(), px = (uint64_t)c->pxsz;
+    for (uint32_t i = 0; i < nimg; i++) {
+        const uint64_t *r = rects + 4ull * i;
+        if (!region_valid(c->W, c->H, r))
+            return fail("bad region of image " + std::to_string(i) + ": {" + std::to_string(r[0]) + ", " + std::to_string(r[1]) + ", " + std::to_string(r[2]) + ", " +
+                        std::to_string(r[3]) + "} is empty or leaves the " + std::to_string(c->W) + " x " + std::to_string(c->H) + " image");
+        if (out_bpr < r[2] * px) return fail("out_bpr is smaller than a row of the region of image " + std::to_string(i));
+        if (!d_outs[i]) return fail("null output buffer");
+    }
+    // the selected tiles of every image and their tile-aligned bounding boxes
+    std::vector<uint32_t> list, sel;
+    std::vector<uint64_t> box(4ull * nimg);  // X0, Y0, X1, Y1
+    uint64_t bw = 0, bh = 0, max_rows = 0;
+    uint32_t max_w = 0, max_h = 0, min_w = ~0u;
+    for (uint32_t i = 0; i < nimg; i++) {
+        region_select(c->tiles, rects + 4ull * i, sel);
+        uint64_t *b = &box[4ull * i];
+        b[0] = b[1] = ~0ull; b[2] = b[3] = 0;
+        for (uint32_t t : sel) {
+            const TileDesc &d = c->tiles[t];
+            b[0] = std::min<uint64_t>(b[0], d.x); b[1] = std::min<uint64_t>(b[1], d.y);
+            b[2] = std::max<uint64_t>(b[2], (uint64_t)d.x + d.w); b[3] = std::max<uint64_t>(b[3], (uint64_t)d.y + d.h);
+            max_w = std::max(max_w, d.w); max_h = std::max(max_h, d.h); min_w = std::min(min_w, d.w);
+            list.push_back((uint32_t)(i * N + t));
+        }
+        bw = std::max(bw, b[2] - b[0]); bh = std::max(bh, b[3] - b[1]);
+        max_rows = std::max(max_rows, rects[4ull * i + 3]);
+    }
+    // biggest tiles first (equal sizes keep their order): neighbouring work items of the wide kernels get chains of equal length.
+    // List launches run unsplit.
+    std::stable_sort(list.begin(), list.end(), [&](uint32_t a, uint32_t b) { return c->tiles[a % N].n > c->tiles[b % N].n; });
+    // staging: image i's box at pitch sbpr in slot i; its virtual base (base - Y0 * sbpr - X0 * pxsz) is 16-byte aligned, so every
+    // pixel lands at the alignment it has in a whole raster of that pitch
+    const uint64_t sbpr = bw * px, slot = rup(bh * sbpr + 16, 256);
+    if (c->cap_region_stage < slot * nimg) {
+        if (c->d_region_stage) {
+            HIPCHK(hipSetDevice(c->device));
+            HIPCHK(hipDeviceSynchronize());  // (an earlier call's kernels may still use the old buffer)
+            HIPCHK(hipFree(c->d_region_stage));
+            c->ws_bytes -= c->cap_region_stage;
+            c->d_region_stage = nullptr; c->cap_region_stage = 0;
+        }
+        HIPCHK(hipSetDevice(c->device));
+        HIPCHK(hipMalloc((void **)&c->d_region_stage, slot * nimg));
+        c->cap_region_stage = slot * nimg;
+        c->ws_bytes += slot * nimg;
+    }
+    if (!c->d_region_meta) {
+        HIPCHK(hipSetDevice(c->device));
+        const uint64_t bytes = rup((uint64_t)c->B * N * 4, 16) + (uint64_t)c->B * sizeof(RegionCopy);
+        HIPCHK(hipMalloc((void **)&c->d_region_meta, bytes));
+        c->ws_bytes += bytes;
+    }
+    std::vector<void *> vbase(nimg);
+    std::vector<RegionCopy> rc(nimg);
+    for (uint32_t i = 0; i < nimg; i++) {
+        const uint64_t *b = &box[4ull * i], *r = rects + 4ull * i;
+        const uint64_t rel = b[1] * sbpr + b[0] * px, base = i * slot + (rel & 15);
+        vbase[i] = c->d_region_stage + base - rel;
+        rc[i] = RegionCopy{base + (r[1] - b[1]) * sbpr + (r[0] - b[0]) * px, (uint8_t *)d_outs[i], (uint32_t)(r[2] * px), (uint32_t)r[3]};
+    }
+    const uint64_t list_bytes = rup((uint64_t)list.size() * 4, 16);
+    std::vector<uint8_t> meta(list_bytes + nimg * sizeof(RegionCopy), 0);
+    memcpy(meta.data(), list.data(), list.size() * 4);
+    memcpy(meta.data() + list_bytes, rc.data(), nimg * sizeof(RegionCopy));
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(c);
+    if (meta != c->h_region_meta) {  // (pageable host memory: the copy is staged synchronously anyway)
+        c->h_region_meta.clear();
+        HIPCHK(hipMemcpyAsync(c->d_region_meta, meta.data(), meta.size(), hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+        c->h_region_meta.swap(meta);
+    }
+    const uint32_t *d_list = reinterpret_cast<const uint32_t *>(c->d_region_meta);
+    const RegionCopy *d_rc = reinterpret_cast<const RegionCopy *>(c->d_region_meta + list_bytes);
+    if (dec_prepare(c, mode, d_blobs, blobs_len, nimg, vbase.data(), s)) return 1;
+    XPNG_REQUIRE(c->d_region_stage, c->d_region_meta);
+    const int rc_launch = mode == 2
+        ? decode_m2_launch(c->dec, nimg, N, c->plane_stride, c->d_tiles, bw, max_w, max_h, c->d_dec_in_ptrs, c->d_blob_len, c->d_status, tile_off, 0, (uint32_t)N,
+                           c->d_dec_out_ptrs, c->d_info2, c->d_blk2, c->d_tabs2, c->d_scratch2, c->d_sbase2, c->d_stream_n2, s, g_err, d_list, (uint32_t)list.size())
+        : decode_m1_launch(c->dec, nimg, N, c->plane_stride, c->d_tiles, bw, max_w, max_h, c->pxsz, c->d_dec_in_ptrs, c->d_blob_len, c->d_status, tile_off, 0, (uint32_t)N,
+                           c->d_dec_out_ptrs, s, g_err, nullptr, nullptr, 0u, min_w, d_list, (uint32_t)list.size());
+    if (rc_launch) return rc_launch;
+    k_region_copy<<<dim3((uint32_t)((max_rows + RC_ROWS - 1) / RC_ROWS), nimg), 256, 0, s>>>(d_rc, c->d_region_stage, sbpr, out_bpr);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+extern "C" int xpnghip_decode_region_device_batch(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
+                                                  const uint64_t *tile_off, const uint64_t *rects, void *const *d_outs, uint64_t out_bpr, void *stream) {
+    try { return region_batch_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, rects, d_outs, out_bpr, stream); }
+    catch (const std::bad_alloc &) { return fail("out of host memory"); }
+    catch (...) { return fail("unexpected C++ exception"); }
+}
+
 // Synchronises `stream` and reports the last decode: 0 = every tile header was consistent, 1 = at least one tile was
 // rejected (its pixels were left untouched), -1 = HIP error.
 extern "C" int xpnghip_ctx_decode_status(xpnghip_ctx *c, void *stream) {
