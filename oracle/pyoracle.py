@@ -54,6 +54,8 @@ def lib():
         L.xo_rans2_encode.restype = u64
         L.xo_rans2_encode.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, u64, C.c_void_p, C.c_int]
         L.xo_rans2_decode.restype = u64
+        L.xo_rans2_encode_table.restype = u64
+        L.xo_rans2_encode_table.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, u64, C.c_void_p, C.c_int, C.c_int]
         L.xo_rans2_decode.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(u64)]
         L.xo_tile_blob_bound.restype = u64
         L.xo_tile_blob_bound.argtypes = [C.POINTER(XoTile), C.c_int]
@@ -135,6 +137,18 @@ def rans2_encode(F: np.ndarray, nominal_n: int, syms: np.ndarray, pb: int) -> by
     syms = np.ascontiguousarray(syms, dtype=np.uint8)
     out = np.zeros(16 + 4 * len(syms) + 4 * 300, dtype=np.uint8)
     sz = lib().xo_rans2_encode(_ptr(F), nominal_n, _ptr(syms), len(syms), _ptr(out), pb)
+    return out[:sz].tobytes()
+
+
+def rans2_encode_table(F, syms: np.ndarray, pb: int, sparse: bool) -> bytes:
+    """A type 3 (dense) or type 4 (sparse) v2 block with the table F written as given (len(F) entries, trailing zeros kept):
+    never raw, never one-symbol, no normalisation.  Each F < 2^pb, sum(F) <= 2^pb, every symbol of syms has F >= 1."""
+    F = np.ascontiguousarray(F, dtype=np.uint32)
+    syms = np.ascontiguousarray(syms, dtype=np.uint8)
+    out = np.zeros(64 + 4 * len(syms) + 4 * 300, dtype=np.uint8)
+    sz = lib().xo_rans2_encode_table(_ptr(F), len(F), _ptr(syms), len(syms), _ptr(out), pb, int(bool(sparse)))
+    if not sz:
+        raise ValueError("rans2_encode_table: table or symbols out of range")
     return out[:sz].tobytes()
 
 

@@ -316,21 +316,10 @@ static uint64_t dword_aligned_bytes(uint64_t bits) { return (bits / 32) * 4 + (b
 
 /* ------------------------------------------------------------------ rANS v2 (mode 1) libxpng.c:307-427 */
 
-uint64_t xo_rans2_encode(uint32_t *F, unsigned nominalN, const uint8_t *in, uint64_t n, uint8_t *out, int pb) {
-    if (pb < 10 || pb > 15) return 0;
-    if (n == 0) { wr32(out, 4); return 4; }
-    int top = (int)nominalN - 1;
-    while (top > 0 && F[top] == 0) top--;
-    const unsigned N = (unsigned)top + 1, rawBits = (unsigned)bit_width((uint32_t)top);
-    uint32_t cum[257], distinct = 0;
-    cum[0] = 0;
-    for (unsigned i = 0; i < N; i++) { cum[i + 1] = cum[i] + F[i]; distinct += F[i] != 0; }
-    if (distinct == 1) {
-        wr32(out, 8u | (1u << 24));
-        wr32(out + 4, (uint32_t)n | ((uint32_t)in[0] << 24));
-        return 8;
-    }
-    normalise_freqs(F, cum, N, n, pb);
+/* Words, states and table of a type 3 (dense) / 4 (sparse) block with the final table F[0..N) and its cum[];
+ * returns the block size, header word 0 written. */
+static uint64_t rans2_emit(const uint32_t *F, const uint32_t *cum, unsigned N, const uint8_t *in, uint64_t n, uint8_t *out,
+                           int pb, int sparse) {
     rans_enc_sym e[256];
     make_enc_syms(e, F, cum, N, pb);
 
@@ -351,8 +340,6 @@ uint64_t xo_rans2_encode(uint32_t *F, unsigned nominalN, const uint8_t *in, uint
     }
     wr64(w, s0); wr64(w + 8, s1); w += 16;
 
-    const uint32_t sparseBits = N + distinct * (uint32_t)pb;
-    const int sparse = sparseBits < N * (uint32_t)pb;
     wr32(out + 4, (uint32_t)n | ((N - 2) << 24));
     wr32(out + 8, (uint32_t)((w - (out + 8)) / 4) | ((uint32_t)pb << 24));
     bitw tb = { 0, 0, w };
@@ -364,6 +351,27 @@ uint64_t xo_rans2_encode(uint32_t *F, unsigned nominalN, const uint8_t *in, uint
     bitw_finish(&tb);
     uint32_t csz = (uint32_t)(tb.p - out);
     wr32(out, csz | ((3u + (uint32_t)sparse) << 24));
+    return csz;
+}
+
+uint64_t xo_rans2_encode(uint32_t *F, unsigned nominalN, const uint8_t *in, uint64_t n, uint8_t *out, int pb) {
+    if (pb < 10 || pb > 15) return 0;
+    if (n == 0) { wr32(out, 4); return 4; }
+    int top = (int)nominalN - 1;
+    while (top > 0 && F[top] == 0) top--;
+    const unsigned N = (unsigned)top + 1, rawBits = (unsigned)bit_width((uint32_t)top);
+    uint32_t cum[257], distinct = 0;
+    cum[0] = 0;
+    for (unsigned i = 0; i < N; i++) { cum[i + 1] = cum[i] + F[i]; distinct += F[i] != 0; }
+    if (distinct == 1) {
+        wr32(out, 8u | (1u << 24));
+        wr32(out + 4, (uint32_t)n | ((uint32_t)in[0] << 24));
+        return 8;
+    }
+    normalise_freqs(F, cum, N, n, pb);
+    const uint32_t sparseBits = N + distinct * (uint32_t)pb;
+    const int sparse = sparseBits < N * (uint32_t)pb;
+    uint32_t csz = (uint32_t)rans2_emit(F, cum, N, in, n, out, pb, sparse);
 
     if (csz >= 8 + dword_aligned_bytes((uint64_t)rawBits * n)) { /* raw beats rANS: type 2 */
         bitw rb = { 0, 0, out + 8 };
@@ -376,6 +384,22 @@ uint64_t xo_rans2_encode(uint32_t *F, unsigned nominalN, const uint8_t *in, uint
         return csz;
     }
     return csz;
+}
+
+/* Test infrastructure: a type 3 / 4 block with the caller's table, bypassing normalise_freqs and the raw / one-symbol
+ * forms.  F[0..N) is written as given (trailing zeros included), each entry below 2^pb, the sum at most 2^pb, every
+ * symbol of in[] with F >= 1.  Returns 0 when the table or the symbols break these rules. */
+uint64_t xo_rans2_encode_table(const uint32_t *F, unsigned N, const uint8_t *in, uint64_t n, uint8_t *out, int pb, int sparse) {
+    if (pb < 10 || pb > 15 || N < 2 || N > 256 || n == 0 || n > 0xFFFFFF) return 0;
+    uint32_t cum[257];
+    cum[0] = 0;
+    for (unsigned i = 0; i < N; i++) {
+        if (F[i] >= (1u << pb)) return 0;
+        cum[i + 1] = cum[i] + F[i];
+    }
+    if (cum[N] > (1u << pb)) return 0;
+    for (uint64_t k = 0; k < n; k++) if (in[k] >= N || !F[in[k]]) return 0;
+    return rans2_emit(F, cum, N, in, n, out, pb, sparse != 0);
 }
 
 /* libxpng.c:429-493 */

@@ -66,6 +66,7 @@ void xo_m1_streams_free(xo_m1_streams *s);
 /* rANS v2 block (libxpng.c:307-427 / 429-493).  F is clobbered (normalised). Returns bytes. */
 uint64_t xo_rans2_encode(uint32_t *F, unsigned nominalN, const uint8_t *in, uint64_t n, uint8_t *out, int pb);
 uint64_t xo_rans2_decode(const uint8_t *in, uint8_t *out, uint64_t *n_out);
+uint64_t xo_rans2_encode_table(const uint32_t *F, unsigned N, const uint8_t *in, uint64_t n, uint8_t *out, int pb, int sparse);
 
 /* Whole tile.  `out` must hold w*h*pxsz + 4 + slack (xo_tile_blob_bound). Returns blob bytes, 0 on error. */
 uint64_t xo_tile_blob_bound(const xo_tile *t, int pxsz);

@@ -924,35 +924,23 @@ def test_context_stream_with_more_probability_bits_on_the_wide_path(gpu, po, mon
     from xpng_amd.synth import synth_raster
     W, H = 1000, 300
     raster = synth_raster("photo", W, H, False, seed=11).copy()
+    import _rans_tables as rt
     blobs = po.encode_tiles(1, raster)
-    tiles = po.tile_table(W, H, 3)
-    out, o, recoded = bytearray(), 0, 0
-    for ti in range(len(tiles)):
-        L = int.from_bytes(blobs[o:o + 3], "little")
-        tile = bytearray(blobs[o:o + L])
-        o += L
-        if tile[3] == 0:                     # raw tile
-            out += tile
-            continue
-        ksz = int.from_bytes(tile[4:8], "little")
-        q, parts = 4 + ksz, [bytes(tile[:4 + ksz])]
-        for c in range(9):
-            b0 = int.from_bytes(tile[q:q + 4], "little")
-            ty, sz = b0 >> 24, (4 if (b0 >> 24) == 0 else b0 & 0xFFFFFF)
-            blk = bytes(tile[q:q + sz])
-            q += sz
-            if ty >= 3 and c % 2 == ti % 2:  # every other rANS-coded context block of the tile
-                n = int.from_bytes(blk[4:7], "little")
-                syms, _ = po.rans2_decode(blk, n)
-                new = po.rans2_encode(np.bincount(syms, minlength=9).astype(np.uint32), 9, syms, pb)
-                if new[3] >= 3 and new[11] == pb:
-                    blk, recoded = new, recoded + 1
-            parts.append(blk)
-        assert q == L
-        body = b"".join(parts)
-        out += len(body).to_bytes(3, "little") + bytes([tile[3]]) + body[4:]
+    recoded = 0
+
+    def recode(ti, c, blk):
+        nonlocal recoded
+        if blk[3] >= 3 and c % 2 == ti % 2:  # every other rANS-coded context block of the tile
+            n = int.from_bytes(blk[4:7], "little")
+            syms, _ = po.rans2_decode(blk, n)
+            new = po.rans2_encode(np.bincount(syms, minlength=9).astype(np.uint32), 9, syms, pb)
+            if new[3] >= 3 and new[11] == pb:
+                recoded += 1
+                return new
+        return None
+
+    out = rt.recode_tiles(blobs, W, H, 3, recode)
     assert recoded >= 4
-    out = bytes(out)
     assert np.array_equal(po.decode_tiles(1, out, W, H, 3), raster)        # the crafted file is a valid one
     assert np.array_equal(api.decode_tiles(1, out, W, H, 3), raster)
 
