@@ -23,6 +23,14 @@ inline const char *probe_env(const char *) { return nullptr; }
 #endif
 inline size_t probe_pad(const char *name) { const char *v = probe_env(name); return v ? (size_t)atoi(v) : 0; }  // bytes of unused dynamic LDS (occupancy throttle)
 
+// Which form a launch sequence takes, by its number of (tile, stream) work items.  Few: latency is the bound, and every stream gets
+// a wavefront of its own (the narrow form); many: instruction issue is the bound, and the rANS chains run a stream per lane (the
+// wide form).  Both forms produce the same bytes; XPNG_NARROW_RANS / XPNG_WIDE_RANS force one of them.  The per-tile kernels beside
+// the chains follow the same threshold: 1024-thread workgroups in the narrow regime, 256-thread ones beyond it.
+constexpr uint64_t NARROW_MAX_ITEMS = 2048;
+inline bool wide_form(uint64_t items) { return !getenv("XPNG_NARROW_RANS") && (items > NARROW_MAX_ITEMS || getenv("XPNG_WIDE_RANS")); }
+inline bool small_blocks(uint64_t items) { return items > NARROW_MAX_ITEMS && !probe_env("XPNG_BIG_BLOCKS"); }
+
 // Streams that carry serial-chain kernels.  tools/wave_probe.py shows that in the pipelined bench the chain WAVES run at their solo
 // speed while the chain KERNELS take 1.7x longer: their workgroups (tens of KB of LDS each) trickle onto CUs that bandwidth kernels
 // with 10^4..10^5 queued workgroups keep full.  Stream priority is the obvious lever and the wrong one (measured: 27.8 against

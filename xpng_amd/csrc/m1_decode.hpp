@@ -32,6 +32,10 @@ struct DecTile {  // per-tile parse result (device)
 
 struct WDec;  // rans2_wide_dec.hpp
 
+// The decode workspace of one context.  It BORROWS the context's side stream and its stream scratch (`arena`: the five symbol /
+// residual planes, 8 B per pixel, are carved out of it - no decode kernel reads the encode's intermediates and no encode kernel runs
+// while a decode of the same context does); dec_prepare (xpng_hip.hip) lends both before every launch.  It OWNS the per-tile
+// tables, which grow on demand, and its events.
 struct DecodeWs {
     uint64_t cap_tiles = 0, cap_plane = 0;
     WDec *d_wdec = nullptr;              // wide rANS decode: per (tile, stream) descriptors and decode tables
@@ -41,40 +45,23 @@ struct DecodeWs {
     uint64_t cap2 = 0;
     std::vector<uint64_t> last_off;      // tile offsets already resident in d_off (skip the upload when unchanged)
     uint32_t last_t0 = 0;
-    hipStream_t side = nullptr;          // alpha branch runs beside the nl-context branch
-    bool side_borrowed = false;          // `side` is the context's one side stream (the encode's alpha chains use it too, never at the same time): not ours to destroy
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipStream_t side2 = nullptr;         // walk / residuals / reconstruction of the smaller tiles, beside the walk of the biggest
-    hipEvent_t ev_ctx = nullptr, ev_small = nullptr;
+    hipStream_t side = nullptr;          // the context's one side stream: alpha branch beside the nl-context branch, big-tile class of a split decode
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_ctx = nullptr, ev_small = nullptr;
     DecTile *d_info = nullptr;
     uint64_t *d_off = nullptr;
-    uint8_t *d_ctxsym = nullptr, *d_asym = nullptr, *d_alpha = nullptr, *d_nlseq = nullptr;
-    uint32_t *d_resid = nullptr, *d_resid_alloc = nullptr;  // d_resid = d_resid_alloc + 16: k_dec_recon_band reads up to 3 words before a tile's first
-    // The five symbol / residual planes (8 B per pixel) are carved out of `arena` when it is big enough: the context hands
-    // in its encode stream scratch, which no decode kernel reads and no encode kernel touches while a decode of the same
-    // context runs (calls on one context are ordered on one stream).  planes_in_arena: those pointers are not ours to free.
+    uint8_t *d_ctxsym = nullptr, *d_asym = nullptr, *d_alpha = nullptr, *d_nlseq = nullptr;  // (inside the arena)
+    uint32_t *d_resid = nullptr;         // (inside the arena, 16 words in: k_dec_recon_band reads up to 3 words before a tile's first)
     uint8_t *arena = nullptr;
     uint64_t arena_bytes = 0;
-    bool planes_in_arena = false;
 };
 inline void decode_ws_free(DecodeWs &w) {
     void *p[] = {w.d_info, w.d_off, w.d_wdec, w.d_dtab, w.d_wdec2, w.d_dtab2};
     for (void *q : p) if (q) (void)hipFree(q);
-    void *planes[] = {w.d_ctxsym, w.d_asym, w.d_alpha, w.d_nlseq, w.d_resid_alloc};
-    for (void *q : planes) if (q && !w.planes_in_arena) (void)hipFree(q);
-    if (w.side && !w.side_borrowed) (void)hipStreamDestroy(w.side);
-    if (w.side2) (void)hipStreamDestroy(w.side2);
-    if (w.ev_ctx) (void)hipEventDestroy(w.ev_ctx);
-    if (w.ev_small) (void)hipEventDestroy(w.ev_small);
-    if (w.ev_fork) (void)hipEventDestroy(w.ev_fork);
-    if (w.ev_join) (void)hipEventDestroy(w.ev_join);
-    uint8_t *arena = w.arena;
-    const uint64_t arena_bytes = w.arena_bytes;
-    hipStream_t lent = w.side_borrowed ? w.side : nullptr;
-    w = DecodeWs();  // (also clears last_off)
-    w.arena = arena; w.arena_bytes = arena_bytes;
-    if (lent) { w.side = lent; w.side_borrowed = true; }  // (what the context lent stays lent)
+    for (hipEvent_t e : {w.ev_fork, w.ev_join, w.ev_ctx, w.ev_small}) if (e) (void)hipEventDestroy(e);
+    w = DecodeWs();
 }
+// an event of the workspace, created when a launch sequence first needs it
+inline bool decode_ws_event(hipEvent_t &e) { return e || hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess; }
 
 // unaligned-safe little-endian u32 load from global memory (tile blobs are only byte-aligned after a raw RGB tile)
 __device__ __forceinline__ uint32_t ld32u(const uint8_t *p) {
@@ -530,86 +517,13 @@ __global__ __launch_bounds__(THREADS) void k_dec_alpha(const DecTile *__restrict
 }
 
 // --------------------------------------------------------------------------------------------------
-// context chain (libxpng.c:803: nl = *cx[nl]++, starting from 0).  Strictly serial per tile, so one wave per tile and
-// the step is made as short as the hardware allows: lane c < 9 owns queue c as an 8-symbol register window (low byte =
-// head) backed by two prefetched 8-byte chunks; a step is v_readlane (head of the current queue -> SGPR), a predicated
-// 8-bit shift on the owning lane, and a scalar pack of the output.  No LDS, no global load on the dependent chain.
-// Output: nl sequence in coded-pixel order.      grid = tiles, block = 64.
-// core of the walk: `base` = 256-byte aligned start of the tile's symbol area, qs = this lane's queue start inside it
-// (lanes 0..8), total = number of symbols to produce.  Single-wave workgroup.
+// context chain (libxpng.c:803: nl = *cx[nl]++, starting from 0).  Strictly serial per tile: one wave per tile, and the step is
+// made as short as the hardware allows.  `base` = 256-byte aligned start of the tile's symbol area, qs = this lane's queue start
+// inside it (lanes 0..8), total = number of symbols to produce; output: the nl sequence in coded-pixel order.  Single-wave workgroup.
 constexpr uint32_t WALK_RING = 512, WALK_UNIT = WALK_RING / 2;  // LDS ring of one context queue, and the unit it is refilled in
-__device__ inline void ctx_walk(const uint8_t *__restrict__ base, uint32_t qs_in, uint32_t total, uint8_t *__restrict__ out) {
-    const uint32_t lane = threadIdx.x & 63;
-    // queue supply: every queue is staged through its own 512-byte LDS ring in 256-byte units (coalesced copies by a quarter
-    // of the wave, triggered at 8-step block boundaries when a queue's read position nears the end of what is staged).  (1 KB
-    // rings until round 3: the walk waves of a pipelined batch held 9 KB of LDS each for their whole life.)
-    __shared__ __align__(16) uint8_t qring[9][WALK_RING];
-    const uint32_t qs = lane < 9 ? qs_in : 0;
-    const uint32_t qsa = qs & ~15u;  // 16-byte aligned start of this lane's queue inside the tile's symbol area
-    for (uint32_t c = 0; c < 9; c++) {
-        const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)qsa, (int)c);
-        const uint4 *src = reinterpret_cast<const uint4 *>(base + a) + lane;
-        if (lane < WALK_RING / 16) reinterpret_cast<uint4 *>(qring[c])[lane] = src[0];  // both units
-    }
-    __syncthreads();
-    uint32_t filled = 2;                      // units staged for this lane's queue
-    const uint32_t p0 = qs & 15u;             // ring position of the queue's first symbol
-    const uint32_t ql = lane < 9 ? lane : 0;  // lanes >= 9 never pop; they alias queue 0 harmlessly
-    uint64_t win = *reinterpret_cast<const uint64_t *>(&qring[ql][p0 & ~7u]) >> (8 * (p0 & 7u));
-    uint32_t have = 8 - (p0 & 7u);
-    uint32_t rdpos = (p0 & ~7u) + 8;          // next ring position to load into the register window
-    uint32_t cur = 0;
-    auto restage = [&]() {  // uniform entry; copies one more unit for every queue that is within 32 bytes of its staged end
-        uint64_t m = __ballot(lane < 9 && rdpos + 32 >= filled * WALK_UNIT);
-        if (m == 0) return;
-        __syncthreads();
-        while (m) {
-            const int c = __ffsll((long long)m) - 1;
-            m &= m - 1;
-            const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)qsa, c);
-            const uint32_t u = (uint32_t)__builtin_amdgcn_readlane((int)filled, c);
-            if (lane < WALK_UNIT / 16) {
-                const uint4 v = (reinterpret_cast<const uint4 *>(base + a) + lane)[u * (WALK_UNIT / 16)];
-                reinterpret_cast<uint4 *>(qring[c])[(u & 1u) * (WALK_UNIT / 16) + lane] = v;
-            }
-            if ((int)lane == c) filled++;
-        }
-        __syncthreads();
-    };
-    auto pop = [&]() -> uint32_t {  // returns the next nl (wave-uniform) and advances the owning queue
-        const uint32_t sym = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)win, (int)cur) & 0xFFu;
-        const bool mine = lane == cur;
-        win >>= mine ? 8 : 0;
-        have -= mine ? 1u : 0u;
-        if (have == 0) {  // divergent, once per 8 pops of a queue: next 8 symbols from the LDS ring
-            win = *reinterpret_cast<const uint64_t *>(&qring[ql][rdpos & (WALK_RING - 1)]);
-            rdpos += 8;
-            have = 8;
-        }
-        cur = sym;
-        return sym;
-    };
-    uint32_t k = 0;
-    for (; k + 8 <= total; k += 8) {
-        restage();
-        uint32_t lo = 0, hi = 0;
-#pragma unroll
-        for (int u = 0; u < 4; u++) lo |= pop() << (8 * u);
-#pragma unroll
-        for (int u = 0; u < 4; u++) hi |= pop() << (8 * u);
-        if (lane == 0) *reinterpret_cast<uint2 *>(out + k) = make_uint2(lo, hi);
-    }
-    restage();
-    for (; k < total; k++) {
-        const uint32_t sy = pop();
-        if (lane == 0) out[k] = (uint8_t)sy;
-    }
-}
-
-// --------------------------------------------------------------------------------------------------
-// The same chain on the SCALAR unit (single image: one wave per tile, latency is everything).  A step of the v_readlane form
-// above is ~16 VALU instructions of which five are dependent (readlane -> s_and -> v_cmp -> v_cndmask -> 64-bit shift ->
-// readlane), 45-60 ns.  Here the nine queue heads are 64-bit SGPR pairs s[40+2c : 41+2c] = (four symbols | marker bit 32) and the
+// The chain runs on the SCALAR unit.  (Its predecessor kept the queue heads in VGPR lanes: a step of ~16 VALU instructions of which
+// five are dependent - readlane -> s_and -> v_cmp -> v_cndmask -> 64-bit shift -> readlane - 45-60 ns.  It has no caller left and is
+// gone; git history has it.)  Here the nine queue heads are 64-bit SGPR pairs s[40+2c : 41+2c] = (four symbols | marker bit 32) and the
 // step is nine scalar instructions, ~21 ns:
 //     m0 = 2 cur;  t = SGPR[40 + m0] (s_movrels_b64);  cur = t & 0xff;  t >>= 8;  t == 1 ? refill;  SGPR[40 + m0] = t;  out lane k = cur
 // The refill (once per four pops of a queue) takes the queue's next dword from lane c's register pair (w0, w1 <- its LDS ring)
@@ -1629,55 +1543,68 @@ __global__ void k_dec_offsets(const uint8_t *const *__restrict__ blobs, const ui
     }
 }
 
-// (re)allocate the decode workspace and bring the tile offsets to the device (tile_off == nullptr: walk them there)
-inline int decode_ws_prepare(DecodeWs &ws, uint32_t B, uint64_t n_tiles, uint64_t plane, const uint64_t *tile_off, uint32_t t0,
-                             uint32_t total, hipStream_t s, std::string &err, const uint8_t *const *d_blob_ptrs = nullptr,
-                             const uint64_t *d_blob_len = nullptr) {
+// One decode job: what a launch sequence decodes, from where, to where.  Filled by dec_launch (xpng_hip.hip), read by
+// decode_m1_launch and decode_m2_launch.
+struct DecodeJob {
+    // geometry: B images of n_tiles tiles, `plane` bytes per symbol plane of the batch, rasters W pixels wide; the widest, tallest
+    // and narrowest tile of the selection
+    uint32_t B; uint64_t n_tiles, plane, W; uint32_t max_w, max_h, min_w; int pxsz;
+    // selection: tiles [t0, t1) of every image, enumerated by `order` (n_big of its tiles form the big-tile size class) or image-major
+    // (order == nullptr); or, for a region decode, the list_n work items of `list` (TileSel::list; t0, t1 = 0, n_tiles; no order:
+    // list launches run unsplit)
+    uint32_t t0, t1; const uint32_t *order; uint32_t n_big; const uint32_t *list; uint32_t list_n;
+    // device tables: tile table, B blob pointers and lengths, B raster pointers, status word; tile_off is a HOST array of blob
+    // offsets (image-major: B * (t1 - t0), or B * n_tiles for a list) or nullptr (walk the sizes on the device)
+    const TileDesc *tiles; const uint8_t *const *blobs; const uint64_t *blob_len; uint8_t *const *rasters; uint32_t *status;
+    const uint64_t *tile_off;
+    hipStream_t s;
+    uint64_t *stamps;  // phase stamps of the narrow chains (probe builds, XPNG_STAMPS) or nullptr
+    uint32_t cnt() const { return list ? list_n : t1 - t0; }        // work items per image (list: in all)
+    uint32_t total() const { return list ? list_n : B * (t1 - t0); }
+    TileSel sel() const { return TileSel{t0, cnt(), (uint32_t)n_tiles, B, list ? nullptr : order, list}; }
+};
+
+// (re)allocate the per-tile tables, place the five planes in the arena and bring the tile offsets to the device
+inline int decode_ws_prepare(DecodeWs &ws, const DecodeJob &j, std::string &err) {
     auto bad = [&](const char *m) { err = m; return 1; };
-    if (ws.cap_tiles < (uint64_t)B * n_tiles || ws.cap_plane < plane) {
-        decode_ws_free(ws);
+    const uint64_t vn = (uint64_t)j.B * j.n_tiles, plane = j.plane;
+    const uint32_t total = j.list ? (uint32_t)vn : j.total();  // offsets to bring
+    if (ws.cap_tiles < vn || ws.cap_plane < plane) {
+        for (void *q : {(void *)ws.d_info, (void *)ws.d_off, (void *)ws.d_wdec, (void *)ws.d_dtab}) if (q) (void)hipFree(q);
+        ws.d_info = nullptr; ws.d_off = nullptr; ws.d_wdec = nullptr; ws.d_dtab = nullptr;
+        ws.cap_tiles = ws.cap_plane = 0;
+        ws.last_off.clear();
         // (the context symbol area carries one largest tile of slack: a corrupt payload can make the walk pop one queue for all
         //  of a tile's steps, i.e. read up to a tile's pixel count past that queue's start)
         const uint64_t sz[5] = {rup(plane + 8192 + 450000, 256), rup(plane + 64, 256), rup(plane + 64, 256), rup(plane + 64, 256), rup(4 * plane + 1024, 256)};
-        void *pl[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        if (ws.arena && ws.arena_bytes >= sz[0] + sz[1] + sz[2] + sz[3] + sz[4] + 256 && !probe_env("XPNG_NO_ARENA")) {
-            uint8_t *q = reinterpret_cast<uint8_t *>(rup(reinterpret_cast<uintptr_t>(ws.arena), 256));
-            for (int i = 0; i < 5; i++) { pl[i] = q; q += sz[i]; }
-            ws.planes_in_arena = true;
-        } else {
-            for (int i = 0; i < 5; i++)
-                if (hipMalloc(&pl[i], sz[i]) != hipSuccess) {
-                    for (int j = 0; j < i; j++) (void)hipFree(pl[j]);
-                    return bad("hipMalloc failed (decode workspace)");
-                }
-        }
-        ws.d_ctxsym = (uint8_t *)pl[0]; ws.d_asym = (uint8_t *)pl[1]; ws.d_alpha = (uint8_t *)pl[2]; ws.d_nlseq = (uint8_t *)pl[3];
-        ws.d_resid_alloc = (uint32_t *)pl[4];
-        if (hipMalloc((void **)&ws.d_info, (uint64_t)B * n_tiles * sizeof(DecTile)) != hipSuccess || hipMalloc((void **)&ws.d_off, (uint64_t)B * n_tiles * 8) != hipSuccess ||
-            hipMalloc((void **)&ws.d_wdec, (uint64_t)B * n_tiles * 10 * sizeof(WDec)) != hipSuccess ||
-            hipMalloc((void **)&ws.d_dtab, (uint64_t)B * n_tiles * 10 * WD_TAB_MAX) != hipSuccess)
+        // (a hipMalloc fallback for the planes existed behind a probe switch; the context's arena always has the room, so it could never run)
+        if (!ws.arena || ws.arena_bytes < sz[0] + sz[1] + sz[2] + sz[3] + sz[4] + 256) return bad("internal error: the decode arena is too small for the symbol planes of this batch");
+        uint8_t *pl[5], *q = reinterpret_cast<uint8_t *>(rup(reinterpret_cast<uintptr_t>(ws.arena), 256));
+        for (int i = 0; i < 5; i++) { pl[i] = q; q += sz[i]; }
+        ws.d_ctxsym = pl[0]; ws.d_asym = pl[1]; ws.d_alpha = pl[2]; ws.d_nlseq = pl[3];
+        ws.d_resid = reinterpret_cast<uint32_t *>(pl[4]) + 16;
+        if (hipMalloc((void **)&ws.d_info, vn * sizeof(DecTile)) != hipSuccess || hipMalloc((void **)&ws.d_off, vn * 8) != hipSuccess ||
+            hipMalloc((void **)&ws.d_wdec, vn * 10 * sizeof(WDec)) != hipSuccess ||
+            hipMalloc((void **)&ws.d_dtab, vn * 10 * WD_TAB_MAX) != hipSuccess)
             return bad("hipMalloc failed (decode workspace)");
-        ws.d_resid = ws.d_resid_alloc + 16;
-        ws.cap_tiles = (uint64_t)B * n_tiles; ws.cap_plane = plane;
+        ws.cap_tiles = vn; ws.cap_plane = plane;
     }
-    if (!tile_off) {
-        if (!d_blob_ptrs || !d_blob_len) return bad("device-side size walk needs the blob tables");
-        k_dec_offsets<<<(B + 63) / 64, 64, 0, s>>>(d_blob_ptrs, d_blob_len, total / B, B, ws.d_off);
+    if (!j.tile_off) {
+        if (!j.blobs || !j.blob_len) return bad("device-side size walk needs the blob tables");
+        k_dec_offsets<<<(j.B + 63) / 64, 64, 0, j.s>>>(j.blobs, j.blob_len, total / j.B, j.B, ws.d_off);
         ws.last_off.clear();
         return 0;
     }
-    if (ws.last_off.size() != total || ws.last_t0 != t0 || memcmp(ws.last_off.data(), tile_off, (size_t)total * 8) != 0) {
+    if (ws.last_off.size() != total || ws.last_t0 != j.t0 || memcmp(ws.last_off.data(), j.tile_off, (size_t)total * 8) != 0) {
         // pageable host memory: the copy is staged synchronously, so only pay for it when the offsets changed
-        if (hipMemcpyAsync(ws.d_off, tile_off, (uint64_t)total * 8, hipMemcpyHostToDevice, s) != hipSuccess) return bad("tile offset upload failed");
-        if (hipStreamSynchronize(s) != hipSuccess) return bad("tile offset upload failed");
-        ws.last_off.assign(tile_off, tile_off + total);
-        ws.last_t0 = t0;
+        if (hipMemcpyAsync(ws.d_off, j.tile_off, (uint64_t)total * 8, hipMemcpyHostToDevice, j.s) != hipSuccess) return bad("tile offset upload failed");
+        if (hipStreamSynchronize(j.s) != hipSuccess) return bad("tile offset upload failed");
+        ws.last_off.assign(j.tile_off, j.tile_off + total);
+        ws.last_t0 = j.t0;
     }
     return 0;
 }
 
-// Launch the whole decode of tiles [t0, t1) of every image of the batch.  d_blob_ptrs / d_raster_ptrs are device arrays
-// of B pointers; tile_off holds B * cnt blob offsets (image-major), relative to each image's blob buffer.
 // geometry of the barrier-free reconstruction launch for tiles up to max_w x max_h (0 = use the barrier form)
 inline void recon_geometry(uint32_t max_w, uint32_t max_h, uint32_t &free_ew, uint32_t &threads, uint32_t &lds) {
     const uint32_t nw = (max_h + 63) / 64;
@@ -1693,137 +1620,137 @@ inline uint32_t recon_grid(uint32_t n) {
     return cap && cap < n ? cap : n;
 }
 
-inline int decode_m1_launch(DecodeWs &ws, uint32_t B, uint64_t n_tiles, uint64_t plane_total, const TileDesc *d_tiles, uint64_t W,
-                            uint32_t max_w, uint32_t max_h, int pxsz, const uint8_t *const *d_blob_ptrs, const uint64_t *d_blob_len,
-                            uint32_t *d_status, const uint64_t *tile_off, uint32_t t0, uint32_t t1,
-                            uint8_t *const *d_raster_ptrs, hipStream_t s, std::string &err, uint64_t *dbg = nullptr,
-                            const uint32_t *d_order = nullptr, uint32_t n_big = 0, uint32_t min_w = 0,
-                            const uint32_t *d_list = nullptr, uint32_t list_n = 0) {
-    // d_list: the tiles of a region decode (TileSel::list, list_n work items; tile_off then holds B * n_tiles full-table offsets).
-    // A list launch runs unsplit (the caller passes no d_order): DESIGN.md 12.
-    const uint32_t cnt = d_list ? list_n : t1 - t0, total = d_list ? list_n : B * cnt, spt = pxsz == 4 ? 10 : 9;
-    // RGBA: the residual kernel rebuilds alpha from its symbols itself (k_dec_resid FOLD) when every tile is at least 4 pixels wide -
-    // every tile of a file the reference can write (RGBA narrower than 4 px is stored at level 7); otherwise k_dec_alpha makes the plane
-    const bool fold = pxsz == 4 && min_w >= 4 && !probe_env("XPNG_NO_ALPHA_FOLD");
-    const TileSel sel{t0, cnt, (uint32_t)n_tiles, B, d_list ? nullptr : d_order, d_list};
-    const uint64_t plane = plane_total;
-    auto bad = [&](const char *m) { err = m; return 1; };
-    dbg_count_sequence();
-    if (decode_ws_prepare(ws, B, n_tiles, plane, tile_off, t0, d_list ? B * (uint32_t)n_tiles : total, s, err, d_blob_ptrs, d_blob_len)) return 1;
-    // (a null workspace pointer handed to a kernel is a GPU fault, i.e. abort(): refuse to launch instead)
-    if (!ws.d_info || !ws.d_off || !ws.d_wdec || !ws.d_dtab || !ws.d_ctxsym || !ws.d_asym || !ws.d_alpha || !ws.d_nlseq || !ws.d_resid || !d_tiles || !d_blob_ptrs || !d_raster_ptrs)
-        return bad("internal error: a decode workspace buffer was never allocated");
-    const uint64_t bpr = W * (uint64_t)pxsz;
-    uint32_t free_ew, rthreads, rlds;
-    recon_geometry(max_w, max_h, free_ew, rthreads, rlds);
-    if (!ws.side && chain_stream_create(&ws.side) != hipSuccess) return bad("stream creation failed");
-    if (!ws.ev_fork && (hipEventCreateWithFlags(&ws.ev_fork, hipEventDisableTiming) != hipSuccess ||
-                        hipEventCreateWithFlags(&ws.ev_join, hipEventDisableTiming) != hipSuccess)) return bad("event creation failed");
-    k_dec_parse<<<(total + 63) / 64, 64, 0, s>>>(d_blob_ptrs, ws.d_off, d_blob_len, cnt, total, spt, pxsz, d_tiles, sel, ws.d_info, d_status);
+// What decode_m1_launch decides before its first kernel.
+struct DecodePlan {
     // Many tiles in flight: instruction issue is the bound, so the rANS chains run 32 streams to a wave (rans2_wide_dec.hpp);
     // few tiles: latency is the bound and a wave per stream (scalar cursors, hot-symbol registers) is quicker.
-    const bool wide = !getenv("XPNG_NARROW_RANS") && ((uint64_t)total * spt > 2048 || getenv("XPNG_WIDE_RANS"));
-    const size_t pad_ch = probe_pad("XPNG_PAD_CHAIN");
+    bool wide;
+    // RGBA: the residual kernel rebuilds alpha from its symbols itself (k_dec_resid FOLD) when every tile is at least 4 pixels wide -
+    // every tile of a file the reference can write (RGBA narrower than 4 px is stored at level 7); otherwise k_dec_alpha makes the plane
+    bool fold;
+    bool band;    // band reconstruction (k_dec_recon_band); otherwise the anti-diagonal form with the geometry below
+    bool split;   // two size classes on two streams (see decode_m1_launch)
+    uint32_t jb;  // split: work items [0, jb) are the big-tile class
+    uint32_t free_ew, rthreads, rlds;  // recon_geometry
+    // probe builds: bytes of unused dynamic LDS per workgroup (occupancy throttles) and the no-store switch; all 0 in the release library.
+    // pad_recon is the occupancy limiter of the band reconstruction (XPNG_RECON_LDS_PAD): its scattered 16-byte loads and stores fill
+    // the memory pipeline's queues and the chain kernels of the other pipeline slots then wait for their words
+    size_t pad_chain, pad_alpha, pad_walk, pad_resid, pad_recon;
+    uint32_t nostore;
+};
+inline DecodePlan decode_m1_plan(const DecodeJob &j) {
+    DecodePlan p{};
+    const uint32_t cnt = j.cnt(), total = j.total(), spt = j.pxsz == 4 ? 10 : 9;
+    p.wide = wide_form((uint64_t)total * spt);
+    p.fold = j.pxsz == 4 && j.min_w >= 4 && !probe_env("XPNG_NO_ALPHA_FOLD");
+    p.band = p.wide && j.max_w <= RB_MAXW && !probe_env("XPNG_WAVEFRONT_RECON");
+    p.split = p.band && !j.list && j.order && j.n_big > 0 && j.n_big < cnt && !probe_env("XPNG_NARROW_WALK") && !getenv("XPNG_NO_SPLIT");
+    p.jb = p.split ? j.n_big * j.B : 0;
+    recon_geometry(j.max_w, j.max_h, p.free_ew, p.rthreads, p.rlds);
+    p.pad_chain = probe_pad("XPNG_PAD_CHAIN"); p.pad_alpha = probe_pad("XPNG_PAD_AL"); p.pad_walk = probe_pad("XPNG_PAD_WALK");
+    p.pad_resid = probe_pad("XPNG_PAD_RS"); p.pad_recon = probe_pad("XPNG_RECON_LDS_PAD");
+    p.nostore = probe_env("XPNG_DBG_NOSTORE") ? 1u : 0u;
+    return p;
+}
+
+// The tail of a size class: residual extraction, then reconstruction, of work items [first, first + n) on stream st.
+// skip_resid / skip_recon: the knock-out names of the two kernels (probe builds).
+template <int PXSZ>
+inline void dec_tail(const DecodeWs &ws, const DecodeJob &j, const DecodePlan &p, const TileSel &sel, uint32_t first, uint32_t n,
+                     hipStream_t st, const char *skip_resid, const char *skip_recon) {
+    const uint64_t bpr = j.W * (uint64_t)PXSZ;
+    const uint32_t total = j.total();
+    if (dbg_skip(skip_resid)) {}
+    else if constexpr (PXSZ == 4) {
+        if (p.wide && p.fold) k_dec_resid<4, 256, true><<<n, 256, p.pad_resid, st>>>(ws.d_info, j.tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, first);
+        else if (p.wide) k_dec_resid<4, 256><<<n, 256, p.pad_resid, st>>>(ws.d_info, j.tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, first);
+        else if (p.fold) k_dec_resid<4, 1024, true><<<n, 1024, 0, st>>>(ws.d_info, j.tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, first);
+        else k_dec_resid<4, 1024><<<n, 1024, 0, st>>>(ws.d_info, j.tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, first);
+    } else {  // (RGB has no alpha to fold)
+        if (p.wide) k_dec_resid<3, 256><<<n, 256, p.pad_resid, st>>>(ws.d_info, j.tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, first);
+        else k_dec_resid<3, 1024><<<n, 1024, 0, st>>>(ws.d_info, j.tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, first);
+    }
+    if (dbg_skip(skip_recon)) {}
+    else if (p.band) k_dec_recon_band<PXSZ><<<recon_grid(n), 64, RB_LDS_BYTES(j.max_w) + p.pad_recon, st>>>(ws.d_info, j.tiles, sel, ws.d_resid, j.rasters, bpr, p.nostore, first, first + n);
+    else if (p.free_ew) k_dec_recon<PXSZ><<<total, p.rthreads, p.rlds, st>>>(ws.d_info, j.tiles, sel, ws.d_alpha, ws.d_resid, j.rasters, bpr, p.free_ew);  // (never split: n == total)
+    else k_dec_recon<PXSZ><<<total, 1024, 0, st>>>(ws.d_info, j.tiles, sel, ws.d_alpha, ws.d_resid, j.rasters, bpr, 0);
+}
+
+// Launch the whole level-1 decode of a job.
+inline int decode_m1_launch(DecodeWs &ws, const DecodeJob &j, std::string &err) {
+    auto bad = [&](const char *m) { err = m; return 1; };
+    const DecodePlan p = decode_m1_plan(j);
+    const TileSel sel = j.sel();
+    const uint32_t cnt = j.cnt(), total = j.total(), spt = j.pxsz == 4 ? 10 : 9, jb = p.jb;
+    const hipStream_t s = j.s, side = ws.side;
+    const bool rgba = j.pxsz == 4;
+    const auto tail = rgba ? &dec_tail<4> : &dec_tail<3>;
+    dbg_count_sequence();
+    if (decode_ws_prepare(ws, j, err)) return 1;
+    // (a null workspace pointer handed to a kernel is a GPU fault, i.e. abort(): refuse to launch instead)
+    if (!ws.d_info || !ws.d_off || !ws.d_wdec || !ws.d_dtab || !ws.d_ctxsym || !ws.d_asym || !ws.d_alpha || !ws.d_nlseq || !ws.d_resid || !j.tiles || !j.blobs || !j.rasters)
+        return bad("internal error: a decode workspace buffer was never allocated");
+    if (!side) return bad("internal error: the decode has no side stream");
+    if (!decode_ws_event(ws.ev_fork) || !decode_ws_event(ws.ev_join) || (p.split && (!decode_ws_event(ws.ev_ctx) || !decode_ws_event(ws.ev_small)))) return bad("event creation failed");
+
+    // ---- parse + prep
+    k_dec_parse<<<(total + 63) / 64, 64, 0, s>>>(j.blobs, ws.d_off, j.blob_len, cnt, total, spt, j.pxsz, j.tiles, sel, ws.d_info, j.status);
     constexpr uint32_t WD_CTX_STREAMS = 32, WD_ALPHA_STREAMS = 32;  // (16 alpha streams per wave - half the LDS per workgroup, twice the waves - measures the same)
     const uint32_t groups = (total + WD_CTX_STREAMS - 1) / WD_CTX_STREAMS, agroups = (total + WD_ALPHA_STREAMS - 1) / WD_ALPHA_STREAMS;
-    if (wide) if (!dbg_skip("dec_prep")) k_rans2_dec_prep<<<total * spt, 64, 0, s>>>(ws.d_info, d_tiles, sel, spt, ws.d_ctxsym, ws.d_asym, ws.d_wdec, ws.d_dtab);
-    // The alpha branch (its rANS block is the longest serial chain of a tile) and the nl-context branch (nine short
-    // rANS blocks, then the serial context walk) are independent until k_dec_resid: run them on two HIP streams.
-    if (pxsz == 4) {
-        if (hipEventRecord(ws.ev_fork, s) != hipSuccess || hipStreamWaitEvent(ws.side, ws.ev_fork, 0) != hipSuccess) return bad("fork failed");
-        if (wide && !probe_env("XPNG_NARROW_ALPHA")) { if (!dbg_skip("dec_chain_a")) k_rans2_dec_chain<true, WD_ALPHA_STREAMS, true><<<agroups, 64, DecChainLds<true, WD_ALPHA_STREAMS>::BYTES + pad_ch, ws.side>>>(ws.d_info, total, 9, 1, ws.d_wdec, ws.d_dtab, ws.d_ctxsym, ws.d_asym); }
-        else k_rans2_decode<15><<<total, 64, 0, ws.side>>>(ws.d_info, d_tiles, sel, 9, 1, 0, ws.d_ctxsym, ws.d_asym, dbg);
-        const size_t pad_al = probe_pad("XPNG_PAD_AL");
-        if (fold || dbg_skip("dec_alpha")) {} else if (wide) k_dec_alpha<256><<<total, 256, pad_al, ws.side>>>(ws.d_info, d_tiles, sel, ws.d_asym, ws.d_alpha);
-        else k_dec_alpha<1024><<<total, 1024, 0, ws.side>>>(ws.d_info, d_tiles, sel, ws.d_asym, ws.d_alpha);
-        if (hipEventRecord(ws.ev_join, ws.side) != hipSuccess) return bad("join record failed");
+    if (p.wide && !dbg_skip("dec_prep")) k_rans2_dec_prep<<<total * spt, 64, 0, s>>>(ws.d_info, j.tiles, sel, spt, ws.d_ctxsym, ws.d_asym, ws.d_wdec, ws.d_dtab);
+
+    // ---- alpha branch, on the side stream: its rANS block is the longest serial chain of a tile, and it is independent of the
+    // nl-context branch (nine short rANS blocks, then the serial context walk) until k_dec_resid
+    if (rgba) {
+        if (hipEventRecord(ws.ev_fork, s) != hipSuccess || hipStreamWaitEvent(side, ws.ev_fork, 0) != hipSuccess) return bad("fork failed");
+        if (p.wide && !probe_env("XPNG_NARROW_ALPHA")) { if (!dbg_skip("dec_chain_a")) k_rans2_dec_chain<true, WD_ALPHA_STREAMS, true><<<agroups, 64, DecChainLds<true, WD_ALPHA_STREAMS>::BYTES + p.pad_chain, side>>>(ws.d_info, total, 9, 1, ws.d_wdec, ws.d_dtab, ws.d_ctxsym, ws.d_asym); }
+        else k_rans2_decode<15><<<total, 64, 0, side>>>(ws.d_info, j.tiles, sel, 9, 1, 0, ws.d_ctxsym, ws.d_asym, j.stamps);
+        if (p.fold || dbg_skip("dec_alpha")) {} else if (p.wide) k_dec_alpha<256><<<total, 256, p.pad_alpha, side>>>(ws.d_info, j.tiles, sel, ws.d_asym, ws.d_alpha);
+        else k_dec_alpha<1024><<<total, 1024, 0, side>>>(ws.d_info, j.tiles, sel, ws.d_asym, ws.d_alpha);
+        if (hipEventRecord(ws.ev_join, side) != hipSuccess) return bad("join record failed");
     }
-    if (wide) {
-        if (!dbg_skip("dec_chain_c")) k_rans2_dec_chain<false, WD_CTX_STREAMS, false><<<groups * 9, 64, DecChainLds<false, WD_CTX_STREAMS>::BYTES + pad_ch, s>>>(ws.d_info, total, 0, 9, ws.d_wdec, ws.d_dtab, ws.d_ctxsym, ws.d_asym);
+
+    // ---- context chains
+    if (p.wide) {
+        if (!dbg_skip("dec_chain_c")) k_rans2_dec_chain<false, WD_CTX_STREAMS, false><<<groups * 9, 64, DecChainLds<false, WD_CTX_STREAMS>::BYTES + p.pad_chain, s>>>(ws.d_info, total, 0, 9, ws.d_wdec, ws.d_dtab, ws.d_ctxsym, ws.d_asym);
         // context streams the small layout cannot hold (PROB_BITS > 12 or more than 16 symbols: never written by the reference)
-        if (!dbg_skip("dec_odd")) k_rans2_decode_rest<15><<<128, 64, 0, s>>>(ws.d_info, d_tiles, sel, total, 0, 9, ws.d_ctxsym, ws.d_asym, dbg, ws.d_wdec);
+        if (!dbg_skip("dec_odd")) k_rans2_decode_rest<15><<<128, 64, 0, s>>>(ws.d_info, j.tiles, sel, total, 0, 9, ws.d_ctxsym, ws.d_asym, j.stamps, ws.d_wdec);
         // (k_rans2_decode_rest resolves slots by binary search: 4.6 KB of LDS, so its 128 workgroups are placed at once - with the
         //  37 KB slot table of k_rans2_decode<15> they waited up to 5 ms, between the chains and the walk, to find nothing to do)
     } else {
-        k_rans2_decode<12><<<total * 9, 64, 0, s>>>(ws.d_info, d_tiles, sel, 0, 9, 0, ws.d_ctxsym, ws.d_asym, dbg);
-        k_rans2_decode<15><<<total * 9, 64, 0, s>>>(ws.d_info, d_tiles, sel, 0, 9, 1, ws.d_ctxsym, ws.d_asym, dbg);  // blocks with PROB_BITS > 12 only
+        k_rans2_decode<12><<<total * 9, 64, 0, s>>>(ws.d_info, j.tiles, sel, 0, 9, 0, ws.d_ctxsym, ws.d_asym, j.stamps);
+        k_rans2_decode<15><<<total * 9, 64, 0, s>>>(ws.d_info, j.tiles, sel, 0, 9, 1, ws.d_ctxsym, ws.d_asym, j.stamps);  // blocks with PROB_BITS > 12 only
     }
+
+    // ---- walk(s) and tail(s)
     // Two size classes: the walk's duration is the chain of the biggest tile, and the work enumeration is sorted by size, so the
     // first n_big tiles of the order (x B images) are walked beside the rest - shorter chains, the lane-per-tile form - and each
     // class goes on to its own residual extraction and reconstruction: what is left behind the longer walk is the tail of ITS tiles only.
-    // [r4] On TWO streams: the small-tile class stays on the caller's stream behind the context chains; the big-tile class runs on the
+    // On TWO streams: the small-tile class stays on the caller's stream behind the context chains; the big-tile class runs on the
     // side stream BEHIND the alpha chains (its walk, ~14 ms, starts ~13 ms later than it could and still ends before the small tiles'
-    // walk, ~28 ms, does).  Rounds 2-3 gave the small-tile class a third stream: every stream alive is a hardware queue, and with
-    // 4 streams per context the fifth and sixth pipeline slot LOST throughput (36 / 33 against 38.5 Gpx/s); with one side stream for
-    // the encode's and the decode's alpha branch and no third stream, 64 x 6 reads 43 where 64 x 4 reads 39 (profiles/r04_experiments.txt).
-    // (probe builds: XPNG_SPLIT3=1 = the three-stream form.)
-    const bool band = wide && max_w <= RB_MAXW && !probe_env("XPNG_WAVEFRONT_RECON");
-    const bool split = band && sel.order && n_big > 0 && n_big < cnt && !probe_env("XPNG_NARROW_WALK") && !getenv("XPNG_NO_SPLIT");
-    const bool split3 = split && probe_env("XPNG_SPLIT3");
-    const uint32_t jb = split ? n_big * B : 0;
-    const uint32_t nostore = probe_env("XPNG_DBG_NOSTORE") ? 1u : 0u;
-    // Occupancy limiter of the band reconstruction: 12 KB of unused LDS per wave keep it at ~10 waves per CU.  Its scattered
-    // 16-byte loads and stores (64 rows per instruction) fill the memory pipeline's queues, and the chain kernels of the other
-    // pipeline slots, which touch memory once per 8-step block, then wait for their words: decode-only rate at 3 slots
-    // 43 -> 51 Gpx/s, combined bench +4 % (XPNG_RECON_LDS_PAD=0 turns it off)
-    const size_t dbg_pad = probe_pad("XPNG_RECON_LDS_PAD");
-    const size_t pad_rs = probe_pad("XPNG_PAD_RS");
-    const uint32_t lpw = probe_env("XPNG_WALK_LPW") ? (uint32_t)atoi(probe_env("XPNG_WALK_LPW")) : 64u;  // tiles per wavefront of the small-tile walk: 64, or (probe builds) 32 / 16 - the same bytes
-    // ts / tb: the streams the small-tile and the big-tile tails run on
-    hipStream_t ts = s, tb = s;
-    if (split) {
-        if (!ws.ev_ctx && (hipEventCreateWithFlags(&ws.ev_ctx, hipEventDisableTiming) != hipSuccess ||
-                           hipEventCreateWithFlags(&ws.ev_small, hipEventDisableTiming) != hipSuccess)) return bad("event creation failed");
-        if (split3) {
-            if (!ws.side2 && chain_stream_create(&ws.side2) != hipSuccess) return bad("stream creation failed");
-            ts = ws.side2;
-        } else tb = ws.side;
-        hipStream_t other = split3 ? ts : tb;  // the stream that is not `s`: it starts behind the context chains
-        if (hipEventRecord(ws.ev_ctx, s) != hipSuccess || hipStreamWaitEvent(other, ws.ev_ctx, 0) != hipSuccess) return bad("fork failed");
-        if (!dbg_skip("walk_small")) {
-            if (lpw == 32) k_dec_walk_wide<32><<<(total - jb + 31) / 32, 64, WALK_WIDE_LDS_BYTES(32) + pad_ch + probe_pad("XPNG_PAD_WALK"), ts>>>(ws.d_info, d_tiles, sel, total, ws.d_ctxsym, ws.d_nlseq, jb);
-            else if (lpw == 16) k_dec_walk_wide<16><<<(total - jb + 15) / 16, 64, WALK_WIDE_LDS_BYTES(16) + pad_ch + probe_pad("XPNG_PAD_WALK"), ts>>>(ws.d_info, d_tiles, sel, total, ws.d_ctxsym, ws.d_nlseq, jb);
-            else k_dec_walk_wide<64><<<(total - jb + 63) / 64, 64, WALK_WIDE_LDS_BYTES(64) + pad_ch + probe_pad("XPNG_PAD_WALK"), ts>>>(ws.d_info, d_tiles, sel, total, ws.d_ctxsym, ws.d_nlseq, jb);
-        }
+    // walk, ~28 ms, does).  A third stream for the small-tile class LOST: every stream alive is a hardware queue, and with 4 streams per
+    // context the fifth and sixth pipeline slot cost throughput (36 / 33 against 38.5 Gpx/s; DESIGN.md 6, profiles/r04_experiments.txt).
+    if (p.split) {
+        if (hipEventRecord(ws.ev_ctx, s) != hipSuccess || hipStreamWaitEvent(side, ws.ev_ctx, 0) != hipSuccess) return bad("fork failed");
+        // (64 tiles per wavefront; 32 gave the same bytes no faster: profiles/r04_experiments.txt)
+        if (!dbg_skip("walk_small")) k_dec_walk_wide<64><<<(total - jb + 63) / 64, 64, WALK_WIDE_LDS_BYTES(64) + p.pad_chain + p.pad_walk, s>>>(ws.d_info, j.tiles, sel, total, ws.d_ctxsym, ws.d_nlseq, jb);
         // the biggest tiles' chains are the longest of the decode: they get the scalar-unit walk, one wave per tile (~40 ns per
         // step against ~95 for the lane-per-tile form; a few waves per CU, so the CU's one scalar ALU is not contended), while
-        // the many smaller tiles keep the lane-per-tile form beside them (XPNG_WIDE_BIG_WALK=1: the old form for both)
-        if (dbg_skip("walk_big")) {} else if (probe_env("XPNG_WIDE_BIG_WALK")) k_dec_walk_wide<64><<<(jb + 63) / 64, 64, WALK_WIDE_LDS_BYTES(64), tb>>>(ws.d_info, d_tiles, sel, jb, ws.d_ctxsym, ws.d_nlseq, 0);
-        else k_dec_walk<<<jb, 64, pad_ch, tb>>>(ws.d_info, d_tiles, sel, ws.d_ctxsym, ws.d_nlseq);
+        // the many smaller tiles keep the lane-per-tile form beside them (the lane-per-tile form for both lost: DESIGN.md 6,
+        // profiles/r03_experiments.txt)
+        if (!dbg_skip("walk_big")) k_dec_walk<<<jb, 64, p.pad_chain, side>>>(ws.d_info, j.tiles, sel, ws.d_ctxsym, ws.d_nlseq);
         // (RGBA: the alpha symbols are complete at ev_join, recorded on the side stream right behind the alpha chains - in front of the
-        //  big-tile walk when that runs there)
-        if (pxsz == 4 && ts != ws.side && hipStreamWaitEvent(ts, ws.ev_join, 0) != hipSuccess) return bad("join failed");
-        if (pxsz == 4) {
-            if (dbg_skip("resid_small")) {} else if (fold) k_dec_resid<4, 256, true><<<total - jb, 256, pad_rs, ts>>>(ws.d_info, d_tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, jb);
-            else k_dec_resid<4, 256><<<total - jb, 256, pad_rs, ts>>>(ws.d_info, d_tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, jb);
-            if (!dbg_skip("recon_small")) k_dec_recon_band<4><<<recon_grid(total - jb), 64, RB_LDS_BYTES(max_w) + dbg_pad, ts>>>(ws.d_info, d_tiles, sel, ws.d_resid, d_raster_ptrs, bpr, nostore, jb, total);
-        } else {
-            k_dec_resid<3, 256><<<total - jb, 256, 0, ts>>>(ws.d_info, d_tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, jb);
-            k_dec_recon_band<3><<<recon_grid(total - jb), 64, RB_LDS_BYTES(max_w) + dbg_pad, ts>>>(ws.d_info, d_tiles, sel, ws.d_resid, d_raster_ptrs, bpr, 0u, jb, total);
-        }
-    } else if (wide && !probe_env("XPNG_NARROW_WALK")) k_dec_walk_wide<64><<<(total + 63) / 64, 64, WALK_WIDE_LDS_BYTES(64), s>>>(ws.d_info, d_tiles, sel, total, ws.d_ctxsym, ws.d_nlseq, 0);
-    else k_dec_walk<<<total, 64, 0, s>>>(ws.d_info, d_tiles, sel, ws.d_ctxsym, ws.d_nlseq);
-    const uint32_t nt = split ? jb : total;  // work items [0, nt): the big-tile class of a split decode (on tb), or everything (on s)
-    if (pxsz == 4 && tb != ws.side && hipStreamWaitEvent(tb, ws.ev_join, 0) != hipSuccess) return bad("join failed");
-    if (pxsz == 4) {
-        if (dbg_skip("resid_big")) {} else if (wide && fold) k_dec_resid<4, 256, true><<<nt, 256, pad_rs, tb>>>(ws.d_info, d_tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, 0);
-        else if (wide) k_dec_resid<4, 256><<<nt, 256, pad_rs, tb>>>(ws.d_info, d_tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, 0);
-        else if (fold) k_dec_resid<4, 1024, true><<<nt, 1024, 0, tb>>>(ws.d_info, d_tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, 0);
-        else k_dec_resid<4, 1024><<<nt, 1024, 0, tb>>>(ws.d_info, d_tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, 0);
-        if (dbg_skip("recon_big")) {} else if (band) k_dec_recon_band<4><<<recon_grid(nt), 64, RB_LDS_BYTES(max_w) + dbg_pad, tb>>>(ws.d_info, d_tiles, sel, ws.d_resid, d_raster_ptrs, bpr, nostore, 0, nt);
-        else if (free_ew) k_dec_recon<4><<<total, rthreads, rlds, tb>>>(ws.d_info, d_tiles, sel, ws.d_alpha, ws.d_resid, d_raster_ptrs, bpr, free_ew);
-        else k_dec_recon<4><<<total, 1024, 0, tb>>>(ws.d_info, d_tiles, sel, ws.d_alpha, ws.d_resid, d_raster_ptrs, bpr, 0);
+        //  big-tile walk, so only the caller's stream has to wait for it)
+        if (rgba && s != side && hipStreamWaitEvent(s, ws.ev_join, 0) != hipSuccess) return bad("join failed");
+        tail(ws, j, p, sel, jb, total - jb, s, "resid_small", "recon_small");
+        tail(ws, j, p, sel, 0, jb, side, "resid_big", "recon_big");
+        // the side stream hands in its tail's end
+        if (hipEventRecord(ws.ev_small, side) != hipSuccess || hipStreamWaitEvent(s, ws.ev_small, 0) != hipSuccess) return bad("join failed");
     } else {
-        if (wide) k_dec_resid<3, 256><<<nt, 256, 0, tb>>>(ws.d_info, d_tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, 0);
-        else k_dec_resid<3, 1024><<<nt, 1024, 0, tb>>>(ws.d_info, d_tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, 0);
-        if (band) k_dec_recon_band<3><<<recon_grid(nt), 64, RB_LDS_BYTES(max_w) + dbg_pad, tb>>>(ws.d_info, d_tiles, sel, ws.d_resid, d_raster_ptrs, bpr, 0u, 0, nt);
-        else if (free_ew) k_dec_recon<3><<<total, rthreads, rlds, tb>>>(ws.d_info, d_tiles, sel, ws.d_alpha, ws.d_resid, d_raster_ptrs, bpr, free_ew);
-        else k_dec_recon<3><<<total, 1024, 0, tb>>>(ws.d_info, d_tiles, sel, ws.d_alpha, ws.d_resid, d_raster_ptrs, bpr, 0);
-    }
-    // everything rejoins the caller's stream: the stream that is not `s` hands in its tail's end
-    if (split) {
-        hipStream_t other = split3 ? ts : tb;
-        if (hipEventRecord(ws.ev_small, other) != hipSuccess || hipStreamWaitEvent(s, ws.ev_small, 0) != hipSuccess) return bad("join failed");
+        if (p.wide && !probe_env("XPNG_NARROW_WALK")) k_dec_walk_wide<64><<<(total + 63) / 64, 64, WALK_WIDE_LDS_BYTES(64), s>>>(ws.d_info, j.tiles, sel, total, ws.d_ctxsym, ws.d_nlseq, 0);
+        else k_dec_walk<<<total, 64, 0, s>>>(ws.d_info, j.tiles, sel, ws.d_ctxsym, ws.d_nlseq);
+        if (rgba && s != side && hipStreamWaitEvent(s, ws.ev_join, 0) != hipSuccess) return bad("join failed");
+        tail(ws, j, p, sel, 0, total, s, "resid_big", "recon_big");
     }
     if (hipGetLastError() != hipSuccess) return bad("decode kernel launch failed");
     return 0;

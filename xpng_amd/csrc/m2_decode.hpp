@@ -7,7 +7,7 @@
 //                    shared bit stream `b` in block order and must be read serially (sparse tables have data-dependent length)
 //   k_rans1_decode   one wave per (tile, stream): forwards over the symbols, state0 refills before state1; same hot-symbol
 //                    cache / LDS tables / scalar word cursor as the v2 decoder
-//   ctx_walk         the nl context chain (shared with mode 1)
+//   ctx_walk_salu    the nl context chain (shared with mode 1)
 //   k_m2_dec_resid   class-stream routing back to pixels (rank by nl: packed prefix sums, four pixels per lane), zig-zag / green add-back
 //   k_m2_dec_recon   fill / raw copy / anti-diagonal wavefront (shared with mode 1); gray tiles use predictor m
 #pragma once
@@ -494,41 +494,37 @@ __global__ __launch_bounds__(64) void k_m2_dec_recon_band(const M2DecTile *__res
     recon_band_core<3>(t, dst, bpr, resid + t.pbase, first, predmode, rb_lds, seam, 0u);
 }
 
-inline int m2_wide_decode(DecodeWs &ws, uint32_t B, uint64_t n_tiles, uint32_t total, const M2DecTile *d_info2, const TileDesc *d_tiles,
-                          TileSel sel, const M2Blk *d_blk2, const uint16_t *d_tabs2, uint8_t *d_scratch2, const uint64_t *d_sbase2,
-                          const uint32_t *d_stream_n2, hipStream_t s, std::string &err);  // rans1_wide_dec.hpp
+// the level-2 buffers of a decode job (the context's; DecodeJob has the rest)
+struct M2DecBufs { M2DecTile *info2; M2Blk *blk2; uint16_t *tabs2; uint8_t *scratch2; const uint64_t *sbase2; uint32_t *stream_n2; };
 
-// Launch the mode-2 decode of tiles [t0, t1) of every image of the batch, or of the tiles of d_list (RGB only).
-inline int decode_m2_launch(DecodeWs &ws, uint32_t B, uint64_t n_tiles, uint64_t plane_total, const TileDesc *d_tiles, uint64_t W,
-                            uint32_t max_w, uint32_t max_h,
-                            const uint8_t *const *d_blob_ptrs, const uint64_t *d_blob_len, uint32_t *d_status,
-                            const uint64_t *tile_off, uint32_t t0, uint32_t t1,
-                            uint8_t *const *d_raster_ptrs, M2DecTile *d_info2, M2Blk *d_blk2, uint16_t *d_tabs2, uint8_t *d_scratch2,
-                            const uint64_t *d_sbase2, uint32_t *d_stream_n2, hipStream_t s, std::string &err,
-                            const uint32_t *d_list = nullptr, uint32_t list_n = 0) {
-    // d_list: the tiles of a region decode (TileSel::list, list_n work items; tile_off then holds B * n_tiles full-table offsets)
-    const uint32_t cnt = d_list ? list_n : t1 - t0, total = d_list ? list_n : B * cnt;
-    const TileSel sel{t0, cnt, (uint32_t)n_tiles, B, nullptr, d_list};
-    if (decode_ws_prepare(ws, B, n_tiles, plane_total, tile_off, t0, d_list ? B * (uint32_t)n_tiles : total, s, err, d_blob_ptrs, d_blob_len)) return 1;
-    if (!ws.d_off || !ws.d_nlseq || !ws.d_resid || !d_info2 || !d_blk2 || !d_tabs2 || !d_scratch2 || !d_sbase2 || !d_stream_n2 || !d_tiles || !d_blob_ptrs || !d_raster_ptrs) {
+inline int m2_wide_decode(DecodeWs &ws, const DecodeJob &j, const M2DecBufs &m, const TileSel &sel, std::string &err);  // rans1_wide_dec.hpp
+
+// Launch the level-2 decode of a job (RGB only).
+inline int decode_m2_launch(DecodeWs &ws, const DecodeJob &j, const M2DecBufs &m, std::string &err) {
+    const uint32_t cnt = j.cnt(), total = j.total();
+    const hipStream_t s = j.s;
+    TileSel sel = j.sel();
+    sel.order = nullptr;  // (level 2 enumerates image-major)
+    if (decode_ws_prepare(ws, j, err)) return 1;
+    if (!ws.d_off || !ws.d_nlseq || !ws.d_resid || !ws.side || !m.info2 || !m.blk2 || !m.tabs2 || !m.scratch2 || !m.sbase2 || !m.stream_n2 || !j.tiles || !j.blobs || !j.rasters) {
         err = "internal error: a mode-2 decode workspace buffer was never allocated";  // (a null pointer in a kernel is a GPU fault = abort())
         return 1;
     }
-    const uint64_t bpr = W * 3;
-    if (hipMemsetAsync(d_blk2, 0, (uint64_t)B * n_tiles * M2_SLOTS * sizeof(M2Blk), s) != hipSuccess) { err = "memset failed"; return 1; }
-    k_m2_dec_parse<<<(total + 63) / 64, 64, 0, s>>>(d_blob_ptrs, ws.d_off, d_blob_len, cnt, total, d_tiles, sel, d_info2, d_blk2, d_tabs2, d_stream_n2, d_status);
-    if (getenv("XPNG_NARROW_RANS") || ((uint64_t)total * M2_STREAMS <= 2048 && !getenv("XPNG_WIDE_RANS"))) {
-        k_rans1_decode<14><<<total * M2_STREAMS, 64, 0, s>>>(d_info2, d_tiles, sel, 0, M2_STREAMS, d_blk2, d_tabs2, d_scratch2, d_sbase2, d_stream_n2);
-        k_rans1_decode<15><<<total, 64, 0, s>>>(d_info2, d_tiles, sel, 17, 1, d_blk2, d_tabs2, d_scratch2, d_sbase2, d_stream_n2);  // gray tiles
-    } else if (m2_wide_decode(ws, B, n_tiles, total, d_info2, d_tiles, sel, d_blk2, d_tabs2, d_scratch2, d_sbase2, d_stream_n2, s, err)) return 1;
-    k_m2_dec_walk<<<total, 64, 0, s>>>(d_info2, d_tiles, sel, d_scratch2, d_sbase2, d_stream_n2, ws.d_nlseq);
-    if ((uint64_t)total * M2_STREAMS > 2048 && !probe_env("XPNG_BIG_BLOCKS")) k_m2_dec_resid<256><<<total, 256, 0, s>>>(d_info2, d_tiles, sel, d_scratch2, d_sbase2, d_stream_n2, ws.d_nlseq, ws.d_resid);
-    else k_m2_dec_resid<1024><<<total, 1024, 0, s>>>(d_info2, d_tiles, sel, d_scratch2, d_sbase2, d_stream_n2, ws.d_nlseq, ws.d_resid);
+    const uint64_t bpr = j.W * 3, items = (uint64_t)total * M2_STREAMS;
+    const bool wide = wide_form(items);
+    if (hipMemsetAsync(m.blk2, 0, (uint64_t)j.B * j.n_tiles * M2_SLOTS * sizeof(M2Blk), s) != hipSuccess) { err = "memset failed"; return 1; }
+    k_m2_dec_parse<<<(total + 63) / 64, 64, 0, s>>>(j.blobs, ws.d_off, j.blob_len, cnt, total, j.tiles, sel, m.info2, m.blk2, m.tabs2, m.stream_n2, j.status);
+    if (!wide) {
+        k_rans1_decode<14><<<total * M2_STREAMS, 64, 0, s>>>(m.info2, j.tiles, sel, 0, M2_STREAMS, m.blk2, m.tabs2, m.scratch2, m.sbase2, m.stream_n2);
+        k_rans1_decode<15><<<total, 64, 0, s>>>(m.info2, j.tiles, sel, 17, 1, m.blk2, m.tabs2, m.scratch2, m.sbase2, m.stream_n2);  // gray tiles
+    } else if (m2_wide_decode(ws, j, m, sel, err)) return 1;
+    k_m2_dec_walk<<<total, 64, 0, s>>>(m.info2, j.tiles, sel, m.scratch2, m.sbase2, m.stream_n2, ws.d_nlseq);
+    if (small_blocks(items)) k_m2_dec_resid<256><<<total, 256, 0, s>>>(m.info2, j.tiles, sel, m.scratch2, m.sbase2, m.stream_n2, ws.d_nlseq, ws.d_resid);
+    else k_m2_dec_resid<1024><<<total, 1024, 0, s>>>(m.info2, j.tiles, sel, m.scratch2, m.sbase2, m.stream_n2, ws.d_nlseq, ws.d_resid);
     uint32_t free_ew, rthreads, rlds;
-    recon_geometry(max_w, max_h, free_ew, rthreads, rlds);
-    const bool wide_recon = !getenv("XPNG_NARROW_RANS") && ((uint64_t)total * M2_STREAMS > 2048 || getenv("XPNG_WIDE_RANS")) && max_w <= RB_MAXW && !probe_env("XPNG_WAVEFRONT_RECON");
-    if (wide_recon) k_m2_dec_recon_band<<<total, 64, RB_LDS_BYTES(max_w), s>>>(d_info2, d_tiles, sel, ws.d_resid, d_raster_ptrs, bpr);
-    else k_m2_dec_recon<<<total, rthreads, rlds, s>>>(d_info2, d_tiles, sel, ws.d_resid, d_raster_ptrs, bpr, free_ew);
+    recon_geometry(j.max_w, j.max_h, free_ew, rthreads, rlds);
+    if (wide && j.max_w <= RB_MAXW && !probe_env("XPNG_WAVEFRONT_RECON")) k_m2_dec_recon_band<<<total, 64, RB_LDS_BYTES(j.max_w), s>>>(m.info2, j.tiles, sel, ws.d_resid, j.rasters, bpr);
+    else k_m2_dec_recon<<<total, rthreads, rlds, s>>>(m.info2, j.tiles, sel, ws.d_resid, j.rasters, bpr, free_ew);
     if (hipGetLastError() != hipSuccess) { err = "mode-2 decode kernel launch failed"; return 1; }
     return 0;
 }

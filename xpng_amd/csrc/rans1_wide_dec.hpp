@@ -306,10 +306,10 @@ __global__ __launch_bounds__(64) void k_rans1_dec_chain(const M2DecTile *__restr
     }
 }
 
-inline int m2_wide_decode(DecodeWs &ws, uint32_t B, uint64_t n_tiles, uint32_t total, const M2DecTile *d_info2, const TileDesc *d_tiles,
-                          TileSel sel, const M2Blk *d_blk2, const uint16_t *d_tabs2, uint8_t *d_scratch2, const uint64_t *d_sbase2,
-                          const uint32_t *d_stream_n2, hipStream_t s, std::string &err) {
-    const uint64_t need = (uint64_t)B * n_tiles * M2_SLOTS;
+inline int m2_wide_decode(DecodeWs &ws, const DecodeJob &j, const M2DecBufs &m, const TileSel &sel, std::string &err) {
+    const uint64_t need = (uint64_t)j.B * j.n_tiles * M2_SLOTS;
+    const uint32_t total = j.total();
+    const hipStream_t s = j.s;
     if (ws.cap2 < need) {
         if (ws.d_wdec2) (void)hipFree(ws.d_wdec2);
         if (ws.d_dtab2) (void)hipFree(ws.d_dtab2);
@@ -321,15 +321,13 @@ inline int m2_wide_decode(DecodeWs &ws, uint32_t B, uint64_t n_tiles, uint32_t t
         ws.cap2 = need;
     }
     const uint32_t groups = (total + 31) / 32;
-    k_rans1_dec_prep<<<total * 18, 64, 0, s>>>(d_info2, d_tiles, sel, d_blk2, d_tabs2, d_scratch2, d_sbase2, d_stream_n2, ws.d_wdec2, ws.d_dtab2);
+    k_rans1_dec_prep<<<total * 18, 64, 0, s>>>(m.info2, j.tiles, sel, m.blk2, m.tabs2, m.scratch2, m.sbase2, m.stream_n2, ws.d_wdec2, ws.d_dtab2);
     // the two chain launches are independent: the big-alphabet slots run on the side stream beside the small ones
-    if (!ws.side && chain_stream_create(&ws.side) != hipSuccess) { err = "stream creation failed"; return 1; }
-    if (!ws.ev_fork && (hipEventCreateWithFlags(&ws.ev_fork, hipEventDisableTiming) != hipSuccess ||
-                        hipEventCreateWithFlags(&ws.ev_join, hipEventDisableTiming) != hipSuccess)) { err = "event creation failed"; return 1; }
+    if (!decode_ws_event(ws.ev_fork) || !decode_ws_event(ws.ev_join)) { err = "event creation failed"; return 1; }
     if (hipEventRecord(ws.ev_fork, s) != hipSuccess || hipStreamWaitEvent(ws.side, ws.ev_fork, 0) != hipSuccess) { err = "fork failed"; return 1; }
-    k_rans1_dec_chain<true><<<groups * 7, 64, Dec1ChainLds<true>::BYTES, ws.side>>>(d_info2, total, ws.d_wdec2, ws.d_dtab2, d_scratch2);
+    k_rans1_dec_chain<true><<<groups * 7, 64, Dec1ChainLds<true>::BYTES, ws.side>>>(m.info2, total, ws.d_wdec2, ws.d_dtab2, m.scratch2);
     if (hipEventRecord(ws.ev_join, ws.side) != hipSuccess) { err = "join record failed"; return 1; }
-    k_rans1_dec_chain<false><<<groups * 11, 64, Dec1ChainLds<false>::BYTES, s>>>(d_info2, total, ws.d_wdec2, ws.d_dtab2, d_scratch2);
+    k_rans1_dec_chain<false><<<groups * 11, 64, Dec1ChainLds<false>::BYTES, s>>>(m.info2, total, ws.d_wdec2, ws.d_dtab2, m.scratch2);
     if (hipStreamWaitEvent(s, ws.ev_join, 0) != hipSuccess) { err = "join failed"; return 1; }
     return 0;
 }

@@ -118,7 +118,7 @@ static void ctx_quiesce(xpnghip_ctx *c) {
     int prev = -1;
     (void)hipGetDevice(&prev);
     if (hipSetDevice(c->device) == hipSuccess) {
-        hipStream_t qs[5] = {c->stream, c->enc_side, c->enc_side2, c->dec.side, c->dec.side2};
+        hipStream_t qs[3] = {c->stream, c->enc_side, c->dec.side};
         for (hipStream_t q : qs) if (q) (void)hipStreamSynchronize(q);
     }
     if (prev >= 0 && prev != c->device) (void)hipSetDevice(prev);
@@ -188,7 +188,7 @@ static std::vector<Shard> make_shards(const std::vector<TileDesc> &tiles, int D)
     }
     return out;
 }
-// ONE device, one ordinary image (the narrow regime: at most 2048 (tile, stream) pairs): the call is cut into tile-row groups
+// ONE device, one ordinary image (the narrow regime: at most NARROW_MAX_ITEMS (tile, stream) pairs): the call is cut into tile-row groups
 // that run on the SAME device, each on a context and stream of its own, so that transfers and kernels of one call overlap
 // (6.1 of the 22.5 ms of a 4096^2 decode call were copies):
 //   encode - group 0 is the first tile row: it holds the biggest tile, whose alpha chain is the critical path of the call, and
@@ -199,7 +199,7 @@ static std::vector<Shard> make_shards(const std::vector<TileDesc> &tiles, int D)
 static bool pipeline_shards(const std::vector<TileDesc> &tiles, int pxsz, uint64_t raster_bytes, int dev, std::vector<Shard> &out) {
     out.clear();
     const uint64_t N = tiles.size();
-    if (N * (pxsz == 4 ? 10 : 9) > 2048 || raster_bytes < (24u << 20) || probe_env("XPNG_NO_PIPELINE_SHARDS")) return false;
+    if (N * (pxsz == 4 ? 10 : 9) > NARROW_MAX_ITEMS || raster_bytes < (24u << 20) || probe_env("XPNG_NO_PIPELINE_SHARDS")) return false;
     std::vector<uint64_t> row_start;  // first tile of every tile row
     for (uint64_t i = 0; i < N; i++) if (i == 0 || tiles[i].y != tiles[i - 1].y) row_start.push_back(i);
     const uint64_t R = row_start.size();

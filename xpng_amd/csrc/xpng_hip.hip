@@ -137,9 +137,7 @@ struct xpnghip_ctx {
     WPrep *d_wprep = nullptr;   // wide entropy stage: per (tile, stream) record, encoder tables, normalised frequencies
     uint8_t *d_wtab = nullptr;
     uint32_t nlh_slots = 0, nlh_generic = 0;  // records per tile in d_nlh (m1_encode.hpp); which transform form wrote them last
-    uint32_t n_big = 0, n_top = 0;  // tiles of the biggest size class (>= 3/4 of the largest pixel count); tiles as large as the largest
-    hipStream_t enc_side2 = nullptr;      // the alpha streams of the biggest tiles, a wavefront each, beside the wide chains of the rest
-    hipEvent_t ev_enc_join2 = nullptr;
+    uint32_t n_big = 0;  // tiles of the biggest size class (>= 3/4 of the largest pixel count)
     uint16_t *d_wF = nullptr;
     // mode 2 (RGB slow level): allocated on first use
     uint8_t *d_scratch2 = nullptr;
@@ -191,8 +189,6 @@ extern "C" void xpnghip_ctx_destroy(xpnghip_ctx *c) {
                     c->d_wprep, c->d_wtab, c->d_wF, c->d_blob_len, c->d_status, c->d_scratch2, c->d_sbase2, c->d_flags2, c->d_stream_n2, c->d_blk2, c->d_mt2, c->d_info2, c->d_tabs2, c->d_w1prep, c->d_w1tab, c->d_w1F, c->d_region_stage, c->d_region_meta};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->enc_side) (void)hipStreamDestroy(c->enc_side);
-    if (c->enc_side2) (void)hipStreamDestroy(c->enc_side2);
-    if (c->ev_enc_join2) (void)hipEventDestroy(c->ev_enc_join2);
     if (c->ev_enc_fork) (void)hipEventDestroy(c->ev_enc_fork);
     if (c->ev_enc_join) (void)hipEventDestroy(c->ev_enc_join);
     decode_ws_free(c->dec);
@@ -273,8 +269,8 @@ static int ctx_create_range_impl(xpnghip_ctx **out, int device, uint64_t w, uint
         std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return c->tiles[a].n > c->tiles[b].n; });
         if (hipMemcpy(c->d_order, ord.data(), ord.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { xpnghip_ctx_destroy(c); return fail("context setup failed"); }
         // size class of the biggest tiles (>= 3/4 of the largest pixel count): the decode walks them beside the rest (m1_decode.hpp)
-        c->n_big = 0; c->n_top = 0;
-        for (uint32_t i : ord) { if ((uint64_t)c->tiles[i].n * 4 >= (uint64_t)c->tiles[ord[0]].n * 3) c->n_big++; if (c->tiles[i].n == c->tiles[ord[0]].n) c->n_top++; }
+        c->n_big = 0;
+        for (uint32_t i : ord) if ((uint64_t)c->tiles[i].n * 4 >= (uint64_t)c->tiles[ord[0]].n * 3) c->n_big++;
     }
     c->stamps = c->d_dbg && probe_env("XPNG_STAMPS") != nullptr;  // (probe builds only)
 #ifdef XPNG_PROBES
@@ -449,8 +445,7 @@ static int launch_encode_m1(xpnghip_ctx *c, uint32_t nimg, uint32_t t0, uint32_t
     const uint64_t bpr = c->W * PXSZ;
     uint32_t max_w = 0;
     for (uint32_t i = t0; i < t1; i++) max_w = c->tiles[i].w > max_w ? c->tiles[i].w : max_w;
-    const bool narrow = getenv("XPNG_NARROW_RANS") || (total * c->spt <= 2048 && !getenv("XPNG_WIDE_RANS"));
-    const bool small_wg = (uint64_t)total * c->spt > 2048 && !probe_env("XPNG_BIG_BLOCKS");
+    const bool narrow = !wide_form((uint64_t)total * c->spt), small_wg = small_blocks((uint64_t)total * c->spt);
     static const size_t pad_tr = probe_pad("XPNG_PAD_TR"), pad_st = probe_pad("XPNG_PAD_ST"), pad_ga = probe_pad("XPNG_PAD_GA");
     if (ensure_planes(c) || ensure_scratch(c)) return 1;  // (before their address is taken below)
     XPNG_REQUIRE(c->d_planes, c->d_in_ptrs, c->d_out_ptrs, c->d_tiles, c->d_scratch, c->d_sums, c->d_ctx_n, c->d_k_n,
@@ -469,33 +464,14 @@ static int launch_encode_m1(xpnghip_ctx *c, uint32_t nimg, uint32_t t0, uint32_t
     if (launch_transform<PXSZ>(c, nimg, t0, t1, s, pad_tr, true)) return 1;
     // Wide form, RGBA: the alpha chains are the longest serial stage of the encode and need only the alpha plane, so their
     // preparation and the chains themselves run on their own stream behind the transform
-    // Size classes of the alpha chains: an experiment of round 4 that LOST (probe builds: XPNG_ENC_SPLIT=1).  The wide chain kernel lasts
-    // as long as its longest chain (the biggest tile: 148 k steps of ~400 cycles at 4096^2; the median wavefront of a launch ends after two
-    // thirds of that) and the wave-per-stream form steps in ~176 cycles, so the alpha streams of the biggest size class (the first n_big
-    // tiles of the sorted enumeration x every image) were given a wavefront each on a third stream, k_rans2_encode with c_first = 9.
-    // Bit-exact, 67 GPU tests green - and 33.7-35.3 against 38.2-40.1 Gpx/s at 64 x 4 (1088 such wavefronts of 26.8 KB of LDS and 176
-    // registers each per launch: two thirds of the chip's LDS for ~11 ms), 42.0 against 44.3 at 128 x 4 (only the 128 tiles as large as
-    // the largest).  profiles/r04_experiments.txt.
-    uint32_t jb = 0;
-    if (alpha_side && sel.order && probe_env("XPNG_ENC_SPLIT")) {
-        const uint32_t nb = (uint64_t)c->n_big * nimg <= 1152 ? c->n_big : ((uint64_t)c->n_top * nimg <= 1152 ? c->n_top : 0u);
-        if (nb > 0 && nb < cnt) jb = nb * nimg;
-    }
-    if (jb && !c->enc_side2) {
-        HIPCHK(chain_stream_create(&c->enc_side2));
-        HIPCHK(hipEventCreateWithFlags(&c->ev_enc_join2, hipEventDisableTiming));
-    }
+    // (Size classes of the alpha chains - the biggest tiles' alpha streams a wavefront each on a third stream - LOST: DESIGN.md 6,
+    //  profiles/r04_experiments.txt.)
     if (alpha_side) {
         HIPCHK(hipEventRecord(c->ev_enc_fork, s));
         hipStream_t as = probe_env("XPNG_ONE_STREAM") ? s : c->enc_side;  // (probe builds: every kernel of the context on the caller's stream)
         HIPCHK(hipStreamWaitEvent(as, c->ev_enc_fork, 0));
-        if (jb) {
-            HIPCHK(hipStreamWaitEvent(c->enc_side2, c->ev_enc_fork, 0));
-            if (!dbg_skip("chain_a")) k_rans2_encode<<<jb, 64, 0, c->enc_side2>>>(c->d_tiles, sel, 9, 1, planesA, c->plane_stride, c->d_scratch, c->d_ctx_n, c->d_blk_sz, c->d_wprep, nullptr);
-            HIPCHK(hipEventRecord(c->ev_enc_join2, c->enc_side2));
-        }
-        if (!dbg_skip("prep_a")) k_rans2_prep<<<total - jb, 64, 0, as>>>(c->d_tiles, sel, 9, 1, planesA, c->plane_stride, c->d_scratch, c->d_ctx_n, c->d_blk_sz, c->d_wprep, c->d_wtab, c->d_wF, jb, watab);
-        if (!dbg_skip("chain_a")) k_rans2_chain2<true><<<(total - jb + 31) / 32, 64, chain2_lds_bytes<true>() + probe_pad("XPNG_PAD_CHAIN"), as>>>(c->d_tiles, sel, total, planesA, c->plane_stride, c->d_scratch, c->d_ctx_n, c->d_wprep, c->d_wtab, jb, watab);
+        if (!dbg_skip("prep_a")) k_rans2_prep<<<total, 64, 0, as>>>(c->d_tiles, sel, 9, 1, planesA, c->plane_stride, c->d_scratch, c->d_ctx_n, c->d_blk_sz, c->d_wprep, c->d_wtab, c->d_wF, 0, watab);
+        if (!dbg_skip("chain_a")) k_rans2_chain2<true><<<(total + 31) / 32, 64, chain2_lds_bytes<true>() + probe_pad("XPNG_PAD_CHAIN"), as>>>(c->d_tiles, sel, total, planesA, c->plane_stride, c->d_scratch, c->d_ctx_n, c->d_wprep, c->d_wtab, 0, watab);
         HIPCHK(hipEventRecord(c->ev_enc_join, as));
     }
     // stream lengths (from the histogram of the nl plane the transform took as it wrote it) -> places of the nine context streams -> routing
@@ -509,7 +485,6 @@ static int launch_encode_m1(xpnghip_ctx *c, uint32_t nimg, uint32_t t0, uint32_t
         if (!dbg_skip("prep_c")) k_rans2_prep<<<total * 9, 64, 0, s>>>(c->d_tiles, sel, 0, 9, planesA, c->plane_stride, c->d_scratch, c->d_ctx_n, c->d_blk_sz, c->d_wprep, c->d_wtab, c->d_wF, 0, watab);
         if (!dbg_skip("chain_c")) k_rans2_chain2<false><<<((total + 31) / 32) * 9, 64, chain2_lds_bytes<false>() + probe_pad("XPNG_PAD_CHAIN"), s>>>(c->d_tiles, sel, total, planesA, c->plane_stride, c->d_scratch, c->d_ctx_n, c->d_wprep, c->d_wtab, 0, watab);
         if (alpha_side) HIPCHK(hipStreamWaitEvent(s, c->ev_enc_join, 0));
-        if (jb) HIPCHK(hipStreamWaitEvent(s, c->ev_enc_join2, 0));
         if (!dbg_skip("finish")) k_rans2_finish<<<total * c->spt, 64, 0, s>>>(c->d_tiles, sel, c->spt, planesA, c->plane_stride, c->d_scratch, c->d_ctx_n, c->d_blk_sz, c->d_wprep, c->d_wF);
     }
     k_tile_sizes<<<(total + 255) / 256, 256, 0, s>>>(c->d_tiles, sel, total, PXSZ, c->spt, c->d_sums, c->d_k_n, c->d_blk_sz, c->d_tile_sz, c->d_tile_hdr);
@@ -553,11 +528,11 @@ static int launch_encode_m2(xpnghip_ctx *c, uint32_t nimg, uint32_t t0, uint32_t
     if (launch_transform<3>(c, nimg, t0, t1, s, 0, true)) return 1;  // chooser (PXSZ = 3, libxpng.c:663) + residual planes (allocates them on first use) + nl histogram
     XPNG_REQUIRE(c->d_planes);
     k_m2_count<<<total, 64, 0, s>>>(c->d_tiles, sel, c->d_flags2, c->d_nlh, c->nlh_slots, c->nlh_generic, c->d_stream_n2);  // stream lengths -> where every stream goes
-    if ((uint64_t)total * M2_STREAMS > 2048 && !probe_env("XPNG_BIG_BLOCKS")) k_m2_streams<256><<<total, 256, 0, s>>>(c->d_tiles, sel, c->d_flags2, c->d_planes, c->plane_stride, c->d_scratch2, c->d_sbase2, c->d_stream_n2);
+    if (small_blocks((uint64_t)total * M2_STREAMS)) k_m2_streams<256><<<total, 256, 0, s>>>(c->d_tiles, sel, c->d_flags2, c->d_planes, c->plane_stride, c->d_scratch2, c->d_sbase2, c->d_stream_n2);
     else k_m2_streams<1024><<<total, 1024, 0, s>>>(c->d_tiles, sel, c->d_flags2, c->d_planes, c->plane_stride, c->d_scratch2, c->d_sbase2, c->d_stream_n2);
     const uint32_t gbpt = (max_n + 256 * M2_GRAY_REPS - 1) / (256 * M2_GRAY_REPS);
     k_m2_gray_syms<<<total * gbpt, 256, 0, s>>>(c->d_in_ptrs, bpr, c->d_tiles, sel, gbpt, c->d_flags2, c->d_scratch2, c->d_sbase2, c->d_stream_n2);
-    if (getenv("XPNG_NARROW_RANS") || ((uint64_t)total * M2_STREAMS <= 2048 && !getenv("XPNG_WIDE_RANS"))) {
+    if (!wide_form((uint64_t)total * M2_STREAMS)) {
         k_rans1_encode<<<total * M2_SLOTS, 64, 0, s>>>(c->d_tiles, sel, c->d_flags2, c->d_scratch2, c->d_sbase2, c->d_stream_n2, c->d_blk2);
     } else {  // every lane a chain: prep -> chains (small and big alphabets) -> finish
         if (!c->d_w1prep) {
@@ -620,17 +595,38 @@ static int dec_prepare(xpnghip_ctx *c, int mode, const void *const *d_blobs, con
     }
     HIPCHK(hipMemsetAsync(c->d_status, 0, 4, s));
     if (ensure_arena(c)) return 1;
-    if (!c->dec.side) {  // (also after decode_ws_prepare rebuilt the workspace: it forgets the loan)
-        if (!c->enc_side) HIPCHK(chain_stream_create(&c->enc_side));
-        c->dec.side = c->enc_side; c->dec.side_borrowed = true;
-    }
-    if (probe_env("XPNG_ONE_STREAM")) { c->dec.side = s; c->dec.side_borrowed = true; }
-    XPNG_REQUIRE(c->d_dec_in_ptrs, c->d_dec_out_ptrs, c->d_blob_len, c->d_status, c->d_tiles, c->dec.arena);
+    if (!c->enc_side) HIPCHK(chain_stream_create(&c->enc_side));
+    c->dec.side = probe_env("XPNG_ONE_STREAM") ? s : c->enc_side;  // (probe builds: every kernel of the context on the caller's stream)
+    XPNG_REQUIRE(c->d_dec_in_ptrs, c->d_dec_out_ptrs, c->d_blob_len, c->d_status, c->d_tiles, c->dec.arena, c->dec.side);
     if (mode == 2) {
         if (ensure_m2(c)) return 1;
         XPNG_REQUIRE(c->d_info2, c->d_blk2, c->d_tabs2, c->d_scratch2, c->d_sbase2, c->d_stream_n2);
     }
     return 0;
+}
+
+// The one description of a decode launch (DecodeJob, m1_decode.hpp), and the launch.  The tile set is the range [t0, t1) of every
+// image, or - a region decode - `list`: virtual tiles (image * N + tile), resident on the device as d_list, decoded into rasters W
+// pixels wide.
+static int dec_launch(xpnghip_ctx *c, int mode, uint32_t nimg, uint64_t W, const uint64_t *tile_off, hipStream_t s, uint32_t t0, uint32_t t1,
+                      const std::vector<uint32_t> *list = nullptr, const uint32_t *d_list = nullptr) {
+    const uint64_t N = c->tiles.size();
+    DecodeJob j{};
+    j.B = nimg; j.n_tiles = N; j.plane = c->plane_stride; j.W = W; j.pxsz = c->pxsz;
+    j.min_w = ~0u;
+    auto scan = [&](const TileDesc &t) { j.max_w = std::max(j.max_w, t.w); j.max_h = std::max(j.max_h, t.h); j.min_w = std::min(j.min_w, t.w); };
+    if (list) for (uint32_t v : *list) scan(c->tiles[v % N]);
+    else for (uint32_t i = t0; i < t1; i++) scan(c->tiles[i]);
+    j.t0 = t0; j.t1 = t1;
+    j.order = list ? nullptr : order_for(c, t0, t1);
+    j.n_big = j.order ? c->n_big : 0u;
+    j.list = d_list; j.list_n = list ? (uint32_t)list->size() : 0u;
+    j.tiles = c->d_tiles; j.blobs = c->d_dec_in_ptrs; j.blob_len = c->d_blob_len; j.rasters = c->d_dec_out_ptrs; j.status = c->d_status;
+    j.tile_off = tile_off;
+    j.s = s;
+    j.stamps = c->stamps && !list ? c->d_dbg + N * c->B * 80 : nullptr;
+    if (mode == 2) return decode_m2_launch(c->dec, j, M2DecBufs{c->d_info2, c->d_blk2, c->d_tabs2, c->d_scratch2, c->d_sbase2, c->d_stream_n2}, g_err);
+    return decode_m1_launch(c->dec, j, g_err);
 }
 
 extern "C" int xpnghip_decode_device_batch(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
@@ -641,14 +637,7 @@ extern "C" int xpnghip_decode_device_batch(xpnghip_ctx *c, int mode, const void 
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(c);
     if (dec_prepare(c, mode, d_blobs, blobs_len, nimg, d_rasters, s)) return 1;
-    uint32_t max_w = 0, max_h = 0, min_w = ~0u;
-    for (uint64_t i = t0; i < t1; i++) { max_w = c->tiles[i].w > max_w ? c->tiles[i].w : max_w; max_h = c->tiles[i].h > max_h ? c->tiles[i].h : max_h; min_w = c->tiles[i].w < min_w ? c->tiles[i].w : min_w; }
-    if (mode == 2)
-        return decode_m2_launch(c->dec, nimg, c->tiles.size(), c->plane_stride, c->d_tiles, c->W, max_w, max_h, c->d_dec_in_ptrs, c->d_blob_len, c->d_status, tile_off, (uint32_t)t0,
-                                (uint32_t)t1, c->d_dec_out_ptrs, c->d_info2, c->d_blk2, c->d_tabs2, c->d_scratch2, c->d_sbase2, c->d_stream_n2, s, g_err);
-    return decode_m1_launch(c->dec, nimg, c->tiles.size(), c->plane_stride, c->d_tiles, c->W, max_w, max_h, c->pxsz, c->d_dec_in_ptrs, c->d_blob_len, c->d_status, tile_off,
-                            (uint32_t)t0, (uint32_t)t1, c->d_dec_out_ptrs, s, g_err, c->stamps ? c->d_dbg + c->tiles.size() * c->B * 80 : nullptr,
-                            order_for(c, (uint32_t)t0, (uint32_t)t1), order_for(c, (uint32_t)t0, (uint32_t)t1) ? c->n_big : 0u, min_w);
+    return dec_launch(c, mode, nimg, c->W, tile_off, s, (uint32_t)t0, (uint32_t)t1);
 }
 extern "C" int xpnghip_decode_device(xpnghip_ctx *c, int mode, const void *d_blobs, uint64_t blobs_len,
                                      const uint64_t *tile_off, uint64_t t0, uint64_t t1, void *d_raster, void *stream) {
@@ -690,7 +679,6 @@ static int region_batch_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
     std::vector<uint32_t> list, sel;
     std::vector<uint64_t> box(4ull * nimg);  // X0, Y0, X1, Y1
     uint64_t bw = 0, bh = 0, max_rows = 0;
-    uint32_t max_w = 0, max_h = 0, min_w = ~0u;
     for (uint32_t i = 0; i < nimg; i++) {
         region_select(c->tiles, rects + 4ull * i, sel);
         uint64_t *b = &box[4ull * i];
@@ -699,7 +687,6 @@ static int region_batch_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
             const TileDesc &d = c->tiles[t];
             b[0] = std::min<uint64_t>(b[0], d.x); b[1] = std::min<uint64_t>(b[1], d.y);
             b[2] = std::max<uint64_t>(b[2], (uint64_t)d.x + d.w); b[3] = std::max<uint64_t>(b[3], (uint64_t)d.y + d.h);
-            max_w = std::max(max_w, d.w); max_h = std::max(max_h, d.h); min_w = std::min(min_w, d.w);
             list.push_back((uint32_t)(i * N + t));
         }
         bw = std::max(bw, b[2] - b[0]); bh = std::max(bh, b[3] - b[1]);
@@ -754,11 +741,7 @@ static int region_batch_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
     const RegionCopy *d_rc = reinterpret_cast<const RegionCopy *>(c->d_region_meta + list_bytes);
     if (dec_prepare(c, mode, d_blobs, blobs_len, nimg, vbase.data(), s)) return 1;
     XPNG_REQUIRE(c->d_region_stage, c->d_region_meta);
-    const int rc_launch = mode == 2
-        ? decode_m2_launch(c->dec, nimg, N, c->plane_stride, c->d_tiles, bw, max_w, max_h, c->d_dec_in_ptrs, c->d_blob_len, c->d_status, tile_off, 0, (uint32_t)N,
-                           c->d_dec_out_ptrs, c->d_info2, c->d_blk2, c->d_tabs2, c->d_scratch2, c->d_sbase2, c->d_stream_n2, s, g_err, d_list, (uint32_t)list.size())
-        : decode_m1_launch(c->dec, nimg, N, c->plane_stride, c->d_tiles, bw, max_w, max_h, c->pxsz, c->d_dec_in_ptrs, c->d_blob_len, c->d_status, tile_off, 0, (uint32_t)N,
-                           c->d_dec_out_ptrs, s, g_err, nullptr, nullptr, 0u, min_w, d_list, (uint32_t)list.size());
+    const int rc_launch = dec_launch(c, mode, nimg, bw, tile_off, s, 0, (uint32_t)N, &list, d_list);
     if (rc_launch) return rc_launch;
     k_region_copy<<<dim3((uint32_t)((max_rows + RC_ROWS - 1) / RC_ROWS), nimg), 256, 0, s>>>(d_rc, c->d_region_stage, sbpr, out_bpr);
     HIPCHK(hipGetLastError());
