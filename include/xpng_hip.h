@@ -187,6 +187,41 @@ int xpnghip_decode_region_device_batch(xpnghip_ctx *ctx, int mode, const void *c
                                        uint32_t nimg, const uint64_t *tile_off, const uint64_t *rects,
                                        void *const *d_outs, uint64_t out_bpr, void *stream);
 
+/* ---- mixed-size batch decode: images of different sizes in one device call (INTEGRATION.md "Mixed-size batches") ----------
+ * A mixed context is DECODE ONLY.  It holds nimg images of one pixel size (pxsz 3 or 4) whose widths and heights differ:
+ * dims = nimg pairs {w, h}.  Its tile table is the concatenation of the images' tile tables, M = sum of their tile counts entries
+ * (M must fit in 32 bits; w, h <= 1 << 24; nimg <= 4096), and every workspace is sized from M and the summed pixel counts.
+ * xpnghip_ctx_tile_count returns M and xpnghip_ctx_tile walks the concatenated table; xpnghip_ctx_mixed_first_tile(ctx, i) is the
+ * table index of image i's first tile, for i == nimg it is M (so image i has first_tile(i + 1) - first_tile(i) tiles); beyond
+ * nimg, or on an ordinary context, it returns UINT64_MAX.  xpnghip_ctx_batch returns nimg.  The encode, transform, tile-range
+ * decode and region decode entry points refuse a mixed context with an error text before any device work. */
+int xpnghip_ctx_create_mixed(xpnghip_ctx **ctx, int device, const uint64_t *dims, uint32_t nimg, int pxsz);
+uint64_t xpnghip_ctx_mixed_first_tile(const xpnghip_ctx *ctx, uint32_t image);
+/* One launch over all M tiles (an explicit work list sorted by decreasing pixel count; unsplit).  One tile mode per
+ * call (mode 2: RGB only).  d_blobs[i] / blobs_len[i]: image i's tile body on the device (64 readable bytes behind it, as above).
+ * tile_off == NULL: the size walk runs on the device, one lane per image; otherwise tile_off holds M offsets, image after image,
+ * each relative to its own blob buffer.
+ *   out_bpr != 0  padded batch: every d_outs[i] (16-byte aligned) is written at this one row pitch, >= (widest image) * pxsz.  The
+ *                 kernels reconstruct straight into the caller's buffers; bytes of a row past w_i * pxsz and rows from h_i on
+ *                 are not written.
+ *   out_bpr == 0  tight rasters: d_outs[i] receives h_i rows of w_i * pxsz bytes, back to back (what xpng_load returns).  The
+ *                 images are reconstructed into a staging raster at the pitch of the widest image and copied out with a pitch per
+ *                 image.  STAGING SIZE: the sum over the images of h_i * P bytes, P = (widest w) * pxsz rounded up to 16, each
+ *                 image's share rounded up to 256; allocated by the first tight call, never shrunk, counted by
+ *                 xpnghip_ctx_workspace_bytes.
+ * nimg must equal the context's.  Every argument is checked before anything reaches the device: a rejected call writes nothing.
+ * xpnghip_ctx_decode_status reports on the launch: a rejected tile leaves its own pixels undefined, every other tile of every
+ * image is decoded. */
+int xpnghip_decode_mixed_device_batch(xpnghip_ctx *ctx, int mode, const void *const *d_blobs, const uint64_t *blobs_len,
+                                      uint32_t nimg, const uint64_t *tile_off, void *const *d_outs, uint64_t out_bpr, void *stream);
+/* Host buffers, one device (T and XPNG_GPUS do not apply): bodies[i] / lens[i] = file i's body after the 8-byte header,
+ * dims = nimg pairs {w, h}, outs[i] = caller-allocated w_i * h_i * pxsz bytes, filled completely.  The sizes are walked on the
+ * host; a truncated body or a rejected tile fails the whole call.  The images are decoded in the padded form and copied back row
+ * by row, so the call needs device memory for the bodies, for sum of h_i rows at the widest image's pitch, and for the context
+ * (about 8 bytes per pixel of the batch): size the batch accordingly (xpng_load_batch keeps a call under 2 GiB of padded rasters). */
+int xpnghip_decode_mixed(int mode, int pxsz, uint32_t nimg, const uint8_t *const *bodies, const uint64_t *lens,
+                         const uint64_t *dims, uint8_t *const *outs);
+
 /* Stage-only run for BASELINE config 2: predictor chooser + per-pixel transform (libxpng.c:92-140 and
  * the arithmetic of 497-519) over tiles [t0, t1); symbol planes stay in the context's workspace. */
 int xpnghip_m1_transform_device(xpnghip_ctx *ctx, const void *d_raster, uint64_t t0, uint64_t t1, void *stream);

@@ -10,7 +10,9 @@ comments dropped) and the resources the code object's metadata records for it.
 
 In a comparison the kernels only one side has are listed, and every other kernel must be identical.  One textual difference is
 tolerated and reported as such: the 32-bit literal of the s_add_u32 that directly follows an s_getpc_b64 - a PC-relative address
-of a constant table, which moves when code in front of it appears or disappears.
+of a constant table, which moves when code in front of it appears or disappears.  So is one difference of layout: the run of
+s_nop (and zero bytes) behind a kernel's last instruction, alignment padding that the disassembler attributes to the kernel in front of it (the
+last kernel of the code object carries the padding to the end of the section, and stops carrying it when a new kernel follows).
 
 Needs the ROCm LLVM tools (llvm-objcopy, clang-offload-bundler, llvm-objdump, llvm-readelf) under ROCM_PATH/llvm/bin, default /opt/rocm;
 names are demangled when llvm-cxxfilt or c++filt is there.  Not part of the tests or the benchmark.
@@ -71,6 +73,14 @@ def kernels_of(lib):
     return out
 
 
+def unpadded(lines):
+    """without the s_nop alignment padding behind the last instruction"""
+    n = len(lines)
+    while n and lines[n - 1] in ("s_nop 0", "..."):  # ("...": the disassembler's mark for a run of zero bytes, the section's very end)
+        n -= 1
+    return lines[:n]
+
+
 def sha(lines):
     return hashlib.sha256("\n".join(lines).encode()).hexdigest()[:16]
 
@@ -104,6 +114,8 @@ def main(argv):
             continue
         if a[d][1] == b[d][1]:
             print("identical up to a PC-relative literal behind s_getpc_b64:", d)
+        elif unpadded(a[d][1]) == unpadded(b[d][1]):
+            print(f"identical up to the s_nop padding behind its end ({len(a[d][0]) - len(unpadded(a[d][0]))} -> {len(b[d][0]) - len(unpadded(b[d][0]))} padding lines):", d)
         else:
             print("CODE DIFFERS:", d)
             bad += 1

@@ -28,11 +28,14 @@ HIP_SYMBOLS = [
     "xpnghip_normalize_device", "xpnghip_encode_tiles_T", "xpnghip_decode_tiles_T", "xpnghip_image_encode_T", "xpnghip_devices_for",
     "xpnghip_shard_ranges", "xpnghip_shutdown", "xpnghip_probes_built",
     "xpnghip_region_tiles", "xpnghip_decode_region", "xpnghip_decode_region_device_batch",
+    "xpnghip_ctx_create_mixed", "xpnghip_ctx_mixed_first_tile", "xpnghip_decode_mixed_device_batch", "xpnghip_decode_mixed",
 ]
 HOST_SYMBOLS = ["xpng_store", "xpng_load", "xpng_from_jpg", "xpng_store_T", "xpng_load_T", "xpng_from_jpg_T",
                 "store_7", "load_7"]
 # libxpng.so's own additions beyond the reference's surface (include/xpng_region.h)
 HOST_EXT_SYMBOLS = ["xpng_load_region"]
+# ... and include/xpng_batch.h
+HOST_BATCH_SYMBOLS = ["xpng_load_batch"]
 
 
 class XpngError(RuntimeError):
@@ -137,6 +140,15 @@ def _bind_hip(path):
         L.xpnghip_decode_region_device_batch.restype = C.c_int
         L.xpnghip_decode_region_device_batch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64), C.c_uint32, C.POINTER(u64),
                                                          C.POINTER(u64), C.POINTER(vp), u64, vp]
+        L.xpnghip_ctx_create_mixed.restype = C.c_int
+        L.xpnghip_ctx_create_mixed.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(u64), C.c_uint32, C.c_int]
+        L.xpnghip_ctx_mixed_first_tile.restype = u64
+        L.xpnghip_ctx_mixed_first_tile.argtypes = [vp, C.c_uint32]
+        L.xpnghip_decode_mixed_device_batch.restype = C.c_int
+        L.xpnghip_decode_mixed_device_batch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64), C.c_uint32, C.POINTER(u64),
+                                                        C.POINTER(vp), u64, vp]
+        L.xpnghip_decode_mixed.restype = C.c_int
+        L.xpnghip_decode_mixed.argtypes = [C.c_int, C.c_int, C.c_uint32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(vp)]
     return L
 
 
@@ -188,6 +200,8 @@ def host_lib():
         L.xpng_load_region.restype = C.c_bool
         L.xpng_load_region.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(XpngT)]
         L.load_7.argtypes = [C.c_char_p, C.POINTER(XpngT)]
+        L.xpng_load_batch.restype = C.c_bool
+        L.xpng_load_batch.argtypes = [C.POINTER(C.c_char_p), C.c_uint64, C.POINTER(XpngT)]
         _host = L
     return _host
 
@@ -351,6 +365,38 @@ def load_region(path: str, x: int, y: int, w: int, h: int) -> np.ndarray:
     return out
 
 
+def decode_mixed(mode: int, bodies, dims, pxsz: int, lib=None) -> list:
+    """Tile bodies (each file after its 8-byte header) of images of different sizes, dims[i] = (w, h), one tile mode and pixel
+    size -> list of (h, w, pxsz) uint8 rasters (xpnghip_decode_mixed: one device call for all of them)."""
+    k = len(bodies)
+    assert len(dims) == k
+    bufs = [np.frombuffer(b, dtype=np.uint8) for b in bodies]
+    outs = [np.zeros((max(int(h), 0), max(int(w), 0), pxsz), dtype=np.uint8) for (w, h) in dims]
+    ins = (C.c_void_p * k)(*[b.ctypes.data for b in bufs])
+    ops = (C.c_void_p * k)(*[o.ctypes.data for o in outs])
+    lens = (C.c_uint64 * k)(*[len(b) for b in bodies])
+    flat = (C.c_uint64 * (2 * k))(*[int(v) for d in dims for v in d])
+    lib = lib or hip_lib()
+    if lib.xpnghip_decode_mixed(mode, pxsz, k, ins, lens, flat, ops):
+        raise XpngError("xpnghip_decode_mixed: " + lib.xpnghip_last_error().decode(errors="replace"))
+    return outs
+
+
+def load_batch(paths) -> list:
+    """xpng_load_batch (include/xpng_batch.h): the (h, w, 3|4) rasters of a list of .xpng files of any sizes; element i equals
+    load(paths[i]).  Files of one (level, bytes per pixel) are decoded by one mixed-size device call."""
+    k = len(paths)
+    arr = (C.c_char_p * k)(*[os.fsencode(p) for p in paths])
+    pms = (XpngT * k)()
+    if k == 0 or host_lib().xpng_load_batch(arr, k, pms):
+        raise XpngError("xpng_load_batch failed")
+    out = []
+    for pm in pms:
+        out.append(np.ctypeslib.as_array(pm.p, shape=(pm.h, pm.w, 3 + int(pm.A))).copy())
+        _libc.free(pm.p)
+    return out
+
+
 def normalize_device(d_rgba: int, npx: int, d_out: int, stream=0):
     """normalize_RGBA (libxpng.c:688-721) on a device-resident RGBA raster -> (bytes per pixel, rewritten into d_out?)."""
     pxsz, rew = C.c_int(0), C.c_int(0)
@@ -481,6 +527,59 @@ class Context:
         if n < 0:
             raise XpngError(f"debug_fetch({what}, {tile}) failed")
         return buf[:n].copy()
+
+
+class MixedContext:
+    """A mixed-size decode context (xpnghip_ctx_create_mixed): images of different sizes, dims[i] = (w, h), one pixel size, decoded
+    by ONE device call.  Decode only.  Device pointers are plain integers; `stream` is a hipStream_t handle or 0."""
+
+    def __init__(self, dims, pxsz: int, device: int = 0):
+        self.dims, self.pxsz, self.device = [(int(w), int(h)) for (w, h) in dims], pxsz, device
+        self.nimg = len(self.dims)
+        self._h = C.c_void_p()
+        flat = (C.c_uint64 * max(2 * self.nimg, 1))(*[v for d in self.dims for v in d])
+        if hip_lib().xpnghip_ctx_create_mixed(C.byref(self._h), device, flat, self.nimg, pxsz):
+            raise XpngError("xpnghip_ctx_create_mixed: " + _err())
+        self.n_tiles = hip_lib().xpnghip_ctx_tile_count(self._h)
+        self.first_tile = [hip_lib().xpnghip_ctx_mixed_first_tile(self._h, i) for i in range(self.nimg + 1)]
+
+    def close(self):
+        if self._h:
+            hip_lib().xpnghip_ctx_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def tile(self, i: int):
+        a = (C.c_uint64 * 4)()
+        if hip_lib().xpnghip_ctx_tile(self._h, i, a):
+            raise IndexError(i)
+        return tuple(a)
+
+    def workspace_bytes(self) -> int:
+        return hip_lib().xpnghip_ctx_workspace_bytes(self._h)
+
+    def decode_status(self, stream=0) -> int:
+        """Synchronise and report whether the last decode accepted every tile header (0) or rejected some (1)."""
+        return hip_lib().xpnghip_ctx_decode_status(self._h, stream)
+
+    def decode_batch(self, mode, d_blobs, lens, d_outs, out_bpr=0, tile_offs=None, stream=0):
+        """One launch over every tile of every image (xpnghip_decode_mixed_device_batch).  out_bpr != 0: every d_outs[i] is
+        written at this row pitch; 0: tight rasters.  tile_offs None: the size walk runs on the device; else per image the blob
+        offsets of its tiles."""
+        k = len(d_blobs)
+        off_arr = None
+        if tile_offs is not None:
+            flat = [o for offs in tile_offs for o in offs]
+            assert len(flat) == self.n_tiles
+            off_arr = (C.c_uint64 * len(flat))(*flat)
+        ins, outs, ln = (C.c_void_p * k)(*d_blobs), (C.c_void_p * len(d_outs))(*d_outs), (C.c_uint64 * len(lens))(*lens)
+        if hip_lib().xpnghip_decode_mixed_device_batch(self._h, mode, ins, ln, k, off_arr, outs, out_bpr, stream):
+            raise XpngError("xpnghip_decode_mixed_device_batch: " + _err())
 
 
 def walk_tile_offsets(blobs: bytes, n_tiles: int):

@@ -181,6 +181,8 @@ struct TileDesc {
 // A region decode (xpnghip_decode_region_device_batch) selects a different set of tiles in every image: an explicit work list
 //   list != nullptr  : work item j decodes virtual tile list[j] (image * N + tile), for j < cnt; t0 and order are not used, and
 //                      the per-image arrays are full tables (nimg * N entries): imglin() is the virtual tile itself.
+// A mixed-size batch (xpnghip_decode_mixed_device_batch; mixed.hpp) is a list launch too: its tile table is the concatenation of the
+// images' tables, N = M entries with nimg = 1, and list[] holds all M of them - the "virtual tile" is then simply the table index.
 // The test is one scalar branch per work item (every kernel resolves its tile once, never per pixel).
 struct TileSel { uint32_t t0, cnt, N, nimg; const uint32_t *order; const uint32_t *list = nullptr; };
 __host__ __device__ inline uint32_t vtile(const TileSel &s, uint32_t j) {

@@ -12,6 +12,7 @@
 #include "../../../include/xpng.h"
 #include "../../../include/xpng_hip.h"
 #include "../../../include/xpng_region.h"
+#include "../../../include/xpng_batch.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -248,6 +249,68 @@ _Bool xpng_load_region(const char *fn, uint64_t x, uint64_t y, uint64_t w, uint6
     if (rc) { free(p); return 1; }
     pm->p = p; pm->w = w; pm->h = h; pm->A = A; pm->s = w * h * (uint64_t)pxsz;
     return 0;
+}
+
+/* include/xpng_batch.h: n files at once.  The header and the two host-only forms are those of xpng_load_T; the files that
+ * reach the tile codec are grouped by (tile mode, bytes per pixel) and each group is decoded by mixed-size device calls
+ * (xpnghip_decode_mixed).  A call takes the group's files in order until it holds 4096 images or its padded rasters - every row
+ * of every image at the widest image's pitch, what the device call allocates beside ~8 B per pixel of workspace - would pass
+ * XPNG_BATCH_BYTES; a file that alone passes the budget is a call of its own, as it is for xpng_load.  So a large collection costs
+ * bounded device memory, and one very wide file does not widen the rows of more than one call.  No MPx/s line is printed. */
+#define XPNG_BATCH_MAX 4096u
+#define XPNG_BATCH_BYTES (2ull << 30)
+_Bool xpng_load_batch(const char *const *paths, uint64_t n, xpng_t *out) {
+    if (!paths || !out || !n) return 1;
+    for (uint64_t i = 0; i < n; i++) memset(&out[i], 0, sizeof(out[i]));
+    uint8_t **buf = calloc(n, sizeof(*buf));
+    uint64_t *flen = calloc(n, sizeof(*flen));
+    uint8_t *group = calloc(n, 1); /* 0 = answered on the host, else 1 + 2 * (mode - 1) + A */
+    const uint8_t **bodies = malloc(XPNG_BATCH_MAX * sizeof(*bodies));
+    uint8_t **outs = malloc(XPNG_BATCH_MAX * sizeof(*outs));
+    uint64_t *lens = malloc(XPNG_BATCH_MAX * sizeof(*lens)), *dims = malloc(2 * XPNG_BATCH_MAX * sizeof(*dims));
+    _Bool rc = !buf || !flen || !group || !bodies || !outs || !lens || !dims;
+    for (uint64_t i = 0; !rc && i < n; i++) {
+        xpng_t *pm = &out[i];
+        if (!paths[i] || !(buf[i] = read_file(paths[i], &flen[i]))) { rc = 1; break; }
+        const uint32_t h0 = get_u32(buf[i]), h1 = get_u32(buf[i] + 4);
+        const uint64_t mode = h0 >> 24;
+        pm->w = (h0 & 0xFFFFFF) + 1; pm->h = (h1 & 0xFFFFFF) + 1; pm->A = (h1 >> 24) & 1;
+        if (!(mode == 1 || mode == 2 || mode == 7)) { rc = 1; break; }
+        const int pxsz = 3 + pm->A;
+        pm->s = pm->w * pm->h * (uint64_t)pxsz;
+        if (!(pm->p = malloc(pm->s))) { rc = 1; break; }
+        if (mode == 7) {
+            if (flen[i] < 8 + pm->s) { rc = 1; break; }
+            memcpy(pm->p, buf[i] + 8, pm->s);
+        } else if (flen[i] == 11u + pm->A && (buf[i][7] & 2)) { /* libxpng.c:976-980 */
+            for (uint64_t k = 0; k < pm->w * pm->h; k++) memcpy(pm->p + k * (uint64_t)pxsz, buf[i] + 8, (size_t)pxsz);
+        } else group[i] = (uint8_t)(1 + 2 * (mode - 1) + pm->A);
+    }
+    for (uint8_t g = 1; !rc && g <= 4; g++) {
+        const int mode = 1 + (g - 1) / 2, pxsz = 3 + (g - 1) % 2;
+        uint64_t i = 0;
+        while (!rc && i < n) {
+            uint32_t k = 0;
+            uint64_t rows = 0, widest = 0;
+            for (; i < n && k < XPNG_BATCH_MAX; i++) {
+                if (group[i] != g) continue;
+                const uint64_t wd = out[i].w > widest ? out[i].w : widest;
+                if (k && (rows + out[i].h) * wd * (uint64_t)pxsz > XPNG_BATCH_BYTES) break; /* the next call starts with this file */
+                rows += out[i].h; widest = wd;
+                bodies[k] = buf[i] + 8; lens[k] = flen[i] - 8; outs[k] = out[i].p;
+                dims[2 * k] = out[i].w; dims[2 * k + 1] = out[i].h;
+                k++;
+            }
+            if (k && xpnghip_decode_mixed(mode, pxsz, k, bodies, lens, dims, outs)) {
+                fprintf(stderr, "xpng: GPU batch decode failed: %s\n", xpnghip_last_error());
+                rc = 1;
+            }
+        }
+    }
+    for (uint64_t i = 0; buf && i < n; i++) free(buf[i]);
+    if (rc) for (uint64_t i = 0; i < n; i++) { free(out[i].p); memset(&out[i], 0, sizeof(out[i])); }
+    free(buf); free(flen); free(group); free(bodies); free(outs); free(lens); free(dims);
+    return rc;
 }
 
 /* libxpng.c:1004-1014: the reference ships this entry point as a stub */

@@ -1543,6 +1543,24 @@ __global__ void k_dec_offsets(const uint8_t *const *__restrict__ blobs, const ui
     }
 }
 
+// The same walk for a mixed-size batch (mixed.hpp), whose images have different tile counts: image b owns entries
+// [first[b], first[b + 1]) of the M-entry concatenated table, and off[] is indexed by table entry.  The same truncation rule: a size
+// that is zero or leaves the buffer parks every later tile of THAT image at the end of its buffer, where the parse rejects it.
+__global__ void k_dec_offsets_mixed(const uint8_t *const *__restrict__ blobs, const uint64_t *__restrict__ blob_len,
+                                    const uint32_t *__restrict__ first, uint32_t nimg, uint64_t *__restrict__ off) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= nimg) return;
+    const uint8_t *p = blobs[b];
+    const uint64_t L = blob_len[b];
+    const uint32_t i1 = first[b + 1];
+    uint64_t o = 0;
+    for (uint32_t i = first[b]; i < i1; i++) {
+        off[i] = o;
+        const uint32_t sz = o + 4 <= L ? ld32u(p + o) & 0xFFFFFFu : 0u;
+        o = sz ? (o + sz <= L ? o + sz : L) : L;
+    }
+}
+
 // One decode job: what a launch sequence decodes, from where, to where.  Filled by dec_launch (xpng_hip.hip), read by
 // decode_m1_launch and decode_m2_launch.
 struct DecodeJob {
@@ -1559,6 +1577,11 @@ struct DecodeJob {
     const uint64_t *tile_off;
     hipStream_t s;
     uint64_t *stamps;  // phase stamps of the narrow chains (probe builds, XPNG_STAMPS) or nullptr
+    // a mixed-size batch (mixed.hpp): B = 1 and n_tiles = M, the concatenated table; `list` holds all M entries.
+    // img_first: device array of img_n + 1 table indices, image i owns [img_first[i], img_first[i + 1]) - the size walk follows it;
+    // tile_off then holds M offsets.  bpr: row pitch of the rasters in bytes when it is not W * pxsz (0: it is)
+    const uint32_t *img_first; uint32_t img_n; uint64_t bpr;
+    uint64_t pitch() const { return bpr ? bpr : W * (uint64_t)pxsz; }
     uint32_t cnt() const { return list ? list_n : t1 - t0; }        // work items per image (list: in all)
     uint32_t total() const { return list ? list_n : B * (t1 - t0); }
     TileSel sel() const { return TileSel{t0, cnt(), (uint32_t)n_tiles, B, list ? nullptr : order, list}; }
@@ -1591,7 +1614,8 @@ inline int decode_ws_prepare(DecodeWs &ws, const DecodeJob &j, std::string &err)
     }
     if (!j.tile_off) {
         if (!j.blobs || !j.blob_len) return bad("device-side size walk needs the blob tables");
-        k_dec_offsets<<<(j.B + 63) / 64, 64, 0, j.s>>>(j.blobs, j.blob_len, total / j.B, j.B, ws.d_off);
+        if (j.img_first) k_dec_offsets_mixed<<<(j.img_n + 63) / 64, 64, 0, j.s>>>(j.blobs, j.blob_len, j.img_first, j.img_n, ws.d_off);
+        else k_dec_offsets<<<(j.B + 63) / 64, 64, 0, j.s>>>(j.blobs, j.blob_len, total / j.B, j.B, ws.d_off);
         ws.last_off.clear();
         return 0;
     }
@@ -1658,7 +1682,7 @@ inline DecodePlan decode_m1_plan(const DecodeJob &j) {
 template <int PXSZ>
 inline void dec_tail(const DecodeWs &ws, const DecodeJob &j, const DecodePlan &p, const TileSel &sel, uint32_t first, uint32_t n,
                      hipStream_t st, const char *skip_resid, const char *skip_recon) {
-    const uint64_t bpr = j.W * (uint64_t)PXSZ;
+    const uint64_t bpr = j.pitch();
     const uint32_t total = j.total();
     if (dbg_skip(skip_resid)) {}
     else if constexpr (PXSZ == 4) {

@@ -510,7 +510,7 @@ inline int decode_m2_launch(DecodeWs &ws, const DecodeJob &j, const M2DecBufs &m
         err = "internal error: a mode-2 decode workspace buffer was never allocated";  // (a null pointer in a kernel is a GPU fault = abort())
         return 1;
     }
-    const uint64_t bpr = j.W * 3, items = (uint64_t)total * M2_STREAMS;
+    const uint64_t bpr = j.pitch(), items = (uint64_t)total * M2_STREAMS;
     const bool wide = wide_form(items);
     if (hipMemsetAsync(m.blk2, 0, (uint64_t)j.B * j.n_tiles * M2_SLOTS * sizeof(M2Blk), s) != hipSuccess) { err = "memset failed"; return 1; }
     k_m2_dec_parse<<<(total + 63) / 64, 64, 0, s>>>(j.blobs, ws.d_off, j.blob_len, cnt, total, j.tiles, sel, m.info2, m.blk2, m.tabs2, m.stream_n2, j.status);

@@ -598,6 +598,67 @@ extern "C" int xpnghip_decode_region(int mode, const uint8_t *blobs, uint64_t bl
     XPNG_GUARDED(decode_region_impl(mode, blobs, blobs_len, w, h, pxsz, rect, out))
 }
 
+// Mixed-size batch from host buffers on one device: the sizes of every body are walked on the host (libxpng.c:982), the bodies
+// go up in one buffer, the images are decoded in the PADDED form (no staging raster, no copy kernel) into one buffer at the widest
+// image's pitch, and hipMemcpy2DAsync brings every image back tight.  Device memory of a call: the bodies, sum of h_i rows at that
+// pitch, and the context's workspace (8 B per pixel of the batch + the per-tile tables).  The context is created for the call and
+// destroyed after it (its geometry is the whole list of sizes: a pool keyed on that would rarely hit).
+static int decode_mixed_host_impl(int mode, int pxsz, uint32_t nimg, const uint8_t *const *bodies, const uint64_t *lens, const uint64_t *dims,
+                                  uint8_t *const *outs) {
+    if (!bodies || !lens || !dims || !outs) return fail("null argument");
+    if (nimg < 1 || nimg > 4096) return fail("a mixed batch holds 1 .. 4096 images");
+    if (pxsz != 3 && pxsz != 4) return fail("bad raster geometry");
+    if (mode != 1 && mode != 2) return fail("tile mode must be 1 or 2");
+    if (mode == 2 && pxsz != 3) return fail("mode 2 codes RGB only");
+    std::vector<uint64_t> off, boff((size_t)nimg + 1, 0), roff((size_t)nimg + 1, 0);
+    uint64_t bpr = 0;
+    for (uint32_t i = 0; i < nimg; i++) bpr = std::max(bpr, rup(dims[2ull * i] * (uint64_t)pxsz, 16));
+    for (uint32_t i = 0; i < nimg; i++) {
+        const uint64_t w = dims[2ull * i], h = dims[2ull * i + 1];
+        if (!bodies[i] || !outs[i]) return fail("null body or output of image " + std::to_string(i));
+        if (!w || !h || w > (1u << 24) || h > (1u << 24)) return fail("bad raster geometry of image " + std::to_string(i));
+        const uint64_t N = tile_count_for(w, h);
+        if (lens[i] / 4 < N) return fail("truncated file: image " + std::to_string(i) + " is shorter than its tile table");
+        uint64_t o = 0;
+        for (uint64_t t = 0; t < N; t++) {  // serial size walk, libxpng.c:982
+            if (o + 4 > lens[i]) return fail("truncated file: the tile table of image " + std::to_string(i) + " runs past the end");
+            uint32_t h0; memcpy(&h0, bodies[i] + o, 4);
+            off.push_back(o); o += h0 & 0xFFFFFF;
+        }
+        if (o > lens[i]) return fail("truncated file: the last tile of image " + std::to_string(i) + " runs past the end");
+        boff[i + 1] = boff[i] + rup(lens[i] + 64, 256);
+        roff[i + 1] = roff[i] + rup(h * bpr, 256);
+    }
+    if (usable_devices() < 1) return fail("no usable HIP device (libxpng_hip has no CPU fallback)");
+    DevGuard guard;
+    HIPCHK(hipSetDevice(base_device()));
+    struct Owned { xpnghip_ctx *c = nullptr; ~Owned() { ctx_quiesce(c); xpnghip_ctx_destroy(c); } } own;
+    if (xpnghip_ctx_create_mixed(&own.c, base_device(), dims, nimg, pxsz)) return 1;
+    xpnghip_ctx *c = own.c;
+    if (off.size() != c->tiles.size()) return fail("internal error: tile count of the mixed table");
+    if (ensure_buf(c->d_raster, c->cap_raster, roff[nimg]) || ensure_buf(c->d_blob_in, c->cap_blob_in, boff[nimg])) return 1;
+    hipStream_t s = ctx_stream(c);
+    std::vector<const void *> bp(nimg);
+    std::vector<void *> op(nimg);
+    for (uint32_t i = 0; i < nimg; i++) {
+        HIPCHK(hipMemcpyAsync(c->d_blob_in + boff[i], bodies[i], lens[i], hipMemcpyHostToDevice, s));
+        bp[i] = c->d_blob_in + boff[i]; op[i] = c->d_raster + roff[i];
+    }
+    if (xpnghip_decode_mixed_device_batch(c, mode, bp.data(), lens, nimg, off.data(), op.data(), bpr, s)) return 1;
+    const int st = xpnghip_ctx_decode_status(c, s);
+    if (st == 1) return fail("corrupt file: a tile header is inconsistent with the tile table");
+    if (st != 0) return fail("decode failed");
+    for (uint32_t i = 0; i < nimg; i++)
+        HIPCHK(hipMemcpy2DAsync(outs[i], dims[2ull * i] * (uint64_t)pxsz, c->d_raster + roff[i], bpr, dims[2ull * i] * (uint64_t)pxsz, dims[2ull * i + 1],
+                                hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+extern "C" int xpnghip_decode_mixed(int mode, int pxsz, uint32_t nimg, const uint8_t *const *bodies, const uint64_t *lens, const uint64_t *dims,
+                                    uint8_t *const *outs) {
+    XPNG_GUARDED(decode_mixed_host_impl(mode, pxsz, nimg, bodies, lens, dims, outs))
+}
+
 // ---- normalize_RGBA and the single-colour test on the device ---------------------------------------------------
 // 16-byte flag blocks for the OR-reductions, per device: checked out for a call and put back, never freed per call (hipFree
 // synchronises the whole device: a pipelined caller of xpnghip_normalize_device would stall all its streams on every call).

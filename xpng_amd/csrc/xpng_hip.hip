@@ -27,6 +27,7 @@
 #include "rans1_wide_dec.hpp"
 #include "tile_container.hpp"
 #include "region.hpp"
+#include "mixed.hpp"
 
 using namespace xpng;
 
@@ -166,6 +167,18 @@ struct xpnghip_ctx {
     uint64_t cap_region_stage = 0;
     uint8_t *d_region_meta = nullptr;
     std::vector<uint8_t> h_region_meta;  // what d_region_meta holds (skip the upload when unchanged)
+    // mixed-size batch (xpnghip_ctx_create_mixed; mixed.hpp): decode only.  `tiles` is then the concatenation of the
+    // B images' tile tables (M entries, img / pbase / sbase as on the device) and W = H = 0
+    bool mixed = false;
+    std::vector<uint64_t> m_dims;      // B pairs {w, h}
+    std::vector<uint32_t> m_first;     // B + 1 table indices: image i owns tiles [m_first[i], m_first[i + 1])
+    std::vector<uint32_t> m_list;      // all M table indices by decreasing pixel count (the work list of every launch)
+    uint64_t m_max_w = 0, m_max_h = 0;
+    uint32_t *d_m_first = nullptr, *d_m_list = nullptr;  // the two on the device (one allocation: d_m_first)
+    uint8_t *d_m_stage = nullptr;      // tight output form: staging raster at the widest image's pitch, allocated on first use
+    uint64_t cap_m_stage = 0;
+    MixedCopy *d_m_copy = nullptr;     // B copy records
+    std::vector<void *> h_m_copy_dst;  // the destinations d_m_copy holds (skip the upload when unchanged)
 };
 
 // the context's own stream, created when a call first needs it (the `stream == NULL` form of the device-resident entry points,
@@ -186,7 +199,7 @@ extern "C" void xpnghip_ctx_destroy(xpnghip_ctx *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void *ptrs[] = {c->d_tiles, c->d_planes, c->d_scratch, c->d_sums, c->d_nlh, c->d_ctx_n, c->d_k_n, c->d_blk_sz, c->d_tile_sz,
                     c->d_tile_hdr, c->d_off, c->d_totals, c->d_raster, c->d_blobs, c->d_blob_in, c->d_dbg, (void *)c->d_in_ptrs, (void *)c->d_out_ptrs, (void *)c->d_dec_in_ptrs, (void *)c->d_dec_out_ptrs, (void *)c->d_order,
-                    c->d_wprep, c->d_wtab, c->d_wF, c->d_blob_len, c->d_status, c->d_scratch2, c->d_sbase2, c->d_flags2, c->d_stream_n2, c->d_blk2, c->d_mt2, c->d_info2, c->d_tabs2, c->d_w1prep, c->d_w1tab, c->d_w1F, c->d_region_stage, c->d_region_meta};
+                    c->d_wprep, c->d_wtab, c->d_wF, c->d_blob_len, c->d_status, c->d_scratch2, c->d_sbase2, c->d_flags2, c->d_stream_n2, c->d_blk2, c->d_mt2, c->d_info2, c->d_tabs2, c->d_w1prep, c->d_w1tab, c->d_w1F, c->d_region_stage, c->d_region_meta, c->d_m_first, c->d_m_stage, c->d_m_copy};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->enc_side) (void)hipStreamDestroy(c->enc_side);
     if (c->ev_enc_fork) (void)hipEventDestroy(c->ev_enc_fork);
@@ -313,6 +326,7 @@ extern "C" uint64_t xpnghip_ctx_workspace_bytes(const xpnghip_ctx *c) { return c
 
 static int check_range(const xpnghip_ctx *c, uint64_t t0, uint64_t t1) {
     if (!c) return fail("null context");
+    if (c->mixed) return fail("a mixed context decodes whole images only: use xpnghip_decode_mixed_device_batch (no encode, transform or tile-range decode)");
     if (t0 >= t1 || t1 > c->tiles.size()) return fail("bad tile range");
     if (t0 < c->r0 || t1 > c->r1) return fail("tile range outside the range this context was created for");
     return 0;
@@ -344,7 +358,7 @@ static const uint32_t *order_for(const xpnghip_ctx *c, uint32_t t0, uint32_t t1)
 // Level-1 stream scratch (k, block slots, context streams: 7.5 B/px, common.hpp) and the decode's symbol / residual planes
 // (8 B/px: DecodeWs::arena) are ONE buffer: a context's encode intermediates are dead by the time the same context decodes.
 static uint64_t scratch_bytes(const xpnghip_ctx *c) {
-    const uint64_t enc = c->scratch_img * c->B + 8192, dec = 8 * c->plane_stride + (2u << 20);
+    const uint64_t enc = c->mixed ? 0 : c->scratch_img * c->B + 8192, dec = 8 * c->plane_stride + (2u << 20);
     return enc > dec ? enc : dec;
 }
 static int ensure_scratch(xpnghip_ctx *c) {
@@ -497,13 +511,14 @@ static int launch_encode_m1(xpnghip_ctx *c, uint32_t nimg, uint32_t t0, uint32_t
 
 static int ensure_m2(xpnghip_ctx *c) {
     if (c->d_scratch2) return 0;
-    const uint64_t N = c->tiles.size(), VN = N * c->B;
+    const uint64_t N = c->tiles.size(), VN = c->mixed ? N : N * c->B;  // (a mixed context's table already holds every image)
     std::vector<uint64_t> sb(VN);
     uint64_t o = 0;
     for (uint64_t v = 0; v < VN; v++) { sb[v] = o; if (v % N >= c->r0 && v % N < c->r1) o += m2_tile_scratch(c->tiles[v % N].n); }
+    // (d_flags2 and d_mt2 are the encode's: a mixed context never encodes)
     if (hipMalloc((void **)&c->d_scratch2, o + 8192) != hipSuccess || hipMalloc((void **)&c->d_sbase2, VN * 8) != hipSuccess ||
-        hipMalloc((void **)&c->d_flags2, VN * 4) != hipSuccess || hipMalloc((void **)&c->d_stream_n2, VN * M2_SLOTS * 4) != hipSuccess ||
-        hipMalloc((void **)&c->d_blk2, VN * M2_SLOTS * sizeof(M2Blk)) != hipSuccess || hipMalloc((void **)&c->d_mt2, VN * sizeof(M2Tile)) != hipSuccess ||
+        (!c->mixed && hipMalloc((void **)&c->d_flags2, VN * 4) != hipSuccess) || hipMalloc((void **)&c->d_stream_n2, VN * M2_SLOTS * 4) != hipSuccess ||
+        hipMalloc((void **)&c->d_blk2, VN * M2_SLOTS * sizeof(M2Blk)) != hipSuccess || (!c->mixed && hipMalloc((void **)&c->d_mt2, VN * sizeof(M2Tile)) != hipSuccess) ||
         hipMalloc((void **)&c->d_info2, VN * sizeof(M2DecTile)) != hipSuccess || hipMalloc((void **)&c->d_tabs2, VN * M2_SLOTS * 512) != hipSuccess)
         return fail("hipMalloc failed (mode-2 workspace)");
     c->ws_bytes += o + 8192;
@@ -609,10 +624,12 @@ static int dec_prepare(xpnghip_ctx *c, int mode, const void *const *d_blobs, con
 // image, or - a region decode - `list`: virtual tiles (image * N + tile), resident on the device as d_list, decoded into rasters W
 // pixels wide.
 static int dec_launch(xpnghip_ctx *c, int mode, uint32_t nimg, uint64_t W, const uint64_t *tile_off, hipStream_t s, uint32_t t0, uint32_t t1,
-                      const std::vector<uint32_t> *list = nullptr, const uint32_t *d_list = nullptr) {
+                      const std::vector<uint32_t> *list = nullptr, const uint32_t *d_list = nullptr, uint64_t bpr = 0) {
     const uint64_t N = c->tiles.size();
     DecodeJob j{};
-    j.B = nimg; j.n_tiles = N; j.plane = c->plane_stride; j.W = W; j.pxsz = c->pxsz;
+    // (a mixed context: ONE table of N = M entries that already spans the images; the size walk follows img_first)
+    if (c->mixed) { j.img_first = c->d_m_first; j.img_n = nimg; j.bpr = bpr; }
+    j.B = c->mixed ? 1 : nimg; j.n_tiles = N; j.plane = c->plane_stride; j.W = W; j.pxsz = c->pxsz;
     j.min_w = ~0u;
     auto scan = [&](const TileDesc &t) { j.max_w = std::max(j.max_w, t.w); j.max_h = std::max(j.max_h, t.h); j.min_w = std::min(j.min_w, t.w); };
     if (list) for (uint32_t v : *list) scan(c->tiles[v % N]);
@@ -661,6 +678,7 @@ static int region_batch_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
                              const uint64_t *tile_off, const uint64_t *rects, void *const *d_outs, uint64_t out_bpr, void *stream) {
     // every argument is checked before anything reaches the device: a rejected call writes nothing
     if (!c) return fail("null context");
+    if (c->mixed) return fail("region decode: a mixed context decodes whole images only (no crops)");
     if (mode != 1 && mode != 2) return fail("tile mode must be 1 or 2");
     if (mode == 2 && c->pxsz != 3) return fail("mode 2 codes RGB only");
     if (nimg < 1 || nimg > c->B) return fail("batch size exceeds the context's batch");
@@ -754,6 +772,141 @@ extern "C" int xpnghip_decode_region_device_batch(xpnghip_ctx *c, int mode, cons
     catch (...) { return fail("unexpected C++ exception"); }
 }
 
+// ---- mixed-size batch decode (mixed.hpp) ---------------------------------------------------------
+static uint64_t tile_count_for(uint64_t W, uint64_t H);  // wrappers.hpp
+
+static int ctx_create_mixed_impl(xpnghip_ctx **out, int device, const uint64_t *dims, uint32_t nimg, int pxsz) {
+    if (!out || !dims || (pxsz != 3 && pxsz != 4)) return fail("bad arguments");
+    if (nimg < 1 || nimg > 4096) return fail("a mixed context holds 1 .. 4096 images");
+    uint64_t M = 0;
+    for (uint32_t i = 0; i < nimg; i++) {
+        const uint64_t w = dims[2ull * i], h = dims[2ull * i + 1];
+        if (!w || !h || w > (1u << 24) || h > (1u << 24))
+            return fail("bad size of image " + std::to_string(i) + ": " + std::to_string(w) + " x " + std::to_string(h) + " (each side must be 1 .. 16777216)");
+        M += tile_count_for(w, h);
+        if (M > 0xFFFFFFFFull) return fail("too many tiles: the concatenated tile table of a mixed context must fit in 32 bits");
+    }
+    if (xpnghip_device_count() <= device || device < 0) return fail("no such HIP device (libxpng_hip has no CPU fallback)");
+    HIPCHK(hipSetDevice(device));
+    xpnghip_ctx *c = new xpnghip_ctx();
+    c->device = device; c->pxsz = pxsz; c->spt = pxsz == 4 ? 10 : 9; c->B = nimg; c->mixed = true;
+    c->m_dims.assign(dims, dims + 2ull * nimg);
+    c->m_first.resize((size_t)nimg + 1);
+    c->tiles.reserve(M);
+    std::vector<TileDesc> one;
+    uint64_t pbase = 0, sbase = 0;
+    for (uint32_t i = 0; i < nimg; i++) {
+        build_tiles(dims[2ull * i], dims[2ull * i + 1], one);
+        c->m_first[i] = (uint32_t)c->tiles.size();
+        const TileDesc &last = one.back();
+        const uint64_t plane_i = last.pbase + rup(last.n + 192, 256), scratch_i = last.sbase + tile_scratch_bytes(last.n);
+        for (TileDesc t : one) { t.img = i; t.pbase += pbase; t.sbase += sbase; c->tiles.push_back(t); }
+        pbase += plane_i; sbase += scratch_i;  // (continue across images, as b * plane_img and b * scratch_img do in a uniform batch)
+        c->m_max_w = std::max(c->m_max_w, dims[2ull * i]); c->m_max_h = std::max(c->m_max_h, dims[2ull * i + 1]);
+    }
+    c->m_first[nimg] = (uint32_t)M;
+    c->r0 = 0; c->r1 = M;
+    c->plane_img = c->plane_stride = pbase;  // the symbol / residual planes of the WHOLE batch (the decode arena is 8 of them)
+    c->scratch_img = sbase;
+    c->m_list.resize(M);
+    for (uint64_t i = 0; i < M; i++) c->m_list[i] = (uint32_t)i;
+    // biggest tiles first (equal sizes keep table order): neighbouring work items of the wide kernels get chains of equal length
+    std::stable_sort(c->m_list.begin(), c->m_list.end(), [&](uint32_t a, uint32_t b) { return c->tiles[a].n > c->tiles[b].n; });
+    const uint64_t first_bytes = rup(((uint64_t)nimg + 1) * 4, 16);
+    std::vector<uint8_t> meta(first_bytes + M * 4, 0);
+    memcpy(meta.data(), c->m_first.data(), ((size_t)nimg + 1) * 4);
+    memcpy(meta.data() + first_bytes, c->m_list.data(), M * 4);
+    auto alloc = [&](void **p, uint64_t bytes) {
+        if (hipMalloc(p, bytes) != hipSuccess) return false;
+        c->ws_bytes += bytes;
+        return true;
+    };
+    // what a decode needs, sized from M and nimg; planes / arena, decode tables and level-2 tables follow on first use (ensure_arena,
+    // decode_ws_prepare, ensure_m2), sized from M and the summed plane lengths too.  No encode workspace at all.
+    if (!alloc((void **)&c->d_tiles, M * sizeof(TileDesc)) || !alloc((void **)&c->d_blob_len, (uint64_t)nimg * 8) || !alloc((void **)&c->d_status, 64) ||
+        !alloc((void **)&c->d_dec_in_ptrs, (uint64_t)nimg * 8) || !alloc((void **)&c->d_dec_out_ptrs, (uint64_t)nimg * 8) ||
+        !alloc((void **)&c->d_m_first, meta.size()) || hipHostMalloc((void **)&c->h_total, (uint64_t)nimg * 8 + 64) != hipSuccess ||
+        hipMemcpy(c->d_tiles, c->tiles.data(), M * sizeof(TileDesc), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(c->d_m_first, meta.data(), meta.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        xpnghip_ctx_destroy(c);
+        return fail("mixed context setup failed (hipMalloc / upload)");
+    }
+    memset(c->h_total, 0, (size_t)nimg * 8 + 64);
+    c->d_m_list = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(c->d_m_first) + first_bytes);
+    *out = c;
+    return 0;
+}
+extern "C" int xpnghip_ctx_create_mixed(xpnghip_ctx **out, int device, const uint64_t *dims, uint32_t nimg, int pxsz) {
+    try { return ctx_create_mixed_impl(out, device, dims, nimg, pxsz); }
+    catch (const std::bad_alloc &) { return fail("out of host memory"); }
+    catch (...) { return fail("unexpected C++ exception"); }
+}
+extern "C" uint64_t xpnghip_ctx_mixed_first_tile(const xpnghip_ctx *c, uint32_t image) {
+    return c && c->mixed && image < c->m_first.size() ? c->m_first[image] : ~0ull;
+}
+
+static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
+                                   const uint64_t *tile_off, void *const *d_outs, uint64_t out_bpr, void *stream) {
+    // every argument is checked before anything reaches the device: a rejected call writes nothing
+    if (!c) return fail("null context");
+    if (!c->mixed) return fail("not a mixed context (xpnghip_ctx_create_mixed)");
+    if (mode != 1 && mode != 2) return fail("tile mode must be 1 or 2");
+    if (mode == 2 && c->pxsz != 3) return fail("mode 2 codes RGB only");
+    if (nimg != c->B) return fail("nimg is " + std::to_string(nimg) + ", the mixed context holds " + std::to_string(c->B) + " images");
+    if (!d_blobs || !blobs_len || !d_outs) return fail("null argument");
+    const uint64_t px = (uint64_t)c->pxsz, widest = c->m_max_w * px;
+    if (out_bpr && out_bpr < widest)
+        return fail("out_bpr " + std::to_string(out_bpr) + " is smaller than the widest row of the batch (" + std::to_string(widest) + " bytes)");
+    for (uint32_t i = 0; i < nimg; i++) {
+        if (!d_blobs[i] || !d_outs[i]) return fail("null blob or output buffer of image " + std::to_string(i));
+        if (((uintptr_t)d_blobs[i] & 3) || (out_bpr && ((uintptr_t)d_outs[i] & 15))) return fail("device buffers must be 16-byte aligned");
+    }
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(c);
+    const uint64_t bpr = out_bpr ? out_bpr : rup(widest, 16);  // (staging rows start 16-byte aligned: the recon kernels take any pitch)
+    std::vector<void *> base(d_outs, d_outs + nimg);
+    if (!out_bpr) {
+        // tight rasters: reconstruct into a staging raster at the widest image's pitch, rounded up to 16 bytes (image i: h_i rows,
+        // its slot 256-byte aligned), then k_mixed_copy moves every image out at its own pitch
+        std::vector<uint64_t> slot((size_t)nimg + 1, 0);
+        for (uint32_t i = 0; i < nimg; i++) slot[i + 1] = slot[i] + rup(c->m_dims[2ull * i + 1] * bpr, 256);
+        if (!c->d_m_stage) {
+            HIPCHK(hipMalloc((void **)&c->d_m_stage, slot[nimg] + 256));
+            c->cap_m_stage = slot[nimg] + 256; c->ws_bytes += c->cap_m_stage;
+        }
+        if (!c->d_m_copy) {
+            HIPCHK(hipMalloc((void **)&c->d_m_copy, (uint64_t)nimg * sizeof(MixedCopy)));
+            c->ws_bytes += (uint64_t)nimg * sizeof(MixedCopy);
+        }
+        if (c->h_m_copy_dst != base) {  // (pageable host memory: the copy is staged synchronously anyway)
+            std::vector<MixedCopy> mc(nimg);
+            for (uint32_t i = 0; i < nimg; i++)
+                mc[i] = MixedCopy{slot[i], (uint8_t *)d_outs[i], (uint32_t)(c->m_dims[2ull * i] * px), (uint32_t)c->m_dims[2ull * i + 1]};
+            c->h_m_copy_dst.clear();
+            HIPCHK(hipMemcpyAsync(c->d_m_copy, mc.data(), (uint64_t)nimg * sizeof(MixedCopy), hipMemcpyHostToDevice, s));
+            HIPCHK(hipStreamSynchronize(s));
+            c->h_m_copy_dst = base;
+        }
+        for (uint32_t i = 0; i < nimg; i++) base[i] = c->d_m_stage + slot[i];
+    }
+    if (dec_prepare(c, mode, d_blobs, blobs_len, nimg, base.data(), s)) return 1;
+    XPNG_REQUIRE(c->d_m_first, c->d_m_list);
+    const int rc = dec_launch(c, mode, nimg, c->m_max_w, tile_off, s, 0, (uint32_t)c->tiles.size(), &c->m_list, c->d_m_list, bpr);
+    if (rc) return rc;
+    if (!out_bpr) {
+        XPNG_REQUIRE(c->d_m_stage, c->d_m_copy);
+        k_mixed_copy<<<dim3((uint32_t)((c->m_max_h + MC_ROWS - 1) / MC_ROWS), nimg), 256, 0, s>>>(c->d_m_copy, c->d_m_stage, bpr);
+        HIPCHK(hipGetLastError());
+    }
+    return 0;
+}
+extern "C" int xpnghip_decode_mixed_device_batch(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
+                                                 const uint64_t *tile_off, void *const *d_outs, uint64_t out_bpr, void *stream) {
+    try { return decode_mixed_batch_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, d_outs, out_bpr, stream); }
+    catch (const std::bad_alloc &) { return fail("out of host memory"); }
+    catch (...) { return fail("unexpected C++ exception"); }
+}
+
 // Synchronises `stream` and reports the last decode: 0 = every tile header was consistent, 1 = at least one tile was
 // rejected (its pixels were left untouched), -1 = HIP error.
 extern "C" int xpnghip_ctx_decode_status(xpnghip_ctx *c, void *stream) {
@@ -795,7 +948,7 @@ extern "C" int xpnghip_probes_built(void) { return 0; }
 #endif
 
 extern "C" int64_t xpnghip_debug_fetch(xpnghip_ctx *c, int what, uint64_t tile, void *out, uint64_t cap) {
-    if (!c || tile >= c->tiles.size() || !out) return -1;
+    if (!c || c->mixed || tile >= c->tiles.size() || !out) return -1;  // (a mixed context never encodes: nothing to fetch)
     if (hipSetDevice(c->device) != hipSuccess || (c->stream && hipStreamSynchronize(c->stream) != hipSuccess)) return -1;  // (debug_fetch follows a call that synchronised its stream or used this one)
     const TileDesc &t = c->tiles[tile];
     const uint8_t *src = nullptr;
