@@ -97,6 +97,42 @@ int xpnghip_image_fetch(xpnghip_image *img, uint8_t *dst);
 void xpnghip_image_end(xpnghip_image *img);
 int xpnghip_normalize_device(const void *d_rgba, uint64_t npx, void *d_out, int *pxsz_out, int *rewritten, void *stream);
 
+/* ---- staged batch: the staged image for a list of images of any sizes (what xpng_store_batch calls) ----------
+ *   xpnghip_images_begin          uploads rasters[i] (dims = nimg pairs {w, h}; pxsz_in[i] = 3 or 4; host memory, tight) once, each
+ *                                 16-byte aligned on the device, and applies normalize_RGBA to every RGBA input: one launch takes
+ *                                 the two flags of every image, a second applies the rewrite each image's flags ask for, and the
+ *                                 flags are read back once for the call.  pxsz_out[i] = bytes per pixel of the normalised raster.
+ *                                 The caller's rasters are free again when it returns.  nimg = 1 .. 4096.
+ *   xpnghip_images_single_colour  the whole-image test of libxpng.c:741-753 for all images in one launch: nimg flags.
+ *   xpnghip_images_encode         modes[i] = 0 (skip), 1 or 2 (RGB only).  The images with a non-zero mode are grouped by (mode,
+ *                                 normalised pxsz) - at most three groups - and each group is ONE tight-form call of
+ *                                 xpnghip_encode_varsize_device_batch on a mixed context created for the call.  blobs[i] is
+ *                                 malloc()ed (caller frees) and lens[i] its length; skipped images get NULL / 0.  On failure
+ *                                 everything allocated is freed and every blobs[i] is NULL.  An RGBA image narrower or shorter
+ *                                 than 4 px must be skipped (store it at level 7).
+ *   xpnghip_images_first_pixel    after xpnghip_images_single_colour: the first pixel of normalised raster i (pxsz_out[i] bytes).
+ *                                 It came back with the flags, so the single-colour file of level 2 costs no fetch of a raster.
+ *   xpnghip_images_fetch          normalised raster i -> host, tight (w_i * h_i * pxsz_out[i] bytes).
+ *   xpnghip_images_end            frees the handle (always call it once begin has returned 0; NULL is allowed).
+ * One device (XPNG_DEVICE; T and XPNG_GPUS do not apply).  DEVICE MEMORY of a handle: the rasters, 3 B per pixel of the RGBA inputs
+ * for the repack, and during encode per group the blob bounds (the raw size) and the mixed context's workspace (xpng_hip.h below):
+ * size the list accordingly (xpng_store_batch keeps a call under 4096 images and 2 GiB of padded rasters).  Handles are independent:
+ * any number of threads may each use their own at the same time; one handle is used by one thread at a time. */
+typedef struct xpnghip_images xpnghip_images;
+int xpnghip_images_begin(xpnghip_images **h, uint32_t nimg, const uint8_t *const *rasters, const uint64_t *dims,
+                         const uint8_t *pxsz_in, uint8_t *pxsz_out);
+int xpnghip_images_single_colour(xpnghip_images *h, uint8_t *single);
+int xpnghip_images_encode(xpnghip_images *h, const uint8_t *modes, uint8_t **blobs, uint64_t *lens);
+int xpnghip_images_first_pixel(xpnghip_images *h, uint32_t i, uint8_t *px);
+int xpnghip_images_fetch(xpnghip_images *h, uint32_t i, uint8_t *dst);
+void xpnghip_images_end(xpnghip_images *h);
+/* host-only (needs no device): where xpng_store_batch cuts a list of n images (dims = n pairs {w, h}, pxsz[i] = bytes per pixel as
+ * handed in) into staged batches.  A batch takes images in order until it holds max_images of them or its padded rasters - every
+ * row of every image at the widest image's pitch - would pass max_bytes; an image that alone passes the budget is a batch of its
+ * own.  starts[k] = first image of batch k; returns the number of batches, -1 on bad arguments or when cap is too small. */
+int xpnghip_batch_cuts(uint32_t n, const uint64_t *dims, const uint8_t *pxsz, uint32_t max_images, uint64_t max_bytes,
+                       uint32_t *starts, int cap);
+
 /* ---- device-resident entry points (bench, multi-GPU sharding, pipelines) ---------------------------
  *
  * A context owns the tile table (libxpng.c:51-83) and every intermediate buffer for one raster
@@ -122,7 +158,8 @@ void xpnghip_ctx_destroy(xpnghip_ctx *ctx);
 uint64_t xpnghip_ctx_tile_count(const xpnghip_ctx *ctx);
 /* tile i -> {x, y, w, h} (pixels); returns non-zero if i is out of range */
 int xpnghip_ctx_tile(const xpnghip_ctx *ctx, uint64_t i, uint64_t xywh[4]);
-/* upper bound of the concatenated blobs of tiles [t0, t1) (raw fallback bound: sum(w*h*pxsz + 4)) */
+/* upper bound of the concatenated blobs of tiles [t0, t1) (raw fallback bound: sum(w*h*pxsz + 4)).  On a mixed context t0 and t1
+ * index the concatenated table: image i's blob buffer needs blob_bound(first_tile(i), first_tile(i + 1)). */
 uint64_t xpnghip_ctx_blob_bound(const xpnghip_ctx *ctx, uint64_t t0, uint64_t t1);
 uint64_t xpnghip_ctx_workspace_bytes(const xpnghip_ctx *ctx);
 
@@ -187,14 +224,16 @@ int xpnghip_decode_region_device_batch(xpnghip_ctx *ctx, int mode, const void *c
                                        uint32_t nimg, const uint64_t *tile_off, const uint64_t *rects,
                                        void *const *d_outs, uint64_t out_bpr, void *stream);
 
-/* ---- mixed-size batch decode: images of different sizes in one device call (INTEGRATION.md "Mixed-size batches") ----------
- * A mixed context is DECODE ONLY.  It holds nimg images of one pixel size (pxsz 3 or 4) whose widths and heights differ:
+/* ---- mixed-size batches: images of different sizes in one device call (INTEGRATION.md "Mixed-size batches") ----------
+ * A mixed context decodes (xpnghip_decode_mixed_device_batch) and encodes (xpnghip_encode_varsize_device_batch) its batch as a
+ * whole.  The constructor allocates what a decode needs; the encode workspace is allocated by the first encode call.  It holds nimg images of one pixel size (pxsz 3 or 4) whose widths and heights differ:
  * dims = nimg pairs {w, h}.  Its tile table is the concatenation of the images' tile tables, M = sum of their tile counts entries
  * (M must fit in 32 bits; w, h <= 1 << 24; nimg <= 4096), and every workspace is sized from M and the summed pixel counts.
  * xpnghip_ctx_tile_count returns M and xpnghip_ctx_tile walks the concatenated table; xpnghip_ctx_mixed_first_tile(ctx, i) is the
  * table index of image i's first tile, for i == nimg it is M (so image i has first_tile(i + 1) - first_tile(i) tiles); beyond
- * nimg, or on an ordinary context, it returns UINT64_MAX.  xpnghip_ctx_batch returns nimg.  The encode, transform, tile-range
- * decode and region decode entry points refuse a mixed context with an error text before any device work. */
+ * nimg, or on an ordinary context, it returns UINT64_MAX.  xpnghip_ctx_batch returns nimg.  The entry points of an ordinary context
+ * (xpnghip_encode_device[_batch], xpnghip_m1_transform_device[_batch], the tile-range decode and the region decode) refuse a mixed
+ * context with an error text before any device work. */
 int xpnghip_ctx_create_mixed(xpnghip_ctx **ctx, int device, const uint64_t *dims, uint32_t nimg, int pxsz);
 uint64_t xpnghip_ctx_mixed_first_tile(const xpnghip_ctx *ctx, uint32_t image);
 /* One launch over all M tiles (an explicit work list sorted by decreasing pixel count; unsplit).  One tile mode per
@@ -221,6 +260,32 @@ int xpnghip_decode_mixed_device_batch(xpnghip_ctx *ctx, int mode, const void *co
  * (about 8 bytes per pixel of the batch): size the batch accordingly (xpng_load_batch keeps a call under 2 GiB of padded rasters). */
 int xpnghip_decode_mixed(int mode, int pxsz, uint32_t nimg, const uint8_t *const *bodies, const uint64_t *lens,
                          const uint64_t *dims, uint8_t *const *outs);
+
+/* Encode every image of a mixed context in one launch sequence: the kernels of xpnghip_encode_device_batch, once over all M tiles
+ * (the size-sorted work list where the uniform batch is tile-major; image after image where it is image-major).  One tile mode
+ * per call: 1 (RGB and RGBA) or 2 (RGB only); an RGBA image narrower or shorter than 4 px is refused, as everywhere.  One
+ * TRANSFORM FORM per call, as in a uniform batch: the strip kernels when no tile of the batch is wider than 672 px, the generic
+ * kernel for all tiles otherwise (an image flatter or narrower than 444 px has such tiles); both give the same bytes.
+ * nimg must equal the context's.
+ *   in_bpr != 0  padded batch: d_rasters[i] (16-byte aligned) holds h_i rows at this one row pitch, >= (widest image) * pxsz, and
+ *                has 16 readable bytes behind its last row (h_i * in_bpr + 16 bytes are always enough): the strip kernels fetch
+ *                rows in aligned 16-byte pieces, as for a band (above).  The kernels read the caller's buffers directly; the bytes
+ *                of a row past w_i * pxsz never influence the output.
+ *   in_bpr == 0  tight rasters: d_rasters[i] holds h_i * w_i * pxsz bytes, rows back to back, at any alignment (what xpng_store
+ *                is handed); nothing behind them is read.  A pack kernel copies them into the context's staging raster - the one
+ *                of the tight decode, same size (STAGING SIZE above), allocated by the first tight call of either kind, counted by
+ *                xpnghip_ctx_workspace_bytes - and the kernels read that.
+ * d_blobs[i]: 4-byte aligned (a padded raster: 16-byte; the error text names the buffer and the alignment), capacity xpnghip_ctx_blob_bound(ctx, first_tile(i), first_tile(i + 1)); exactly the returned length
+ * is written, nothing at or past the bound.  blobs_len, if not NULL, receives nimg lengths after one stream sync; with NULL read
+ * xpnghip_ctx_last_blobs_len_at(ctx, i) after synchronising the stream yourself.
+ * WORKSPACE: the first encode call allocates the encode workspace (about 4 or 5 B per pixel of the batch for the symbol planes,
+ * 7.5 B per pixel + ~6 KB per tile of stream scratch - shared with the decode's planes, re-allocated once if a decode came first
+ * and it is the larger: that one call waits for the context's earlier work and frees a buffer, which may make the runtime wait for
+ * the whole device - and the per-tile tables, sized from M); mode 2 adds its own on first use.  All of it is counted by
+ * xpnghip_ctx_workspace_bytes.  Every argument is checked before anything reaches the device: a rejected call writes nothing and
+ * xpnghip_last_error() says why. */
+int xpnghip_encode_varsize_device_batch(xpnghip_ctx *ctx, int mode, const void *const *d_rasters, uint64_t in_bpr,
+                                        uint32_t nimg, void *const *d_blobs, uint64_t *blobs_len, void *stream);
 
 /* Stage-only run for BASELINE config 2: predictor chooser + per-pixel transform (libxpng.c:92-140 and
  * the arithmetic of 497-519) over tiles [t0, t1); symbol planes stay in the context's workspace. */

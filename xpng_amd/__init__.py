@@ -6,9 +6,9 @@ xpng.h / xpng.c).  This package only binds those libraries with ctypes for tests
 torch.distributed sharding.  It never falls back to a CPU codec: if the HIP library is missing or no GPU
 is visible, compute calls raise.
 """
-from .api import (Context, MixedContext, XpngError, build_native, decode_mixed, decode_region, decode_tiles, device_count,
-                  encode_tiles, hip_lib, host_lib, load, load_batch, load_region, native_paths, normalize_device, region_tiles, store)
+from .api import (Context, MixedContext, StagedImages, XpngError, build_native, decode_mixed, decode_region, decode_tiles, device_count,
+                  encode_tiles, hip_lib, host_lib, load, load_batch, load_region, native_paths, normalize_device, region_tiles, store, store_batch)
 
-__all__ = ["Context", "MixedContext", "XpngError", "build_native", "decode_mixed", "decode_region", "decode_tiles", "device_count",
+__all__ = ["Context", "MixedContext", "StagedImages", "XpngError", "build_native", "decode_mixed", "decode_region", "decode_tiles", "device_count",
            "encode_tiles", "hip_lib", "host_lib", "load", "load_batch", "load_region", "native_paths", "normalize_device",
-           "region_tiles", "store"]
+           "region_tiles", "store", "store_batch"]

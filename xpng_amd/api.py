@@ -29,6 +29,9 @@ HIP_SYMBOLS = [
     "xpnghip_shard_ranges", "xpnghip_shutdown", "xpnghip_probes_built",
     "xpnghip_region_tiles", "xpnghip_decode_region", "xpnghip_decode_region_device_batch",
     "xpnghip_ctx_create_mixed", "xpnghip_ctx_mixed_first_tile", "xpnghip_decode_mixed_device_batch", "xpnghip_decode_mixed",
+    "xpnghip_encode_varsize_device_batch",
+    "xpnghip_images_begin", "xpnghip_images_single_colour", "xpnghip_images_encode", "xpnghip_images_fetch", "xpnghip_images_end",
+    "xpnghip_images_first_pixel", "xpnghip_batch_cuts",
 ]
 HOST_SYMBOLS = ["xpng_store", "xpng_load", "xpng_from_jpg", "xpng_store_T", "xpng_load_T", "xpng_from_jpg_T",
                 "store_7", "load_7"]
@@ -36,6 +39,8 @@ HOST_SYMBOLS = ["xpng_store", "xpng_load", "xpng_from_jpg", "xpng_store_T", "xpn
 HOST_EXT_SYMBOLS = ["xpng_load_region"]
 # ... and include/xpng_batch.h
 HOST_BATCH_SYMBOLS = ["xpng_load_batch"]
+# ... and include/xpng_store_batch.h
+HOST_STORE_BATCH_SYMBOLS = ["xpng_store_batch"]
 
 
 class XpngError(RuntimeError):
@@ -147,6 +152,23 @@ def _bind_hip(path):
         L.xpnghip_decode_mixed_device_batch.restype = C.c_int
         L.xpnghip_decode_mixed_device_batch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64), C.c_uint32, C.POINTER(u64),
                                                         C.POINTER(vp), u64, vp]
+        L.xpnghip_encode_varsize_device_batch.restype = C.c_int
+        L.xpnghip_encode_varsize_device_batch.argtypes = [vp, C.c_int, C.POINTER(vp), u64, C.c_uint32, C.POINTER(vp), C.POINTER(u64), vp]
+        u8p = C.POINTER(C.c_uint8)
+        L.xpnghip_images_begin.restype = C.c_int
+        L.xpnghip_images_begin.argtypes = [C.POINTER(vp), C.c_uint32, C.POINTER(vp), C.POINTER(u64), u8p, u8p]
+        L.xpnghip_images_single_colour.restype = C.c_int
+        L.xpnghip_images_single_colour.argtypes = [vp, u8p]
+        L.xpnghip_images_encode.restype = C.c_int
+        L.xpnghip_images_encode.argtypes = [vp, u8p, C.POINTER(u8p), C.POINTER(u64)]
+        L.xpnghip_images_fetch.restype = C.c_int
+        L.xpnghip_images_fetch.argtypes = [vp, C.c_uint32, vp]
+        L.xpnghip_images_first_pixel.restype = C.c_int
+        L.xpnghip_images_first_pixel.argtypes = [vp, C.c_uint32, vp]
+        L.xpnghip_batch_cuts.restype = C.c_int
+        L.xpnghip_batch_cuts.argtypes = [C.c_uint32, C.POINTER(u64), u8p, C.c_uint32, u64, C.POINTER(C.c_uint32), C.c_int]
+        L.xpnghip_images_end.restype = None
+        L.xpnghip_images_end.argtypes = [vp]
         L.xpnghip_decode_mixed.restype = C.c_int
         L.xpnghip_decode_mixed.argtypes = [C.c_int, C.c_int, C.c_uint32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(vp)]
     return L
@@ -202,6 +224,8 @@ def host_lib():
         L.load_7.argtypes = [C.c_char_p, C.POINTER(XpngT)]
         L.xpng_load_batch.restype = C.c_bool
         L.xpng_load_batch.argtypes = [C.POINTER(C.c_char_p), C.c_uint64, C.POINTER(XpngT)]
+        L.xpng_store_batch.restype = C.c_bool
+        L.xpng_store_batch.argtypes = [C.c_uint64, C.POINTER(XpngT), C.POINTER(C.c_char_p), C.c_uint64]
         _host = L
     return _host
 
@@ -397,6 +421,96 @@ def load_batch(paths) -> list:
     return out
 
 
+def batch_cuts(dims, pxsz, max_images: int = 4096, max_bytes: int = 2 << 30) -> list:
+    """First image of every staged batch xpng_store_batch makes of a list (xpnghip_batch_cuts; host-only, needs no GPU):
+    dims[i] = (w, h), pxsz[i] = bytes per pixel as handed in; the defaults are xpng_store_batch's budgets."""
+    k = len(dims)
+    flat = (C.c_uint64 * max(2 * k, 1))(*[int(v) for d in dims for v in d])
+    px, starts = (C.c_uint8 * max(k, 1))(*pxsz), (C.c_uint32 * max(k, 1))()
+    n = hip_lib().xpnghip_batch_cuts(k, flat, px, max_images, max_bytes, starts, k)
+    if n < 0:
+        raise XpngError("xpnghip_batch_cuts failed")
+    return list(starts[:n])
+
+
+def store_batch(mode: int, rasters, paths) -> None:
+    """xpng_store_batch (include/xpng_store_batch.h): file i is what store(mode, rasters[i], paths[i]) writes; the tile stage of
+    all images of one (tile mode, bytes per pixel) is one mixed-size device call."""
+    k = len(rasters)
+    assert len(paths) == k
+    rs = [np.ascontiguousarray(r, dtype=np.uint8) for r in rasters]
+    pms = (XpngT * max(k, 1))(*[XpngT(r.ctypes.data_as(C.POINTER(C.c_uint8)), r.shape[1], r.shape[0], r.size, r.shape[2] == 4) for r in rs])
+    arr = (C.c_char_p * max(k, 1))(*[os.fsencode(p) for p in paths])
+    if host_lib().xpng_store_batch(mode, pms, arr, k):
+        raise XpngError("xpng_store_batch failed")
+
+
+class StagedImages:
+    """The staged batch of xpng_store_batch (xpnghip_images_begin .. _end): a list of (h, w, 3|4) uint8 rasters of any sizes,
+    uploaded once and normalised on the device.  pxsz[i] = bytes per pixel of the normalised raster i."""
+
+    def __init__(self, rasters, lib=None):
+        self._lib = lib or hip_lib()
+        rs = [np.ascontiguousarray(r, dtype=np.uint8) for r in rasters]
+        k = self.n = len(rs)
+        self.dims = [(r.shape[1], r.shape[0]) for r in rs]
+        ptrs = (C.c_void_p * max(k, 1))(*[r.ctypes.data for r in rs])
+        flat = (C.c_uint64 * max(2 * k, 1))(*[v for d in self.dims for v in d])
+        pin, pout = (C.c_uint8 * max(k, 1))(*[r.shape[2] for r in rs]), (C.c_uint8 * max(k, 1))()
+        self._h = C.c_void_p()
+        if self._lib.xpnghip_images_begin(C.byref(self._h), k, ptrs, flat, pin, pout):
+            raise XpngError("xpnghip_images_begin: " + self._lib.xpnghip_last_error().decode(errors="replace"))
+        self.pxsz = list(pout)[:k]
+
+    def _fail(self, what):
+        raise XpngError(what + ": " + self._lib.xpnghip_last_error().decode(errors="replace"))
+
+    def single_colour(self) -> list:
+        out = (C.c_uint8 * self.n)()
+        if self._lib.xpnghip_images_single_colour(self._h, out):
+            self._fail("xpnghip_images_single_colour")
+        return [bool(v) for v in out]
+
+    def first_pixel(self, i: int) -> bytes:
+        """After single_colour(): the first pixel of normalised raster i."""
+        out = (C.c_uint8 * 4)()
+        if self._lib.xpnghip_images_first_pixel(self._h, i, out):
+            self._fail("xpnghip_images_first_pixel")
+        return bytes(out[: self.pxsz[i]])
+
+    def fetch(self, i: int) -> np.ndarray:
+        w, h = self.dims[i]
+        out = np.zeros((h, w, self.pxsz[i]), dtype=np.uint8)
+        if self._lib.xpnghip_images_fetch(self._h, i, out.ctypes.data_as(C.c_void_p)):
+            self._fail("xpnghip_images_fetch")
+        return out
+
+    def encode(self, modes) -> list:
+        """modes[i] = 0 (skip), 1 or 2 -> list of tile blobs (bytes), None for the skipped images."""
+        assert len(modes) == self.n
+        m, blobs, lens = (C.c_uint8 * self.n)(*modes), (C.POINTER(C.c_uint8) * self.n)(), (C.c_uint64 * self.n)()
+        if self._lib.xpnghip_images_encode(self._h, m, blobs, lens):
+            assert not any(bool(b) for b in blobs)
+            self._fail("xpnghip_images_encode")
+        out = []
+        for b, n in zip(blobs, lens):
+            out.append(C.string_at(b, n) if b else None)
+            if b:
+                _libc.free(b)
+        return out
+
+    def end(self):
+        if self._h:
+            self._lib.xpnghip_images_end(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.end()
+        except Exception:
+            pass
+
+
 def normalize_device(d_rgba: int, npx: int, d_out: int, stream=0):
     """normalize_RGBA (libxpng.c:688-721) on a device-resident RGBA raster -> (bytes per pixel, rewritten into d_out?)."""
     pxsz, rew = C.c_int(0), C.c_int(0)
@@ -530,8 +644,8 @@ class Context:
 
 
 class MixedContext:
-    """A mixed-size decode context (xpnghip_ctx_create_mixed): images of different sizes, dims[i] = (w, h), one pixel size, decoded
-    by ONE device call.  Decode only.  Device pointers are plain integers; `stream` is a hipStream_t handle or 0."""
+    """A mixed-size context (xpnghip_ctx_create_mixed): images of different sizes, dims[i] = (w, h), one pixel size, decoded or
+    encoded by ONE device call.  Device pointers are plain integers; `stream` is a hipStream_t handle or 0."""
 
     def __init__(self, dims, pxsz: int, device: int = 0):
         self.dims, self.pxsz, self.device = [(int(w), int(h)) for (w, h) in dims], pxsz, device
@@ -566,6 +680,23 @@ class MixedContext:
     def decode_status(self, stream=0) -> int:
         """Synchronise and report whether the last decode accepted every tile header (0) or rejected some (1)."""
         return hip_lib().xpnghip_ctx_decode_status(self._h, stream)
+
+    def blob_bound(self, i: int) -> int:
+        """Capacity the blob buffer of image i needs (xpnghip_ctx_blob_bound over the image's span of the concatenated table)."""
+        return hip_lib().xpnghip_ctx_blob_bound(self._h, self.first_tile[i], self.first_tile[i + 1])
+
+    def encode_batch(self, mode, d_rasters, d_blobs, in_bpr=0, stream=0, sync=True):
+        """One launch sequence over every tile of every image (xpnghip_encode_varsize_device_batch).  in_bpr != 0: every
+        d_rasters[i] holds its rows at this pitch; 0: tight rasters.  Returns the list of blob lengths (sync=True) or None (read
+        them with last_blobs_len_at after synchronising)."""
+        k = len(d_rasters)
+        ins, outs, lens = (C.c_void_p * k)(*d_rasters), (C.c_void_p * len(d_blobs))(*d_blobs), (C.c_uint64 * max(k, 1))()
+        if hip_lib().xpnghip_encode_varsize_device_batch(self._h, mode, ins, in_bpr, k, outs, lens if sync else None, stream):
+            raise XpngError("xpnghip_encode_varsize_device_batch: " + _err())
+        return list(lens)[:k] if sync else None
+
+    def last_blobs_len_at(self, i: int) -> int:
+        return hip_lib().xpnghip_ctx_last_blobs_len_at(self._h, i)
 
     def decode_batch(self, mode, d_blobs, lens, d_outs, out_bpr=0, tile_offs=None, stream=0):
         """One launch over every tile of every image (xpnghip_decode_mixed_device_batch).  out_bpr != 0: every d_outs[i] is

@@ -13,6 +13,7 @@
 #include "../../../include/xpng_hip.h"
 #include "../../../include/xpng_region.h"
 #include "../../../include/xpng_batch.h"
+#include "../../../include/xpng_store_batch.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -310,6 +311,135 @@ _Bool xpng_load_batch(const char *const *paths, uint64_t n, xpng_t *out) {
     for (uint64_t i = 0; buf && i < n; i++) free(buf[i]);
     if (rc) for (uint64_t i = 0; i < n; i++) { free(out[i].p); memset(&out[i], 0, sizeof(out[i])); }
     free(buf); free(flen); free(group); free(bodies); free(outs); free(lens); free(dims);
+    return rc;
+}
+
+/* include/xpng_store_batch.h: n rasters at once.  What xpng_store_T and store_on_device decide stays here, per image and in their
+ * order; the staged image becomes a staged batch (xpnghip_images_*) and the tile stage of a batch is one mixed-size device call per
+ * (tile mode, bytes per pixel).  Every file's header and body are kept in memory and written only when all of them exist. */
+typedef struct {
+    uint8_t hdr[8];
+    const uint8_t *body; /* pm->p, or `owned` */
+    uint8_t *owned;
+    uint64_t len;
+} batch_file;
+
+/* one staged batch: images idx[0 .. k) of the list, all of which reach the device (levels 1 and 2, more than one pixel) */
+static _Bool store_batch_on_device(uint64_t mode, const xpng_t *pms, const uint64_t *idx, uint32_t k, batch_file *files) {
+    const uint8_t **rasters = malloc(k * sizeof(*rasters));
+    uint64_t *dims = malloc(2ull * k * sizeof(*dims)), *lens = calloc(k, sizeof(*lens));
+    uint8_t *pin = malloc(k), *pout = malloc(k), *single = calloc(k, 1), *modes = calloc(k, 1);
+    uint8_t **blobs = calloc(k, sizeof(*blobs));
+    xpnghip_images *h = NULL;
+    _Bool rc = 1;
+    if (!rasters || !dims || !lens || !pin || !pout || !single || !modes || !blobs) goto done;
+    for (uint32_t j = 0; j < k; j++) {
+        const xpng_t *pm = &pms[idx[j]];
+        rasters[j] = pm->p; dims[2 * j] = pm->w; dims[2 * j + 1] = pm->h; pin[j] = (uint8_t)(3 + pm->A);
+    }
+    if (xpnghip_images_begin(&h, k, rasters, dims, pin, pout)) {
+        fprintf(stderr, "xpng: GPU staging failed: %s\n", xpnghip_last_error());
+        goto done;
+    }
+    if (mode == 2 && xpnghip_images_single_colour(h, single)) goto done; /* libxpng.c:741-753 */
+    for (uint32_t j = 0; j < k; j++) {
+        const xpng_t *pm = &pms[idx[j]];
+        batch_file *f = &files[idx[j]];
+        const _Bool A = pout[j] == 4;
+        const uint64_t s = pm->w * pm->h * (uint64_t)pout[j];
+        put_u32(f->hdr, (uint32_t)(pm->w - 1) | ((uint32_t)mode << 24));
+        put_u32(f->hdr + 4, (uint32_t)(pm->h - 1) | ((uint32_t)A << 24));
+        if (mode == 2 && single[j]) { /* the file holds one pixel: it came back with the flags, the raster stays on the device */
+            if (!(f->owned = malloc(4)) || xpnghip_images_first_pixel(h, j, f->owned)) goto done;
+            f->hdr[7] |= 2;
+            f->body = f->owned; f->len = pout[j];
+            continue;
+        }
+        modes[j] = (uint8_t)mode;
+        if (A && mode == 2) { modes[j] = 1; f->hdr[3] = 1; } /* libxpng.c:755 */
+        if (A && (pm->w < 4 || pm->h < 4)) { /* reference behaviour undefined here: store uncompressed */
+            if (!(f->owned = malloc(s)) || xpnghip_images_fetch(h, j, f->owned)) goto done;
+            f->hdr[3] = XPNG_COMPRESSION_TYPE_UNCOMPRESSED;
+            f->body = f->owned; f->len = s;
+            modes[j] = 0;
+        }
+    }
+    if (xpnghip_images_encode(h, modes, blobs, lens)) {
+        fprintf(stderr, "xpng: GPU batch encode failed: %s\n", xpnghip_last_error());
+        goto done;
+    }
+    for (uint32_t j = 0; j < k; j++) {
+        if (!modes[j]) continue;
+        const xpng_t *pm = &pms[idx[j]];
+        batch_file *f = &files[idx[j]];
+        const uint64_t s = pm->w * pm->h * (uint64_t)pout[j];
+        if (lens[j] >= s) { /* libxpng.c:771-777 */
+            if (!(f->owned = malloc(s)) || xpnghip_images_fetch(h, j, f->owned)) goto done;
+            f->hdr[3] = XPNG_COMPRESSION_TYPE_UNCOMPRESSED;
+            f->body = f->owned; f->len = s;
+        } else {
+            f->owned = blobs[j]; blobs[j] = NULL;
+            f->body = f->owned; f->len = lens[j];
+        }
+    }
+    rc = 0;
+done:
+    xpnghip_images_end(h);
+    for (uint32_t j = 0; blobs && j < k; j++) free(blobs[j]);
+    free(rasters); free(dims); free(lens); free(pin); free(pout); free(single); free(modes); free(blobs);
+    return rc;
+}
+
+_Bool xpng_store_batch(uint64_t mode, const xpng_t *pms, const char *const *paths, uint64_t n) {
+    if (!pms || !paths || !n || !(mode == 1 || mode == 2 || mode == 7)) return 1;
+    for (uint64_t i = 0; i < n; i++) { /* libxpng.c:729-731, for every image before any work */
+        const xpng_t *pm = &pms[i];
+        if (!paths[i] || !pm->p || !pm->w || !pm->h || pm->w > XPNG_MAX_DIM || pm->h > XPNG_MAX_DIM || pm->w * pm->h * (3u + pm->A) != pm->s) return 1;
+    }
+    batch_file *files = calloc(n, sizeof(*files));
+    uint64_t *idx = malloc(n * sizeof(*idx));
+    uint8_t *dev = calloc(n, 1); /* 1: the image reaches the tile codec */
+    _Bool rc = !files || !idx || !dev;
+    for (uint64_t i = 0; !rc && i < n; i++) {
+        const xpng_t *pm = &pms[i];
+        batch_file *f = &files[i];
+        if (mode == 2 && !pm->A && pm->w * pm->h > 1 && all_pixels_equal(pm->p, pm->w * pm->h, 3)) { /* libxpng.c:741-753, RGB input */
+            put_u32(f->hdr, (uint32_t)(pm->w - 1) | (2u << 24));
+            put_u32(f->hdr + 4, (uint32_t)(pm->h - 1));
+            f->hdr[7] |= 2;
+            f->body = pm->p; f->len = 3;
+            continue;
+        }
+        if (mode != 7 && pm->w * pm->h > 1) { dev[i] = 1; continue; }
+        uint64_t s;
+        _Bool A;
+        if (normalize_rgba(pm, &f->owned, &s, &A)) { rc = 1; break; }
+        put_u32(f->hdr, (uint32_t)(pm->w - 1) | (7u << 24)); /* explicit level 7, or s <= 4: libxpng.c:735 */
+        put_u32(f->hdr + 4, (uint32_t)(pm->h - 1) | ((uint32_t)A << 24));
+        f->body = f->owned ? f->owned : pm->p; f->len = s;
+    }
+    uint64_t nd = 0; /* the images that reach the device, in order, and where that list is cut: the chunking rule of xpng_load_batch */
+    for (uint64_t i = 0; !rc && i < n; i++) if (dev[i]) idx[nd++] = i;
+    if (!rc && nd > 0xFFFFFFFFull) rc = 1;
+    if (!rc && nd) {
+        uint64_t *dims = malloc(2 * nd * sizeof(*dims));
+        uint8_t *px = malloc(nd);
+        uint32_t *starts = malloc(nd * sizeof(*starts));
+        int calls = -1;
+        if (dims && px && starts) {
+            for (uint64_t j = 0; j < nd; j++) { dims[2 * j] = pms[idx[j]].w; dims[2 * j + 1] = pms[idx[j]].h; px[j] = (uint8_t)(3 + pms[idx[j]].A); }
+            calls = xpnghip_batch_cuts((uint32_t)nd, dims, px, XPNG_BATCH_MAX, XPNG_BATCH_BYTES, starts, (int)nd);
+        }
+        rc = calls < 1;
+        for (int k = 0; !rc && k < calls; k++) {
+            const uint64_t b = starts[k], e = k + 1 < calls ? starts[k + 1] : nd;
+            rc = store_batch_on_device(mode, pms, idx + b, (uint32_t)(e - b), files);
+        }
+        free(dims); free(px); free(starts);
+    }
+    for (uint64_t j = 0; !rc && j < n; j++) rc = write_file(paths[j], files[j].hdr, files[j].body, files[j].len);
+    for (uint64_t j = 0; files && j < n; j++) free(files[j].owned);
+    free(files); free(idx); free(dev);
     return rc;
 }
 

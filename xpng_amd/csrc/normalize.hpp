@@ -91,4 +91,100 @@ __global__ __launch_bounds__(256) void k_any_differs(const uint8_t *__restrict__
     if (__ballot(diff) && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
 }
 
+// ---- a list of images (xpnghip_images_*, wrappers.hpp): the same rules with the image index in blockIdx.y -------------------------
+// One record per image; the flags of image i are flags[IMG_FLAGS * i + 0..2] = hidden, translucent, "some pixel differs from the
+// first", and [3] = the first pixel of the normalised raster (k_any_differs_batch).
+struct ImgRec {
+    uint8_t *in;     // the uploaded raster, tight, 16-byte aligned; hidden colours are zeroed in place
+    uint8_t *norm;   // RGBA inputs: room for the repack to RGB (npx * 3 bytes, 16-byte aligned)
+    uint64_t npx;
+    uint32_t pxsz_in, spare;
+};
+constexpr uint32_t IMG_FLAGS = 4;
+
+// the staged (normalised) raster of an image and its bytes per pixel, from the flags k_norm_flags_batch left
+__device__ __forceinline__ const uint8_t *img_cur(const ImgRec &r, const uint32_t *__restrict__ f, uint32_t &pxsz) {
+    const bool repacked = r.pxsz_in == 4 && !f[0] && !f[1];
+    pxsz = (r.pxsz_in == 4 && !repacked) ? 4u : 3u;
+    return repacked ? r.norm : r.in;
+}
+
+// grid (blocks, nimg): k_norm_flags for every RGBA image of the list in one launch (an RGB image's workgroups return at once)
+__global__ __launch_bounds__(256) void k_norm_flags_batch(const ImgRec *__restrict__ rec, uint32_t *__restrict__ flags_all) {
+    const ImgRec r = rec[blockIdx.y];
+    if (r.pxsz_in != 4) return;
+    uint32_t *flags = flags_all + IMG_FLAGS * blockIdx.y;
+    const uint32_t *px = reinterpret_cast<const uint32_t *>(r.in);
+    const uint64_t n = r.npx;
+    uint32_t hidden = 0, transl = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, n4 = n / 4;  // (the rasters are 16-byte aligned: no head pixels)
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const uint4 v = reinterpret_cast<const uint4 *>(px)[i];
+        const uint32_t p[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const uint32_t a = p[k] >> 24;
+            hidden |= (a == 0 && (p[k] & 0xFFFFFFu)) ? 1u : 0u;
+            transl |= a != 255 ? 1u : 0u;
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {  // tail pixels
+        const uint32_t v = px[n4 * 4 + threadIdx.x], a = v >> 24;
+        hidden |= (a == 0 && (v & 0xFFFFFFu)) ? 1u : 0u;
+        transl |= a != 255 ? 1u : 0u;
+    }
+    if (__ballot(hidden) && (threadIdx.x & 63) == 0) atomicOr(&flags[0], 1u);
+    if (__ballot(transl) && (threadIdx.x & 63) == 0) atomicOr(&flags[1], 1u);
+}
+
+// grid (blocks, nimg), launched behind k_norm_flags_batch on the same stream: the rewrite each image's flags ask for, decided on
+// the device (the host reads the flags once, for the whole list, and only to learn the pixel sizes).  hidden: pixels with alpha 0
+// become 0 in place (k_norm_zero_hidden_if); no translucent pixel: repack to RGB into norm (k_norm_to_rgb); else nothing.
+__global__ __launch_bounds__(256) void k_norm_rewrite_batch(const ImgRec *__restrict__ rec, const uint32_t *__restrict__ flags_all) {
+    const ImgRec r = rec[blockIdx.y];
+    if (r.pxsz_in != 4) return;
+    const uint32_t *flags = flags_all + IMG_FLAGS * blockIdx.y;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, n = r.npx, first = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t *px = reinterpret_cast<uint32_t *>(r.in);
+    if (flags[0]) {
+        for (uint64_t i = first; i < n; i += stride) {
+            const uint32_t v = px[i];
+            if ((v >> 24) == 0 && v) px[i] = 0u;
+        }
+    } else if (!flags[1]) {
+        const uint64_t n4 = n / 4;
+        for (uint64_t i = first; i < n4; i += stride) {
+            const uint4 v = reinterpret_cast<const uint4 *>(px)[i];
+            const uint32_t a = v.x & 0xFFFFFFu, b = v.y & 0xFFFFFFu, c = v.z & 0xFFFFFFu, d = v.w & 0xFFFFFFu;
+            uint32_t *o = reinterpret_cast<uint32_t *>(r.norm) + 3 * i;
+            o[0] = a | (b << 24); o[1] = (b >> 8) | (c << 16); o[2] = (c >> 16) | (d << 8);
+        }
+        if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+            const uint64_t i = n4 * 4 + threadIdx.x;
+            const uint32_t v = px[i];
+            r.norm[3 * i] = (uint8_t)v; r.norm[3 * i + 1] = (uint8_t)(v >> 8); r.norm[3 * i + 2] = (uint8_t)(v >> 16);
+        }
+    }
+}
+
+// grid (blocks, nimg): the whole-image single-colour test (k_any_differs) of every normalised raster of the list
+__global__ __launch_bounds__(256) void k_any_differs_batch(const ImgRec *__restrict__ rec, uint32_t *__restrict__ flags_all) {
+    const ImgRec r = rec[blockIdx.y];
+    uint32_t *flags = flags_all + IMG_FLAGS * blockIdx.y;
+    uint32_t pxsz;
+    const uint8_t *p = img_cur(r, flags, pxsz);
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, first = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t diff = 0;
+    if (pxsz == 4) {
+        const uint32_t v0 = reinterpret_cast<const uint32_t *>(p)[0];
+        for (uint64_t i = first; i < r.npx; i += stride) diff |= reinterpret_cast<const uint32_t *>(p)[i] != v0 ? 1u : 0u;
+    } else {
+        const uint32_t v0 = load_px<3>(p);
+        for (uint64_t i = first; i < r.npx; i += stride) diff |= load_px<3>(p + 3 * i) != v0 ? 1u : 0u;
+    }
+    if (__ballot(diff) && (threadIdx.x & 63) == 0) atomicOr(&flags[2], 1u);
+    // the first pixel travels with the flags: a single-colour file holds nothing else, so the host never fetches that raster
+    if (blockIdx.x == 0 && threadIdx.x == 0) flags[3] = pxsz == 4 ? reinterpret_cast<const uint32_t *>(p)[0] : load_px<3>(p);
+}
+
 }  // namespace xpng

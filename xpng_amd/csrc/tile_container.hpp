@@ -93,6 +93,40 @@ __global__ __launch_bounds__(1024) void k_tile_offsets(const uint32_t *__restric
     if (tid == 0) { off[cnt] = s_base; totals[blockIdx.x] = s_base; }
 }
 
+// K5b, mixed-size batch (xpnghip_encode_varsize_device_batch): the images own different numbers of tiles, so the scan is segmented
+// by the concatenated table's first[] (nimg + 1 entries).  One workgroup per image over [first[img], first[img + 1]): off[i], one
+// entry per TABLE entry, is tile i's byte offset inside ITS image's blob buffer; the image's total goes to totals[img].  The
+// launch enumerates the table as one image of M tiles (TileSel{0, M, M, 1}), so imglin() is the table index and both gathers
+// find off[] where they look for it (il + il / cnt = il, j / cnt * (cnt + 1) + j % cnt = j).
+__global__ __launch_bounds__(256) void k_tile_offsets_seg(const uint32_t *__restrict__ tile_sz, const uint32_t *__restrict__ first,
+                                                          uint64_t *__restrict__ off, uint64_t *__restrict__ totals) {
+    __shared__ uint64_t s_wave[4];
+    __shared__ uint64_t s_base;
+    const uint32_t b = first[blockIdx.x], e = first[blockIdx.x + 1], cnt = e - b;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (tid == 0) s_base = 0;
+    __syncthreads();
+    for (uint32_t i0 = 0; i0 < cnt; i0 += 256) {
+        const uint32_t i = i0 + tid;
+        const uint64_t v = i < cnt ? tile_sz[b + i] : 0;
+        uint64_t incl = v;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint64_t o = __shfl_up(incl, d);
+            if ((int)lane >= d) incl += o;
+        }
+        if (lane == 63) s_wave[wv] = incl;
+        __syncthreads();
+        uint64_t base = s_base;
+        for (uint32_t w2 = 0; w2 < wv; w2++) base += s_wave[w2];
+        if (i < cnt) off[b + i] = base + incl - v;
+        __syncthreads();
+        if (tid == 255) s_base = base + incl;
+        __syncthreads();
+    }
+    if (tid == 0) totals[blockIdx.x] = s_base;
+}
+
 __device__ __forceinline__ void block_copy(uint8_t *dst, const uint8_t *src, uint64_t bytes) {
     if ((((uintptr_t)dst | (uintptr_t)src) & 3) == 0) {
         const uint64_t words = bytes >> 2;

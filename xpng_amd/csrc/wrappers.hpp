@@ -969,6 +969,211 @@ static int image_encode_impl(xpnghip_image *im, uint64_t T, int mode, uint8_t **
 }
 extern "C" int xpnghip_image_encode_T(xpnghip_image *im, uint64_t T, int mode, uint8_t **blobs, uint64_t *blobs_len) { XPNG_GUARDED(image_encode_impl(im, T, mode, blobs, blobs_len)) }
 extern "C" int xpnghip_image_encode(xpnghip_image *im, int mode, uint8_t **blobs, uint64_t *blobs_len) { XPNG_GUARDED(image_encode_impl(im, 1, mode, blobs, blobs_len)) }
+// ---- staged batch: what the staged image does, for a list of images ------------------------------------------------------
+// One handle for n images of any sizes, RGB and RGBA mixed (include/xpng_hip.h).  The rasters go up once into ONE device buffer,
+// tight, each 16-byte aligned; normalize_RGBA runs for all RGBA images in two launches (flags, then the rewrite each image's flags
+// ask for, decided on the device) with ONE read-back of the flags for the call; the single-colour test is one launch; the encode
+// groups the images by (tile mode, normalised bytes per pixel) and hands each group to one tight-form mixed encode
+// (xpnghip_encode_varsize_device_batch) on a mixed context created for the call.  A handle owns its buffers and its stream: handles
+// are independent of each other, and no lock is held across a HIP call.
+struct xpnghip_images {
+    int dev = 0;
+    uint32_t n = 0;
+    std::vector<uint64_t> dims;       // n pairs {w, h}
+    std::vector<uint8_t> px_in, px;   // bytes per pixel as uploaded / after normalisation
+    std::vector<const uint8_t *> cur; // the staged (normalised) rasters
+    uint8_t *d_in = nullptr, *d_norm = nullptr;
+    ImgRec *d_rec = nullptr;
+    uint32_t *d_flags = nullptr;      // IMG_FLAGS per image
+    uint32_t blocks = 1;              // grid.x of the per-list launches (from the largest image)
+    bool have_single = false;
+    std::vector<uint32_t> h_flags;
+    hipStream_t stream = nullptr;
+};
+constexpr uint64_t IMAGES_MAX_WG = 1u << 16;
+static void images_destroy(xpnghip_images *h) {
+    if (!h) return;
+    (void)hipSetDevice(h->dev);
+    if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
+    for (void *p : {(void *)h->d_in, (void *)h->d_norm, (void *)h->d_rec, (void *)h->d_flags}) if (p) (void)hipFree(p);
+    delete h;
+}
+static int images_begin_impl(xpnghip_images **out, uint32_t nimg, const uint8_t *const *rasters, const uint64_t *dims, const uint8_t *pxsz_in, uint8_t *pxsz_out) {
+    if (!out) return fail("null argument");
+    *out = nullptr;
+    if (!rasters || !dims || !pxsz_in || !pxsz_out) return fail("null argument");
+    if (nimg < 1 || nimg > 4096) return fail("a staged batch holds 1 .. 4096 images");
+    std::vector<uint64_t> off_in((size_t)nimg + 1, 0), off_norm((size_t)nimg + 1, 0);
+    uint64_t max_npx = 0;
+    for (uint32_t i = 0; i < nimg; i++) {
+        if (!rasters[i]) return fail("null raster of image " + std::to_string(i));
+        if (!dims[2ull * i] || !dims[2ull * i + 1] || dims[2ull * i] > (1u << 24) || dims[2ull * i + 1] > (1u << 24) || (pxsz_in[i] != 3 && pxsz_in[i] != 4))
+            return fail("bad raster geometry of image " + std::to_string(i));
+        const uint64_t npx = dims[2ull * i] * dims[2ull * i + 1];
+        off_in[i + 1] = off_in[i] + rup(npx * pxsz_in[i], 16);
+        off_norm[i + 1] = off_norm[i] + (pxsz_in[i] == 4 ? rup(npx * 3, 16) : 0);
+        max_npx = std::max(max_npx, npx);
+    }
+    if (usable_devices() < 1) return fail("no usable HIP device (libxpng_hip has no CPU fallback)");
+    DevGuard guard;
+    HIPCHK(hipSetDevice(base_device()));
+    xpnghip_images *h = new xpnghip_images();
+    h->dev = base_device(); h->n = nimg;
+    h->dims.assign(dims, dims + 2ull * nimg);
+    h->px_in.assign(pxsz_in, pxsz_in + nimg);
+    h->px = h->px_in;
+    // grid.x of the list launches (grid.y = image): what the largest image wants, but at most IMAGES_MAX_WG workgroups per launch -
+    // most images of a long list are far smaller than its largest and their surplus workgroups only start and return.  Every
+    // kernel strides by its grid, so any value is correct.
+    h->blocks = (uint32_t)std::min<uint64_t>(std::min<uint64_t>((max_npx / 4 + 255) / 256 + 1, 256 * 16), std::max<uint64_t>(IMAGES_MAX_WG / nimg, 1));
+    auto body = [&]() -> int {
+        HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+        HIPCHK(hipMalloc((void **)&h->d_in, off_in[nimg] + 16));
+        if (off_norm[nimg]) HIPCHK(hipMalloc((void **)&h->d_norm, off_norm[nimg] + 16));
+        HIPCHK(hipMalloc((void **)&h->d_rec, (uint64_t)nimg * sizeof(ImgRec)));
+        HIPCHK(hipMalloc((void **)&h->d_flags, (uint64_t)nimg * IMG_FLAGS * 4));
+        std::vector<ImgRec> rec(nimg);
+        for (uint32_t i = 0; i < nimg; i++) {
+            const uint64_t npx = dims[2ull * i] * dims[2ull * i + 1];
+            rec[i] = ImgRec{h->d_in + off_in[i], pxsz_in[i] == 4 ? h->d_norm + off_norm[i] : nullptr, npx, pxsz_in[i], 0};
+            HIPCHK(hipMemcpyAsync(rec[i].in, rasters[i], npx * pxsz_in[i], hipMemcpyHostToDevice, h->stream));
+        }
+        HIPCHK(hipMemcpyAsync(h->d_rec, rec.data(), (uint64_t)nimg * sizeof(ImgRec), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemsetAsync(h->d_flags, 0, (uint64_t)nimg * IMG_FLAGS * 4, h->stream));
+        h->h_flags.assign((size_t)nimg * IMG_FLAGS, 0);
+        if (off_norm[nimg]) {  // (some image is RGBA)
+            k_norm_flags_batch<<<dim3(h->blocks, nimg), 256, 0, h->stream>>>(h->d_rec, h->d_flags);
+            k_norm_rewrite_batch<<<dim3(h->blocks, nimg), 256, 0, h->stream>>>(h->d_rec, h->d_flags);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(h->h_flags.data(), h->d_flags, (uint64_t)nimg * IMG_FLAGS * 4, hipMemcpyDeviceToHost, h->stream));
+        }
+        HIPCHK(hipStreamSynchronize(h->stream));  // the one read-back; the caller's rasters are free again
+        h->cur.resize(nimg);
+        for (uint32_t i = 0; i < nimg; i++) {
+            const uint32_t *f = &h->h_flags[(size_t)i * IMG_FLAGS];
+            const bool repacked = pxsz_in[i] == 4 && !f[0] && !f[1];
+            h->px[i] = repacked ? 3 : pxsz_in[i];
+            h->cur[i] = repacked ? rec[i].norm : rec[i].in;
+        }
+        return 0;
+    };
+    if (body()) { images_destroy(h); return 1; }
+    memcpy(pxsz_out, h->px.data(), nimg);
+    *out = h;
+    return 0;
+}
+static int images_single_colour_impl(xpnghip_images *h, uint8_t *single) {
+    if (!h || !single) return fail("no staged batch");
+    DevGuard guard;
+    HIPCHK(hipSetDevice(h->dev));
+    if (!h->have_single) {
+        k_any_differs_batch<<<dim3(h->blocks, h->n), 256, 0, h->stream>>>(h->d_rec, h->d_flags);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h->h_flags.data(), h->d_flags, (uint64_t)h->n * IMG_FLAGS * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        h->have_single = true;
+    }
+    for (uint32_t i = 0; i < h->n; i++) single[i] = h->h_flags[(size_t)i * IMG_FLAGS + 2] ? 0 : 1;
+    return 0;
+}
+static int images_first_pixel_impl(xpnghip_images *h, uint32_t i, uint8_t *px) {
+    if (!h || !px) return fail("no staged batch");
+    if (i >= h->n) return fail("image index beyond the staged batch");
+    if (!h->have_single) return fail("xpnghip_images_first_pixel follows xpnghip_images_single_colour (the pixel comes back with its flags)");
+    memcpy(px, &h->h_flags[(size_t)i * IMG_FLAGS + 3], h->px[i]);
+    return 0;
+}
+static int images_fetch_impl(xpnghip_images *h, uint32_t i, uint8_t *dst) {
+    if (!h || !dst) return fail("no staged batch");
+    if (i >= h->n) return fail("image index beyond the staged batch");
+    DevGuard guard;
+    HIPCHK(hipSetDevice(h->dev));
+    HIPCHK(hipMemcpyAsync(dst, h->cur[i], h->dims[2ull * i] * h->dims[2ull * i + 1] * h->px[i], hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+static int images_encode_impl(xpnghip_images *h, const uint8_t *modes, uint8_t **blobs, uint64_t *lens) {
+    if (!h || !modes || !blobs || !lens) return fail("no staged batch");
+    for (uint32_t i = 0; i < h->n; i++) { blobs[i] = nullptr; lens[i] = 0; }
+    for (uint32_t i = 0; i < h->n; i++) {
+        if (modes[i] > 2) return fail("tile mode of image " + std::to_string(i) + " must be 0 (skip), 1 or 2");
+        if (modes[i] == 2 && h->px[i] != 3) return fail("image " + std::to_string(i) + ": mode 2 codes RGB only (the driver sends RGBA to mode 1, libxpng.c:755)");
+        if (modes[i] && h->px[i] == 4 && (h->dims[2ull * i] < 4 || h->dims[2ull * i + 1] < 4))
+            return fail("RGBA image " + std::to_string(i) + " is narrower than 4 px: undefined in the reference; store level 7");
+    }
+    DevGuard guard;
+    HIPCHK(hipSetDevice(h->dev));
+    struct Owned {
+        xpnghip_ctx *c = nullptr; uint8_t *d = nullptr;
+        void drop() { if (c) { ctx_quiesce(c); xpnghip_ctx_destroy(c); c = nullptr; } if (d) { (void)hipFree(d); d = nullptr; } }
+        ~Owned() { drop(); }
+    } own;
+    auto group = [&](int mode, int px) -> int {
+        std::vector<uint32_t> idx;
+        std::vector<uint64_t> gd;
+        for (uint32_t i = 0; i < h->n; i++)
+            if (modes[i] == mode && h->px[i] == px) { idx.push_back(i); gd.push_back(h->dims[2ull * i]); gd.push_back(h->dims[2ull * i + 1]); }
+        if (idx.empty()) return 0;
+        const uint32_t k = (uint32_t)idx.size();
+        if (xpnghip_ctx_create_mixed(&own.c, h->dev, gd.data(), k, px)) return 1;
+        std::vector<uint64_t> boff((size_t)k + 1, 0), glen(k);
+        for (uint32_t j = 0; j < k; j++) boff[j + 1] = boff[j] + rup(xpnghip_ctx_blob_bound(own.c, own.c->m_first[j], own.c->m_first[j + 1]), 256);
+        HIPCHK(hipMalloc((void **)&own.d, boff[k]));
+        std::vector<const void *> in(k);
+        std::vector<void *> outp(k);
+        for (uint32_t j = 0; j < k; j++) { in[j] = h->cur[idx[j]]; outp[j] = own.d + boff[j]; }
+        if (xpnghip_encode_varsize_device_batch(own.c, mode, in.data(), 0, k, outp.data(), glen.data(), h->stream)) return 1;
+        for (uint32_t j = 0; j < k; j++) {
+            if (!(blobs[idx[j]] = (uint8_t *)malloc(glen[j] ? glen[j] : 1))) return fail("malloc failed");
+            lens[idx[j]] = glen[j];
+            HIPCHK(hipMemcpyAsync(blobs[idx[j]], outp[j], glen[j], hipMemcpyDeviceToHost, h->stream));
+        }
+        HIPCHK(hipStreamSynchronize(h->stream));
+        own.drop();
+        return 0;
+    };
+    if (group(1, 3) || group(1, 4) || group(2, 3)) {
+        (void)hipStreamSynchronize(h->stream);
+        for (uint32_t i = 0; i < h->n; i++) { free(blobs[i]); blobs[i] = nullptr; lens[i] = 0; }
+        return 1;
+    }
+    return 0;
+}
+// host-only (needs no device): where a list of images is cut into device calls.  A call takes images in order until it holds
+// max_images of them or its padded rasters - every row of every image at the widest image's pitch - would pass max_bytes; an image
+// that alone passes the budget is a call of its own.  starts[k] = first image of call k; returns the number of calls.
+static int batch_cuts_impl(uint32_t n, const uint64_t *dims, const uint8_t *pxsz, uint32_t max_images, uint64_t max_bytes, uint32_t *starts, int cap) {
+    if (!n || !dims || !pxsz || !starts || !max_images || cap < 1) return -1;
+    int calls = 0;
+    uint32_t i = 0;
+    while (i < n) {
+        if (calls >= cap) return -1;
+        starts[calls++] = i;
+        uint32_t k = 0;
+        uint64_t rows = 0, widest = 0;
+        for (; i < n && k < max_images; i++, k++) {
+            const uint64_t rb = dims[2ull * i] * pxsz[i], wd = std::max(rb, widest);
+            if (k && (rows + dims[2ull * i + 1]) * wd > max_bytes) break;  // the next call starts with this image
+            rows += dims[2ull * i + 1]; widest = wd;
+        }
+    }
+    return calls;
+}
+extern "C" int xpnghip_batch_cuts(uint32_t n, const uint64_t *dims, const uint8_t *pxsz, uint32_t max_images, uint64_t max_bytes, uint32_t *starts, int cap) {
+    try { return batch_cuts_impl(n, dims, pxsz, max_images, max_bytes, starts, cap); } catch (...) { return -1; }
+}
+extern "C" int xpnghip_images_begin(xpnghip_images **h, uint32_t nimg, const uint8_t *const *rasters, const uint64_t *dims, const uint8_t *pxsz_in, uint8_t *pxsz_out) {
+    XPNG_GUARDED(images_begin_impl(h, nimg, rasters, dims, pxsz_in, pxsz_out))
+}
+extern "C" int xpnghip_images_single_colour(xpnghip_images *h, uint8_t *single) { XPNG_GUARDED(images_single_colour_impl(h, single)) }
+extern "C" int xpnghip_images_encode(xpnghip_images *h, const uint8_t *modes, uint8_t **blobs, uint64_t *lens) { XPNG_GUARDED(images_encode_impl(h, modes, blobs, lens)) }
+extern "C" int xpnghip_images_first_pixel(xpnghip_images *h, uint32_t i, uint8_t *px) { XPNG_GUARDED(images_first_pixel_impl(h, i, px)) }
+extern "C" int xpnghip_images_fetch(xpnghip_images *h, uint32_t i, uint8_t *dst) { XPNG_GUARDED(images_fetch_impl(h, i, dst)) }
+extern "C" void xpnghip_images_end(xpnghip_images *h) {
+    if (!h) return;
+    try { DevGuard guard; images_destroy(h); } catch (...) {}
+}
+
 // devices a call with worker count T would use on an image of this geometry (what xpng_store_T prints in its MPx/s line)
 extern "C" int xpnghip_devices_for(uint64_t T, uint64_t w, uint64_t h) {
     if (!w || !h || w > (1u << 24) || h > (1u << 24)) return 0;

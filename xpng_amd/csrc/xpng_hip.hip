@@ -167,9 +167,12 @@ struct xpnghip_ctx {
     uint64_t cap_region_stage = 0;
     uint8_t *d_region_meta = nullptr;
     std::vector<uint8_t> h_region_meta;  // what d_region_meta holds (skip the upload when unchanged)
-    // mixed-size batch (xpnghip_ctx_create_mixed; mixed.hpp): decode only.  `tiles` is then the concatenation of the
-    // B images' tile tables (M entries, img / pbase / sbase as on the device) and W = H = 0
+    // mixed-size batch (xpnghip_ctx_create_mixed; mixed.hpp).  `tiles` is then the concatenation of the
+    // B images' tile tables (M entries, img / pbase / sbase as on the device) and W = H = 0.  The constructor allocates what a
+    // decode needs; the encode workspace follows with the first encode (ensure_mixed_encode)
     bool mixed = false;
+    bool m_enc = false;                // the encode workspace exists (and d_scratch has the encode's share)
+    uint64_t cap_scratch = 0;          // bytes of d_scratch
     std::vector<uint64_t> m_dims;      // B pairs {w, h}
     std::vector<uint32_t> m_first;     // B + 1 table indices: image i owns tiles [m_first[i], m_first[i + 1])
     std::vector<uint32_t> m_list;      // all M table indices by decreasing pixel count (the work list of every launch)
@@ -179,6 +182,8 @@ struct xpnghip_ctx {
     uint64_t cap_m_stage = 0;
     MixedCopy *d_m_copy = nullptr;     // B copy records
     std::vector<void *> h_m_copy_dst;  // the destinations d_m_copy holds (skip the upload when unchanged)
+    MixedPack *d_m_pack = nullptr;     // tight input form of the encode: B pack records
+    std::vector<const void *> h_m_pack_src;  // the sources d_m_pack holds
 };
 
 // the context's own stream, created when a call first needs it (the `stream == NULL` form of the device-resident entry points,
@@ -199,7 +204,7 @@ extern "C" void xpnghip_ctx_destroy(xpnghip_ctx *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void *ptrs[] = {c->d_tiles, c->d_planes, c->d_scratch, c->d_sums, c->d_nlh, c->d_ctx_n, c->d_k_n, c->d_blk_sz, c->d_tile_sz,
                     c->d_tile_hdr, c->d_off, c->d_totals, c->d_raster, c->d_blobs, c->d_blob_in, c->d_dbg, (void *)c->d_in_ptrs, (void *)c->d_out_ptrs, (void *)c->d_dec_in_ptrs, (void *)c->d_dec_out_ptrs, (void *)c->d_order,
-                    c->d_wprep, c->d_wtab, c->d_wF, c->d_blob_len, c->d_status, c->d_scratch2, c->d_sbase2, c->d_flags2, c->d_stream_n2, c->d_blk2, c->d_mt2, c->d_info2, c->d_tabs2, c->d_w1prep, c->d_w1tab, c->d_w1F, c->d_region_stage, c->d_region_meta, c->d_m_first, c->d_m_stage, c->d_m_copy};
+                    c->d_wprep, c->d_wtab, c->d_wF, c->d_blob_len, c->d_status, c->d_scratch2, c->d_sbase2, c->d_flags2, c->d_stream_n2, c->d_blk2, c->d_mt2, c->d_info2, c->d_tabs2, c->d_w1prep, c->d_w1tab, c->d_w1F, c->d_region_stage, c->d_region_meta, c->d_m_first, c->d_m_stage, c->d_m_copy, c->d_m_pack};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->enc_side) (void)hipStreamDestroy(c->enc_side);
     if (c->ev_enc_fork) (void)hipEventDestroy(c->ev_enc_fork);
@@ -326,7 +331,7 @@ extern "C" uint64_t xpnghip_ctx_workspace_bytes(const xpnghip_ctx *c) { return c
 
 static int check_range(const xpnghip_ctx *c, uint64_t t0, uint64_t t1) {
     if (!c) return fail("null context");
-    if (c->mixed) return fail("a mixed context decodes whole images only: use xpnghip_decode_mixed_device_batch (no encode, transform or tile-range decode)");
+    if (c->mixed) return fail("a mixed context codes whole images only: use xpnghip_decode_mixed_device_batch / xpnghip_encode_varsize_device_batch (no tile ranges, no transform-only run)");
     if (t0 >= t1 || t1 > c->tiles.size()) return fail("bad tile range");
     if (t0 < c->r0 || t1 > c->r1) return fail("tile range outside the range this context was created for");
     return 0;
@@ -357,14 +362,27 @@ static const uint32_t *order_for(const xpnghip_ctx *c, uint32_t t0, uint32_t t1)
 
 // Level-1 stream scratch (k, block slots, context streams: 7.5 B/px, common.hpp) and the decode's symbol / residual planes
 // (8 B/px: DecodeWs::arena) are ONE buffer: a context's encode intermediates are dead by the time the same context decodes.
+// (A mixed context's scratch_img already spans its images, and it pays for the encode's share only from its first encode on.)
 static uint64_t scratch_bytes(const xpnghip_ctx *c) {
-    const uint64_t enc = c->mixed ? 0 : c->scratch_img * c->B + 8192, dec = 8 * c->plane_stride + (2u << 20);
+    const uint64_t enc = c->mixed ? (c->m_enc ? c->scratch_img + 8192 : 0) : c->scratch_img * c->B + 8192, dec = 8 * c->plane_stride + (2u << 20);
     return enc > dec ? enc : dec;
 }
-static int ensure_scratch(xpnghip_ctx *c) {
-    if (c->d_scratch) return 0;
+static int ensure_scratch(xpnghip_ctx *c, hipStream_t s = nullptr) {
     const uint64_t bytes = scratch_bytes(c);
+    if (c->d_scratch && c->cap_scratch >= bytes) return 0;
+    if (c->d_scratch) {
+        // a mixed context that decoded before its first encode, and whose encode streams need more than its decode planes (many
+        // tiny images: a tile's stream scratch has ~6 KB of fixed room): once per context.  The decode places its planes again.
+        // The context is a single-queue object: its earlier work is on the call's stream, its own stream or its side stream.
+        // (hipFree itself may still wait for the device: xpng_hip.h says so.)
+        for (hipStream_t q : {s, c->stream, c->enc_side}) if (q) HIPCHK(hipStreamSynchronize(q));
+        HIPCHK(hipFree(c->d_scratch));
+        c->ws_bytes -= c->cap_scratch;
+        c->d_scratch = nullptr; c->cap_scratch = 0;
+        c->dec.arena = nullptr; c->dec.arena_bytes = 0; c->dec.cap_plane = 0;
+    }
     HIPCHK(hipMalloc((void **)&c->d_scratch, bytes));
+    c->cap_scratch = bytes;
     c->ws_bytes += bytes;
     return 0;
 }
@@ -383,13 +401,32 @@ static int ensure_planes(xpnghip_ctx *c) {
     return 0;
 }
 
+// What an encode launch sequence enumerates.  An ordinary context: tiles [t0, t0 + cnt) of each of nimg rasters of ONE geometry,
+// W * pxsz bytes per row.  A mixed context: its concatenated table as one image of M tiles (TileSel{0, M, M, 1}: vtile(j) is j or
+// order[j], imglin() the table index, TileDesc::img finds the raster and the blob buffer), every raster at the call's one pitch.
+struct EncSpan {
+    uint32_t t0, cnt, N, nimg;   // the TileSel
+    uint32_t images;             // rasters in, blob buffers and totals out
+    uint64_t VN;                 // entries of the context's device tile table (what the per-tile arrays are sized from)
+    uint64_t bpr, raster_bytes;  // row pitch; where the 16-byte loads of the strip transforms clamp (~0: the caller keeps 16 readable bytes behind every raster)
+    const uint32_t *order;       // the size-sorted enumeration, for the kernels that use one
+};
+static EncSpan enc_span(const xpnghip_ctx *c, uint32_t nimg, uint32_t t0, uint32_t t1) {
+    const uint64_t N = c->tiles.size();
+    return EncSpan{t0, t1 - t0, (uint32_t)N, nimg, nimg, N * c->B, c->W * (uint64_t)c->pxsz, c->W * c->H * (uint64_t)c->pxsz, order_for(c, t0, t1)};
+}
+static EncSpan enc_span_mixed(const xpnghip_ctx *c, uint64_t bpr) {
+    const uint32_t M = (uint32_t)c->tiles.size();
+    return EncSpan{0, M, M, 1, c->B, M, bpr, ~0ull, probe_env("XPNG_IMAGE_MAJOR") ? nullptr : c->d_m_list};
+}
+
 // predictor chooser (pp_rgbx).  Launch only.
 // (probe builds: occupancy throttles of the bandwidth kernels in the pipelined paths, bytes of unused dynamic LDS per workgroup)
 template <int PXSZ>
-static int launch_chooser(xpnghip_ctx *c, uint32_t nimg, uint32_t t0, uint32_t t1, hipStream_t s, size_t pad = 0) {
-    const uint32_t cnt = t1 - t0, total = nimg * cnt;
-    const TileSel sel{t0, cnt, (uint32_t)c->tiles.size(), nimg, nullptr};
-    const uint64_t bpr = c->W * PXSZ;
+static int launch_chooser(xpnghip_ctx *c, const EncSpan &e, hipStream_t s, size_t pad = 0) {
+    const uint32_t t0 = e.t0, t1 = e.t0 + e.cnt, cnt = e.cnt, nimg = e.nimg, total = nimg * cnt;
+    const TileSel sel{t0, cnt, e.N, nimg, nullptr};
+    const uint64_t bpr = e.bpr;
     XPNG_REQUIRE(c->d_in_ptrs, c->d_tiles, c->d_sums);
     if (dbg_skip("chooser")) return 0;
     if (t0 == 0 && t1 == c->tiles.size()) HIPCHK(hipMemsetAsync(c->d_sums, 0, (uint64_t)nimg * sel.N * 16, s));
@@ -402,27 +439,27 @@ static int launch_chooser(xpnghip_ctx *c, uint32_t nimg, uint32_t t0, uint32_t t
 // chooser + transform (BASELINE config 2).  Launch only; no sync.  d_in_ptrs already holds the raster pointers.
 // hist: the transform also leaves the histogram of the nl plane in d_nlh (the stream lengths of the routing kernels come from it)
 template <int PXSZ>
-static int launch_transform(xpnghip_ctx *c, uint32_t nimg, uint32_t t0, uint32_t t1, hipStream_t s, size_t pad = 0, bool hist = false) {
+static int launch_transform(xpnghip_ctx *c, const EncSpan &e, hipStream_t s, size_t pad = 0, bool hist = false) {
     if (ensure_planes(c)) return 1;
-    const uint32_t cnt = t1 - t0, total = nimg * cnt;
+    const uint32_t t0 = e.t0, t1 = e.t0 + e.cnt, cnt = e.cnt, nimg = e.nimg, total = nimg * cnt;
     // image-major here: these two kernels stream the rasters, and neighbouring workgroups on neighbouring rows of ONE raster
     // keep HBM pages open (measured with 64 distinct rasters: 2.25 ms per launch against 2.4-2.6 tile-major)
-    const TileSel sel{t0, cnt, (uint32_t)c->tiles.size(), nimg, nullptr};
-    const uint64_t bpr = c->W * PXSZ;
+    const TileSel sel{t0, cnt, e.N, nimg, nullptr};
+    const uint64_t bpr = e.bpr;
     uint32_t max_n = 0;
     for (uint32_t i = t0; i < t1; i++) max_n = c->tiles[i].n > max_n ? c->tiles[i].n : max_n;
-    if (launch_chooser<PXSZ>(c, nimg, t0, t1, s, pad)) return 1;
+    if (launch_chooser<PXSZ>(c, e, s, pad)) return 1;
     XPNG_REQUIRE(c->d_planes, c->d_nlh);
     uint32_t *nlh = hist ? c->d_nlh : nullptr;
     uint32_t max_w = 0, max_h = 0;
     for (uint32_t i = t0; i < t1; i++) { max_w = c->tiles[i].w > max_w ? c->tiles[i].w : max_w; max_h = c->tiles[i].h > max_h ? c->tiles[i].h : max_h; }
     if (PXSZ == 4 && max_w <= TR_MAXW && !probe_env("XPNG_GENERIC_TRANSFORM")) {
         const uint32_t spt_ = (max_h + TR_ROWS - 1) / TR_ROWS;
-        if (!dbg_skip("transform")) k_m1_transform_rgba<<<(total * spt_ + 7) & ~7u, 256, pad, s>>>(c->d_in_ptrs, bpr, c->W * c->H * 4, c->d_tiles, sel, spt_, c->d_sums, c->d_planes, c->plane_stride, total * spt_, nlh, c->nlh_slots);
+        if (!dbg_skip("transform")) k_m1_transform_rgba<<<(total * spt_ + 7) & ~7u, 256, pad, s>>>(c->d_in_ptrs, bpr, e.raster_bytes, c->d_tiles, sel, spt_, c->d_sums, c->d_planes, c->plane_stride, total * spt_, nlh, c->nlh_slots);
         c->nlh_generic = 0;
     } else if (PXSZ == 3 && max_w <= TR_MAXW && !probe_env("XPNG_GENERIC_TRANSFORM")) {
         const uint32_t spt_ = (max_h + TR_ROWS - 1) / TR_ROWS;
-        k_m1_transform_rgb<<<(total * spt_ + 7) & ~7u, 256, pad, s>>>(c->d_in_ptrs, bpr, c->W * c->H * 3, c->d_tiles, sel, spt_, c->d_sums, c->d_planes, c->plane_stride, total * spt_, nlh, c->nlh_slots);
+        k_m1_transform_rgb<<<(total * spt_ + 7) & ~7u, 256, pad, s>>>(c->d_in_ptrs, bpr, e.raster_bytes, c->d_tiles, sel, spt_, c->d_sums, c->d_planes, c->plane_stride, total * spt_, nlh, c->nlh_slots);
         c->nlh_generic = 0;
     } else {
         const uint32_t bpt = (max_n + 1024 * TG_REPS - 1) / (1024 * TG_REPS);
@@ -439,7 +476,8 @@ extern "C" int xpnghip_m1_transform_device(xpnghip_ctx *c, const void *d_raster,
     hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(c);
     void *dummy = c->d_out_ptrs;  // no output buffer in this stage
     if (set_ptrs(c, &d_raster, &dummy, 1, s)) return 1;
-    return c->pxsz == 4 ? launch_transform<4>(c, 1, (uint32_t)t0, (uint32_t)t1, s, 0, true) : launch_transform<3>(c, 1, (uint32_t)t0, (uint32_t)t1, s, 0, true);  // (with the nl histogram: the kernel the encode runs)
+    const EncSpan e = enc_span(c, 1, (uint32_t)t0, (uint32_t)t1);
+    return c->pxsz == 4 ? launch_transform<4>(c, e, s, 0, true) : launch_transform<3>(c, e, s, 0, true);  // (with the nl histogram: the kernel the encode runs)
 }
 
 extern "C" int xpnghip_m1_transform_device_batch(xpnghip_ctx *c, const void *const *d_rasters, uint32_t nimg, uint64_t t0, uint64_t t1, void *stream) {
@@ -448,24 +486,25 @@ extern "C" int xpnghip_m1_transform_device_batch(xpnghip_ctx *c, const void *con
     hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(c);
     std::vector<void *> dummy(nimg, (void *)c->d_out_ptrs);  // no output buffers in this stage
     if (set_ptrs(c, d_rasters, dummy.data(), nimg, s)) return 1;
-    return c->pxsz == 4 ? launch_transform<4>(c, nimg, (uint32_t)t0, (uint32_t)t1, s, 0, true) : launch_transform<3>(c, nimg, (uint32_t)t0, (uint32_t)t1, s, 0, true);
+    const EncSpan e = enc_span(c, nimg, (uint32_t)t0, (uint32_t)t1);
+    return c->pxsz == 4 ? launch_transform<4>(c, e, s, 0, true) : launch_transform<3>(c, e, s, 0, true);
 }
 
 template <int PXSZ>
-static int launch_encode_m1(xpnghip_ctx *c, uint32_t nimg, uint32_t t0, uint32_t t1, hipStream_t s) {
+static int launch_encode_m1(xpnghip_ctx *c, const EncSpan &e, hipStream_t s) {
     dbg_count_sequence();
-    const uint32_t cnt = t1 - t0, total = nimg * cnt;
-    const TileSel sel{t0, cnt, (uint32_t)c->tiles.size(), nimg, order_for(c, t0, t1)};
-    const uint64_t bpr = c->W * PXSZ;
+    const uint32_t t0 = e.t0, t1 = e.t0 + e.cnt, cnt = e.cnt, nimg = e.nimg, total = nimg * cnt;
+    const TileSel sel{t0, cnt, e.N, nimg, e.order};
+    const uint64_t bpr = e.bpr;
     uint32_t max_w = 0;
     for (uint32_t i = t0; i < t1; i++) max_w = c->tiles[i].w > max_w ? c->tiles[i].w : max_w;
     const bool narrow = !wide_form((uint64_t)total * c->spt), small_wg = small_blocks((uint64_t)total * c->spt);
     static const size_t pad_tr = probe_pad("XPNG_PAD_TR"), pad_st = probe_pad("XPNG_PAD_ST"), pad_ga = probe_pad("XPNG_PAD_GA");
-    if (ensure_planes(c) || ensure_scratch(c)) return 1;  // (before their address is taken below)
+    if (ensure_planes(c) || ensure_scratch(c, s)) return 1;  // (before their address is taken below)
     XPNG_REQUIRE(c->d_planes, c->d_in_ptrs, c->d_out_ptrs, c->d_tiles, c->d_scratch, c->d_sums, c->d_ctx_n, c->d_k_n,
                  c->d_blk_sz, c->d_tile_sz, c->d_tile_hdr, c->d_off, c->d_totals, c->d_wprep, c->d_wtab, c->d_wF, c->h_total);
     const uint8_t *planesA = c->d_planes;
-    uint8_t *const watab = c->d_wtab + (((uint64_t)c->tiles.size() * c->B * WTAB_TILE_BYTES + 4096 + 511) & ~511ull);
+    uint8_t *const watab = c->d_wtab + ((e.VN * WTAB_TILE_BYTES + 4096 + 511) & ~511ull);
     const bool alpha_side = !narrow && PXSZ == 4;
     if (alpha_side && !c->enc_side) HIPCHK(chain_stream_create(&c->enc_side));
     if (alpha_side && !c->ev_enc_fork) {
@@ -475,7 +514,7 @@ static int launch_encode_m1(xpnghip_ctx *c, uint32_t nimg, uint32_t t0, uint32_t
     // (A fused transform + routing kernel - no nl / r / g / b planes, 3.7 B/px less HBM traffic - existed through round 3 behind
     //  XPNG_FUSED: one long-lived 28 KB workgroup per tile, 12 % slower in the pipeline every time it was measured, and it cannot
     //  know the stream lengths before it routes.  Removed with the worst-case stream layout; git history has it.)
-    if (launch_transform<PXSZ>(c, nimg, t0, t1, s, pad_tr, true)) return 1;
+    if (launch_transform<PXSZ>(c, e, s, pad_tr, true)) return 1;
     // Wide form, RGBA: the alpha chains are the longest serial stage of the encode and need only the alpha plane, so their
     // preparation and the chains themselves run on their own stream behind the transform
     // (Size classes of the alpha chains - the biggest tiles' alpha streams a wavefront each on a third stream - LOST: DESIGN.md 6,
@@ -502,10 +541,11 @@ static int launch_encode_m1(xpnghip_ctx *c, uint32_t nimg, uint32_t t0, uint32_t
         if (!dbg_skip("finish")) k_rans2_finish<<<total * c->spt, 64, 0, s>>>(c->d_tiles, sel, c->spt, planesA, c->plane_stride, c->d_scratch, c->d_ctx_n, c->d_blk_sz, c->d_wprep, c->d_wF);
     }
     k_tile_sizes<<<(total + 255) / 256, 256, 0, s>>>(c->d_tiles, sel, total, PXSZ, c->spt, c->d_sums, c->d_k_n, c->d_blk_sz, c->d_tile_sz, c->d_tile_hdr);
-    k_tile_offsets<<<nimg, 256, 0, s>>>(c->d_tile_sz, cnt, c->d_off, c->d_totals);
+    if (c->mixed) k_tile_offsets_seg<<<e.images, 256, 0, s>>>(c->d_tile_sz, c->d_m_first, c->d_off, c->d_totals);  // (per image over its own span of the table)
+    else k_tile_offsets<<<nimg, 256, 0, s>>>(c->d_tile_sz, cnt, c->d_off, c->d_totals);
     if (!dbg_skip("gather")) k_tile_gather<<<total, 256, pad_ga, s>>>(c->d_in_ptrs, bpr, PXSZ, c->d_tiles, sel, c->spt, c->d_scratch, c->d_k_n, c->d_ctx_n, c->d_blk_sz, c->d_tile_hdr, c->d_off, c->d_out_ptrs);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->h_total, c->d_totals, (uint64_t)nimg * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(c->h_total, c->d_totals, (uint64_t)e.images * 8, hipMemcpyDeviceToHost, s));
     return 0;
 }
 
@@ -515,7 +555,7 @@ static int ensure_m2(xpnghip_ctx *c) {
     std::vector<uint64_t> sb(VN);
     uint64_t o = 0;
     for (uint64_t v = 0; v < VN; v++) { sb[v] = o; if (v % N >= c->r0 && v % N < c->r1) o += m2_tile_scratch(c->tiles[v % N].n); }
-    // (d_flags2 and d_mt2 are the encode's: a mixed context never encodes)
+    // (d_flags2 and d_mt2 are the encode's: a mixed context allocates them with its first level-2 encode, launch_encode_m2)
     if (hipMalloc((void **)&c->d_scratch2, o + 8192) != hipSuccess || hipMalloc((void **)&c->d_sbase2, VN * 8) != hipSuccess ||
         (!c->mixed && hipMalloc((void **)&c->d_flags2, VN * 4) != hipSuccess) || hipMalloc((void **)&c->d_stream_n2, VN * M2_SLOTS * 4) != hipSuccess ||
         hipMalloc((void **)&c->d_blk2, VN * M2_SLOTS * sizeof(M2Blk)) != hipSuccess || (!c->mixed && hipMalloc((void **)&c->d_mt2, VN * sizeof(M2Tile)) != hipSuccess) ||
@@ -527,11 +567,19 @@ static int ensure_m2(xpnghip_ctx *c) {
 }
 
 // mode 2: RGB only (libxpng.c:755 sends RGBA to mode 1 before the tile stage)
-static int launch_encode_m2(xpnghip_ctx *c, uint32_t nimg, uint32_t t0, uint32_t t1, hipStream_t s) {
+static int launch_encode_m2(xpnghip_ctx *c, const EncSpan &e, hipStream_t s) {
     if (ensure_m2(c)) return 1;
-    const uint32_t cnt = t1 - t0, total = nimg * cnt;
-    const TileSel sel{t0, cnt, (uint32_t)c->tiles.size(), nimg, nullptr};
-    const uint64_t bpr = c->W * 3, VN = (uint64_t)c->B * sel.N;
+    const uint32_t t0 = e.t0, t1 = e.t0 + e.cnt, cnt = e.cnt, nimg = e.nimg, total = nimg * cnt;
+    const TileSel sel{t0, cnt, e.N, nimg, nullptr};
+    const uint64_t bpr = e.bpr, VN = e.VN;
+    if (c->mixed && !c->d_flags2) {
+        if (hipMalloc((void **)&c->d_flags2, VN * 4) != hipSuccess) return fail("hipMalloc failed (mode-2 encode workspace)");
+        c->ws_bytes += VN * 4;
+    }
+    if (c->mixed && !c->d_mt2) {
+        if (hipMalloc((void **)&c->d_mt2, VN * sizeof(M2Tile)) != hipSuccess) return fail("hipMalloc failed (mode-2 encode workspace)");
+        c->ws_bytes += VN * sizeof(M2Tile);
+    }
     uint32_t max_n = 0;
     for (uint32_t i = t0; i < t1; i++) max_n = c->tiles[i].n > max_n ? c->tiles[i].n : max_n;
     XPNG_REQUIRE(c->d_scratch2, c->d_sbase2, c->d_flags2, c->d_stream_n2, c->d_blk2, c->d_mt2, c->d_in_ptrs, c->d_out_ptrs, c->d_tiles, c->d_sums, c->d_tile_sz, c->d_off,
@@ -540,7 +588,7 @@ static int launch_encode_m2(xpnghip_ctx *c, uint32_t nimg, uint32_t t0, uint32_t
     HIPCHK(hipMemsetAsync(c->d_stream_n2, 0, VN * M2_SLOTS * 4, s));
     HIPCHK(hipMemsetAsync(c->d_blk2, 0, VN * M2_SLOTS * sizeof(M2Blk), s));
     k_m2_classify<<<total * 16, 256, 0, s>>>(c->d_in_ptrs, bpr, c->d_tiles, sel, 16, c->d_flags2);
-    if (launch_transform<3>(c, nimg, t0, t1, s, 0, true)) return 1;  // chooser (PXSZ = 3, libxpng.c:663) + residual planes (allocates them on first use) + nl histogram
+    if (launch_transform<3>(c, e, s, 0, true)) return 1;  // chooser (PXSZ = 3, libxpng.c:663) + residual planes (allocates them on first use) + nl histogram
     XPNG_REQUIRE(c->d_planes);
     k_m2_count<<<total, 64, 0, s>>>(c->d_tiles, sel, c->d_flags2, c->d_nlh, c->nlh_slots, c->nlh_generic, c->d_stream_n2);  // stream lengths -> where every stream goes
     if (small_blocks((uint64_t)total * M2_STREAMS)) k_m2_streams<256><<<total, 256, 0, s>>>(c->d_tiles, sel, c->d_flags2, c->d_planes, c->plane_stride, c->d_scratch2, c->d_sbase2, c->d_stream_n2);
@@ -564,10 +612,11 @@ static int launch_encode_m2(xpnghip_ctx *c, uint32_t nimg, uint32_t t0, uint32_t
     }
     k_m2_select<<<(total + 255) / 256, 256, 0, s>>>(c->d_tiles, sel, total, c->d_flags2, c->d_blk2, c->d_mt2, c->d_tile_sz);
     k_m2_bits<<<total, 256, 0, s>>>(c->d_in_ptrs, bpr, c->d_tiles, sel, c->d_mt2, c->d_blk2, c->d_scratch2, c->d_sbase2, c->d_stream_n2);
-    k_tile_offsets<<<nimg, 256, 0, s>>>(c->d_tile_sz, cnt, c->d_off, c->d_totals);
+    if (c->mixed) k_tile_offsets_seg<<<e.images, 256, 0, s>>>(c->d_tile_sz, c->d_m_first, c->d_off, c->d_totals);
+    else k_tile_offsets<<<nimg, 256, 0, s>>>(c->d_tile_sz, cnt, c->d_off, c->d_totals);
     k_m2_gather<<<total, 256, 0, s>>>(c->d_in_ptrs, bpr, c->d_tiles, sel, c->d_sums, c->d_mt2, c->d_blk2, c->d_scratch2, c->d_sbase2, c->d_off, c->d_out_ptrs);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->h_total, c->d_totals, (uint64_t)nimg * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(c->h_total, c->d_totals, (uint64_t)e.images * 8, hipMemcpyDeviceToHost, s));
     return 0;
 }
 
@@ -582,8 +631,8 @@ extern "C" int xpnghip_encode_device_batch(xpnghip_ctx *c, int mode, const void 
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(c);
     if (set_ptrs(c, d_rasters, d_blobs, nimg, s)) return 1;
-    const int rc = mode == 2 ? launch_encode_m2(c, nimg, (uint32_t)t0, (uint32_t)t1, s)
-                   : c->pxsz == 4 ? launch_encode_m1<4>(c, nimg, (uint32_t)t0, (uint32_t)t1, s) : launch_encode_m1<3>(c, nimg, (uint32_t)t0, (uint32_t)t1, s);
+    const EncSpan e = enc_span(c, nimg, (uint32_t)t0, (uint32_t)t1);
+    const int rc = mode == 2 ? launch_encode_m2(c, e, s) : c->pxsz == 4 ? launch_encode_m1<4>(c, e, s) : launch_encode_m1<3>(c, e, s);
     if (rc) return rc;
     if (blobs_len) {
         HIPCHK(hipStreamSynchronize(s));
@@ -822,7 +871,7 @@ static int ctx_create_mixed_impl(xpnghip_ctx **out, int device, const uint64_t *
         return true;
     };
     // what a decode needs, sized from M and nimg; planes / arena, decode tables and level-2 tables follow on first use (ensure_arena,
-    // decode_ws_prepare, ensure_m2), sized from M and the summed plane lengths too.  No encode workspace at all.
+    // decode_ws_prepare, ensure_m2), sized from M and the summed plane lengths too.  The encode workspace: ensure_mixed_encode.
     if (!alloc((void **)&c->d_tiles, M * sizeof(TileDesc)) || !alloc((void **)&c->d_blob_len, (uint64_t)nimg * 8) || !alloc((void **)&c->d_status, 64) ||
         !alloc((void **)&c->d_dec_in_ptrs, (uint64_t)nimg * 8) || !alloc((void **)&c->d_dec_out_ptrs, (uint64_t)nimg * 8) ||
         !alloc((void **)&c->d_m_first, meta.size()) || hipHostMalloc((void **)&c->h_total, (uint64_t)nimg * 8 + 64) != hipSuccess ||
@@ -843,6 +892,21 @@ extern "C" int xpnghip_ctx_create_mixed(xpnghip_ctx **out, int device, const uin
 }
 extern "C" uint64_t xpnghip_ctx_mixed_first_tile(const xpnghip_ctx *c, uint32_t image) {
     return c && c->mixed && image < c->m_first.size() ? c->m_first[image] : ~0ull;
+}
+
+// The staging raster of the tight forms (decode: reconstruct into it, k_mixed_copy out of it; encode: k_mixed_pack into it, the
+// kernels read it): image i's h_i rows at the pitch bpr in slot[i], every slot 256-byte aligned, 256 spare bytes behind the last.
+// ONE layout and one buffer for both directions; allocated by the first tight call, never shrunk.
+static int mixed_stage_slots(xpnghip_ctx *c, uint64_t bpr, std::vector<uint64_t> &slot) {
+    const uint32_t nimg = c->B;
+    slot.assign((size_t)nimg + 1, 0);
+    for (uint32_t i = 0; i < nimg; i++) slot[i + 1] = slot[i] + rup(c->m_dims[2ull * i + 1] * bpr, 256);
+    const uint64_t need = slot[nimg] + 256;
+    if (c->cap_m_stage >= need) return 0;
+    if (c->d_m_stage) return fail("internal error: the staging raster of a mixed context was allocated for another layout");  // (bpr is a function of the context: this cannot happen)
+    HIPCHK(hipMalloc((void **)&c->d_m_stage, need));
+    c->cap_m_stage = need; c->ws_bytes += need;
+    return 0;
 }
 
 static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
@@ -868,12 +932,8 @@ static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *
     if (!out_bpr) {
         // tight rasters: reconstruct into a staging raster at the widest image's pitch, rounded up to 16 bytes (image i: h_i rows,
         // its slot 256-byte aligned), then k_mixed_copy moves every image out at its own pitch
-        std::vector<uint64_t> slot((size_t)nimg + 1, 0);
-        for (uint32_t i = 0; i < nimg; i++) slot[i + 1] = slot[i] + rup(c->m_dims[2ull * i + 1] * bpr, 256);
-        if (!c->d_m_stage) {
-            HIPCHK(hipMalloc((void **)&c->d_m_stage, slot[nimg] + 256));
-            c->cap_m_stage = slot[nimg] + 256; c->ws_bytes += c->cap_m_stage;
-        }
+        std::vector<uint64_t> slot;
+        if (mixed_stage_slots(c, bpr, slot)) return 1;
         if (!c->d_m_copy) {
             HIPCHK(hipMalloc((void **)&c->d_m_copy, (uint64_t)nimg * sizeof(MixedCopy)));
             c->ws_bytes += (uint64_t)nimg * sizeof(MixedCopy);
@@ -903,6 +963,97 @@ static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *
 extern "C" int xpnghip_decode_mixed_device_batch(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
                                                  const uint64_t *tile_off, void *const *d_outs, uint64_t out_bpr, void *stream) {
     try { return decode_mixed_batch_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, d_outs, out_bpr, stream); }
+    catch (const std::bad_alloc &) { return fail("out of host memory"); }
+    catch (...) { return fail("unexpected C++ exception"); }
+}
+
+// ---- mixed-size batch encode (mixed.hpp) ---------------------------------------------------------
+// The encode workspace of a mixed context, allocated by its first encode: what ctx_create_range_impl allocates for an ordinary
+// context, sized from M (the concatenated table) and nimg.  The planes, the stream scratch and the level-2 buffers follow in the
+// launch sequences (ensure_planes, ensure_scratch, ensure_m2 / launch_encode_m2).
+static int ensure_mixed_encode(xpnghip_ctx *c) {
+    if (c->m_enc) return 0;
+    const uint64_t M = c->tiles.size(), nimg = c->B;
+    for (const TileDesc &t : c->tiles) c->nlh_slots = std::max(c->nlh_slots, std::max(nlh_records(t.w, t.h, false), nlh_records(t.w, t.h, true)));
+    auto alloc = [&](void **p, uint64_t bytes) {
+        if (*p) return true;  // (an earlier attempt got this far)
+        if (hipMalloc(p, bytes) != hipSuccess) return false;
+        c->ws_bytes += bytes;
+        return true;
+    };
+    if (!alloc((void **)&c->d_sums, M * 16) || !alloc((void **)&c->d_nlh, M * c->nlh_slots * NLH_STRIDE * 4 + 64) || !alloc((void **)&c->d_ctx_n, M * 9 * 4) ||
+        !alloc((void **)&c->d_k_n, M * 4) || !alloc((void **)&c->d_blk_sz, M * 10 * 4) || !alloc((void **)&c->d_tile_sz, M * 4) ||
+        !alloc((void **)&c->d_tile_hdr, M * 4) || !alloc((void **)&c->d_off, (M + nimg) * 8) || !alloc((void **)&c->d_totals, nimg * 8) ||
+        !alloc((void **)&c->d_wprep, M * 10 * sizeof(WPrep)) || !alloc((void **)&c->d_wtab, M * WTAB_TILE_BYTES + 4096 + watab_bytes(M)) ||
+        !alloc((void **)&c->d_wF, M * 10 * 512) || !alloc((void **)&c->d_in_ptrs, nimg * 8) || !alloc((void **)&c->d_out_ptrs, nimg * 8))
+        return fail("hipMalloc failed (encode workspace of a mixed context)");
+    c->m_enc = true;  // (from here on scratch_bytes() includes the encode's share)
+    return 0;
+}
+
+static int encode_varsize_impl(xpnghip_ctx *c, int mode, const void *const *d_rasters, uint64_t in_bpr, uint32_t nimg, void *const *d_blobs,
+                               uint64_t *blobs_len, void *stream) {
+    // every argument is checked before anything reaches the device: a rejected call writes nothing
+    if (!c) return fail("null context");
+    if (!c->mixed) return fail("not a mixed context (xpnghip_ctx_create_mixed)");
+    if (mode != 1 && mode != 2) return fail("tile mode must be 1 or 2");
+    if (mode == 2 && c->pxsz != 3) return fail("mode 2 codes RGB only (the driver sends RGBA to mode 1, libxpng.c:755)");
+    if (nimg != c->B) return fail("nimg is " + std::to_string(nimg) + ", the mixed context holds " + std::to_string(c->B) + " images");
+    if (!d_rasters || !d_blobs) return fail("null argument");
+    const uint64_t px = (uint64_t)c->pxsz, widest = c->m_max_w * px;
+    if (in_bpr && in_bpr < widest)
+        return fail("in_bpr " + std::to_string(in_bpr) + " is smaller than the widest row of the batch (" + std::to_string(widest) + " bytes)");
+    for (uint32_t i = 0; i < nimg; i++) {
+        if (!d_rasters[i] || !d_blobs[i]) return fail("null raster or blob buffer of image " + std::to_string(i));
+        if ((uintptr_t)d_blobs[i] & 3) return fail("blob buffer of image " + std::to_string(i) + " must be 4-byte aligned");
+        if (in_bpr && ((uintptr_t)d_rasters[i] & 15)) return fail("padded raster of image " + std::to_string(i) + " must be 16-byte aligned");
+        if (c->pxsz == 4 && (c->m_dims[2ull * i] < 4 || c->m_dims[2ull * i + 1] < 4))
+            return fail("RGBA image " + std::to_string(i) + " is narrower than 4 px: undefined in the reference; store level 7");
+    }
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(c);
+    if (ensure_mixed_encode(c)) return 1;
+    const uint64_t bpr = in_bpr ? in_bpr : rup(widest, 16);
+    std::vector<const void *> base(d_rasters, d_rasters + nimg);
+    if (!in_bpr) {
+        // tight rasters: k_mixed_pack brings every image into the staging raster at the widest image's pitch, rounded up to 16 bytes
+        // (image i: h_i rows, its slot 256-byte aligned - the buffer, and the layout, of the tight decode), and the kernels read that
+        std::vector<uint64_t> slot;
+        if (mixed_stage_slots(c, bpr, slot)) return 1;
+        if (!c->d_m_pack) {
+            HIPCHK(hipMalloc((void **)&c->d_m_pack, (uint64_t)nimg * sizeof(MixedPack)));
+            c->ws_bytes += (uint64_t)nimg * sizeof(MixedPack);
+        }
+        if (c->h_m_pack_src != base) {  // (pageable host memory: the copy is staged synchronously anyway)
+            std::vector<MixedPack> mp(nimg);
+            for (uint32_t i = 0; i < nimg; i++)
+                mp[i] = MixedPack{slot[i], (const uint8_t *)d_rasters[i], (uint32_t)(c->m_dims[2ull * i] * px), (uint32_t)c->m_dims[2ull * i + 1]};
+            c->h_m_pack_src.clear();
+            HIPCHK(hipMemcpyAsync(c->d_m_pack, mp.data(), (uint64_t)nimg * sizeof(MixedPack), hipMemcpyHostToDevice, s));
+            HIPCHK(hipStreamSynchronize(s));
+            c->h_m_pack_src = base;
+        }
+        for (uint32_t i = 0; i < nimg; i++) base[i] = c->d_m_stage + slot[i];
+    }
+    if (set_ptrs(c, base.data(), d_blobs, nimg, s)) return 1;
+    XPNG_REQUIRE(c->d_m_first, c->d_m_list);
+    if (!in_bpr) {
+        XPNG_REQUIRE(c->d_m_stage, c->d_m_pack);
+        k_mixed_pack<<<dim3((uint32_t)((c->m_max_h + MC_ROWS - 1) / MC_ROWS), nimg), 256, 0, s>>>(c->d_m_pack, c->d_m_stage, bpr);
+        HIPCHK(hipGetLastError());
+    }
+    const EncSpan e = enc_span_mixed(c, bpr);
+    const int rc = mode == 2 ? launch_encode_m2(c, e, s) : c->pxsz == 4 ? launch_encode_m1<4>(c, e, s) : launch_encode_m1<3>(c, e, s);
+    if (rc) return rc;
+    if (blobs_len) {
+        HIPCHK(hipStreamSynchronize(s));
+        for (uint32_t b = 0; b < nimg; b++) blobs_len[b] = c->h_total[b];
+    }
+    return 0;
+}
+extern "C" int xpnghip_encode_varsize_device_batch(xpnghip_ctx *c, int mode, const void *const *d_rasters, uint64_t in_bpr, uint32_t nimg,
+                                                   void *const *d_blobs, uint64_t *blobs_len, void *stream) {
+    try { return encode_varsize_impl(c, mode, d_rasters, in_bpr, nimg, d_blobs, blobs_len, stream); }
     catch (const std::bad_alloc &) { return fail("out of host memory"); }
     catch (...) { return fail("unexpected C++ exception"); }
 }
@@ -948,7 +1099,7 @@ extern "C" int xpnghip_probes_built(void) { return 0; }
 #endif
 
 extern "C" int64_t xpnghip_debug_fetch(xpnghip_ctx *c, int what, uint64_t tile, void *out, uint64_t cap) {
-    if (!c || c->mixed || tile >= c->tiles.size() || !out) return -1;  // (a mixed context never encodes: nothing to fetch)
+    if (!c || c->mixed || tile >= c->tiles.size() || !out) return -1;  // (the introspection is the ordinary context's)
     if (hipSetDevice(c->device) != hipSuccess || (c->stream && hipStreamSynchronize(c->stream) != hipSuccess)) return -1;  // (debug_fetch follows a call that synchronised its stream or used this one)
     const TileDesc &t = c->tiles[tile];
     const uint8_t *src = nullptr;
