@@ -287,6 +287,35 @@ int xpnghip_decode_mixed(int mode, int pxsz, uint32_t nimg, const uint8_t *const
 int xpnghip_encode_varsize_device_batch(xpnghip_ctx *ctx, int mode, const void *const *d_rasters, uint64_t in_bpr,
                                         uint32_t nimg, void *const *d_blobs, uint64_t *blobs_len, void *stream);
 
+/* ---- layouts: decode into and encode from planar, BGR and 3/4-channel device buffers (INTEGRATION.md "Layouts") ----------
+ * The two calls above hand pixels over in the file's own form, interleaved R,G,B[,A].  The two below take a LAYOUT word for the
+ * caller's buffers and do the rearrangement in the copy pass the tight forms already pay (the kernel that moves every image out of,
+ * or into, the staging raster), so it costs no further pass over the pixels and no second copy of the batch. */
+#define XPNGHIP_LAYOUT_PLANAR 0x001u  /* (C, H, W): plane c is h*w bytes at byte offset c*h*w, rows of w bytes back to back.
+                                         Clear: interleaved (H, W, C), rows of w*C bytes back to back */
+#define XPNGHIP_LAYOUT_BGR    0x002u  /* colour order B, G, R; alpha, when present, stays the last channel */
+#define XPNGHIP_LAYOUT_C3     0x300u  /* bits 8..11 = channels C of the CALLER's buffers: 3 or 4; 0 = the context's pxsz */
+#define XPNGHIP_LAYOUT_C4     0x400u
+/* host-only: C (3 or 4) of a buffer of this layout on a context of `pxsz` bytes per pixel; -1 for unknown bits, a channel
+ * field other than 0/3/4, or pxsz other than 3/4 */
+int xpnghip_layout_channels(uint32_t layout, int pxsz);
+/* Buffers in a layout are always TIGHT: image i is exactly C * w_i * h_i bytes at any alignment; nothing before or behind them is
+ * read or written (there is no pitch).  The layout is checked with the other arguments before anything reaches the device: a
+ * rejected call writes nothing and xpnghip_last_error() names the layout.
+ *
+ * Decode: xpnghip_decode_mixed_device_batch with out_bpr == 0 in everything but the copy-out - same checks, blobs, size walk,
+ * xpnghip_ctx_decode_status and staging raster (STAGING SIZE above; no second buffer).  C == pxsz passes the channels through;
+ * C == 4 on an RGB context writes alpha 255; C == 3 on an RGBA context drops alpha (the colours are the file's: a pixel of alpha 0
+ * is 0,0,0, as the format stores it).  Layout 0 gives byte for byte what the tight form gives (it IS the tight form). */
+int xpnghip_decode_varsize_device_batch_as(xpnghip_ctx *ctx, int mode, const void *const *d_blobs, const uint64_t *blobs_len,
+                                           uint32_t nimg, const uint64_t *tile_off, void *const *d_outs, uint32_t layout, void *stream);
+/* Encode: xpnghip_encode_varsize_device_batch with in_bpr == 0 in everything but the pack-in.  C must equal the context's pxsz - a
+ * lossless encoder does not drop or invent a channel - and a mismatch is refused with both numbers in the text.  The blobs are
+ * byte for byte those of the tight-form encode of the equivalent interleaved R,G,B[,A] raster.  Of the caller's buffers only the
+ * aligned dwords they occupy are read. */
+int xpnghip_encode_varsize_device_batch_from(xpnghip_ctx *ctx, int mode, const void *const *d_rasters, uint32_t layout,
+                                             uint32_t nimg, void *const *d_blobs, uint64_t *blobs_len, void *stream);
+
 /* Stage-only run for BASELINE config 2: predictor chooser + per-pixel transform (libxpng.c:92-140 and
  * the arithmetic of 497-519) over tiles [t0, t1); symbol planes stay in the context's workspace. */
 int xpnghip_m1_transform_device(xpnghip_ctx *ctx, const void *d_raster, uint64_t t0, uint64_t t1, void *stream);

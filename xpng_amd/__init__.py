@@ -7,8 +7,8 @@ torch.distributed sharding.  It never falls back to a CPU codec: if the HIP libr
 is visible, compute calls raise.
 """
 from .api import (Context, MixedContext, StagedImages, XpngError, build_native, decode_mixed, decode_region, decode_tiles, device_count,
-                  encode_tiles, hip_lib, host_lib, load, load_batch, load_region, native_paths, normalize_device, region_tiles, store, store_batch)
+                  encode_tiles, hip_lib, host_lib, layout, layout_channels, load, load_batch, load_region, native_paths, normalize_device, region_tiles, store, store_batch)
 
 __all__ = ["Context", "MixedContext", "StagedImages", "XpngError", "build_native", "decode_mixed", "decode_region", "decode_tiles", "device_count",
-           "encode_tiles", "hip_lib", "host_lib", "load", "load_batch", "load_region", "native_paths", "normalize_device",
+           "encode_tiles", "hip_lib", "host_lib", "layout", "layout_channels", "load", "load_batch", "load_region", "native_paths", "normalize_device",
            "region_tiles", "store", "store_batch"]

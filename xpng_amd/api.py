@@ -32,6 +32,7 @@ HIP_SYMBOLS = [
     "xpnghip_encode_varsize_device_batch",
     "xpnghip_images_begin", "xpnghip_images_single_colour", "xpnghip_images_encode", "xpnghip_images_fetch", "xpnghip_images_end",
     "xpnghip_images_first_pixel", "xpnghip_batch_cuts",
+    "xpnghip_layout_channels", "xpnghip_decode_varsize_device_batch_as", "xpnghip_encode_varsize_device_batch_from",
 ]
 HOST_SYMBOLS = ["xpng_store", "xpng_load", "xpng_from_jpg", "xpng_store_T", "xpng_load_T", "xpng_from_jpg_T",
                 "store_7", "load_7"]
@@ -154,6 +155,13 @@ def _bind_hip(path):
                                                         C.POINTER(vp), u64, vp]
         L.xpnghip_encode_varsize_device_batch.restype = C.c_int
         L.xpnghip_encode_varsize_device_batch.argtypes = [vp, C.c_int, C.POINTER(vp), u64, C.c_uint32, C.POINTER(vp), C.POINTER(u64), vp]
+        L.xpnghip_layout_channels.restype = C.c_int
+        L.xpnghip_layout_channels.argtypes = [C.c_uint32, C.c_int]
+        L.xpnghip_decode_varsize_device_batch_as.restype = C.c_int
+        L.xpnghip_decode_varsize_device_batch_as.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64), C.c_uint32, C.POINTER(u64),
+                                                             C.POINTER(vp), C.c_uint32, vp]
+        L.xpnghip_encode_varsize_device_batch_from.restype = C.c_int
+        L.xpnghip_encode_varsize_device_batch_from.argtypes = [vp, C.c_int, C.POINTER(vp), C.c_uint32, C.c_uint32, C.POINTER(vp), C.POINTER(u64), vp]
         u8p = C.POINTER(C.c_uint8)
         L.xpnghip_images_begin.restype = C.c_int
         L.xpnghip_images_begin.argtypes = [C.POINTER(vp), C.c_uint32, C.POINTER(vp), C.POINTER(u64), u8p, u8p]
@@ -431,6 +439,25 @@ def batch_cuts(dims, pxsz, max_images: int = 4096, max_bytes: int = 2 << 30) -> 
     if n < 0:
         raise XpngError("xpnghip_batch_cuts failed")
     return list(starts[:n])
+
+
+LAYOUT_PLANAR, LAYOUT_BGR = 0x001, 0x002  # include/xpng_hip.h XPNGHIP_LAYOUT_*; the channels of the caller's buffers sit in bits 8..11
+
+
+def layout(planar: bool = False, bgr: bool = False, channels: int = 0) -> int:
+    """The layout word of a device buffer (include/xpng_hip.h XPNGHIP_LAYOUT_*): planar (C, H, W) or interleaved (H, W, C),
+    B,G,R or R,G,B colour order, channels 3, 4 or 0 = what the context has."""
+    if channels not in (0, 3, 4):
+        raise XpngError(f"layout: channels must be 0 (the context's), 3 or 4, not {channels!r}")
+    return (LAYOUT_PLANAR if planar else 0) | (LAYOUT_BGR if bgr else 0) | (channels << 8)
+
+
+def layout_channels(layout: int, pxsz: int) -> int:
+    """Channels of a buffer of this layout on a context of pxsz bytes per pixel (xpnghip_layout_channels; host-only)."""
+    n = hip_lib().xpnghip_layout_channels(layout, pxsz)
+    if n < 0:
+        raise XpngError(f"bad layout word {layout:#x} or pxsz {pxsz}")
+    return n
 
 
 def store_batch(mode: int, rasters, paths) -> None:
@@ -711,6 +738,29 @@ class MixedContext:
         ins, outs, ln = (C.c_void_p * k)(*d_blobs), (C.c_void_p * len(d_outs))(*d_outs), (C.c_uint64 * len(lens))(*lens)
         if hip_lib().xpnghip_decode_mixed_device_batch(self._h, mode, ins, ln, k, off_arr, outs, out_bpr, stream):
             raise XpngError("xpnghip_decode_mixed_device_batch: " + _err())
+
+
+    def decode_batch_as(self, mode, d_blobs, lens, d_outs, layout, tile_offs=None, stream=0):
+        """decode_batch in its tight form, with every d_outs[i] written in `layout` (api.layout(); C * w * h bytes at any
+        alignment): xpnghip_decode_varsize_device_batch_as."""
+        k = len(d_blobs)
+        off_arr = None
+        if tile_offs is not None:
+            flat = [o for offs in tile_offs for o in offs]
+            assert len(flat) == self.n_tiles
+            off_arr = (C.c_uint64 * len(flat))(*flat)
+        ins, outs, ln = (C.c_void_p * k)(*d_blobs), (C.c_void_p * len(d_outs))(*d_outs), (C.c_uint64 * len(lens))(*lens)
+        if hip_lib().xpnghip_decode_varsize_device_batch_as(self._h, mode, ins, ln, k, off_arr, outs, layout, stream):
+            raise XpngError("xpnghip_decode_varsize_device_batch_as: " + _err())
+
+    def encode_batch_from(self, mode, d_rasters, layout, d_blobs, stream=0, sync=True):
+        """encode_batch in its tight form, with every d_rasters[i] read in `layout` (api.layout(); its channels must be the
+        context's): xpnghip_encode_varsize_device_batch_from.  Returns the list of blob lengths (sync=True) or None."""
+        k = len(d_rasters)
+        ins, outs, lens = (C.c_void_p * k)(*d_rasters), (C.c_void_p * len(d_blobs))(*d_blobs), (C.c_uint64 * max(k, 1))()
+        if hip_lib().xpnghip_encode_varsize_device_batch_from(self._h, mode, ins, layout, k, outs, lens if sync else None, stream):
+            raise XpngError("xpnghip_encode_varsize_device_batch_from: " + _err())
+        return list(lens)[:k] if sync else None
 
 
 def walk_tile_offsets(blobs: bytes, n_tiles: int):

@@ -52,7 +52,7 @@ __global__ void k_m2_dec_parse(const uint8_t *const *__restrict__ blobs, const u
     const uint64_t avail = blob_len[t.img] > off[il] ? blob_len[t.img] - off[il] : 0;
     bool ok = avail >= 4;
     const uint32_t h0 = ok ? ld32u(d.blob) : 0, ty = h0 >> 24, L = h0 & 0xFFFFFF;
-    ok = ok && L <= avail && L >= 8;
+    ok = ok && L <= avail && L >= 5;  // (the shortest tile: its word and one byte; raw gray of three pixels is 7 bytes, libxpng.c:875-878)
     M2Blk *mb = blk + (uint64_t)tile * M2_SLOTS;
     uint32_t *sn = stream_n + (uint64_t)tile * M2_SLOTS;  // symbol counts of the tile's streams: where the decoded streams go (m2_off_stream)
     for (uint32_t s = 0; s < M2_SLOTS; s++) sn[s] = 0;
@@ -61,6 +61,7 @@ __global__ void k_m2_dec_parse(const uint8_t *const *__restrict__ blobs, const u
     else if ((ty >> 4) == 2) { d.kind = (ty & 8) ? 3 : 2; d.m = ty & 3; if (d.kind == 3) ok = ok && L == t.n + 4; }
     else if ((ty >> 4) == 1) { d.kind = 1; d.m = ty & 3; }
     else ok = false;
+    if (d.kind == 1 || d.kind == 2) ok = ok && L >= 8;
     if (ok && (d.kind == 1 || d.kind == 2)) {
         d.bsz = ld32u(d.blob + 4);
         ok = d.bsz >= 8 && (d.bsz & 3) == 0 && 4 + (uint64_t)d.bsz + 4 <= L;

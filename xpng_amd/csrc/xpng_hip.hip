@@ -184,6 +184,11 @@ struct xpnghip_ctx {
     std::vector<void *> h_m_copy_dst;  // the destinations d_m_copy holds (skip the upload when unchanged)
     MixedPack *d_m_pack = nullptr;     // tight input form of the encode: B pack records
     std::vector<const void *> h_m_pack_src;  // the sources d_m_pack holds
+    // buffers in a layout (XPNGHIP_LAYOUT_*): B records per direction.  A record holds the slot, the buffer, w and h -
+    // nothing that depends on the layout word, which only selects the kernel - so the pointers are the whole cache key
+    MixedLayout *d_m_as = nullptr, *d_m_from = nullptr;
+    std::vector<void *> h_m_as_dst;          // the destinations d_m_as holds
+    std::vector<const void *> h_m_from_src;  // the sources d_m_from holds
 };
 
 // the context's own stream, created when a call first needs it (the `stream == NULL` form of the device-resident entry points,
@@ -204,7 +209,7 @@ extern "C" void xpnghip_ctx_destroy(xpnghip_ctx *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void *ptrs[] = {c->d_tiles, c->d_planes, c->d_scratch, c->d_sums, c->d_nlh, c->d_ctx_n, c->d_k_n, c->d_blk_sz, c->d_tile_sz,
                     c->d_tile_hdr, c->d_off, c->d_totals, c->d_raster, c->d_blobs, c->d_blob_in, c->d_dbg, (void *)c->d_in_ptrs, (void *)c->d_out_ptrs, (void *)c->d_dec_in_ptrs, (void *)c->d_dec_out_ptrs, (void *)c->d_order,
-                    c->d_wprep, c->d_wtab, c->d_wF, c->d_blob_len, c->d_status, c->d_scratch2, c->d_sbase2, c->d_flags2, c->d_stream_n2, c->d_blk2, c->d_mt2, c->d_info2, c->d_tabs2, c->d_w1prep, c->d_w1tab, c->d_w1F, c->d_region_stage, c->d_region_meta, c->d_m_first, c->d_m_stage, c->d_m_copy, c->d_m_pack};
+                    c->d_wprep, c->d_wtab, c->d_wF, c->d_blob_len, c->d_status, c->d_scratch2, c->d_sbase2, c->d_flags2, c->d_stream_n2, c->d_blk2, c->d_mt2, c->d_info2, c->d_tabs2, c->d_w1prep, c->d_w1tab, c->d_w1F, c->d_region_stage, c->d_region_meta, c->d_m_first, c->d_m_stage, c->d_m_copy, c->d_m_pack, c->d_m_as, c->d_m_from};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->enc_side) (void)hipStreamDestroy(c->enc_side);
     if (c->ev_enc_fork) (void)hipEventDestroy(c->ev_enc_fork);
@@ -894,6 +899,51 @@ extern "C" uint64_t xpnghip_ctx_mixed_first_tile(const xpnghip_ctx *c, uint32_t 
     return c && c->mixed && image < c->m_first.size() ? c->m_first[image] : ~0ull;
 }
 
+// ---- layouts of the caller's buffers (XPNGHIP_LAYOUT_*; mixed.hpp) --------------------------------
+extern "C" int xpnghip_layout_channels(uint32_t layout, int pxsz) {
+    const uint32_t ch = (layout >> 8) & 0xFu;
+    if ((layout & ~(XPNGHIP_LAYOUT_PLANAR | XPNGHIP_LAYOUT_BGR | 0xF00u)) || (ch != 0 && ch != 3 && ch != 4) || (pxsz != 3 && pxsz != 4)) return -1;
+    return ch ? (int)ch : pxsz;
+}
+static std::string layout_hex(uint32_t layout) {
+    char b[16];
+    snprintf(b, sizeof b, "0x%x", layout);
+    return b;
+}
+// the per-image records of a layout call: image i's slot, its buffer and its size; uploaded when the buffers changed
+static int layout_records(xpnghip_ctx *c, MixedLayout **d_tab, const std::vector<uint64_t> &slot, const void *const *bufs, hipStream_t s) {
+    const uint32_t nimg = c->B;
+    if (!*d_tab) {
+        HIPCHK(hipMalloc((void **)d_tab, (uint64_t)nimg * sizeof(MixedLayout)));
+        c->ws_bytes += (uint64_t)nimg * sizeof(MixedLayout);
+    }
+    std::vector<MixedLayout> ml(nimg);
+    for (uint32_t i = 0; i < nimg; i++)
+        ml[i] = MixedLayout{slot[i], (uint8_t *)const_cast<void *>(bufs[i]), (uint32_t)c->m_dims[2ull * i], (uint32_t)c->m_dims[2ull * i + 1]};
+    HIPCHK(hipMemcpyAsync(*d_tab, ml.data(), (uint64_t)nimg * sizeof(MixedLayout), hipMemcpyHostToDevice, s));  // (pageable host memory: the copy is staged synchronously anyway)
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+template <int PX>
+static void launch_copy_as(const xpnghip_ctx *c, uint32_t layout, int C, uint64_t bpr, hipStream_t s) {
+    const dim3 grid((uint32_t)((c->m_max_h + MC_ROWS - 1) / MC_ROWS), c->B);
+    const uint32_t bgr = layout & XPNGHIP_LAYOUT_BGR;
+    if (layout & XPNGHIP_LAYOUT_PLANAR) {
+        if (C == 3) k_mixed_copy_as<PX, 3, true><<<grid, 256, 0, s>>>(c->d_m_as, c->d_m_stage, bpr, bgr);
+        else k_mixed_copy_as<PX, 4, true><<<grid, 256, 0, s>>>(c->d_m_as, c->d_m_stage, bpr, bgr);
+    } else {
+        if (C == 3) k_mixed_copy_as<PX, 3, false><<<grid, 256, 0, s>>>(c->d_m_as, c->d_m_stage, bpr, bgr);
+        else k_mixed_copy_as<PX, 4, false><<<grid, 256, 0, s>>>(c->d_m_as, c->d_m_stage, bpr, bgr);
+    }
+}
+template <int PX>
+static void launch_pack_from(const xpnghip_ctx *c, uint32_t layout, uint64_t bpr, hipStream_t s) {
+    const dim3 grid((uint32_t)((c->m_max_h + MC_ROWS - 1) / MC_ROWS), c->B);
+    const uint32_t bgr = layout & XPNGHIP_LAYOUT_BGR;
+    if (layout & XPNGHIP_LAYOUT_PLANAR) k_mixed_pack_from<PX, true><<<grid, 256, 0, s>>>(c->d_m_from, c->d_m_stage, bpr, bgr);
+    else k_mixed_pack_from<PX, false><<<grid, 256, 0, s>>>(c->d_m_from, c->d_m_stage, bpr, bgr);
+}
+
 // The staging raster of the tight forms (decode: reconstruct into it, k_mixed_copy out of it; encode: k_mixed_pack into it, the
 // kernels read it): image i's h_i rows at the pitch bpr in slot[i], every slot 256-byte aligned, 256 spare bytes behind the last.
 // ONE layout and one buffer for both directions; allocated by the first tight call, never shrunk.
@@ -909,11 +959,16 @@ static int mixed_stage_slots(xpnghip_ctx *c, uint64_t bpr, std::vector<uint64_t>
     return 0;
 }
 
+// `layout` != NULL: the call of xpnghip_decode_varsize_device_batch_as (out_bpr == 0: its buffers are tight)
 static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
-                                   const uint64_t *tile_off, void *const *d_outs, uint64_t out_bpr, void *stream) {
+                                   const uint64_t *tile_off, void *const *d_outs, uint64_t out_bpr, void *stream, const uint32_t *layout = nullptr) {
     // every argument is checked before anything reaches the device: a rejected call writes nothing
     if (!c) return fail("null context");
     if (!c->mixed) return fail("not a mixed context (xpnghip_ctx_create_mixed)");
+    const int C = layout ? xpnghip_layout_channels(*layout, c->pxsz) : c->pxsz;
+    if (C < 0) return fail("bad layout word " + layout_hex(*layout) + " (XPNGHIP_LAYOUT_PLANAR | XPNGHIP_LAYOUT_BGR | channels 0, 3 or 4 in bits 8..11)");
+    // (interleaved, the file's colour order and channel count: the tight form itself, k_mixed_copy and its records)
+    const bool as = layout && ((*layout & (XPNGHIP_LAYOUT_PLANAR | XPNGHIP_LAYOUT_BGR)) || C != c->pxsz);
     if (mode != 1 && mode != 2) return fail("tile mode must be 1 or 2");
     if (mode == 2 && c->pxsz != 3) return fail("mode 2 codes RGB only");
     if (nimg != c->B) return fail("nimg is " + std::to_string(nimg) + ", the mixed context holds " + std::to_string(c->B) + " images");
@@ -934,11 +989,17 @@ static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *
         // its slot 256-byte aligned), then k_mixed_copy moves every image out at its own pitch
         std::vector<uint64_t> slot;
         if (mixed_stage_slots(c, bpr, slot)) return 1;
-        if (!c->d_m_copy) {
+        if (as) {
+            if (c->h_m_as_dst != base) {
+                c->h_m_as_dst.clear();
+                if (layout_records(c, &c->d_m_as, slot, d_outs, s)) return 1;
+                c->h_m_as_dst = base;
+            }
+        } else if (!c->d_m_copy) {
             HIPCHK(hipMalloc((void **)&c->d_m_copy, (uint64_t)nimg * sizeof(MixedCopy)));
             c->ws_bytes += (uint64_t)nimg * sizeof(MixedCopy);
         }
-        if (c->h_m_copy_dst != base) {  // (pageable host memory: the copy is staged synchronously anyway)
+        if (!as && c->h_m_copy_dst != base) {  // (pageable host memory: the copy is staged synchronously anyway)
             std::vector<MixedCopy> mc(nimg);
             for (uint32_t i = 0; i < nimg; i++)
                 mc[i] = MixedCopy{slot[i], (uint8_t *)d_outs[i], (uint32_t)(c->m_dims[2ull * i] * px), (uint32_t)c->m_dims[2ull * i + 1]};
@@ -953,7 +1014,12 @@ static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *
     XPNG_REQUIRE(c->d_m_first, c->d_m_list);
     const int rc = dec_launch(c, mode, nimg, c->m_max_w, tile_off, s, 0, (uint32_t)c->tiles.size(), &c->m_list, c->d_m_list, bpr);
     if (rc) return rc;
-    if (!out_bpr) {
+    if (as) {
+        XPNG_REQUIRE(c->d_m_stage, c->d_m_as);
+        if (c->pxsz == 4) launch_copy_as<4>(c, *layout, C, bpr, s);
+        else launch_copy_as<3>(c, *layout, C, bpr, s);
+        HIPCHK(hipGetLastError());
+    } else if (!out_bpr) {
         XPNG_REQUIRE(c->d_m_stage, c->d_m_copy);
         k_mixed_copy<<<dim3((uint32_t)((c->m_max_h + MC_ROWS - 1) / MC_ROWS), nimg), 256, 0, s>>>(c->d_m_copy, c->d_m_stage, bpr);
         HIPCHK(hipGetLastError());
@@ -963,6 +1029,12 @@ static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *
 extern "C" int xpnghip_decode_mixed_device_batch(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
                                                  const uint64_t *tile_off, void *const *d_outs, uint64_t out_bpr, void *stream) {
     try { return decode_mixed_batch_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, d_outs, out_bpr, stream); }
+    catch (const std::bad_alloc &) { return fail("out of host memory"); }
+    catch (...) { return fail("unexpected C++ exception"); }
+}
+extern "C" int xpnghip_decode_varsize_device_batch_as(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
+                                                      const uint64_t *tile_off, void *const *d_outs, uint32_t layout, void *stream) {
+    try { return decode_mixed_batch_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, d_outs, 0, stream, &layout); }
     catch (const std::bad_alloc &) { return fail("out of host memory"); }
     catch (...) { return fail("unexpected C++ exception"); }
 }
@@ -991,11 +1063,18 @@ static int ensure_mixed_encode(xpnghip_ctx *c) {
     return 0;
 }
 
+// `layout` != NULL: the call of xpnghip_encode_varsize_device_batch_from (in_bpr == 0: its buffers are tight)
 static int encode_varsize_impl(xpnghip_ctx *c, int mode, const void *const *d_rasters, uint64_t in_bpr, uint32_t nimg, void *const *d_blobs,
-                               uint64_t *blobs_len, void *stream) {
+                               uint64_t *blobs_len, void *stream, const uint32_t *layout = nullptr) {
     // every argument is checked before anything reaches the device: a rejected call writes nothing
     if (!c) return fail("null context");
     if (!c->mixed) return fail("not a mixed context (xpnghip_ctx_create_mixed)");
+    const int C = layout ? xpnghip_layout_channels(*layout, c->pxsz) : c->pxsz;
+    if (C < 0) return fail("bad layout word " + layout_hex(*layout) + " (XPNGHIP_LAYOUT_PLANAR | XPNGHIP_LAYOUT_BGR | channels 0, 3 or 4 in bits 8..11)");
+    if (C != c->pxsz)
+        return fail("the layout has " + std::to_string(C) + " channels, the context " + std::to_string(c->pxsz) + " bytes per pixel: a lossless encoder does not drop or invent a channel");
+    // (interleaved in the file's colour order: the tight form itself, k_mixed_pack and its records)
+    const bool from = layout && (*layout & (XPNGHIP_LAYOUT_PLANAR | XPNGHIP_LAYOUT_BGR));
     if (mode != 1 && mode != 2) return fail("tile mode must be 1 or 2");
     if (mode == 2 && c->pxsz != 3) return fail("mode 2 codes RGB only (the driver sends RGBA to mode 1, libxpng.c:755)");
     if (nimg != c->B) return fail("nimg is " + std::to_string(nimg) + ", the mixed context holds " + std::to_string(c->B) + " images");
@@ -1020,11 +1099,17 @@ static int encode_varsize_impl(xpnghip_ctx *c, int mode, const void *const *d_ra
         // (image i: h_i rows, its slot 256-byte aligned - the buffer, and the layout, of the tight decode), and the kernels read that
         std::vector<uint64_t> slot;
         if (mixed_stage_slots(c, bpr, slot)) return 1;
-        if (!c->d_m_pack) {
+        if (from) {
+            if (c->h_m_from_src != base) {
+                c->h_m_from_src.clear();
+                if (layout_records(c, &c->d_m_from, slot, d_rasters, s)) return 1;
+                c->h_m_from_src = base;
+            }
+        } else if (!c->d_m_pack) {
             HIPCHK(hipMalloc((void **)&c->d_m_pack, (uint64_t)nimg * sizeof(MixedPack)));
             c->ws_bytes += (uint64_t)nimg * sizeof(MixedPack);
         }
-        if (c->h_m_pack_src != base) {  // (pageable host memory: the copy is staged synchronously anyway)
+        if (!from && c->h_m_pack_src != base) {  // (pageable host memory: the copy is staged synchronously anyway)
             std::vector<MixedPack> mp(nimg);
             for (uint32_t i = 0; i < nimg; i++)
                 mp[i] = MixedPack{slot[i], (const uint8_t *)d_rasters[i], (uint32_t)(c->m_dims[2ull * i] * px), (uint32_t)c->m_dims[2ull * i + 1]};
@@ -1037,7 +1122,12 @@ static int encode_varsize_impl(xpnghip_ctx *c, int mode, const void *const *d_ra
     }
     if (set_ptrs(c, base.data(), d_blobs, nimg, s)) return 1;
     XPNG_REQUIRE(c->d_m_first, c->d_m_list);
-    if (!in_bpr) {
+    if (from) {
+        XPNG_REQUIRE(c->d_m_stage, c->d_m_from);
+        if (c->pxsz == 4) launch_pack_from<4>(c, *layout, bpr, s);
+        else launch_pack_from<3>(c, *layout, bpr, s);
+        HIPCHK(hipGetLastError());
+    } else if (!in_bpr) {
         XPNG_REQUIRE(c->d_m_stage, c->d_m_pack);
         k_mixed_pack<<<dim3((uint32_t)((c->m_max_h + MC_ROWS - 1) / MC_ROWS), nimg), 256, 0, s>>>(c->d_m_pack, c->d_m_stage, bpr);
         HIPCHK(hipGetLastError());
@@ -1054,6 +1144,12 @@ static int encode_varsize_impl(xpnghip_ctx *c, int mode, const void *const *d_ra
 extern "C" int xpnghip_encode_varsize_device_batch(xpnghip_ctx *c, int mode, const void *const *d_rasters, uint64_t in_bpr, uint32_t nimg,
                                                    void *const *d_blobs, uint64_t *blobs_len, void *stream) {
     try { return encode_varsize_impl(c, mode, d_rasters, in_bpr, nimg, d_blobs, blobs_len, stream); }
+    catch (const std::bad_alloc &) { return fail("out of host memory"); }
+    catch (...) { return fail("unexpected C++ exception"); }
+}
+extern "C" int xpnghip_encode_varsize_device_batch_from(xpnghip_ctx *c, int mode, const void *const *d_rasters, uint32_t layout, uint32_t nimg,
+                                                        void *const *d_blobs, uint64_t *blobs_len, void *stream) {
+    try { return encode_varsize_impl(c, mode, d_rasters, 0, nimg, d_blobs, blobs_len, stream, &layout); }
     catch (const std::bad_alloc &) { return fail("out of host memory"); }
     catch (...) { return fail("unexpected C++ exception"); }
 }
