@@ -316,6 +316,37 @@ int xpnghip_decode_varsize_device_batch_as(xpnghip_ctx *ctx, int mode, const voi
 int xpnghip_encode_varsize_device_batch_from(xpnghip_ctx *ctx, int mode, const void *const *d_rasters, uint32_t layout,
                                              uint32_t nimg, void *const *d_blobs, uint64_t *blobs_len, void *stream);
 
+/* ---- float layouts: decode straight into normalised f16 / bf16 / f32 buffers -------------
+ * A model reads floats, not the file's bytes.  The call below is xpnghip_decode_varsize_device_batch_as with one difference: the
+ * copy-out pass converts while it rearranges, so the conversion costs no further pass over the pixels, no launch per image and no
+ * intermediate uint8 buffer.  For every output element, with v the stored byte (0 .. 255) and c the channel's position in the
+ * CALLER's buffer (after a BGR exchange, alpha last: with XPNGHIP_LAYOUT_BGR scale[0] belongs to blue):
+ *     y   = fmaf((float)v, scale[c], bias[c])     one fp32 fused multiply-add, IEEE, subnormals kept
+ *     out = (T)y                                  round to nearest even to T (f32: y itself); overflow of T gives +-inf
+ * The alpha an RGB context does not store (C == 4 on pxsz == 3) is v = 255 through the same formula with c = 3; C == 3 on an RGBA
+ * context drops alpha.  The dtype is an argument of its own, not a part of the layout word. */
+#define XPNGHIP_DTYPE_F16  1u
+#define XPNGHIP_DTYPE_BF16 2u
+#define XPNGHIP_DTYPE_F32  3u
+/* host-only: bytes of one element: 2, 2, 4; -1 for anything else (0 included: uint8 is not a dtype of the float call) */
+int xpnghip_dtype_bytes(uint32_t dtype);
+/* host-only, needs no device: the 256 outputs of channel position c for c = 0 .. C-1, i.e. table[c*256 + v] as an element of
+ * `dtype`, computed with fmaf() and a round-to-nearest-even conversion on the host: bit for bit what the device call writes for the
+ * byte v, so a caller that answers some images from host bytes stays consistent with it.  C = 1 .. 4.  -1 on a bad dtype, C, NULL,
+ * or a non-finite scale / bias. */
+int xpnghip_float_table(uint32_t dtype, int C, const float *scale, const float *bias, void *table);
+/* scale and bias: C = xpnghip_layout_channels(layout, pxsz) floats each on the HOST, read during the call (they travel in the
+ * kernel's arguments: no upload, no synchronisation); NULL scale = all ones, NULL bias = all zeros; every value must be finite.
+ * Image i's buffer is TIGHT: C * w_i * h_i elements in the layout's order, aligned to the element size (2 or 4 bytes); exactly
+ * C * w_i * h_i * sizeof(T) bytes are written and nothing before or behind them.  Same checks, blobs, size walk,
+ * xpnghip_ctx_decode_status and staging raster as the layout call (no second buffer; the workspace grows by one record table).
+ * Refused before anything reaches the device, with the offending value in xpnghip_last_error() and nothing written: a bad layout
+ * word, a dtype outside 1 .. 3 (uint8 buffers are written by xpnghip_decode_varsize_device_batch_as), a non-finite constant, a
+ * misaligned or NULL buffer, a context that is not mixed, a NULL context. */
+int xpnghip_decode_varsize_device_batch_as_float(xpnghip_ctx *ctx, int mode, const void *const *d_blobs, const uint64_t *blobs_len,
+                                                 uint32_t nimg, const uint64_t *tile_off, void *const *d_outs, uint32_t layout,
+                                                 uint32_t dtype, const float *scale, const float *bias, void *stream);
+
 /* Stage-only run for BASELINE config 2: predictor chooser + per-pixel transform (libxpng.c:92-140 and
  * the arithmetic of 497-519) over tiles [t0, t1); symbol planes stay in the context's workspace. */
 int xpnghip_m1_transform_device(xpnghip_ctx *ctx, const void *d_raster, uint64_t t0, uint64_t t1, void *stream);

@@ -33,6 +33,7 @@ HIP_SYMBOLS = [
     "xpnghip_images_begin", "xpnghip_images_single_colour", "xpnghip_images_encode", "xpnghip_images_fetch", "xpnghip_images_end",
     "xpnghip_images_first_pixel", "xpnghip_batch_cuts",
     "xpnghip_layout_channels", "xpnghip_decode_varsize_device_batch_as", "xpnghip_encode_varsize_device_batch_from",
+    "xpnghip_dtype_bytes", "xpnghip_float_table", "xpnghip_decode_varsize_device_batch_as_float",
 ]
 HOST_SYMBOLS = ["xpng_store", "xpng_load", "xpng_from_jpg", "xpng_store_T", "xpng_load_T", "xpng_from_jpg_T",
                 "store_7", "load_7"]
@@ -162,6 +163,14 @@ def _bind_hip(path):
                                                              C.POINTER(vp), C.c_uint32, vp]
         L.xpnghip_encode_varsize_device_batch_from.restype = C.c_int
         L.xpnghip_encode_varsize_device_batch_from.argtypes = [vp, C.c_int, C.POINTER(vp), C.c_uint32, C.c_uint32, C.POINTER(vp), C.POINTER(u64), vp]
+        f32p = C.POINTER(C.c_float)
+        L.xpnghip_dtype_bytes.restype = C.c_int
+        L.xpnghip_dtype_bytes.argtypes = [C.c_uint32]
+        L.xpnghip_float_table.restype = C.c_int
+        L.xpnghip_float_table.argtypes = [C.c_uint32, C.c_int, f32p, f32p, vp]
+        L.xpnghip_decode_varsize_device_batch_as_float.restype = C.c_int
+        L.xpnghip_decode_varsize_device_batch_as_float.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64), C.c_uint32, C.POINTER(u64),
+                                                                   C.POINTER(vp), C.c_uint32, C.c_uint32, f32p, f32p, vp]
         u8p = C.POINTER(C.c_uint8)
         L.xpnghip_images_begin.restype = C.c_int
         L.xpnghip_images_begin.argtypes = [C.POINTER(vp), C.c_uint32, C.POINTER(vp), C.POINTER(u64), u8p, u8p]
@@ -460,6 +469,43 @@ def layout_channels(layout: int, pxsz: int) -> int:
     return n
 
 
+DTYPE_F16, DTYPE_BF16, DTYPE_F32 = 1, 2, 3  # include/xpng_hip.h XPNGHIP_DTYPE_*: the element of a float buffer
+
+
+def dtype_bytes(dtype: int) -> int:
+    """Bytes of one element of a float buffer (xpnghip_dtype_bytes; host-only)."""
+    n = hip_lib().xpnghip_dtype_bytes(dtype)
+    if n < 0:
+        raise XpngError(f"bad dtype {dtype!r} (DTYPE_F16 = 1, DTYPE_BF16 = 2, DTYPE_F32 = 3)")
+    return n
+
+
+def _floats(name, values, n=None):
+    """a scalar or a sequence of numbers as a C array of floats (None stays None: the call's default)"""
+    if values is None:
+        return None
+    try:
+        vals = [float(v) for v in values] if hasattr(values, "__len__") or hasattr(values, "__iter__") else [float(values)] * (n or 1)
+    except (TypeError, ValueError):
+        raise XpngError(f"{name} must be a number or a sequence of numbers, not {values!r}") from None
+    if n is not None and len(vals) != n:
+        raise XpngError(f"{name} has {len(vals)} values, the buffers have {n} channels")
+    return (C.c_float * len(vals))(*vals)
+
+
+def float_table(dtype: int, scale, bias) -> bytes:
+    """The outputs of the float decode for every byte value: len(scale) * 256 elements of `dtype` as raw bytes, element
+    c * 256 + v being the conversion of fmaf(v, scale[c], bias[c]) (xpnghip_float_table; host-only, needs no device).  Bit for
+    bit what MixedContext.decode_batch_as_float writes."""
+    sc, bi = _floats("scale", scale), _floats("bias", bias)
+    if sc is None or bi is None or len(sc) != len(bi):
+        raise XpngError("float_table: scale and bias must be sequences of the same length")
+    buf = C.create_string_buffer(max(len(sc), 1) * 256 * dtype_bytes(dtype))
+    if hip_lib().xpnghip_float_table(dtype, len(sc), sc, bi, buf):
+        raise XpngError("xpnghip_float_table: " + _err())
+    return buf.raw[:len(sc) * 256 * dtype_bytes(dtype)]
+
+
 def store_batch(mode: int, rasters, paths) -> None:
     """xpng_store_batch (include/xpng_store_batch.h): file i is what store(mode, rasters[i], paths[i]) writes; the tile stage of
     all images of one (tile mode, bytes per pixel) is one mixed-size device call."""
@@ -752,6 +798,22 @@ class MixedContext:
         ins, outs, ln = (C.c_void_p * k)(*d_blobs), (C.c_void_p * len(d_outs))(*d_outs), (C.c_uint64 * len(lens))(*lens)
         if hip_lib().xpnghip_decode_varsize_device_batch_as(self._h, mode, ins, ln, k, off_arr, outs, layout, stream):
             raise XpngError("xpnghip_decode_varsize_device_batch_as: " + _err())
+
+    def decode_batch_as_float(self, mode, d_blobs, lens, d_outs, layout, dtype, scale=None, bias=None, tile_offs=None, stream=0):
+        """decode_batch_as with every d_outs[i] written as C * w * h elements of `dtype` (DTYPE_F16, DTYPE_BF16, DTYPE_F32), aligned
+        to the element: element = fmaf(byte, scale[c], bias[c]) rounded to nearest even, c the channel's position in the buffer.
+        scale / bias: one number per channel of the buffers or None (ones / zeros): xpnghip_decode_varsize_device_batch_as_float."""
+        k = len(d_blobs)
+        off_arr = None
+        if tile_offs is not None:
+            flat = [o for offs in tile_offs for o in offs]
+            assert len(flat) == self.n_tiles
+            off_arr = (C.c_uint64 * len(flat))(*flat)
+        ch = hip_lib().xpnghip_layout_channels(layout, self.pxsz)
+        sc, bi = _floats("scale", scale, ch if ch > 0 else None), _floats("bias", bias, ch if ch > 0 else None)
+        ins, outs, ln = (C.c_void_p * k)(*d_blobs), (C.c_void_p * len(d_outs))(*d_outs), (C.c_uint64 * len(lens))(*lens)
+        if hip_lib().xpnghip_decode_varsize_device_batch_as_float(self._h, mode, ins, ln, k, off_arr, outs, layout, dtype, sc, bi, stream):
+            raise XpngError("xpnghip_decode_varsize_device_batch_as_float: " + _err())
 
     def encode_batch_from(self, mode, d_rasters, layout, d_blobs, stream=0, sync=True):
         """encode_batch in its tight form, with every d_rasters[i] read in `layout` (api.layout(); its channels must be the

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -28,6 +29,7 @@
 #include "tile_container.hpp"
 #include "region.hpp"
 #include "mixed.hpp"
+#include "mixed_float.hpp"
 
 using namespace xpng;
 
@@ -189,6 +191,10 @@ struct xpnghip_ctx {
     MixedLayout *d_m_as = nullptr, *d_m_from = nullptr;
     std::vector<void *> h_m_as_dst;          // the destinations d_m_as holds
     std::vector<const void *> h_m_from_src;  // the sources d_m_from holds
+    // ... and of the float form of the decode (XPNGHIP_DTYPE_*): the same records - nothing in them depends on the
+    // dtype or the constants either - in a table of their own, cached on the pointers
+    MixedLayout *d_m_asf = nullptr;
+    std::vector<void *> h_m_asf_dst;
 };
 
 // the context's own stream, created when a call first needs it (the `stream == NULL` form of the device-resident entry points,
@@ -209,7 +215,7 @@ extern "C" void xpnghip_ctx_destroy(xpnghip_ctx *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void *ptrs[] = {c->d_tiles, c->d_planes, c->d_scratch, c->d_sums, c->d_nlh, c->d_ctx_n, c->d_k_n, c->d_blk_sz, c->d_tile_sz,
                     c->d_tile_hdr, c->d_off, c->d_totals, c->d_raster, c->d_blobs, c->d_blob_in, c->d_dbg, (void *)c->d_in_ptrs, (void *)c->d_out_ptrs, (void *)c->d_dec_in_ptrs, (void *)c->d_dec_out_ptrs, (void *)c->d_order,
-                    c->d_wprep, c->d_wtab, c->d_wF, c->d_blob_len, c->d_status, c->d_scratch2, c->d_sbase2, c->d_flags2, c->d_stream_n2, c->d_blk2, c->d_mt2, c->d_info2, c->d_tabs2, c->d_w1prep, c->d_w1tab, c->d_w1F, c->d_region_stage, c->d_region_meta, c->d_m_first, c->d_m_stage, c->d_m_copy, c->d_m_pack, c->d_m_as, c->d_m_from};
+                    c->d_wprep, c->d_wtab, c->d_wF, c->d_blob_len, c->d_status, c->d_scratch2, c->d_sbase2, c->d_flags2, c->d_stream_n2, c->d_blk2, c->d_mt2, c->d_info2, c->d_tabs2, c->d_w1prep, c->d_w1tab, c->d_w1F, c->d_region_stage, c->d_region_meta, c->d_m_first, c->d_m_stage, c->d_m_copy, c->d_m_pack, c->d_m_as, c->d_m_from, c->d_m_asf};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->enc_side) (void)hipStreamDestroy(c->enc_side);
     if (c->ev_enc_fork) (void)hipEventDestroy(c->ev_enc_fork);
@@ -944,6 +950,85 @@ static void launch_pack_from(const xpnghip_ctx *c, uint32_t layout, uint64_t bpr
     else k_mixed_pack_from<PX, false><<<grid, 256, 0, s>>>(c->d_m_from, c->d_m_stage, bpr, bgr);
 }
 
+// ---- float layouts (XPNGHIP_DTYPE_*; mixed_float.hpp) -----------------------------------------------------
+extern "C" int xpnghip_dtype_bytes(uint32_t dtype) {
+    return dtype == XPNGHIP_DTYPE_F16 || dtype == XPNGHIP_DTYPE_BF16 ? 2 : dtype == XPNGHIP_DTYPE_F32 ? 4 : -1;
+}
+// fp32 -> the bits of the nearest f16 / bf16, ties to even, on the host (what v_cvt_pk_f16_f32 / v_cvt_pk_bf16_f32 give on the device)
+static uint16_t f16_bits_rne(float f) {
+    uint32_t x;
+    memcpy(&x, &f, 4);
+    const uint32_t sign = (x >> 16) & 0x8000u, a = x & 0x7FFFFFFFu;
+    if (a >= 0x7F800000u) return (uint16_t)(sign | 0x7C00u | (a > 0x7F800000u ? 0x200u : 0));  // inf, NaN
+    if (a >= 0x477FF000u) return (uint16_t)(sign | 0x7C00u);  // >= 65520 rounds to inf
+    if (a < 0x33000001u) return (uint16_t)sign;               // <= 2^-25 rounds to zero (the tie 2^-25 goes to even 0)
+    const int32_t e = (int32_t)(a >> 23) - 127;
+    uint32_t m = (a & 0x7FFFFFu) | 0x800000u, shift = e < -14 ? (uint32_t)(13 + (-14 - e)) : 13u;  // bits that fall off the f16 mantissa
+    const uint32_t q = m >> shift, rest = m & ((1u << shift) - 1), half = 1u << (shift - 1);
+    uint32_t h = e < -14 ? q : (((uint32_t)(e + 15) << 10) + (q - 0x400u));  // subnormal: no hidden bit, exponent field 0
+    if (rest > half || (rest == half && (h & 1))) h++;  // (a carry out of the mantissa runs into the exponent, as it should)
+    return (uint16_t)(sign | h);
+}
+static uint16_t bf16_bits_rne(float f) {
+    uint32_t x;
+    memcpy(&x, &f, 4);
+    if ((x & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((x >> 16) | 0x40u);  // NaN stays NaN
+    return (uint16_t)((x + 0x7FFFu + ((x >> 16) & 1)) >> 16);
+}
+static bool float_consts(int C, const float *scale, const float *bias, FloatConsts &k, std::string &why) {
+    for (int c = 0; c < 4; c++) {
+        k.scale[c] = scale && c < C ? scale[c] : 1.0f;
+        k.bias[c] = bias && c < C ? bias[c] : 0.0f;
+        if (!std::isfinite(k.scale[c]) || !std::isfinite(k.bias[c])) {
+            const bool sc = !std::isfinite(k.scale[c]);
+            char b[64];
+            snprintf(b, sizeof b, "%s[%d] is %g", sc ? "scale" : "bias", c, (double)(sc ? k.scale[c] : k.bias[c]));
+            why = std::string(b) + ": the constants must be finite";
+            return false;
+        }
+    }
+    return true;
+}
+extern "C" int xpnghip_float_table(uint32_t dtype, int C, const float *scale, const float *bias, void *table) {
+    const int es = xpnghip_dtype_bytes(dtype);
+    if (es < 0) return fail("bad dtype " + std::to_string(dtype) + " (XPNGHIP_DTYPE_F16 = 1, _BF16 = 2, _F32 = 3)"), -1;
+    if (C < 1 || C > 4) return fail("xpnghip_float_table: C is " + std::to_string(C) + ", not 1 .. 4"), -1;
+    if (!scale || !bias || !table) return fail("xpnghip_float_table: null argument"), -1;
+    FloatConsts k;
+    std::string why;
+    if (!float_consts(C, scale, bias, k, why)) return fail(why), -1;
+    for (int c = 0; c < C; c++)
+        for (int v = 0; v < 256; v++) {
+            const float y = fmaf((float)v, k.scale[c], k.bias[c]);
+            if (dtype == XPNGHIP_DTYPE_F32) reinterpret_cast<float *>(table)[c * 256 + v] = y;
+            else reinterpret_cast<uint16_t *>(table)[c * 256 + v] = dtype == XPNGHIP_DTYPE_F16 ? f16_bits_rne(y) : bf16_bits_rne(y);
+        }
+    return 0;
+}
+// what the float form of the decode adds to the arguments of the layout form
+struct FloatCall {
+    uint32_t dtype;
+    const float *scale, *bias;
+};
+template <int PX, class T>
+static void launch_copy_as_float(const xpnghip_ctx *c, uint32_t layout, int C, uint64_t bpr, const FloatConsts &k, hipStream_t s) {
+    const dim3 grid((uint32_t)((c->m_max_h + MC_ROWS - 1) / MC_ROWS), c->B);
+    const uint32_t bgr = layout & XPNGHIP_LAYOUT_BGR;
+    if (layout & XPNGHIP_LAYOUT_PLANAR) {
+        if (C == 3) k_mixed_copy_as_float<PX, 3, true, T><<<grid, 256, 0, s>>>(c->d_m_asf, c->d_m_stage, bpr, bgr, k);
+        else k_mixed_copy_as_float<PX, 4, true, T><<<grid, 256, 0, s>>>(c->d_m_asf, c->d_m_stage, bpr, bgr, k);
+    } else {
+        if (C == 3) k_mixed_copy_as_float<PX, 3, false, T><<<grid, 256, 0, s>>>(c->d_m_asf, c->d_m_stage, bpr, bgr, k);
+        else k_mixed_copy_as_float<PX, 4, false, T><<<grid, 256, 0, s>>>(c->d_m_asf, c->d_m_stage, bpr, bgr, k);
+    }
+}
+template <int PX>
+static void launch_copy_as_float(const xpnghip_ctx *c, uint32_t layout, int C, uint64_t bpr, uint32_t dtype, const FloatConsts &k, hipStream_t s) {
+    if (dtype == XPNGHIP_DTYPE_F16) launch_copy_as_float<PX, f16_t>(c, layout, C, bpr, k, s);
+    else if (dtype == XPNGHIP_DTYPE_BF16) launch_copy_as_float<PX, bf16_t>(c, layout, C, bpr, k, s);
+    else launch_copy_as_float<PX, float>(c, layout, C, bpr, k, s);
+}
+
 // The staging raster of the tight forms (decode: reconstruct into it, k_mixed_copy out of it; encode: k_mixed_pack into it, the
 // kernels read it): image i's h_i rows at the pitch bpr in slot[i], every slot 256-byte aligned, 256 spare bytes behind the last.
 // ONE layout and one buffer for both directions; allocated by the first tight call, never shrunk.
@@ -959,16 +1044,26 @@ static int mixed_stage_slots(xpnghip_ctx *c, uint64_t bpr, std::vector<uint64_t>
     return 0;
 }
 
-// `layout` != NULL: the call of xpnghip_decode_varsize_device_batch_as (out_bpr == 0: its buffers are tight)
+// `layout` != NULL: the call of xpnghip_decode_varsize_device_batch_as (out_bpr == 0: its buffers are tight); `fc` != NULL beside
+// it: the call of xpnghip_decode_varsize_device_batch_as_float (its buffers hold elements of fc->dtype)
 static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
-                                   const uint64_t *tile_off, void *const *d_outs, uint64_t out_bpr, void *stream, const uint32_t *layout = nullptr) {
+                                   const uint64_t *tile_off, void *const *d_outs, uint64_t out_bpr, void *stream, const uint32_t *layout = nullptr,
+                                   const FloatCall *fc = nullptr) {
     // every argument is checked before anything reaches the device: a rejected call writes nothing
     if (!c) return fail("null context");
     if (!c->mixed) return fail("not a mixed context (xpnghip_ctx_create_mixed)");
     const int C = layout ? xpnghip_layout_channels(*layout, c->pxsz) : c->pxsz;
     if (C < 0) return fail("bad layout word " + layout_hex(*layout) + " (XPNGHIP_LAYOUT_PLANAR | XPNGHIP_LAYOUT_BGR | channels 0, 3 or 4 in bits 8..11)");
     // (interleaved, the file's colour order and channel count: the tight form itself, k_mixed_copy and its records)
-    const bool as = layout && ((*layout & (XPNGHIP_LAYOUT_PLANAR | XPNGHIP_LAYOUT_BGR)) || C != c->pxsz);
+    const bool as = !fc && layout && ((*layout & (XPNGHIP_LAYOUT_PLANAR | XPNGHIP_LAYOUT_BGR)) || C != c->pxsz);
+    const int es = fc ? xpnghip_dtype_bytes(fc->dtype) : 1;
+    if (es < 0)
+        return fail("bad dtype " + std::to_string(fc->dtype) + " (XPNGHIP_DTYPE_F16 = 1, _BF16 = 2, _F32 = 3; uint8 buffers are written by xpnghip_decode_varsize_device_batch_as)");
+    FloatConsts fk{};
+    if (fc) {
+        std::string why;
+        if (!float_consts(C, fc->scale, fc->bias, fk, why)) return fail(why);
+    }
     if (mode != 1 && mode != 2) return fail("tile mode must be 1 or 2");
     if (mode == 2 && c->pxsz != 3) return fail("mode 2 codes RGB only");
     if (nimg != c->B) return fail("nimg is " + std::to_string(nimg) + ", the mixed context holds " + std::to_string(c->B) + " images");
@@ -979,6 +1074,11 @@ static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *
     for (uint32_t i = 0; i < nimg; i++) {
         if (!d_blobs[i] || !d_outs[i]) return fail("null blob or output buffer of image " + std::to_string(i));
         if (((uintptr_t)d_blobs[i] & 3) || (out_bpr && ((uintptr_t)d_outs[i] & 15))) return fail("device buffers must be 16-byte aligned");
+        if ((uintptr_t)d_outs[i] & (uintptr_t)(es - 1)) {
+            char b[32];
+            snprintf(b, sizeof b, "%p", d_outs[i]);
+            return fail("output buffer " + std::string(b) + " of image " + std::to_string(i) + " is not aligned to its " + std::to_string(es) + "-byte elements");
+        }
     }
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(c);
@@ -989,7 +1089,13 @@ static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *
         // its slot 256-byte aligned), then k_mixed_copy moves every image out at its own pitch
         std::vector<uint64_t> slot;
         if (mixed_stage_slots(c, bpr, slot)) return 1;
-        if (as) {
+        if (fc) {
+            if (c->h_m_asf_dst != base) {
+                c->h_m_asf_dst.clear();
+                if (layout_records(c, &c->d_m_asf, slot, d_outs, s)) return 1;
+                c->h_m_asf_dst = base;
+            }
+        } else if (as) {
             if (c->h_m_as_dst != base) {
                 c->h_m_as_dst.clear();
                 if (layout_records(c, &c->d_m_as, slot, d_outs, s)) return 1;
@@ -999,7 +1105,7 @@ static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *
             HIPCHK(hipMalloc((void **)&c->d_m_copy, (uint64_t)nimg * sizeof(MixedCopy)));
             c->ws_bytes += (uint64_t)nimg * sizeof(MixedCopy);
         }
-        if (!as && c->h_m_copy_dst != base) {  // (pageable host memory: the copy is staged synchronously anyway)
+        if (!as && !fc && c->h_m_copy_dst != base) {  // (pageable host memory: the copy is staged synchronously anyway)
             std::vector<MixedCopy> mc(nimg);
             for (uint32_t i = 0; i < nimg; i++)
                 mc[i] = MixedCopy{slot[i], (uint8_t *)d_outs[i], (uint32_t)(c->m_dims[2ull * i] * px), (uint32_t)c->m_dims[2ull * i + 1]};
@@ -1014,7 +1120,12 @@ static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *
     XPNG_REQUIRE(c->d_m_first, c->d_m_list);
     const int rc = dec_launch(c, mode, nimg, c->m_max_w, tile_off, s, 0, (uint32_t)c->tiles.size(), &c->m_list, c->d_m_list, bpr);
     if (rc) return rc;
-    if (as) {
+    if (fc) {
+        XPNG_REQUIRE(c->d_m_stage, c->d_m_asf);
+        if (c->pxsz == 4) launch_copy_as_float<4>(c, *layout, C, bpr, fc->dtype, fk, s);
+        else launch_copy_as_float<3>(c, *layout, C, bpr, fc->dtype, fk, s);
+        HIPCHK(hipGetLastError());
+    } else if (as) {
         XPNG_REQUIRE(c->d_m_stage, c->d_m_as);
         if (c->pxsz == 4) launch_copy_as<4>(c, *layout, C, bpr, s);
         else launch_copy_as<3>(c, *layout, C, bpr, s);
@@ -1035,6 +1146,14 @@ extern "C" int xpnghip_decode_mixed_device_batch(xpnghip_ctx *c, int mode, const
 extern "C" int xpnghip_decode_varsize_device_batch_as(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
                                                       const uint64_t *tile_off, void *const *d_outs, uint32_t layout, void *stream) {
     try { return decode_mixed_batch_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, d_outs, 0, stream, &layout); }
+    catch (const std::bad_alloc &) { return fail("out of host memory"); }
+    catch (...) { return fail("unexpected C++ exception"); }
+}
+extern "C" int xpnghip_decode_varsize_device_batch_as_float(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
+                                                            const uint64_t *tile_off, void *const *d_outs, uint32_t layout, uint32_t dtype,
+                                                            const float *scale, const float *bias, void *stream) {
+    const FloatCall fc{dtype, scale, bias};
+    try { return decode_mixed_batch_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, d_outs, 0, stream, &layout, &fc); }
     catch (const std::bad_alloc &) { return fail("out of host memory"); }
     catch (...) { return fail("unexpected C++ exception"); }
 }

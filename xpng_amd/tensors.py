@@ -1,8 +1,9 @@
-"""torch front end: .xpng files -> uint8 device tensors in the layout a model reads, the pixels never leaving HBM.
+"""torch front end: .xpng files -> device tensors in the layout and the data type a model reads, the pixels never leaving HBM.
 
 `load_files` is what `api.load_batch` is for host arrays.  The files that reach the tile codec are grouped by (tile mode, bytes per
 pixel) and every group is decoded by mixed-size device calls straight into tensors of the final layout
-(MixedContext.decode_batch_as: the layout is written by the copy-out pass of the decode, include/xpng_hip.h XPNGHIP_LAYOUT_*).
+(MixedContext.decode_batch_as: the layout is written by the copy-out pass of the decode, include/xpng_hip.h XPNGHIP_LAYOUT_*;
+MixedContext.decode_batch_as_float when a float dtype is asked for: the same pass converts and normalises, XPNGHIP_DTYPE_*).
 api.py stays free of torch; this module is the only one of the package that imports it at load time."""
 from __future__ import annotations
 
@@ -28,25 +29,91 @@ def _arrange(t: torch.Tensor, layout: str, channels, bgr: bool) -> torch.Tensor:
     return (t.permute(2, 0, 1) if layout == "chw" else t).contiguous()
 
 
-def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, device=None) -> list:
-    """The images of a list of .xpng files of any sizes as uint8 tensors on `device` (default: the current cuda device), each of
+_DTYPES = {torch.float16: api.DTYPE_F16, torch.bfloat16: api.DTYPE_BF16, torch.float32: api.DTYPE_F32}
+
+
+def _per_channel(name, value, default, C):
+    """mean / std as C Python floats: None -> the default, a scalar -> repeated, a sequence -> one per channel position"""
+    if value is None:
+        return [default] * C
+    if isinstance(value, torch.Tensor):
+        value = value.tolist()
+    vals = [float(v) for v in value] if isinstance(value, (list, tuple)) else [float(value)] * C
+    if len(vals) != C:
+        raise XpngError(f"load_files: {name} has {len(vals)} values, the tensors have {C} channels")
+    return vals
+
+
+def _scale_bias(mean, std, C):
+    """y = (v / 255 - mean) / std as y = v * scale + bias: computed in Python doubles, rounded once to fp32"""
+    m, s = _per_channel("mean", mean, 0.0, C), _per_channel("std", std, 1.0, C)
+    if any(x == 0 for x in s):
+        raise XpngError("load_files: std must not be 0")
+    f32 = lambda x: torch.tensor(x, dtype=torch.float64).to(torch.float32).item()   # noqa: E731  (round to nearest fp32)
+    return [f32(1.0 / (255.0 * x)) for x in s], [f32(-a / x) for a, x in zip(m, s)]
+
+
+def _lookup(t: torch.Tensor, layout: str, dtype, dt: int, scale, bias) -> torch.Tensor:
+    """an arranged uint8 tensor through api.float_table: bit for bit what the device call writes for these bytes"""
+    C = t.shape[0] if layout == "chw" else t.shape[2]
+    raw = api.float_table(dt, scale[:C], bias[:C])
+    table = torch.frombuffer(bytearray(raw), dtype=dtype).view(C, 256)
+    idx = t.to(torch.int64)
+    if layout == "chw":
+        return torch.stack([table[c][idx[c]] for c in range(C)], dim=0).contiguous()
+    return torch.stack([table[c][idx[..., c]] for c in range(C)], dim=2).contiguous()
+
+
+def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, device=None, dtype=torch.uint8, mean=None, std=None,
+               stack: bool = False):
+    """The images of a list of .xpng files of any sizes as tensors on `device` (default: the current cuda device), each of
     shape (C, h, w) for layout "chw" or (h, w, C) for "hwc".  channels None keeps each file's own count (3 or 4); 3 drops the
     alpha of an RGBA file, 4 gives an RGB file alpha 255; bgr=True orders the colours B, G, R (alpha stays last).
     load_files(p, "hwc")[i] equals api.load(p[i]).  Level-7 and whole-image single-colour files are answered from the host bytes
     without a codec call, so a list of only those also loads with device="cpu"; any other list needs a GPU.  Any failure raises
-    XpngError and nothing is returned."""
+    XpngError and nothing is returned.
+
+    dtype torch.uint8 (the default) gives the file's bytes; mean or std with it is an error.  dtype torch.float16, torch.bfloat16
+    or torch.float32 gives y = (v / 255 - mean[c]) / std[c], torchvision's ToTensor + Normalize: mean and std are a number or one
+    number per channel position of the RETURNED tensor (with bgr=True the first belongs to blue; alpha is last), default 0 and 1.
+    The conversion is done by the decode's own copy-out pass (MixedContext.decode_batch_as_float) as ONE fp32 fused multiply-add
+    y = fmaf(v, scale[c], bias[c]), rounded to nearest even to the dtype, with scale[c] = float32(1 / (255 * std[c])) and
+    bias[c] = float32(-mean[c] / std[c]) computed here in Python doubles and rounded once to fp32.  A caller who needs another
+    affine map, or other constants bit for bit, calls decode_batch_as_float directly.  Host-answered files go through
+    api.float_table, the same arithmetic on the host, so they are bit-identical to what the kernel writes.
+
+    stack=True returns ONE tensor (N, C, h, w) or (N, h, w, C) instead of the list: every image must have the same (C, h, w) after
+    `channels` is applied (XpngError names the first that differs); the device calls write straight into its slices."""
     if layout not in ("chw", "hwc"):
         raise XpngError(f"load_files: layout must be 'chw' or 'hwc', not {layout!r}")
     if channels not in (None, 3, 4):
         raise XpngError(f"load_files: channels must be None, 3 or 4, not {channels!r}")
+    if dtype != torch.uint8 and dtype not in _DTYPES:
+        raise XpngError(f"load_files: dtype must be torch.uint8, float16, bfloat16 or float32, not {dtype!r}")
+    if dtype == torch.uint8 and (mean is not None or std is not None):
+        raise XpngError("load_files: mean and std need a float dtype (dtype=torch.uint8 returns the file's bytes)")
+    mean, std = (x.tolist() if isinstance(x, torch.Tensor) else x for x in (mean, std))
+    dt = _DTYPES.get(dtype)                                        # None: the uint8 path, exactly as without the argument
+    cache = {}
+
+    def consts(C):
+        """(scale, bias) of a C-channel tensor; a per-channel mean or std of another length is an error"""
+        if C not in cache:
+            cache[C] = _scale_bias(mean, std, C)
+        return cache[C]
+
+    if dt:
+        _scale_bias(None, std, len(std) if isinstance(std, (list, tuple)) else 1)   # std == 0 is refused whatever the files hold
+        if channels:
+            consts(channels)
     paths = list(paths)
     if not paths:
         raise XpngError("load_files: empty list")
     dev = torch.device("cuda" if device is None else device)
     if dev.type == "cuda" and not torch.cuda.is_available():
         raise XpngError("load_files: no GPU is visible (device='cpu' answers level-7 and single-colour files without one)")
-    out, groups = [None] * len(paths), {}
-    for i, p in enumerate(paths):
+    heads, bufs = [], []
+    for p in paths:
         try:
             with open(p, "rb") as f:
                 buf = f.read()
@@ -56,19 +123,42 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
             raise XpngError(f"load_files: {os.fspath(p)!r} is shorter than a header")
         h0, h1 = int.from_bytes(buf[0:4], "little"), int.from_bytes(buf[4:8], "little")
         mode, w, h, alpha = h0 >> 24, (h0 & 0xFFFFFF) + 1, (h1 & 0xFFFFFF) + 1, (h1 >> 24) & 1
-        px = 3 + alpha
         if mode not in (1, 2, 7):
             raise XpngError(f"load_files: {os.fspath(p)!r} has level {mode}")
+        heads.append((mode, w, h, 3 + alpha))
+        bufs.append(buf)
+    if dt:
+        for (_, _, _, px) in heads:
+            consts(channels or px)
+    shape = lambda C, h, w: (C, h, w) if layout == "chw" else (h, w, C)   # noqa: E731
+    whole = None
+    if stack:
+        first = (channels or heads[0][3], heads[0][2], heads[0][1])
+        for p, (_, w, h, px) in zip(paths, heads):
+            if (channels or px, h, w) != first:
+                raise XpngError(f"load_files: stack=True needs images of one shape, but {os.fspath(p)!r} is (C, h, w) = "
+                                f"{(channels or px, h, w)} and the first is {first}")
+        whole = torch.empty((len(paths),) + shape(*first), dtype=dtype, device=dev)
+    out, groups = [None] * len(paths), {}
+    for i, (p, buf, (mode, w, h, px)) in enumerate(zip(paths, bufs, heads)):
+        alpha = px - 3
+        t = None
         if mode == 7:
             if len(buf) < 8 + w * h * px:
                 raise XpngError(f"load_files: {os.fspath(p)!r} is shorter than its raster")
             t = torch.frombuffer(bytearray(buf[8:8 + w * h * px]), dtype=torch.uint8).view(h, w, px)
-            out[i] = _arrange(t, layout, channels, bgr).to(dev)
         elif len(buf) == 11 + alpha and buf[7] & 2:              # whole-image single colour: the file holds one pixel
             t = torch.frombuffer(bytearray(buf[8:8 + px]), dtype=torch.uint8).view(1, 1, px).expand(h, w, px)
-            out[i] = _arrange(t, layout, channels, bgr).to(dev)
-        else:
+        if t is None:
             groups.setdefault((mode, px), []).append((i, w, h, buf))
+            continue
+        t = _arrange(t, layout, channels, bgr)
+        if dt:
+            t = _lookup(t, layout, dtype, dt, *consts(channels or px))
+        if whole is not None:
+            whole[i].copy_(t)
+        else:
+            out[i] = t.to(dev)
     if groups and dev.type != "cuda":
         raise XpngError("load_files: these files need the tile codec, which runs on a GPU only (there is no CPU fallback)")
     for (mode, px), members in sorted(groups.items()):
@@ -88,12 +178,18 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
                 host[o:o + len(buf) - 8] = buf[8:]
             with torch.cuda.device(index):
                 d_in = torch.frombuffer(host, dtype=torch.uint8).to(dev)
-                outs = [torch.empty((C, h, w) if layout == "chw" else (h, w, C), dtype=torch.uint8, device=dev) for (_, w, h, _) in part]
+                if whole is not None:                             # (the kernels take any pointers: the slices are the buffers)
+                    outs = [whole[i] for (i, _, _, _) in part]
+                else:
+                    outs = [torch.empty(shape(C, h, w), dtype=dtype, device=dev) for (_, w, h, _) in part]
                 torch.cuda.current_stream().synchronize()          # the upload is there before the context's stream reads it
                 ctx = api.MixedContext([(w, h) for (_, w, h, _) in part], px, device=index)
                 try:
-                    ctx.decode_batch_as(mode, [d_in.data_ptr() + o for o in offs], [len(buf) - 8 for (_, _, _, buf) in part],
-                                        [t.data_ptr() for t in outs], word)
+                    ins, lens = [d_in.data_ptr() + o for o in offs], [len(buf) - 8 for (_, _, _, buf) in part]
+                    if dt:
+                        ctx.decode_batch_as_float(mode, ins, lens, [t.data_ptr() for t in outs], word, dt, *consts(C))
+                    else:
+                        ctx.decode_batch_as(mode, ins, lens, [t.data_ptr() for t in outs], word)
                     status = ctx.decode_status()                  # (synchronises the context's stream: the tensors are complete)
                 finally:
                     ctx.close()
@@ -101,4 +197,4 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
                 raise XpngError("load_files: a tile of a level-%d file was rejected or the device call failed (status %d)" % (mode, status))
             for (i, _, _, _), t in zip(part, outs):
                 out[i] = t
-    return out
+    return whole if whole is not None else out
