@@ -1,8 +1,8 @@
-"""CPU: the two layout kernels (xpng_amd/csrc/mixed.hpp k_mixed_copy_as, k_mixed_pack_from) run on the host.
+"""CPU: the staging copy kernels (xpng_amd/csrc/mixed.hpp k_mixed_copy, k_mixed_pack, k_mixed_copy_as, k_mixed_pack_from) run on the host.
 
 Their text is cut out of mixed.hpp and compiled into tests/layout_kernels_host.cpp, a stand-alone program with shims for the three
 device operations they use, built with a statically linked AddressSanitizer where the toolchain has one.  It runs every thread of
-every block one after another for both pixel sizes, all 12 layouts out of a staging raster and the 4 + 4 layouts into it, on widths 1 .. 9 (every alignment of a row and of a
+every block one after another for both pixel sizes, the tight pair, all 12 layouts out of a staging raster and the 4 + 4 layouts into it, on widths 1 .. 9 (every alignment of a row and of a
 plane row), wider rows than a wave covers and several images per launch in both orders, and checks every byte: the values, the
 sentinels around every caller's buffer, the untouched padding of the staging rows, and that ld32u reads only aligned dwords that
 hold a byte of the buffer it is reading."""
@@ -22,7 +22,7 @@ def test_layout_kernels_on_the_host(tmp_path):
     src = open(os.path.join(ROOT, "xpng_amd", "csrc", "mixed.hpp")).read()
     a, b = src.index("struct MixedLayout {"), src.rindex("}  // namespace xpng")
     text = src[a:b]
-    assert "k_mixed_copy_as" in text and "k_mixed_pack_from" in text and "k_mixed_copy(" not in text
+    assert all(k in text for k in ("k_mixed_copy(", "k_mixed_pack(", "k_mixed_copy_as(", "k_mixed_pack_from("))
     inc = tmp_path / "layout_kernels.inc"
     inc.write_text(text)
     exe = tmp_path / "layout_kernels_host"

@@ -13,6 +13,8 @@
 // (xpnghip_decode_varsize_device_batch_as / xpnghip_encode_varsize_device_batch_from):
 //   k_mixed_copy_as      (here) staging raster -> planar or interleaved, RGB or BGR, 3 or 4 channels;
 //   k_mixed_pack_from    (here) planar or BGR rasters of the context's own channel count -> staging raster.
+// All of them (and k_mixed_copy_as_float, mixed_float.hpp) read the same per-image record, MixedLayout: one table of B records per
+// direction, whatever the form of the call ("The record table").
 #pragma once
 #include <stdint.h>
 
@@ -21,74 +23,62 @@
 
 namespace xpng {
 
-// one image's way out of the staging raster: `rows` rows of `row_bytes` bytes from stage + src (the launch's pitch) to dst, rows
-// back to back (the destination pitch IS row_bytes)
-struct MixedCopy {
-    uint64_t src;
-    uint8_t *dst;
-    uint32_t row_bytes, rows;
-};
-
-constexpr uint32_t MC_ROWS = 8;  // rows per workgroup of k_mixed_copy
-
-// grid (ceil(tallest image / MC_ROWS), nimg), 256 threads.  A tight RGB row is w * 3 bytes, so the destination rows of one image
-// start at every alignment: each row is written as a head of up to 3 bytes, whole ALIGNED dwords (each assembled from the source
-// by ld32u: two aligned loads and a shift when the source sits at another alignment), and a tail of up to 3 bytes.  Exactly
-// rows * row_bytes bytes of dst are written.  ld32u may read the aligned dword behind the last source byte: the staging raster
-// keeps 256 spare bytes behind its last slot.
-__global__ __launch_bounds__(256) void k_mixed_copy(const MixedCopy *__restrict__ mc, const uint8_t *__restrict__ stage, uint64_t stage_bpr) {
-    const MixedCopy r = mc[blockIdx.y];
-    const uint32_t y0 = blockIdx.x * MC_ROWS;
-    if (y0 >= r.rows) return;
-    for (uint32_t y = y0; y < y0 + MC_ROWS && y < r.rows; y++) {
-        const uint8_t *s = stage + r.src + (uint64_t)y * stage_bpr;
-        uint8_t *d = r.dst + (uint64_t)y * r.row_bytes;
-        uint32_t head = (4u - (uint32_t)((uintptr_t)d & 3)) & 3u;
-        if (head > r.row_bytes) head = r.row_bytes;
-        const uint32_t nw = (r.row_bytes - head) / 4, tail0 = head + 4 * nw;
-        if (threadIdx.x < head) d[threadIdx.x] = s[threadIdx.x];
-        uint32_t *d4 = reinterpret_cast<uint32_t *>(d + head);
-        for (uint32_t k = threadIdx.x; k < nw; k += 256) d4[k] = ld32u(s + head + 4 * k);
-        if (tail0 + threadIdx.x < r.row_bytes) d[tail0 + threadIdx.x] = s[tail0 + threadIdx.x];
-    }
-}
-
-// one image's way INTO the staging raster: `rows` rows of `row_bytes` bytes from src, rows back to back, to stage + dst at the
-// launch's pitch
-struct MixedPack {
-    uint64_t dst;
-    const uint8_t *src;
-    uint32_t row_bytes, rows;
-};
-
-// grid (ceil(tallest image / MC_ROWS), nimg), 256 threads.  The mirror of k_mixed_copy: the rows of a tight raster start at every
-// alignment (w * 3 bytes each) and the staging rows are 16-byte aligned, so each row is written as whole aligned dwords (each
-// assembled by ld32u: its two aligned loads both hold a byte of the row, so nothing outside the dwords the source occupies is
-// read) and a tail of up to 3 single bytes.  Exactly row_bytes bytes of each of the `rows` staging rows are written; the bytes of
-// a staging row behind them keep whatever they held (no encode kernel lets them reach the output).
-__global__ __launch_bounds__(256) void k_mixed_pack(const MixedPack *__restrict__ mp, uint8_t *__restrict__ stage, uint64_t stage_bpr) {
-    const MixedPack r = mp[blockIdx.y];
-    const uint32_t y0 = blockIdx.x * MC_ROWS;
-    if (y0 >= r.rows) return;
-    const uint32_t nw = r.row_bytes / 4, tail0 = 4 * nw;
-    for (uint32_t y = y0; y < y0 + MC_ROWS && y < r.rows; y++) {
-        const uint8_t *s = r.src + (uint64_t)y * r.row_bytes;
-        uint8_t *d = stage + r.dst + (uint64_t)y * stage_bpr;
-        uint32_t *d4 = reinterpret_cast<uint32_t *>(d);
-        for (uint32_t k = threadIdx.x; k < nw; k += 256) d4[k] = ld32u(s + 4 * k);
-        if (tail0 + threadIdx.x < r.row_bytes) d[tail0 + threadIdx.x] = s[tail0 + threadIdx.x];
-    }
-}
-
-// ---- layouts (include/xpng_hip.h XPNGHIP_LAYOUT_*; DESIGN.md 15) ------------------------------------------------------------
-// one image's buffer in a layout, either direction: its slot of the staging raster (the launch's pitch), the caller's tight
-// buffer of C * w * h bytes at any alignment, and the image's size in pixels
+// one image of a mixed batch at the staging raster, either direction and every form: its slot of the staging raster (the launch's
+// pitch), the caller's tight buffer at any alignment, and the image's size in pixels.  What a row of the buffer is - w * px bytes,
+// w bytes of a plane, w * C elements - is the kernel's business, so the record depends on nothing but the buffers
 struct MixedLayout {
     uint64_t stage;
     uint8_t *buf;
     uint32_t w, h;
 };
 
+constexpr uint32_t MC_ROWS = 8;  // rows per workgroup of every staging copy kernel (here and mixed_float.hpp)
+
+// grid (ceil(tallest image / MC_ROWS), nimg), 256 threads.  A tight RGB row is w * 3 bytes, so the destination rows of one image
+// start at every alignment: each row is written as a head of up to 3 bytes, whole ALIGNED dwords (each assembled from the source
+// by ld32u: two aligned loads and a shift when the source sits at another alignment), and a tail of up to 3 bytes.  Exactly
+// rows * row_bytes bytes of dst are written.  ld32u may read the aligned dword behind the last source byte: the staging raster
+// keeps 256 spare bytes behind its last slot.  px = bytes per pixel of the context: a row is w * px bytes, and the destination
+// pitch IS that.
+__global__ __launch_bounds__(256) void k_mixed_copy(const MixedLayout *__restrict__ ml, const uint8_t *__restrict__ stage, uint64_t stage_bpr, uint32_t px) {
+    const MixedLayout r = ml[blockIdx.y];
+    const uint32_t row_bytes = r.w * px, rows = r.h;
+    const uint32_t y0 = blockIdx.x * MC_ROWS;
+    if (y0 >= rows) return;
+    for (uint32_t y = y0; y < y0 + MC_ROWS && y < rows; y++) {
+        const uint8_t *s = stage + r.stage + (uint64_t)y * stage_bpr;
+        uint8_t *d = r.buf + (uint64_t)y * row_bytes;
+        uint32_t head = (4u - (uint32_t)((uintptr_t)d & 3)) & 3u;
+        if (head > row_bytes) head = row_bytes;
+        const uint32_t nw = (row_bytes - head) / 4, tail0 = head + 4 * nw;
+        if (threadIdx.x < head) d[threadIdx.x] = s[threadIdx.x];
+        uint32_t *d4 = reinterpret_cast<uint32_t *>(d + head);
+        for (uint32_t k = threadIdx.x; k < nw; k += 256) d4[k] = ld32u(s + head + 4 * k);
+        if (tail0 + threadIdx.x < row_bytes) d[tail0 + threadIdx.x] = s[tail0 + threadIdx.x];
+    }
+}
+
+// grid (ceil(tallest image / MC_ROWS), nimg), 256 threads.  The mirror of k_mixed_copy: the rows of a tight raster start at every
+// alignment (w * 3 bytes each) and the staging rows are 16-byte aligned, so each row is written as whole aligned dwords (each
+// assembled by ld32u: its two aligned loads both hold a byte of the row, so nothing outside the dwords the source occupies is
+// read) and a tail of up to 3 single bytes.  Exactly row_bytes bytes of each of the `rows` staging rows are written; the bytes of
+// a staging row behind them keep whatever they held (no encode kernel lets them reach the output).  px as in k_mixed_copy.
+__global__ __launch_bounds__(256) void k_mixed_pack(const MixedLayout *__restrict__ ml, uint8_t *__restrict__ stage, uint64_t stage_bpr, uint32_t px) {
+    const MixedLayout r = ml[blockIdx.y];
+    const uint32_t row_bytes = r.w * px, rows = r.h;
+    const uint32_t y0 = blockIdx.x * MC_ROWS;
+    if (y0 >= rows) return;
+    const uint32_t nw = row_bytes / 4, tail0 = 4 * nw;
+    for (uint32_t y = y0; y < y0 + MC_ROWS && y < rows; y++) {
+        const uint8_t *s = r.buf + (uint64_t)y * row_bytes;
+        uint8_t *d = stage + r.stage + (uint64_t)y * stage_bpr;
+        uint32_t *d4 = reinterpret_cast<uint32_t *>(d);
+        for (uint32_t k = threadIdx.x; k < nw; k += 256) d4[k] = ld32u(s + 4 * k);
+        if (tail0 + threadIdx.x < row_bytes) d[tail0 + threadIdx.x] = s[tail0 + threadIdx.x];
+    }
+}
+
+// ---- layouts (include/xpng_hip.h XPNGHIP_LAYOUT_*; DESIGN.md 15) ------------------------------------------------------------
 // 16 bytes at a dword-aligned address (staging rows are 16-byte aligned, so every pixel group of a row starts on a dword)
 struct __attribute__((aligned(4))) Dw4 {
     uint32_t x, y, z, w;

@@ -575,12 +575,6 @@ static int decode_region_impl(int mode, const uint8_t *blobs, uint64_t blobs_len
     return 0;
 }
 
-// extern "C" must not leak C++ exceptions (std::bad_alloc from a header that claims an absurd geometry)
-#define XPNG_GUARDED(expr)                                               \
-    try { return (expr); }                                               \
-    catch (const std::bad_alloc &) { return fail("out of host memory"); } \
-    catch (...) { return fail("unexpected C++ exception"); }
-
 extern "C" int xpnghip_encode_tiles_T(uint64_t T, int mode, const uint8_t *raster, uint64_t w, uint64_t h, int pxsz, uint8_t **blobs, uint64_t *blobs_len) {
     XPNG_GUARDED(encode_tiles_impl(T, mode, raster, w, h, pxsz, blobs, blobs_len))
 }

@@ -41,6 +41,12 @@ static int fail(const std::string &m) { g_err = m; return 1; }
         if (e_ != hipSuccess) return fail(std::string(#call) + ": " + hipGetErrorString(e_));          \
     } while (0)
 
+// extern "C" must not leak C++ exceptions (std::bad_alloc from a header that claims an absurd geometry)
+#define XPNG_GUARDED(expr)                                               \
+    try { return (expr); }                                               \
+    catch (const std::bad_alloc &) { return fail("out of host memory"); } \
+    catch (...) { return fail("unexpected C++ exception"); }
+
 // A kernel that dereferences a device pointer nobody allocated does not fail - it FAULTS: the ROCm runtime's fault handler prints
 // "Memory access fault by GPU node ..." and calls abort(), past every catch of the extern "C" entry points (that is what took
 // the test process down in gpurun_out/r2_t14.log: a working tree in which the five symbol planes had just become lazily
@@ -182,19 +188,11 @@ struct xpnghip_ctx {
     uint32_t *d_m_first = nullptr, *d_m_list = nullptr;  // the two on the device (one allocation: d_m_first)
     uint8_t *d_m_stage = nullptr;      // tight output form: staging raster at the widest image's pitch, allocated on first use
     uint64_t cap_m_stage = 0;
-    MixedCopy *d_m_copy = nullptr;     // B copy records
-    std::vector<void *> h_m_copy_dst;  // the destinations d_m_copy holds (skip the upload when unchanged)
-    MixedPack *d_m_pack = nullptr;     // tight input form of the encode: B pack records
-    std::vector<const void *> h_m_pack_src;  // the sources d_m_pack holds
-    // buffers in a layout (XPNGHIP_LAYOUT_*): B records per direction.  A record holds the slot, the buffer, w and h -
-    // nothing that depends on the layout word, which only selects the kernel - so the pointers are the whole cache key
-    MixedLayout *d_m_as = nullptr, *d_m_from = nullptr;
-    std::vector<void *> h_m_as_dst;          // the destinations d_m_as holds
-    std::vector<const void *> h_m_from_src;  // the sources d_m_from holds
-    // ... and of the float form of the decode (XPNGHIP_DTYPE_*): the same records - nothing in them depends on the
-    // dtype or the constants either - in a table of their own, cached on the pointers
-    MixedLayout *d_m_asf = nullptr;
-    std::vector<void *> h_m_asf_dst;
+    // the record tables of the tight forms (mixed_records): B MixedLayout per direction - the caller's output buffers of a decode,
+    // its input buffers of an encode.  A record holds the slot, the buffer, w and h: nothing that depends on the form of the call
+    // (tight, layout word, dtype, constants - they only select the kernel), so the pointers are the whole cache key
+    MixedLayout *d_m_out = nullptr, *d_m_in = nullptr;
+    std::vector<const void *> h_m_out, h_m_in;  // the buffers the two tables hold (skip the upload when unchanged)
 };
 
 // the context's own stream, created when a call first needs it (the `stream == NULL` form of the device-resident entry points,
@@ -215,7 +213,7 @@ extern "C" void xpnghip_ctx_destroy(xpnghip_ctx *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void *ptrs[] = {c->d_tiles, c->d_planes, c->d_scratch, c->d_sums, c->d_nlh, c->d_ctx_n, c->d_k_n, c->d_blk_sz, c->d_tile_sz,
                     c->d_tile_hdr, c->d_off, c->d_totals, c->d_raster, c->d_blobs, c->d_blob_in, c->d_dbg, (void *)c->d_in_ptrs, (void *)c->d_out_ptrs, (void *)c->d_dec_in_ptrs, (void *)c->d_dec_out_ptrs, (void *)c->d_order,
-                    c->d_wprep, c->d_wtab, c->d_wF, c->d_blob_len, c->d_status, c->d_scratch2, c->d_sbase2, c->d_flags2, c->d_stream_n2, c->d_blk2, c->d_mt2, c->d_info2, c->d_tabs2, c->d_w1prep, c->d_w1tab, c->d_w1F, c->d_region_stage, c->d_region_meta, c->d_m_first, c->d_m_stage, c->d_m_copy, c->d_m_pack, c->d_m_as, c->d_m_from, c->d_m_asf};
+                    c->d_wprep, c->d_wtab, c->d_wF, c->d_blob_len, c->d_status, c->d_scratch2, c->d_sbase2, c->d_flags2, c->d_stream_n2, c->d_blk2, c->d_mt2, c->d_info2, c->d_tabs2, c->d_w1prep, c->d_w1tab, c->d_w1F, c->d_region_stage, c->d_region_meta, c->d_m_first, c->d_m_stage, c->d_m_out, c->d_m_in};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->enc_side) (void)hipStreamDestroy(c->enc_side);
     if (c->ev_enc_fork) (void)hipEventDestroy(c->ev_enc_fork);
@@ -230,9 +228,7 @@ extern "C" void xpnghip_ctx_destroy(xpnghip_ctx *c) {
 static int ctx_create_range_impl(xpnghip_ctx **out, int device, uint64_t w, uint64_t h, int pxsz, uint32_t batch, uint64_t r0, uint64_t r1);
 extern "C" int xpnghip_ctx_create_range(xpnghip_ctx **out, int device, uint64_t w, uint64_t h, int pxsz, uint32_t batch,
                                         uint64_t r0, uint64_t r1) {
-    try { return ctx_create_range_impl(out, device, w, h, pxsz, batch, r0, r1); }
-    catch (const std::bad_alloc &) { return fail("out of host memory"); }
-    catch (...) { return fail("unexpected C++ exception"); }
+    XPNG_GUARDED(ctx_create_range_impl(out, device, w, h, pxsz, batch, r0, r1))
 }
 static int ctx_create_range_impl(xpnghip_ctx **out, int device, uint64_t w, uint64_t h, int pxsz, uint32_t batch, uint64_t r0, uint64_t r1) {
     if (!out || !w || !h || w > (1u << 24) || h > (1u << 24) || (pxsz != 3 && pxsz != 4) || batch < 1 || batch > 4096 || r0 >= r1) return fail("bad arguments");
@@ -827,9 +823,7 @@ static int region_batch_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
 }
 extern "C" int xpnghip_decode_region_device_batch(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
                                                   const uint64_t *tile_off, const uint64_t *rects, void *const *d_outs, uint64_t out_bpr, void *stream) {
-    try { return region_batch_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, rects, d_outs, out_bpr, stream); }
-    catch (const std::bad_alloc &) { return fail("out of host memory"); }
-    catch (...) { return fail("unexpected C++ exception"); }
+    XPNG_GUARDED(region_batch_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, rects, d_outs, out_bpr, stream))
 }
 
 // ---- mixed-size batch decode (mixed.hpp) ---------------------------------------------------------
@@ -897,9 +891,7 @@ static int ctx_create_mixed_impl(xpnghip_ctx **out, int device, const uint64_t *
     return 0;
 }
 extern "C" int xpnghip_ctx_create_mixed(xpnghip_ctx **out, int device, const uint64_t *dims, uint32_t nimg, int pxsz) {
-    try { return ctx_create_mixed_impl(out, device, dims, nimg, pxsz); }
-    catch (const std::bad_alloc &) { return fail("out of host memory"); }
-    catch (...) { return fail("unexpected C++ exception"); }
+    XPNG_GUARDED(ctx_create_mixed_impl(out, device, dims, nimg, pxsz))
 }
 extern "C" uint64_t xpnghip_ctx_mixed_first_tile(const xpnghip_ctx *c, uint32_t image) {
     return c && c->mixed && image < c->m_first.size() ? c->m_first[image] : ~0ull;
@@ -916,18 +908,23 @@ static std::string layout_hex(uint32_t layout) {
     snprintf(b, sizeof b, "0x%x", layout);
     return b;
 }
-// the per-image records of a layout call: image i's slot, its buffer and its size; uploaded when the buffers changed
-static int layout_records(xpnghip_ctx *c, MixedLayout **d_tab, const std::vector<uint64_t> &slot, const void *const *bufs, hipStream_t s) {
+// The per-image records of a tight call, either direction and every form: image i's slot, its buffer and its size.  `table` and
+// `cache` are the context's pair for the direction; the table is allocated on first use and uploaded when the buffers changed.
+static int mixed_records(xpnghip_ctx *c, MixedLayout *&table, std::vector<const void *> &cache, const std::vector<uint64_t> &slot,
+                         const void *const *bufs, hipStream_t s) {
     const uint32_t nimg = c->B;
-    if (!*d_tab) {
-        HIPCHK(hipMalloc((void **)d_tab, (uint64_t)nimg * sizeof(MixedLayout)));
+    if (!table) {
+        HIPCHK(hipMalloc((void **)&table, (uint64_t)nimg * sizeof(MixedLayout)));
         c->ws_bytes += (uint64_t)nimg * sizeof(MixedLayout);
     }
+    if (cache.size() == nimg && std::equal(cache.begin(), cache.end(), bufs)) return 0;
     std::vector<MixedLayout> ml(nimg);
     for (uint32_t i = 0; i < nimg; i++)
         ml[i] = MixedLayout{slot[i], (uint8_t *)const_cast<void *>(bufs[i]), (uint32_t)c->m_dims[2ull * i], (uint32_t)c->m_dims[2ull * i + 1]};
-    HIPCHK(hipMemcpyAsync(*d_tab, ml.data(), (uint64_t)nimg * sizeof(MixedLayout), hipMemcpyHostToDevice, s));  // (pageable host memory: the copy is staged synchronously anyway)
+    cache.clear();  // (a failed upload must not leave a cache that claims the table is current)
+    HIPCHK(hipMemcpyAsync(table, ml.data(), (uint64_t)nimg * sizeof(MixedLayout), hipMemcpyHostToDevice, s));  // (pageable host memory: the copy is staged synchronously anyway)
     HIPCHK(hipStreamSynchronize(s));
+    cache.assign(bufs, bufs + nimg);
     return 0;
 }
 template <int PX>
@@ -935,19 +932,19 @@ static void launch_copy_as(const xpnghip_ctx *c, uint32_t layout, int C, uint64_
     const dim3 grid((uint32_t)((c->m_max_h + MC_ROWS - 1) / MC_ROWS), c->B);
     const uint32_t bgr = layout & XPNGHIP_LAYOUT_BGR;
     if (layout & XPNGHIP_LAYOUT_PLANAR) {
-        if (C == 3) k_mixed_copy_as<PX, 3, true><<<grid, 256, 0, s>>>(c->d_m_as, c->d_m_stage, bpr, bgr);
-        else k_mixed_copy_as<PX, 4, true><<<grid, 256, 0, s>>>(c->d_m_as, c->d_m_stage, bpr, bgr);
+        if (C == 3) k_mixed_copy_as<PX, 3, true><<<grid, 256, 0, s>>>(c->d_m_out, c->d_m_stage, bpr, bgr);
+        else k_mixed_copy_as<PX, 4, true><<<grid, 256, 0, s>>>(c->d_m_out, c->d_m_stage, bpr, bgr);
     } else {
-        if (C == 3) k_mixed_copy_as<PX, 3, false><<<grid, 256, 0, s>>>(c->d_m_as, c->d_m_stage, bpr, bgr);
-        else k_mixed_copy_as<PX, 4, false><<<grid, 256, 0, s>>>(c->d_m_as, c->d_m_stage, bpr, bgr);
+        if (C == 3) k_mixed_copy_as<PX, 3, false><<<grid, 256, 0, s>>>(c->d_m_out, c->d_m_stage, bpr, bgr);
+        else k_mixed_copy_as<PX, 4, false><<<grid, 256, 0, s>>>(c->d_m_out, c->d_m_stage, bpr, bgr);
     }
 }
 template <int PX>
 static void launch_pack_from(const xpnghip_ctx *c, uint32_t layout, uint64_t bpr, hipStream_t s) {
     const dim3 grid((uint32_t)((c->m_max_h + MC_ROWS - 1) / MC_ROWS), c->B);
     const uint32_t bgr = layout & XPNGHIP_LAYOUT_BGR;
-    if (layout & XPNGHIP_LAYOUT_PLANAR) k_mixed_pack_from<PX, true><<<grid, 256, 0, s>>>(c->d_m_from, c->d_m_stage, bpr, bgr);
-    else k_mixed_pack_from<PX, false><<<grid, 256, 0, s>>>(c->d_m_from, c->d_m_stage, bpr, bgr);
+    if (layout & XPNGHIP_LAYOUT_PLANAR) k_mixed_pack_from<PX, true><<<grid, 256, 0, s>>>(c->d_m_in, c->d_m_stage, bpr, bgr);
+    else k_mixed_pack_from<PX, false><<<grid, 256, 0, s>>>(c->d_m_in, c->d_m_stage, bpr, bgr);
 }
 
 // ---- float layouts (XPNGHIP_DTYPE_*; mixed_float.hpp) -----------------------------------------------------
@@ -1015,11 +1012,11 @@ static void launch_copy_as_float(const xpnghip_ctx *c, uint32_t layout, int C, u
     const dim3 grid((uint32_t)((c->m_max_h + MC_ROWS - 1) / MC_ROWS), c->B);
     const uint32_t bgr = layout & XPNGHIP_LAYOUT_BGR;
     if (layout & XPNGHIP_LAYOUT_PLANAR) {
-        if (C == 3) k_mixed_copy_as_float<PX, 3, true, T><<<grid, 256, 0, s>>>(c->d_m_asf, c->d_m_stage, bpr, bgr, k);
-        else k_mixed_copy_as_float<PX, 4, true, T><<<grid, 256, 0, s>>>(c->d_m_asf, c->d_m_stage, bpr, bgr, k);
+        if (C == 3) k_mixed_copy_as_float<PX, 3, true, T><<<grid, 256, 0, s>>>(c->d_m_out, c->d_m_stage, bpr, bgr, k);
+        else k_mixed_copy_as_float<PX, 4, true, T><<<grid, 256, 0, s>>>(c->d_m_out, c->d_m_stage, bpr, bgr, k);
     } else {
-        if (C == 3) k_mixed_copy_as_float<PX, 3, false, T><<<grid, 256, 0, s>>>(c->d_m_asf, c->d_m_stage, bpr, bgr, k);
-        else k_mixed_copy_as_float<PX, 4, false, T><<<grid, 256, 0, s>>>(c->d_m_asf, c->d_m_stage, bpr, bgr, k);
+        if (C == 3) k_mixed_copy_as_float<PX, 3, false, T><<<grid, 256, 0, s>>>(c->d_m_out, c->d_m_stage, bpr, bgr, k);
+        else k_mixed_copy_as_float<PX, 4, false, T><<<grid, 256, 0, s>>>(c->d_m_out, c->d_m_stage, bpr, bgr, k);
     }
 }
 template <int PX>
@@ -1089,31 +1086,7 @@ static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *
         // its slot 256-byte aligned), then k_mixed_copy moves every image out at its own pitch
         std::vector<uint64_t> slot;
         if (mixed_stage_slots(c, bpr, slot)) return 1;
-        if (fc) {
-            if (c->h_m_asf_dst != base) {
-                c->h_m_asf_dst.clear();
-                if (layout_records(c, &c->d_m_asf, slot, d_outs, s)) return 1;
-                c->h_m_asf_dst = base;
-            }
-        } else if (as) {
-            if (c->h_m_as_dst != base) {
-                c->h_m_as_dst.clear();
-                if (layout_records(c, &c->d_m_as, slot, d_outs, s)) return 1;
-                c->h_m_as_dst = base;
-            }
-        } else if (!c->d_m_copy) {
-            HIPCHK(hipMalloc((void **)&c->d_m_copy, (uint64_t)nimg * sizeof(MixedCopy)));
-            c->ws_bytes += (uint64_t)nimg * sizeof(MixedCopy);
-        }
-        if (!as && !fc && c->h_m_copy_dst != base) {  // (pageable host memory: the copy is staged synchronously anyway)
-            std::vector<MixedCopy> mc(nimg);
-            for (uint32_t i = 0; i < nimg; i++)
-                mc[i] = MixedCopy{slot[i], (uint8_t *)d_outs[i], (uint32_t)(c->m_dims[2ull * i] * px), (uint32_t)c->m_dims[2ull * i + 1]};
-            c->h_m_copy_dst.clear();
-            HIPCHK(hipMemcpyAsync(c->d_m_copy, mc.data(), (uint64_t)nimg * sizeof(MixedCopy), hipMemcpyHostToDevice, s));
-            HIPCHK(hipStreamSynchronize(s));
-            c->h_m_copy_dst = base;
-        }
+        if (mixed_records(c, c->d_m_out, c->h_m_out, slot, d_outs, s)) return 1;
         for (uint32_t i = 0; i < nimg; i++) base[i] = c->d_m_stage + slot[i];
     }
     if (dec_prepare(c, mode, d_blobs, blobs_len, nimg, base.data(), s)) return 1;
@@ -1121,41 +1094,35 @@ static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *
     const int rc = dec_launch(c, mode, nimg, c->m_max_w, tile_off, s, 0, (uint32_t)c->tiles.size(), &c->m_list, c->d_m_list, bpr);
     if (rc) return rc;
     if (fc) {
-        XPNG_REQUIRE(c->d_m_stage, c->d_m_asf);
+        XPNG_REQUIRE(c->d_m_stage, c->d_m_out);
         if (c->pxsz == 4) launch_copy_as_float<4>(c, *layout, C, bpr, fc->dtype, fk, s);
         else launch_copy_as_float<3>(c, *layout, C, bpr, fc->dtype, fk, s);
         HIPCHK(hipGetLastError());
     } else if (as) {
-        XPNG_REQUIRE(c->d_m_stage, c->d_m_as);
+        XPNG_REQUIRE(c->d_m_stage, c->d_m_out);
         if (c->pxsz == 4) launch_copy_as<4>(c, *layout, C, bpr, s);
         else launch_copy_as<3>(c, *layout, C, bpr, s);
         HIPCHK(hipGetLastError());
     } else if (!out_bpr) {
-        XPNG_REQUIRE(c->d_m_stage, c->d_m_copy);
-        k_mixed_copy<<<dim3((uint32_t)((c->m_max_h + MC_ROWS - 1) / MC_ROWS), nimg), 256, 0, s>>>(c->d_m_copy, c->d_m_stage, bpr);
+        XPNG_REQUIRE(c->d_m_stage, c->d_m_out);
+        k_mixed_copy<<<dim3((uint32_t)((c->m_max_h + MC_ROWS - 1) / MC_ROWS), nimg), 256, 0, s>>>(c->d_m_out, c->d_m_stage, bpr, (uint32_t)px);
         HIPCHK(hipGetLastError());
     }
     return 0;
 }
 extern "C" int xpnghip_decode_mixed_device_batch(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
                                                  const uint64_t *tile_off, void *const *d_outs, uint64_t out_bpr, void *stream) {
-    try { return decode_mixed_batch_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, d_outs, out_bpr, stream); }
-    catch (const std::bad_alloc &) { return fail("out of host memory"); }
-    catch (...) { return fail("unexpected C++ exception"); }
+    XPNG_GUARDED(decode_mixed_batch_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, d_outs, out_bpr, stream))
 }
 extern "C" int xpnghip_decode_varsize_device_batch_as(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
                                                       const uint64_t *tile_off, void *const *d_outs, uint32_t layout, void *stream) {
-    try { return decode_mixed_batch_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, d_outs, 0, stream, &layout); }
-    catch (const std::bad_alloc &) { return fail("out of host memory"); }
-    catch (...) { return fail("unexpected C++ exception"); }
+    XPNG_GUARDED(decode_mixed_batch_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, d_outs, 0, stream, &layout))
 }
 extern "C" int xpnghip_decode_varsize_device_batch_as_float(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
                                                             const uint64_t *tile_off, void *const *d_outs, uint32_t layout, uint32_t dtype,
                                                             const float *scale, const float *bias, void *stream) {
     const FloatCall fc{dtype, scale, bias};
-    try { return decode_mixed_batch_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, d_outs, 0, stream, &layout, &fc); }
-    catch (const std::bad_alloc &) { return fail("out of host memory"); }
-    catch (...) { return fail("unexpected C++ exception"); }
+    XPNG_GUARDED(decode_mixed_batch_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, d_outs, 0, stream, &layout, &fc))
 }
 
 // ---- mixed-size batch encode (mixed.hpp) ---------------------------------------------------------
@@ -1218,37 +1185,19 @@ static int encode_varsize_impl(xpnghip_ctx *c, int mode, const void *const *d_ra
         // (image i: h_i rows, its slot 256-byte aligned - the buffer, and the layout, of the tight decode), and the kernels read that
         std::vector<uint64_t> slot;
         if (mixed_stage_slots(c, bpr, slot)) return 1;
-        if (from) {
-            if (c->h_m_from_src != base) {
-                c->h_m_from_src.clear();
-                if (layout_records(c, &c->d_m_from, slot, d_rasters, s)) return 1;
-                c->h_m_from_src = base;
-            }
-        } else if (!c->d_m_pack) {
-            HIPCHK(hipMalloc((void **)&c->d_m_pack, (uint64_t)nimg * sizeof(MixedPack)));
-            c->ws_bytes += (uint64_t)nimg * sizeof(MixedPack);
-        }
-        if (!from && c->h_m_pack_src != base) {  // (pageable host memory: the copy is staged synchronously anyway)
-            std::vector<MixedPack> mp(nimg);
-            for (uint32_t i = 0; i < nimg; i++)
-                mp[i] = MixedPack{slot[i], (const uint8_t *)d_rasters[i], (uint32_t)(c->m_dims[2ull * i] * px), (uint32_t)c->m_dims[2ull * i + 1]};
-            c->h_m_pack_src.clear();
-            HIPCHK(hipMemcpyAsync(c->d_m_pack, mp.data(), (uint64_t)nimg * sizeof(MixedPack), hipMemcpyHostToDevice, s));
-            HIPCHK(hipStreamSynchronize(s));
-            c->h_m_pack_src = base;
-        }
+        if (mixed_records(c, c->d_m_in, c->h_m_in, slot, d_rasters, s)) return 1;
         for (uint32_t i = 0; i < nimg; i++) base[i] = c->d_m_stage + slot[i];
     }
     if (set_ptrs(c, base.data(), d_blobs, nimg, s)) return 1;
     XPNG_REQUIRE(c->d_m_first, c->d_m_list);
     if (from) {
-        XPNG_REQUIRE(c->d_m_stage, c->d_m_from);
+        XPNG_REQUIRE(c->d_m_stage, c->d_m_in);
         if (c->pxsz == 4) launch_pack_from<4>(c, *layout, bpr, s);
         else launch_pack_from<3>(c, *layout, bpr, s);
         HIPCHK(hipGetLastError());
     } else if (!in_bpr) {
-        XPNG_REQUIRE(c->d_m_stage, c->d_m_pack);
-        k_mixed_pack<<<dim3((uint32_t)((c->m_max_h + MC_ROWS - 1) / MC_ROWS), nimg), 256, 0, s>>>(c->d_m_pack, c->d_m_stage, bpr);
+        XPNG_REQUIRE(c->d_m_stage, c->d_m_in);
+        k_mixed_pack<<<dim3((uint32_t)((c->m_max_h + MC_ROWS - 1) / MC_ROWS), nimg), 256, 0, s>>>(c->d_m_in, c->d_m_stage, bpr, (uint32_t)px);
         HIPCHK(hipGetLastError());
     }
     const EncSpan e = enc_span_mixed(c, bpr);
@@ -1262,15 +1211,11 @@ static int encode_varsize_impl(xpnghip_ctx *c, int mode, const void *const *d_ra
 }
 extern "C" int xpnghip_encode_varsize_device_batch(xpnghip_ctx *c, int mode, const void *const *d_rasters, uint64_t in_bpr, uint32_t nimg,
                                                    void *const *d_blobs, uint64_t *blobs_len, void *stream) {
-    try { return encode_varsize_impl(c, mode, d_rasters, in_bpr, nimg, d_blobs, blobs_len, stream); }
-    catch (const std::bad_alloc &) { return fail("out of host memory"); }
-    catch (...) { return fail("unexpected C++ exception"); }
+    XPNG_GUARDED(encode_varsize_impl(c, mode, d_rasters, in_bpr, nimg, d_blobs, blobs_len, stream))
 }
 extern "C" int xpnghip_encode_varsize_device_batch_from(xpnghip_ctx *c, int mode, const void *const *d_rasters, uint32_t layout, uint32_t nimg,
                                                         void *const *d_blobs, uint64_t *blobs_len, void *stream) {
-    try { return encode_varsize_impl(c, mode, d_rasters, 0, nimg, d_blobs, blobs_len, stream, &layout); }
-    catch (const std::bad_alloc &) { return fail("out of host memory"); }
-    catch (...) { return fail("unexpected C++ exception"); }
+    XPNG_GUARDED(encode_varsize_impl(c, mode, d_rasters, 0, nimg, d_blobs, blobs_len, stream, &layout))
 }
 
 // Synchronises `stream` and reports the last decode: 0 = every tile header was consistent, 1 = at least one tile was
