@@ -347,6 +347,42 @@ int xpnghip_decode_varsize_device_batch_as_float(xpnghip_ctx *ctx, int mode, con
                                                  uint32_t nimg, const uint64_t *tile_off, void *const *d_outs, uint32_t layout,
                                                  uint32_t dtype, const float *scale, const float *bias, void *stream);
 
+/* ---- crop, resize and flip in the same pass -------------------------------------------------
+ * The float call above up to the copy-out - the same checks, blobs, size walk, staging raster and xpnghip_ctx_decode_status; every
+ * tile is reconstructed as always - but the copy-out writes, for every image, a source rectangle resampled to ONE output size
+ * out_h x out_w (each 1 .. 16384) with plain 2 x 2-tap bilinear interpolation (half-pixel centres, no antialiasing), optionally
+ * mirrored left to right.  Image i has the rectangle {x, y, w, h} = rects[4i .. 4i+3] (valid as for the region decode: not empty,
+ * inside the image; rects == NULL: every whole image) and the flip flips[i] (0 or 1; flips == NULL: none).  With
+ *     kx = (float)rw / (float)out_w,  ky = (float)rh / (float)out_h           one IEEE fp32 division each, on the host
+ * output column ox (rows alike with ky, rh and no flip), u = flip ? out_w - 1 - ox : ox, is
+ *     sx = max(fmaf((float)u + 0.5f, kx, -0.5f), 0.0f)
+ *     x0 = min((uint32_t)sx, rw - 1)     x1 = min(x0 + 1, rw - 1)     lx = sx - (float)x0
+ * and with p00 p01 / p10 p11 the bytes at (y + y0|y1, x + x0|x1) as floats - the byte of channel position c chosen as in the float
+ * call: BGR exchange, alpha last, the alpha an RGB context lacks is 255 -
+ *     a = fmaf(lx, p01 - p00, p00)   b = fmaf(lx, p11 - p10, p10)   v = fmaf(ly, b - a, a)
+ *     y = fmaf(v, scale[c], bias[c])   out = (T)y                   round to nearest even
+ * Edges clamp to the RECTANGLE, not the image.  A rectangle of the output's size is a pure crop (lx == ly == 0), bit for bit the
+ * slice of the float call's output; a flip is a mirror on the bits.
+ * d_outs[i] is exactly C * out_h * out_w elements in the layout's order, aligned to the element size (slices of one
+ * (N, C, out_h, out_w) tensor qualify); nothing else is written.  The rectangle table (32 bytes per image) is uploaded on every
+ * call and never cached; for that upload the call synchronises `stream` once BEFORE it queues its own kernels (the records are in
+ * pageable host memory that ends with the call), so it waits for the caller's earlier work on the stream, never for its own.
+ * Refused before anything reaches the device, with the offending value in xpnghip_last_error() and nothing written: a rectangle
+ * that is empty or leaves its image (the text names the image), out_w or out_h outside 1 .. 16384, a flip byte other than 0 or 1,
+ * and everything the float call refuses.  A rejected tile leaves the output elements with a tap inside it undefined; every other
+ * element is written. */
+int xpnghip_decode_varsize_device_batch_resized(xpnghip_ctx *ctx, int mode, const void *const *d_blobs, const uint64_t *blobs_len,
+                                                uint32_t nimg, const uint64_t *tile_off, void *const *d_outs, uint32_t layout,
+                                                uint32_t dtype, const float *scale, const float *bias, const uint64_t *rects,
+                                                const uint8_t *flips, uint32_t out_w, uint32_t out_h, void *stream);
+/* host-only, needs no device: the same rule, bit for bit, applied to a tight interleaved host raster of h rows of w * pxsz bytes
+ * (pxsz 3 or 4; w, h <= 1 << 24).  rect: {x, y, w, h} or NULL for the whole raster; flip 0 or 1; out: C * out_h * out_w elements
+ * of `dtype` in `layout`, aligned to the element size.  What xpnghip_float_table is to the float call: for a caller that answers
+ * some images without the codec.  0 on success; non-zero, with the offending value in xpnghip_last_error() and nothing written, on
+ * a bad pxsz, layout, dtype, size, rectangle or flip, a non-finite constant, a NULL raster, or a NULL or misaligned out. */
+int xpnghip_resize_host(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip, uint32_t out_w,
+                        uint32_t out_h, uint32_t layout, uint32_t dtype, const float *scale, const float *bias, void *out);
+
 /* Stage-only run for BASELINE config 2: predictor chooser + per-pixel transform (libxpng.c:92-140 and
  * the arithmetic of 497-519) over tiles [t0, t1); symbol planes stay in the context's workspace. */
 int xpnghip_m1_transform_device(xpnghip_ctx *ctx, const void *d_raster, uint64_t t0, uint64_t t1, void *stream);

@@ -34,6 +34,7 @@ HIP_SYMBOLS = [
     "xpnghip_images_first_pixel", "xpnghip_batch_cuts",
     "xpnghip_layout_channels", "xpnghip_decode_varsize_device_batch_as", "xpnghip_encode_varsize_device_batch_from",
     "xpnghip_dtype_bytes", "xpnghip_float_table", "xpnghip_decode_varsize_device_batch_as_float",
+    "xpnghip_decode_varsize_device_batch_resized", "xpnghip_resize_host",
 ]
 HOST_SYMBOLS = ["xpng_store", "xpng_load", "xpng_from_jpg", "xpng_store_T", "xpng_load_T", "xpng_from_jpg_T",
                 "store_7", "load_7"]
@@ -172,6 +173,13 @@ def _bind_hip(path):
         L.xpnghip_decode_varsize_device_batch_as_float.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64), C.c_uint32, C.POINTER(u64),
                                                                    C.POINTER(vp), C.c_uint32, C.c_uint32, f32p, f32p, vp]
         u8p = C.POINTER(C.c_uint8)
+        L.xpnghip_decode_varsize_device_batch_resized.restype = C.c_int
+        L.xpnghip_decode_varsize_device_batch_resized.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64), C.c_uint32, C.POINTER(u64),
+                                                                  C.POINTER(vp), C.c_uint32, C.c_uint32, f32p, f32p, C.POINTER(u64), u8p,
+                                                                  C.c_uint32, C.c_uint32, vp]
+        L.xpnghip_resize_host.restype = C.c_int
+        L.xpnghip_resize_host.argtypes = [C.c_int, vp, u64, u64, C.POINTER(u64), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                          f32p, f32p, vp]
         L.xpnghip_images_begin.restype = C.c_int
         L.xpnghip_images_begin.argtypes = [C.POINTER(vp), C.c_uint32, C.POINTER(vp), C.POINTER(u64), u8p, u8p]
         L.xpnghip_images_single_colour.restype = C.c_int
@@ -506,6 +514,42 @@ def float_table(dtype: int, scale, bias) -> bytes:
     return buf.raw[:len(sc) * 256 * dtype_bytes(dtype)]
 
 
+def _rect_array(name, rects, n):
+    """n rectangles (x, y, w, h) as a flat C array of uint64 (None stays None: every whole image)"""
+    if rects is None:
+        return None
+    rects = list(rects)
+    if len(rects) != n or any(len(r) != 4 for r in rects):
+        raise XpngError(f"{name}: rects must be {n} tuples (x, y, w, h)")
+    try:
+        return (C.c_uint64 * max(4 * n, 1))(*[int(v) for r in rects for v in r])
+    except (TypeError, ValueError):
+        raise XpngError(f"{name}: a rectangle is four non-negative integers (x, y, w, h)") from None
+
+
+def resize_host(raster, size, layout: int, dtype: int, scale=None, bias=None, rect=None, flip=False) -> bytes:
+    """The rule of MixedContext.decode_batch_resized on the host (xpnghip_resize_host; needs no device): `raster` is an
+    (h, w, 3|4) uint8 array in the file's form, size = (OH, OW), rect = (x, y, w, h) or None for the whole raster.  Returns the
+    C * OH * OW elements of `dtype` in `layout` as raw bytes, bit for bit what the device call writes for these pixels."""
+    r = np.ascontiguousarray(raster, dtype=np.uint8)
+    if r.ndim != 3 or r.shape[2] not in (3, 4):
+        raise XpngError("resize_host: the raster must be (h, w, 3) or (h, w, 4) uint8")
+    try:
+        oh, ow = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise XpngError(f"resize_host: size must be (OH, OW), not {size!r}") from None
+    px = r.shape[2]
+    ch = hip_lib().xpnghip_layout_channels(layout, px)
+    sc, bi = _floats("scale", scale, ch if ch > 0 else None), _floats("bias", bias, ch if ch > 0 else None)
+    ra = _rect_array("resize_host", None if rect is None else [rect], 1)
+    ok = ch > 0 and 1 <= oh <= 16384 and 1 <= ow <= 16384          # (anything else the library refuses, naming the value)
+    buf = np.empty(ch * oh * ow if ok else 1, dtype=np.uint32)     # 4-byte aligned, room for the widest element
+    if hip_lib().xpnghip_resize_host(px, r.ctypes.data, r.shape[1], r.shape[0], ra, int(flip), ow & 0xFFFFFFFF, oh & 0xFFFFFFFF, layout, dtype, sc, bi,
+                                     buf.ctypes.data):
+        raise XpngError("xpnghip_resize_host: " + _err())
+    return buf.tobytes()[:ch * oh * ow * dtype_bytes(dtype)]
+
+
 def store_batch(mode: int, rasters, paths) -> None:
     """xpng_store_batch (include/xpng_store_batch.h): file i is what store(mode, rasters[i], paths[i]) writes; the tile stage of
     all images of one (tile mode, bytes per pixel) is one mixed-size device call."""
@@ -814,6 +858,34 @@ class MixedContext:
         ins, outs, ln = (C.c_void_p * k)(*d_blobs), (C.c_void_p * len(d_outs))(*d_outs), (C.c_uint64 * len(lens))(*lens)
         if hip_lib().xpnghip_decode_varsize_device_batch_as_float(self._h, mode, ins, ln, k, off_arr, outs, layout, dtype, sc, bi, stream):
             raise XpngError("xpnghip_decode_varsize_device_batch_as_float: " + _err())
+
+    def decode_batch_resized(self, mode, d_blobs, lens, d_outs, layout, dtype, size, scale=None, bias=None, rects=None, flips=None,
+                             tile_offs=None, stream=0):
+        """decode_batch_as_float with a crop, a bilinear resize and a left-right flip in the copy-out: every d_outs[i] is
+        C * OH * OW elements of `dtype`, size = (OH, OW), the resampling of rects[i] = (x, y, w, h) of image i (None: every whole
+        image), mirrored where flips[i] is true (None: none): xpnghip_decode_varsize_device_batch_resized."""
+        k = len(d_blobs)
+        off_arr = None
+        if tile_offs is not None:
+            flat = [o for offs in tile_offs for o in offs]
+            assert len(flat) == self.n_tiles
+            off_arr = (C.c_uint64 * len(flat))(*flat)
+        try:
+            oh, ow = (int(v) & 0xFFFFFFFF for v in size)
+        except (TypeError, ValueError):
+            raise XpngError(f"decode_batch_resized: size must be (OH, OW), not {size!r}") from None
+        ch = hip_lib().xpnghip_layout_channels(layout, self.pxsz)
+        sc, bi = _floats("scale", scale, ch if ch > 0 else None), _floats("bias", bias, ch if ch > 0 else None)
+        ra = _rect_array("decode_batch_resized", rects, k)
+        fl = None
+        if flips is not None:
+            flips = list(flips)
+            if len(flips) != k:
+                raise XpngError(f"decode_batch_resized: flips has {len(flips)} entries for {k} images")
+            fl = (C.c_uint8 * max(k, 1))(*[int(f) & 0xFF for f in flips])
+        ins, outs, ln = (C.c_void_p * k)(*d_blobs), (C.c_void_p * len(d_outs))(*d_outs), (C.c_uint64 * len(lens))(*lens)
+        if hip_lib().xpnghip_decode_varsize_device_batch_resized(self._h, mode, ins, ln, k, off_arr, outs, layout, dtype, sc, bi, ra, fl, ow, oh, stream):
+            raise XpngError("xpnghip_decode_varsize_device_batch_resized: " + _err())
 
     def encode_batch_from(self, mode, d_rasters, layout, d_blobs, stream=0, sync=True):
         """encode_batch in its tight form, with every d_rasters[i] read in `layout` (api.layout(); its channels must be the

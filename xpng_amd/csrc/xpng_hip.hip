@@ -30,6 +30,7 @@
 #include "region.hpp"
 #include "mixed.hpp"
 #include "mixed_float.hpp"
+#include "mixed_resize.hpp"
 
 using namespace xpng;
 
@@ -193,6 +194,7 @@ struct xpnghip_ctx {
     // (tight, layout word, dtype, constants - they only select the kernel), so the pointers are the whole cache key
     MixedLayout *d_m_out = nullptr, *d_m_in = nullptr;
     std::vector<const void *> h_m_out, h_m_in;  // the buffers the two tables hold (skip the upload when unchanged)
+    ResizeRec *d_m_rect = nullptr;     // the rectangle table of a resized decode (mixed_resize.hpp): B records, uploaded by every call
 };
 
 // the context's own stream, created when a call first needs it (the `stream == NULL` form of the device-resident entry points,
@@ -213,7 +215,7 @@ extern "C" void xpnghip_ctx_destroy(xpnghip_ctx *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void *ptrs[] = {c->d_tiles, c->d_planes, c->d_scratch, c->d_sums, c->d_nlh, c->d_ctx_n, c->d_k_n, c->d_blk_sz, c->d_tile_sz,
                     c->d_tile_hdr, c->d_off, c->d_totals, c->d_raster, c->d_blobs, c->d_blob_in, c->d_dbg, (void *)c->d_in_ptrs, (void *)c->d_out_ptrs, (void *)c->d_dec_in_ptrs, (void *)c->d_dec_out_ptrs, (void *)c->d_order,
-                    c->d_wprep, c->d_wtab, c->d_wF, c->d_blob_len, c->d_status, c->d_scratch2, c->d_sbase2, c->d_flags2, c->d_stream_n2, c->d_blk2, c->d_mt2, c->d_info2, c->d_tabs2, c->d_w1prep, c->d_w1tab, c->d_w1F, c->d_region_stage, c->d_region_meta, c->d_m_first, c->d_m_stage, c->d_m_out, c->d_m_in};
+                    c->d_wprep, c->d_wtab, c->d_wF, c->d_blob_len, c->d_status, c->d_scratch2, c->d_sbase2, c->d_flags2, c->d_stream_n2, c->d_blk2, c->d_mt2, c->d_info2, c->d_tabs2, c->d_w1prep, c->d_w1tab, c->d_w1F, c->d_region_stage, c->d_region_meta, c->d_m_first, c->d_m_stage, c->d_m_out, c->d_m_in, c->d_m_rect};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->enc_side) (void)hipStreamDestroy(c->enc_side);
     if (c->ev_enc_fork) (void)hipEventDestroy(c->ev_enc_fork);
@@ -1026,6 +1028,132 @@ static void launch_copy_as_float(const xpnghip_ctx *c, uint32_t layout, int C, u
     else launch_copy_as_float<PX, float>(c, layout, C, bpr, k, s);
 }
 
+// ---- crop, resize and flip in the copy-out (mixed_resize.hpp) ------------------------------------------------
+// what the resized form of the decode adds to the arguments of the float form
+struct ResizeCall {
+    const uint64_t *rects;
+    const uint8_t *flips;
+    uint32_t out_w, out_h;
+};
+static bool resize_size_ok(uint32_t out_w, uint32_t out_h, std::string &why) {
+    if (out_w >= 1 && out_w <= 16384 && out_h >= 1 && out_h <= 16384) return true;
+    why = "bad output size " + std::to_string(out_w) + " x " + std::to_string(out_h) + " (out_w and out_h must each be 1 .. 16384)";
+    return false;
+}
+// the record of one image: rect == NULL is the whole W x H image.  false, with the reason, for a rectangle that is empty or leaves
+// the image and for a flip byte other than 0 or 1
+static bool resize_record(uint64_t W, uint64_t H, const uint64_t *rect, uint32_t flip, uint32_t out_w, uint32_t out_h, ResizeRec &z, std::string &why) {
+    const uint64_t whole[4] = {0, 0, W, H}, *r = rect ? rect : whole;
+    if (!region_valid(W, H, r)) {
+        why = "bad rectangle {" + std::to_string(r[0]) + ", " + std::to_string(r[1]) + ", " + std::to_string(r[2]) + ", " + std::to_string(r[3]) +
+              "}: it is empty or leaves the " + std::to_string(W) + " x " + std::to_string(H) + " image";
+        return false;
+    }
+    if (flip > 1) {
+        why = "bad flip " + std::to_string(flip) + " (a flip is 0 or 1)";
+        return false;
+    }
+    // one IEEE fp32 division each (both operands are below 2^24 + 1: exact as floats)
+    z = ResizeRec{(uint32_t)r[0], (uint32_t)r[1], (uint32_t)r[2], (uint32_t)r[3], (float)r[2] / (float)out_w, (float)r[3] / (float)out_h, flip, 0};
+    return true;
+}
+// The twin of k_mixed_resize_as_float on the host: the same operations in the same order.  Every multiplication of the rule is
+// inside an explicit fmaf(), and contraction is off for this function on top of that.
+static ResizeTap resize_tap_host(uint32_t u, float k, uint32_t n) {
+#pragma clang fp contract(off)
+    const float c = (float)u + 0.5f;
+    const float f = fmaf(c, k, -0.5f);
+    const float s = f > 0.0f ? f : 0.0f;
+    const uint32_t t = (uint32_t)s;
+    ResizeTap r;
+    r.i0 = t < n - 1 ? t : n - 1;
+    r.i1 = r.i0 + 1 < n - 1 ? r.i0 + 1 : n - 1;
+    r.l = s - (float)r.i0;
+    return r;
+}
+static int resize_host_impl(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip, uint32_t out_w, uint32_t out_h,
+                            uint32_t layout, uint32_t dtype, const float *scale, const float *bias, void *out) {
+#pragma clang fp contract(off)
+    const int C = xpnghip_layout_channels(layout, pxsz);
+    if (pxsz != 3 && pxsz != 4) return fail("xpnghip_resize_host: pxsz is " + std::to_string(pxsz) + ", not 3 or 4");
+    if (C < 0) return fail("bad layout word " + layout_hex(layout) + " (XPNGHIP_LAYOUT_PLANAR | XPNGHIP_LAYOUT_BGR | channels 0, 3 or 4 in bits 8..11)");
+    const int es = xpnghip_dtype_bytes(dtype);
+    if (es < 0) return fail("bad dtype " + std::to_string(dtype) + " (XPNGHIP_DTYPE_F16 = 1, _BF16 = 2, _F32 = 3)");
+    FloatConsts k;
+    std::string why;
+    if (!float_consts(C, scale, bias, k, why)) return fail(why);
+    if (!raster || !out) return fail("xpnghip_resize_host: null raster or output buffer");
+    if ((uintptr_t)out & (uintptr_t)(es - 1)) {
+        char b[32];
+        snprintf(b, sizeof b, "%p", out);
+        return fail("output buffer " + std::string(b) + " is not aligned to its " + std::to_string(es) + "-byte elements");
+    }
+    if (!w || !h || w > (1u << 24) || h > (1u << 24)) return fail("bad image size " + std::to_string(w) + " x " + std::to_string(h) + " (each side must be 1 .. 16777216)");
+    if (!resize_size_ok(out_w, out_h, why)) return fail(why);
+    ResizeRec z;
+    if (!resize_record(w, h, rect, (uint32_t)flip, out_w, out_h, z, why)) return fail(why);
+    const bool planar = layout & XPNGHIP_LAYOUT_PLANAR, bgr = layout & XPNGHIP_LAYOUT_BGR;
+    std::vector<ResizeTap> tx(out_w);
+    for (uint32_t ox = 0; ox < out_w; ox++) tx[ox] = resize_tap_host(z.flip ? out_w - 1 - ox : ox, z.kx, z.rw);
+    for (uint32_t oy = 0; oy < out_h; oy++) {
+        const ResizeTap ty = resize_tap_host(oy, z.ky, z.rh);
+        const uint8_t *s0 = raster + ((uint64_t)(z.ry + ty.i0) * w + z.rx) * pxsz, *s1 = raster + ((uint64_t)(z.ry + ty.i1) * w + z.rx) * pxsz;
+        for (uint32_t ox = 0; ox < out_w; ox++)
+            for (int c = 0; c < C; c++) {
+                float v = 255.0f;  // the alpha an RGB raster does not store
+                if (!(pxsz == 3 && c == 3)) {
+                    const uint32_t sc = bgr && c < 3 ? 2 - c : c, o0 = tx[ox].i0 * pxsz + sc, o1 = tx[ox].i1 * pxsz + sc;
+                    const float p00 = (float)s0[o0], p01 = (float)s0[o1], p10 = (float)s1[o0], p11 = (float)s1[o1];
+                    const float d0 = p01 - p00, d1 = p11 - p10;
+                    const float a = fmaf(tx[ox].l, d0, p00), b = fmaf(tx[ox].l, d1, p10);
+                    const float d = b - a;
+                    v = fmaf(ty.l, d, a);
+                }
+                const float y = fmaf(v, k.scale[c], k.bias[c]);
+                const uint64_t e = planar ? ((uint64_t)c * out_h + oy) * out_w + ox : ((uint64_t)oy * out_w + ox) * C + c;
+                if (dtype == XPNGHIP_DTYPE_F32) reinterpret_cast<float *>(out)[e] = y;
+                else reinterpret_cast<uint16_t *>(out)[e] = dtype == XPNGHIP_DTYPE_F16 ? f16_bits_rne(y) : bf16_bits_rne(y);
+            }
+    }
+    return 0;
+}
+extern "C" int xpnghip_resize_host(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip, uint32_t out_w, uint32_t out_h,
+                                   uint32_t layout, uint32_t dtype, const float *scale, const float *bias, void *out) {
+    XPNG_GUARDED(resize_host_impl(pxsz, raster, w, h, rect, flip, out_w, out_h, layout, dtype, scale, bias, out))
+}
+template <int PX, class T>
+static void launch_resize(const xpnghip_ctx *c, uint32_t layout, int C, uint64_t bpr, const ResizeCall &rz, const FloatConsts &k, hipStream_t s) {
+    const dim3 grid((rz.out_h + MC_ROWS - 1) / MC_ROWS, c->B);
+    const uint32_t bgr = layout & XPNGHIP_LAYOUT_BGR;
+    if (layout & XPNGHIP_LAYOUT_PLANAR) {
+        if (C == 3) k_mixed_resize_as_float<PX, 3, true, T><<<grid, 256, 0, s>>>(c->d_m_out, c->d_m_rect, c->d_m_stage, bpr, bgr, rz.out_w, rz.out_h, k);
+        else k_mixed_resize_as_float<PX, 4, true, T><<<grid, 256, 0, s>>>(c->d_m_out, c->d_m_rect, c->d_m_stage, bpr, bgr, rz.out_w, rz.out_h, k);
+    } else {
+        if (C == 3) k_mixed_resize_as_float<PX, 3, false, T><<<grid, 256, 0, s>>>(c->d_m_out, c->d_m_rect, c->d_m_stage, bpr, bgr, rz.out_w, rz.out_h, k);
+        else k_mixed_resize_as_float<PX, 4, false, T><<<grid, 256, 0, s>>>(c->d_m_out, c->d_m_rect, c->d_m_stage, bpr, bgr, rz.out_w, rz.out_h, k);
+    }
+}
+template <int PX>
+static void launch_resize(const xpnghip_ctx *c, uint32_t layout, int C, uint64_t bpr, uint32_t dtype, const ResizeCall &rz, const FloatConsts &k, hipStream_t s) {
+    if (dtype == XPNGHIP_DTYPE_F16) launch_resize<PX, f16_t>(c, layout, C, bpr, rz, k, s);
+    else if (dtype == XPNGHIP_DTYPE_BF16) launch_resize<PX, bf16_t>(c, layout, C, bpr, rz, k, s);
+    else launch_resize<PX, float>(c, layout, C, bpr, rz, k, s);
+}
+// The rectangle table of a resized call: allocated on first use, uploaded by EVERY call (rectangles change with every batch, so
+// there is nothing to cache).  The records are in pageable host memory that dies with this call, so the stream is synchronised
+// behind the copy.  The copy is queued before the decode's own kernels, so that wait covers only what the caller had queued on the
+// stream earlier, never this call's work.
+static int resize_records(xpnghip_ctx *c, const std::vector<ResizeRec> &recs, hipStream_t s) {
+    const uint64_t bytes = (uint64_t)c->B * sizeof(ResizeRec);
+    if (!c->d_m_rect) {
+        HIPCHK(hipMalloc((void **)&c->d_m_rect, bytes));
+        c->ws_bytes += bytes;
+    }
+    HIPCHK(hipMemcpyAsync(c->d_m_rect, recs.data(), bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+
 // The staging raster of the tight forms (decode: reconstruct into it, k_mixed_copy out of it; encode: k_mixed_pack into it, the
 // kernels read it): image i's h_i rows at the pitch bpr in slot[i], every slot 256-byte aligned, 256 spare bytes behind the last.
 // ONE layout and one buffer for both directions; allocated by the first tight call, never shrunk.
@@ -1042,10 +1170,11 @@ static int mixed_stage_slots(xpnghip_ctx *c, uint64_t bpr, std::vector<uint64_t>
 }
 
 // `layout` != NULL: the call of xpnghip_decode_varsize_device_batch_as (out_bpr == 0: its buffers are tight); `fc` != NULL beside
-// it: the call of xpnghip_decode_varsize_device_batch_as_float (its buffers hold elements of fc->dtype)
+// it: the call of xpnghip_decode_varsize_device_batch_as_float (its buffers hold elements of fc->dtype); `rz` != NULL beside both:
+// the call of xpnghip_decode_varsize_device_batch_resized (every buffer holds C * rz->out_h * rz->out_w such elements)
 static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
                                    const uint64_t *tile_off, void *const *d_outs, uint64_t out_bpr, void *stream, const uint32_t *layout = nullptr,
-                                   const FloatCall *fc = nullptr) {
+                                   const FloatCall *fc = nullptr, const ResizeCall *rz = nullptr) {
     // every argument is checked before anything reaches the device: a rejected call writes nothing
     if (!c) return fail("null context");
     if (!c->mixed) return fail("not a mixed context (xpnghip_ctx_create_mixed)");
@@ -1068,6 +1197,16 @@ static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *
     const uint64_t px = (uint64_t)c->pxsz, widest = c->m_max_w * px;
     if (out_bpr && out_bpr < widest)
         return fail("out_bpr " + std::to_string(out_bpr) + " is smaller than the widest row of the batch (" + std::to_string(widest) + " bytes)");
+    std::vector<ResizeRec> recs;
+    if (rz) {
+        std::string why;
+        if (!resize_size_ok(rz->out_w, rz->out_h, why)) return fail(why);
+        recs.resize(nimg);
+        for (uint32_t i = 0; i < nimg; i++)
+            if (!resize_record(c->m_dims[2ull * i], c->m_dims[2ull * i + 1], rz->rects ? rz->rects + 4ull * i : nullptr, rz->flips ? rz->flips[i] : 0u,
+                               rz->out_w, rz->out_h, recs[i], why))
+                return fail(why + " (image " + std::to_string(i) + ")");
+    }
     for (uint32_t i = 0; i < nimg; i++) {
         if (!d_blobs[i] || !d_outs[i]) return fail("null blob or output buffer of image " + std::to_string(i));
         if (((uintptr_t)d_blobs[i] & 3) || (out_bpr && ((uintptr_t)d_outs[i] & 15))) return fail("device buffers must be 16-byte aligned");
@@ -1087,13 +1226,19 @@ static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *
         std::vector<uint64_t> slot;
         if (mixed_stage_slots(c, bpr, slot)) return 1;
         if (mixed_records(c, c->d_m_out, c->h_m_out, slot, d_outs, s)) return 1;
+        if (rz && resize_records(c, recs, s)) return 1;
         for (uint32_t i = 0; i < nimg; i++) base[i] = c->d_m_stage + slot[i];
     }
     if (dec_prepare(c, mode, d_blobs, blobs_len, nimg, base.data(), s)) return 1;
     XPNG_REQUIRE(c->d_m_first, c->d_m_list);
     const int rc = dec_launch(c, mode, nimg, c->m_max_w, tile_off, s, 0, (uint32_t)c->tiles.size(), &c->m_list, c->d_m_list, bpr);
     if (rc) return rc;
-    if (fc) {
+    if (rz) {
+        XPNG_REQUIRE(c->d_m_stage, c->d_m_out, c->d_m_rect);
+        if (c->pxsz == 4) launch_resize<4>(c, *layout, C, bpr, fc->dtype, *rz, fk, s);
+        else launch_resize<3>(c, *layout, C, bpr, fc->dtype, *rz, fk, s);
+        HIPCHK(hipGetLastError());
+    } else if (fc) {
         XPNG_REQUIRE(c->d_m_stage, c->d_m_out);
         if (c->pxsz == 4) launch_copy_as_float<4>(c, *layout, C, bpr, fc->dtype, fk, s);
         else launch_copy_as_float<3>(c, *layout, C, bpr, fc->dtype, fk, s);
@@ -1123,6 +1268,14 @@ extern "C" int xpnghip_decode_varsize_device_batch_as_float(xpnghip_ctx *c, int 
                                                             const float *scale, const float *bias, void *stream) {
     const FloatCall fc{dtype, scale, bias};
     XPNG_GUARDED(decode_mixed_batch_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, d_outs, 0, stream, &layout, &fc))
+}
+extern "C" int xpnghip_decode_varsize_device_batch_resized(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
+                                                           const uint64_t *tile_off, void *const *d_outs, uint32_t layout, uint32_t dtype,
+                                                           const float *scale, const float *bias, const uint64_t *rects, const uint8_t *flips,
+                                                           uint32_t out_w, uint32_t out_h, void *stream) {
+    const FloatCall fc{dtype, scale, bias};
+    const ResizeCall rz{rects, flips, out_w, out_h};
+    XPNG_GUARDED(decode_mixed_batch_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, d_outs, 0, stream, &layout, &fc, &rz))
 }
 
 // ---- mixed-size batch encode (mixed.hpp) ---------------------------------------------------------

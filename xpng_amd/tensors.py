@@ -3,10 +3,12 @@
 `load_files` is what `api.load_batch` is for host arrays.  The files that reach the tile codec are grouped by (tile mode, bytes per
 pixel) and every group is decoded by mixed-size device calls straight into tensors of the final layout
 (MixedContext.decode_batch_as: the layout is written by the copy-out pass of the decode, include/xpng_hip.h XPNGHIP_LAYOUT_*;
-MixedContext.decode_batch_as_float when a float dtype is asked for: the same pass converts and normalises, XPNGHIP_DTYPE_*).
+MixedContext.decode_batch_as_float when a float dtype is asked for: the same pass converts and normalises, XPNGHIP_DTYPE_*;
+MixedContext.decode_batch_resized when an output size is asked for: the same pass also crops, resizes and flips).
 api.py stays free of torch; this module is the only one of the package that imports it at load time."""
 from __future__ import annotations
 
+import math
 import os
 
 import torch
@@ -64,8 +66,47 @@ def _lookup(t: torch.Tensor, layout: str, dtype, dt: int, scale, bias) -> torch.
     return torch.stack([table[c][idx[..., c]] for c in range(C)], dim=2).contiguous()
 
 
+def random_resized_crops(dims, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), generator=None):
+    """One rectangle (x, y, w, h) per image of dims = [(w, h), ...], drawn as torchvision's RandomResizedCrop.get_params draws it:
+    up to ten tries of an area in `scale` times the image's and an aspect ratio log-uniform in `ratio`, the first that fits placed
+    uniformly; then the centre crop of the whole image clamped to `ratio`.  A pure host function; with a seeded torch.Generator
+    the list is reproducible.  What load_files(..., size=..., crops=...) takes."""
+    log_lo, log_hi = math.log(ratio[0]), math.log(ratio[1])
+    out = []
+    for (width, height) in dims:
+        width, height = int(width), int(height)
+        if width < 1 or height < 1:
+            raise XpngError(f"random_resized_crops: bad image size {width} x {height}")
+        area, rect = width * height, None
+        for _ in range(10):
+            target = area * torch.empty(1).uniform_(scale[0], scale[1], generator=generator).item()
+            aspect = math.exp(torch.empty(1).uniform_(log_lo, log_hi, generator=generator).item())
+            w, h = int(round(math.sqrt(target * aspect))), int(round(math.sqrt(target / aspect)))
+            if 0 < w <= width and 0 < h <= height:
+                y = int(torch.randint(0, height - h + 1, (1,), generator=generator).item())
+                x = int(torch.randint(0, width - w + 1, (1,), generator=generator).item())
+                rect = (x, y, w, h)
+                break
+        if rect is None:
+            rect = centre_crop(width, height, ratio)
+        out.append(rect)
+    return out
+
+
+def centre_crop(width, height, ratio=(3.0 / 4.0, 4.0 / 3.0)):
+    """the fallback of random_resized_crops: the largest centred rectangle of the image whose aspect ratio lies in `ratio`"""
+    in_ratio = width / height
+    if in_ratio < min(ratio):
+        w, h = width, min(height, max(1, int(round(width / min(ratio)))))
+    elif in_ratio > max(ratio):
+        w, h = min(width, max(1, int(round(height * max(ratio))))), height
+    else:
+        w, h = width, height
+    return ((width - w) // 2, (height - h) // 2, w, h)
+
+
 def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, device=None, dtype=torch.uint8, mean=None, std=None,
-               stack: bool = False):
+               stack: bool = False, size=None, crops=None, flips=None):
     """The images of a list of .xpng files of any sizes as tensors on `device` (default: the current cuda device), each of
     shape (C, h, w) for layout "chw" or (h, w, C) for "hwc".  channels None keeps each file's own count (3 or 4); 3 drops the
     alpha of an RGBA file, 4 gives an RGB file alpha 255; bgr=True orders the colours B, G, R (alpha stays last).
@@ -83,7 +124,15 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
     api.float_table, the same arithmetic on the host, so they are bit-identical to what the kernel writes.
 
     stack=True returns ONE tensor (N, C, h, w) or (N, h, w, C) instead of the list: every image must have the same (C, h, w) after
-    `channels` is applied (XpngError names the first that differs); the device calls write straight into its slices."""
+    `channels` is applied (XpngError names the first that differs); the device calls write straight into its slices.
+
+    size=(OH, OW) makes every returned tensor (C, OH, OW) or (OH, OW, C): the same pass of the decode crops, resizes with plain
+    2 x 2-tap bilinear interpolation (half-pixel centres as F.interpolate(mode="bilinear", align_corners=False, antialias=False);
+    NOT an antialiased resize) and flips (MixedContext.decode_batch_resized; the rule is in include/xpng_hip.h).  It needs a float
+    dtype.  crops is one rectangle (x, y, w, h) per path (random_resized_crops makes them) or None for the whole images; flips one
+    bool per path (True mirrors left to right) or None.  stack=True then works for files of ANY sizes - only C must agree.
+    Host-answered files go through api.resize_host and are bit-identical.  Without size the function runs exactly the path above;
+    crops or flips without size is an error."""
     if layout not in ("chw", "hwc"):
         raise XpngError(f"load_files: layout must be 'chw' or 'hwc', not {layout!r}")
     if channels not in (None, 3, 4):
@@ -92,6 +141,17 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
         raise XpngError(f"load_files: dtype must be torch.uint8, float16, bfloat16 or float32, not {dtype!r}")
     if dtype == torch.uint8 and (mean is not None or std is not None):
         raise XpngError("load_files: mean and std need a float dtype (dtype=torch.uint8 returns the file's bytes)")
+    if size is None and (crops is not None or flips is not None):
+        raise XpngError("load_files: crops and flips need size=(OH, OW)")
+    if size is not None:
+        if dtype == torch.uint8:
+            raise XpngError("load_files: size needs a float dtype (torch.float16, bfloat16 or float32): the resize interpolates")
+        try:
+            OH, OW = (int(v) for v in size)
+        except (TypeError, ValueError):
+            raise XpngError(f"load_files: size must be (OH, OW), not {size!r}") from None
+        if not (1 <= OH <= 16384 and 1 <= OW <= 16384):
+            raise XpngError(f"load_files: size {(OH, OW)} is outside 1 .. 16384")
     mean, std = (x.tolist() if isinstance(x, torch.Tensor) else x for x in (mean, std))
     dt = _DTYPES.get(dtype)                                        # None: the uint8 path, exactly as without the argument
     cache = {}
@@ -109,6 +169,13 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
     paths = list(paths)
     if not paths:
         raise XpngError("load_files: empty list")
+    if size is not None:
+        crops = [None] * len(paths) if crops is None else [None if r is None else tuple(int(v) for v in r) for r in crops]
+        flips = [False] * len(paths) if flips is None else [bool(f) for f in flips]
+        if len(crops) != len(paths) or len(flips) != len(paths):
+            raise XpngError(f"load_files: {len(paths)} paths, {len(crops)} crops and {len(flips)} flips: one of each per path")
+        if any(r is not None and len(r) != 4 for r in crops):
+            raise XpngError("load_files: a crop is (x, y, w, h)")
     dev = torch.device("cuda" if device is None else device)
     if dev.type == "cuda" and not torch.cuda.is_available():
         raise XpngError("load_files: no GPU is visible (device='cpu' answers level-7 and single-colour files without one)")
@@ -130,11 +197,19 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
     if dt:
         for (_, _, _, px) in heads:
             consts(channels or px)
-    shape = lambda C, h, w: (C, h, w) if layout == "chw" else (h, w, C)   # noqa: E731
+    def shape(C, h, w):
+        if size is not None:                                           # every tensor has the output's size, whatever the file's
+            h, w = OH, OW
+        return (C, h, w) if layout == "chw" else (h, w, C)
+
     whole = None
     if stack:
         first = (channels or heads[0][3], heads[0][2], heads[0][1])
+        if size is not None:
+            first = (first[0], OH, OW)
         for p, (_, w, h, px) in zip(paths, heads):
+            if size is not None:
+                w, h = OW, OH
             if (channels or px, h, w) != first:
                 raise XpngError(f"load_files: stack=True needs images of one shape, but {os.fspath(p)!r} is (C, h, w) = "
                                 f"{(channels or px, h, w)} and the first is {first}")
@@ -152,9 +227,15 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
         if t is None:
             groups.setdefault((mode, px), []).append((i, w, h, buf))
             continue
-        t = _arrange(t, layout, channels, bgr)
-        if dt:
-            t = _lookup(t, layout, dtype, dt, *consts(channels or px))
+        if size is not None:
+            C = channels or px
+            raw = api.resize_host(t.numpy(), (OH, OW), api.layout(planar=layout == "chw", bgr=bgr, channels=C), dt, *consts(C),
+                                  rect=crops[i], flip=flips[i])
+            t = torch.frombuffer(bytearray(raw), dtype=dtype).view(shape(C, h, w))
+        else:
+            t = _arrange(t, layout, channels, bgr)
+            if dt:
+                t = _lookup(t, layout, dtype, dt, *consts(channels or px))
         if whole is not None:
             whole[i].copy_(t)
         else:
@@ -186,7 +267,10 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
                 ctx = api.MixedContext([(w, h) for (_, w, h, _) in part], px, device=index)
                 try:
                     ins, lens = [d_in.data_ptr() + o for o in offs], [len(buf) - 8 for (_, _, _, buf) in part]
-                    if dt:
+                    if size is not None:
+                        ctx.decode_batch_resized(mode, ins, lens, [t.data_ptr() for t in outs], word, dt, (OH, OW), *consts(C),
+                                                 rects=[crops[i] or (0, 0, w, h) for (i, w, h, _) in part], flips=[flips[i] for (i, _, _, _) in part])
+                    elif dt:
                         ctx.decode_batch_as_float(mode, ins, lens, [t.data_ptr() for t in outs], word, dt, *consts(C))
                     else:
                         ctx.decode_batch_as(mode, ins, lens, [t.data_ptr() for t in outs], word)
