@@ -24,7 +24,7 @@ $(LIB)/libxpng_hip_probes.so: $(HIPSRC) $(HIPHDR)
 	$(HIPCC) $(HIPFLAGS) -DXPNG_PROBES $(HIPSRC) -o $@
 
 host: $(LIB)/libxpng.so $(BIN)/xpng $(BIN)/seven $(BIN)/tool
-$(LIB)/libxpng.so: $(CSRC)/host/xpng_api.c $(CSRC)/host/seven.c include/xpng.h include/xpng_hip.h include/xpng_region.h include/xpng_batch.h include/xpng_store_batch.h $(LIB)/libxpng_hip.so
+$(LIB)/libxpng.so: $(CSRC)/host/xpng_api.c $(CSRC)/host/seven.c include/xpng.h include/xpng_hip.h include/xpng_region.h include/xpng_batch.h include/xpng_store_batch.h include/xpng_store_tensors.h $(LIB)/libxpng_hip.so
 	$(CC) -O2 -std=gnu11 -Wall -Wextra -shared -fPIC $(CSRC)/host/xpng_api.c $(CSRC)/host/seven.c -o $@ \
 	    -L$(LIB) -lxpng_hip -Wl,-rpath,'$$ORIGIN'
 $(BIN)/tool: $(CSRC)/host/tool_cli.c $(LIB)/libxpng.so

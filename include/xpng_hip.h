@@ -383,6 +383,40 @@ int xpnghip_decode_varsize_device_batch_resized(xpnghip_ctx *ctx, int mode, cons
 int xpnghip_resize_host(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip, uint32_t out_w,
                         uint32_t out_h, uint32_t layout, uint32_t dtype, const float *scale, const float *bias, void *out);
 
+/* ---- staged batch from device tensors: the inverse of the float call --------------------------
+ * A model writes floats, not the file's bytes.  The call below is xpnghip_images_begin with the upload replaced by one staging
+ * kernel that reads the caller's DEVICE buffers - planar or interleaved, RGB or BGR, uint8, f16, bf16 or f32 - and writes the
+ * interleaved R,G,B[,A] bytes of the staged rasters, so model outputs reach .xpng files without crossing to the host and back and
+ * without a torch op per image.  For every element x of a buffer - f16 or bf16 widened exactly to fp32 (subnormals kept), f32 as it
+ * is - and c the channel's position in the CALLER's buffer (with XPNGHIP_LAYOUT_BGR scale[0] belongs to blue; alpha is always
+ * last: the float call's convention):
+ *     y = fmaf(x, scale[c], bias[c])      one fp32 fused multiply-add, IEEE, subnormals kept, a value of its own
+ *     v = 0      if y is NaN or y <= 0    (-0 and -inf included)
+ *         255    if y >= 255              (+inf included)
+ *         (uint8_t)rintf(y) otherwise     round half to even: 0.5 -> 0, 1.5 -> 2, 254.5 -> 254
+ * dtype 0 means the buffer already holds uint8: v = x, and scale and bias must both be NULL (the call is refused otherwise).
+ *
+ * d_bufs[i] is TIGHT: channels[i] * w_i * h_i elements of `dtype` (dims = nimg pairs {w, h}; channels[i] = 3 or 4, per image) in
+ * the layout's order, aligned to the element size; of a buffer only the aligned dwords it occupies are read.  `layout` carries the
+ * PLANAR and BGR bits only: a channel field other than 0 is refused, the count is per image.  scale and bias: four floats each on
+ * the HOST (they travel in the kernel's arguments), NULL = all ones / all zeros, every value finite.  The staging kernel is queued
+ * on `stream` (a stream of `device`, or NULL), so it runs behind whatever produced the buffers there; the handle's own stream
+ * waits for it through an event, and normalize_RGBA and the one read-back of the flags follow as in xpnghip_images_begin.  When
+ * the call returns the caller's buffers are free again, pxsz_out[i] = bytes per pixel of the normalised raster, and every other
+ * xpnghip_images_* call works on the handle unchanged.  The handle lives on `device` (XPNG_DEVICE does not apply).
+ * Refused before anything reaches the device, with the offending value in xpnghip_last_error() and *h == NULL: a NULL or
+ * misaligned buffer, a side outside 1 .. 1 << 24, a channel count other than 3 or 4, a bad layout word or dtype, constants with
+ * dtype 0, a non-finite constant, nimg outside 1 .. 4096, no such device. */
+int xpnghip_images_begin_device(xpnghip_images **h, int device, uint32_t nimg, const void *const *d_bufs, const uint64_t *dims,
+                                const uint8_t *channels, uint32_t layout, uint32_t dtype, const float *scale, const float *bias,
+                                void *stream, uint8_t *pxsz_out);
+/* host-only, needs no device: the same rule, bit for bit, applied to a tight HOST buffer of C * npx elements (C = 3 or 4) in
+ * `layout` (PLANAR and BGR bits only); out receives npx * C interleaved R,G,B[,A] bytes.  For a caller that answers some images on
+ * the host.  0 on success; non-zero, with the offending value in xpnghip_last_error() and nothing written, on a bad layout, dtype
+ * or C, constants with dtype 0, a non-finite constant, or a NULL buffer. */
+int xpnghip_quantize_host(uint32_t layout, uint32_t dtype, int C, const void *src, uint64_t npx, const float *scale,
+                          const float *bias, uint8_t *out);
+
 /* Stage-only run for BASELINE config 2: predictor chooser + per-pixel transform (libxpng.c:92-140 and
  * the arithmetic of 497-519) over tiles [t0, t1); symbol planes stay in the context's workspace. */
 int xpnghip_m1_transform_device(xpnghip_ctx *ctx, const void *d_raster, uint64_t t0, uint64_t t1, void *stream);

@@ -35,6 +35,7 @@ HIP_SYMBOLS = [
     "xpnghip_layout_channels", "xpnghip_decode_varsize_device_batch_as", "xpnghip_encode_varsize_device_batch_from",
     "xpnghip_dtype_bytes", "xpnghip_float_table", "xpnghip_decode_varsize_device_batch_as_float",
     "xpnghip_decode_varsize_device_batch_resized", "xpnghip_resize_host",
+    "xpnghip_images_begin_device", "xpnghip_quantize_host",
 ]
 HOST_SYMBOLS = ["xpng_store", "xpng_load", "xpng_from_jpg", "xpng_store_T", "xpng_load_T", "xpng_from_jpg_T",
                 "store_7", "load_7"]
@@ -44,6 +45,8 @@ HOST_EXT_SYMBOLS = ["xpng_load_region"]
 HOST_BATCH_SYMBOLS = ["xpng_load_batch"]
 # ... and include/xpng_store_batch.h
 HOST_STORE_BATCH_SYMBOLS = ["xpng_store_batch"]
+# ... and include/xpng_store_tensors.h
+HOST_STORE_TENSORS_SYMBOLS = ["xpng_store_tensors"]
 
 
 class XpngError(RuntimeError):
@@ -182,6 +185,11 @@ def _bind_hip(path):
                                           f32p, f32p, vp]
         L.xpnghip_images_begin.restype = C.c_int
         L.xpnghip_images_begin.argtypes = [C.POINTER(vp), C.c_uint32, C.POINTER(vp), C.POINTER(u64), u8p, u8p]
+        L.xpnghip_images_begin_device.restype = C.c_int
+        L.xpnghip_images_begin_device.argtypes = [C.POINTER(vp), C.c_int, C.c_uint32, C.POINTER(vp), C.POINTER(u64), u8p, C.c_uint32, C.c_uint32,
+                                                  f32p, f32p, vp, u8p]
+        L.xpnghip_quantize_host.restype = C.c_int
+        L.xpnghip_quantize_host.argtypes = [C.c_uint32, C.c_uint32, C.c_int, vp, u64, f32p, f32p, vp]
         L.xpnghip_images_single_colour.restype = C.c_int
         L.xpnghip_images_single_colour.argtypes = [vp, u8p]
         L.xpnghip_images_encode.restype = C.c_int
@@ -251,6 +259,9 @@ def host_lib():
         L.xpng_load_batch.argtypes = [C.POINTER(C.c_char_p), C.c_uint64, C.POINTER(XpngT)]
         L.xpng_store_batch.restype = C.c_bool
         L.xpng_store_batch.argtypes = [C.c_uint64, C.POINTER(XpngT), C.POINTER(C.c_char_p), C.c_uint64]
+        L.xpng_store_tensors.restype = C.c_bool
+        L.xpng_store_tensors.argtypes = [C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint8), C.c_uint32,
+                                         C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_void_p, C.POINTER(C.c_char_p)]
         _host = L
     return _host
 
@@ -550,6 +561,52 @@ def resize_host(raster, size, layout: int, dtype: int, scale=None, bias=None, re
     return buf.tobytes()[:ch * oh * ow * dtype_bytes(dtype)]
 
 
+def quantize_host(src, npx: int, channels: int, layout: int, dtype: int, scale=None, bias=None) -> np.ndarray:
+    """The quantisation rule of StagedImages.from_device on the host (xpnghip_quantize_host; needs no device): `src` is a tight
+    buffer of channels * npx elements of `dtype` (0 = uint8, DTYPE_F16, DTYPE_BF16, DTYPE_F32) in `layout` (LAYOUT_PLANAR and
+    LAYOUT_BGR bits only) - a numpy array of any element type of the right size (its bytes are what counts), or a host address.
+    Returns the (npx, channels) uint8 array of interleaved R,G,B[,A] bytes, bit for bit what the device call stages for them."""
+    if isinstance(src, int):
+        addr = src
+    else:
+        keep = np.ascontiguousarray(src)
+        addr = keep.ctypes.data
+        es = 1 if dtype == 0 else hip_lib().xpnghip_dtype_bytes(dtype)
+        if es > 0 and channels in (3, 4) and keep.nbytes != channels * npx * es:
+            raise XpngError(f"quantize_host: the buffer holds {keep.nbytes} bytes, not {channels} * {npx} * {es}")
+    sc, bi = _floats("scale", scale, 4), _floats("bias", bias, 4)
+    out = np.empty((max(npx, 0), channels if channels in (3, 4) else 1), dtype=np.uint8)
+    if hip_lib().xpnghip_quantize_host(layout, dtype, channels, addr, npx, sc, bi, out.ctypes.data):
+        raise XpngError("xpnghip_quantize_host: " + _err())
+    return out
+
+
+def _tensor_args(ptrs, dims, channels):
+    """the per-image arguments of the two device-buffer calls as C arrays"""
+    k = len(ptrs)
+    if len(dims) != k or len(channels) != k:
+        raise XpngError(f"{k} buffers, {len(dims)} sizes and {len(channels)} channel counts: one of each per image")
+    try:
+        return ((C.c_void_p * max(k, 1))(*[int(p) for p in ptrs]), (C.c_uint64 * max(2 * k, 1))(*[int(v) for d in dims for v in d]),
+                (C.c_uint8 * max(k, 1))(*[int(c) & 0xFF for c in channels]))
+    except (TypeError, ValueError):
+        raise XpngError("buffers are addresses, sizes are (w, h) and channel counts are integers") from None
+
+
+def store_tensors(mode: int, ptrs, dims, channels, layout: int, dtype: int, paths, scale=None, bias=None, device: int = 0, stream=0) -> None:
+    """xpng_store_tensors (include/xpng_store_tensors.h): file i is what store(mode, raster_i, paths[i]) writes for the quantised
+    raster of device buffer ptrs[i] (dims[i] = (w, h), channels[i] = 3 or 4; layout, dtype, scale, bias as in
+    StagedImages.from_device).  The pixels stay on the device; the call is ordered behind `stream`."""
+    k = len(ptrs)
+    if len(paths) != k:
+        raise XpngError(f"store_tensors: {k} buffers and {len(paths)} paths")
+    p, flat, ch = _tensor_args(ptrs, dims, channels)
+    sc, bi = _floats("scale", scale, 4), _floats("bias", bias, 4)
+    arr = (C.c_char_p * max(k, 1))(*[os.fsencode(q) for q in paths])
+    if host_lib().xpng_store_tensors(mode, k, p, flat, ch, layout, dtype, sc, bi, device, stream, arr):
+        raise XpngError("xpng_store_tensors failed: " + _err())
+
+
 def store_batch(mode: int, rasters, paths) -> None:
     """xpng_store_batch (include/xpng_store_batch.h): file i is what store(mode, rasters[i], paths[i]) writes; the tile stage of
     all images of one (tile mode, bytes per pixel) is one mixed-size device call."""
@@ -578,6 +635,28 @@ class StagedImages:
         if self._lib.xpnghip_images_begin(C.byref(self._h), k, ptrs, flat, pin, pout):
             raise XpngError("xpnghip_images_begin: " + self._lib.xpnghip_last_error().decode(errors="replace"))
         self.pxsz = list(pout)[:k]
+
+    @classmethod
+    def from_device(cls, ptrs, dims, channels, layout: int = 0, dtype: int = 0, scale=None, bias=None, device: int = 0, stream=0, lib=None):
+        """The staged batch filled from device buffers (xpnghip_images_begin_device): ptrs[i] is a tight buffer of
+        channels[i] * w * h elements (dims[i] = (w, h), channels[i] = 3 or 4) of `dtype` (0 = uint8, DTYPE_F16, DTYPE_BF16,
+        DTYPE_F32) in `layout` (LAYOUT_PLANAR and LAYOUT_BGR bits only), aligned to its element.  A float element x is staged as
+        round-half-to-even(clamp(fmaf(x, scale[c], bias[c]), 0, 255)) with c the channel's position in the buffer (scale, bias: a
+        number or four numbers; None = 1 and 0; not allowed with dtype 0).  The staging kernel is queued on `stream`; when the call
+        returns the buffers are free again.  Everything else is StagedImages."""
+        self = cls.__new__(cls)
+        self._lib = lib or hip_lib()
+        self._h = C.c_void_p()
+        k = self.n = len(ptrs)
+        p, flat, ch = _tensor_args(ptrs, dims, channels)
+        self.dims = [(int(w), int(h)) for (w, h) in dims]
+        sc, bi = _floats("scale", scale, 4), _floats("bias", bias, 4)
+        pout = (C.c_uint8 * max(k, 1))()
+        if self._lib.xpnghip_images_begin_device(C.byref(self._h), device, k, p, flat, ch, layout, dtype, sc, bi, stream, pout):
+            assert not self._h
+            raise XpngError("xpnghip_images_begin_device: " + self._lib.xpnghip_last_error().decode(errors="replace"))
+        self.pxsz = list(pout)[:k]
+        return self
 
     def _fail(self, what):
         raise XpngError(what + ": " + self._lib.xpnghip_last_error().decode(errors="replace"))

@@ -14,6 +14,7 @@
 #include "../../../include/xpng_region.h"
 #include "../../../include/xpng_batch.h"
 #include "../../../include/xpng_store_batch.h"
+#include "../../../include/xpng_store_tensors.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -324,8 +325,19 @@ typedef struct {
     uint64_t len;
 } batch_file;
 
-/* one staged batch: images idx[0 .. k) of the list, all of which reach the device (levels 1 and 2, more than one pixel) */
-static _Bool store_batch_on_device(uint64_t mode, const xpng_t *pms, const uint64_t *idx, uint32_t k, batch_file *files) {
+/* the second way to stage a batch: the caller's device buffers (xpng_store_tensors) instead of host rasters.  Image i of the list has
+ * buffer d_bufs[i]; its size and channel count are in pms[i] (w, h, A; p is NULL) */
+typedef struct {
+    const void *const *d_bufs;
+    uint32_t layout, dtype;
+    const float *scale, *bias;
+    int device;
+    void *stream;
+} tensor_src;
+
+/* one staged batch: images idx[0 .. k) of the list, all of which reach the device (host rasters: levels 1 and 2, more than one
+ * pixel; device buffers, ts != NULL: every image, so an explicit level 7 and the one-pixel image are here too) */
+static _Bool store_batch_on_device(uint64_t mode, const xpng_t *pms, const tensor_src *ts, const uint64_t *idx, uint32_t k, batch_file *files) {
     const uint8_t **rasters = malloc(k * sizeof(*rasters));
     uint64_t *dims = malloc(2ull * k * sizeof(*dims)), *lens = calloc(k, sizeof(*lens));
     uint8_t *pin = malloc(k), *pout = malloc(k), *single = calloc(k, 1), *modes = calloc(k, 1);
@@ -335,9 +347,10 @@ static _Bool store_batch_on_device(uint64_t mode, const xpng_t *pms, const uint6
     if (!rasters || !dims || !lens || !pin || !pout || !single || !modes || !blobs) goto done;
     for (uint32_t j = 0; j < k; j++) {
         const xpng_t *pm = &pms[idx[j]];
-        rasters[j] = pm->p; dims[2 * j] = pm->w; dims[2 * j + 1] = pm->h; pin[j] = (uint8_t)(3 + pm->A);
+        rasters[j] = ts ? (const uint8_t *)ts->d_bufs[idx[j]] : pm->p; dims[2 * j] = pm->w; dims[2 * j + 1] = pm->h; pin[j] = (uint8_t)(3 + pm->A);
     }
-    if (xpnghip_images_begin(&h, k, rasters, dims, pin, pout)) {
+    if (ts ? xpnghip_images_begin_device(&h, ts->device, k, (const void *const *)rasters, dims, pin, ts->layout, ts->dtype, ts->scale, ts->bias, ts->stream, pout)
+           : xpnghip_images_begin(&h, k, rasters, dims, pin, pout)) {
         fprintf(stderr, "xpng: GPU staging failed: %s\n", xpnghip_last_error());
         goto done;
     }
@@ -349,6 +362,12 @@ static _Bool store_batch_on_device(uint64_t mode, const xpng_t *pms, const uint6
         const uint64_t s = pm->w * pm->h * (uint64_t)pout[j];
         put_u32(f->hdr, (uint32_t)(pm->w - 1) | ((uint32_t)mode << 24));
         put_u32(f->hdr + 4, (uint32_t)(pm->h - 1) | ((uint32_t)A << 24));
+        if (mode == 7 || s <= 4) { /* explicit level 7, or s <= 4: libxpng.c:735 (host rasters never come here with either) */
+            if (!(f->owned = malloc(s)) || xpnghip_images_fetch(h, j, f->owned)) goto done;
+            f->hdr[3] = XPNG_COMPRESSION_TYPE_UNCOMPRESSED;
+            f->body = f->owned; f->len = s;
+            continue;
+        }
         if (mode == 2 && single[j]) { /* the file holds one pixel: it came back with the flags, the raster stays on the device */
             if (!(f->owned = malloc(4)) || xpnghip_images_first_pixel(h, j, f->owned)) goto done;
             f->hdr[7] |= 2;
@@ -433,13 +452,47 @@ _Bool xpng_store_batch(uint64_t mode, const xpng_t *pms, const char *const *path
         rc = calls < 1;
         for (int k = 0; !rc && k < calls; k++) {
             const uint64_t b = starts[k], e = k + 1 < calls ? starts[k + 1] : nd;
-            rc = store_batch_on_device(mode, pms, idx + b, (uint32_t)(e - b), files);
+            rc = store_batch_on_device(mode, pms, NULL, idx + b, (uint32_t)(e - b), files);
         }
         free(dims); free(px); free(starts);
     }
     for (uint64_t j = 0; !rc && j < n; j++) rc = write_file(paths[j], files[j].hdr, files[j].body, files[j].len);
     for (uint64_t j = 0; files && j < n; j++) free(files[j].owned);
     free(files); free(idx); free(dev);
+    return rc;
+}
+
+/* include/xpng_store_tensors.h: xpng_store_batch for images that are device buffers.  Nothing of an image is known on the host, so
+ * every image is staged (xpnghip_images_begin_device quantises and rearranges it on the device) and everything xpng_store decides
+ * is decided from what the staged batch reports; the list is cut as xpng_store_batch cuts it. */
+_Bool xpng_store_tensors(uint64_t mode, uint64_t n, const void *const *d_bufs, const uint64_t *dims, const uint8_t *channels, uint32_t layout,
+                         uint32_t dtype, const float *scale, const float *bias, int device, void *stream, const char *const *paths) {
+    if (!d_bufs || !dims || !channels || !paths || !n || n > 0xFFFFFFFFull || !(mode == 1 || mode == 2 || mode == 7)) return 1;
+    for (uint64_t i = 0; i < n; i++) /* (what the staged batch would refuse is refused here for the whole list, before any work) */
+        if (!paths[i] || !d_bufs[i] || !dims[2 * i] || !dims[2 * i + 1] || dims[2 * i] > XPNG_MAX_DIM || dims[2 * i + 1] > XPNG_MAX_DIM ||
+            (channels[i] != 3 && channels[i] != 4)) return 1;
+    batch_file *files = calloc(n, sizeof(*files));
+    xpng_t *pms = calloc(n, sizeof(*pms));
+    uint64_t *idx = malloc(n * sizeof(*idx));
+    uint32_t *starts = malloc(n * sizeof(*starts));
+    const tensor_src ts = {d_bufs, layout, dtype, scale, bias, device, stream};
+    _Bool rc = !files || !pms || !idx || !starts;
+    int calls = -1;
+    if (!rc) {
+        for (uint64_t i = 0; i < n; i++) {
+            idx[i] = i;
+            pms[i].w = dims[2 * i]; pms[i].h = dims[2 * i + 1]; pms[i].A = channels[i] == 4; pms[i].s = pms[i].w * pms[i].h * channels[i];
+        }
+        calls = xpnghip_batch_cuts((uint32_t)n, dims, channels, XPNG_BATCH_MAX, XPNG_BATCH_BYTES, starts, (int)(n > 0x7FFFFFFF ? 0x7FFFFFFF : n));
+        rc = calls < 1;
+    }
+    for (int k = 0; !rc && k < calls; k++) {
+        const uint64_t b = starts[k], e = k + 1 < calls ? starts[k + 1] : n;
+        rc = store_batch_on_device(mode, pms, &ts, idx + b, (uint32_t)(e - b), files);
+    }
+    for (uint64_t j = 0; !rc && j < n; j++) rc = write_file(paths[j], files[j].hdr, files[j].body, files[j].len);
+    for (uint64_t j = 0; files && j < n; j++) free(files[j].owned);
+    free(files); free(pms); free(idx); free(starts);
     return rc;
 }
 

@@ -978,6 +978,7 @@ struct xpnghip_images {
     std::vector<const uint8_t *> cur; // the staged (normalised) rasters
     uint8_t *d_in = nullptr, *d_norm = nullptr;
     ImgRec *d_rec = nullptr;
+    const uint8_t **d_src = nullptr;  // xpnghip_images_begin_device: the caller's buffers, for the staging kernel
     uint32_t *d_flags = nullptr;      // IMG_FLAGS per image
     uint32_t blocks = 1;              // grid.x of the per-list launches (from the largest image)
     bool have_single = false;
@@ -989,18 +990,20 @@ static void images_destroy(xpnghip_images *h) {
     if (!h) return;
     (void)hipSetDevice(h->dev);
     if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
-    for (void *p : {(void *)h->d_in, (void *)h->d_norm, (void *)h->d_rec, (void *)h->d_flags}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)h->d_in, (void *)h->d_norm, (void *)h->d_rec, (void *)h->d_src, (void *)h->d_flags}) if (p) (void)hipFree(p);
     delete h;
 }
-static int images_begin_impl(xpnghip_images **out, uint32_t nimg, const uint8_t *const *rasters, const uint64_t *dims, const uint8_t *pxsz_in, uint8_t *pxsz_out) {
-    if (!out) return fail("null argument");
-    *out = nullptr;
-    if (!rasters || !dims || !pxsz_in || !pxsz_out) return fail("null argument");
-    if (nimg < 1 || nimg > 4096) return fail("a staged batch holds 1 .. 4096 images");
+// What xpnghip_images_begin and xpnghip_images_begin_device share: everything but the way the staged rasters are filled.  `dev` is
+// the handle's device (-1: the library's own); fill(h, rec) queues the fill of rec[i].in for every image - on the handle's
+// stream, or ordered in front of what that stream does next - and is the only part that reads through `bufs` (host rasters, or
+// the caller's device buffers).
+template <class Fill>
+static int images_begin_common(xpnghip_images **out, int dev, uint32_t nimg, const void *const *bufs, const uint64_t *dims, const uint8_t *pxsz_in, uint8_t *pxsz_out,
+                               Fill fill) {
     std::vector<uint64_t> off_in((size_t)nimg + 1, 0), off_norm((size_t)nimg + 1, 0);
     uint64_t max_npx = 0;
     for (uint32_t i = 0; i < nimg; i++) {
-        if (!rasters[i]) return fail("null raster of image " + std::to_string(i));
+        if (!bufs[i]) return fail("null raster of image " + std::to_string(i));
         if (!dims[2ull * i] || !dims[2ull * i + 1] || dims[2ull * i] > (1u << 24) || dims[2ull * i + 1] > (1u << 24) || (pxsz_in[i] != 3 && pxsz_in[i] != 4))
             return fail("bad raster geometry of image " + std::to_string(i));
         const uint64_t npx = dims[2ull * i] * dims[2ull * i + 1];
@@ -1008,11 +1011,14 @@ static int images_begin_impl(xpnghip_images **out, uint32_t nimg, const uint8_t 
         off_norm[i + 1] = off_norm[i] + (pxsz_in[i] == 4 ? rup(npx * 3, 16) : 0);
         max_npx = std::max(max_npx, npx);
     }
-    if (usable_devices() < 1) return fail("no usable HIP device (libxpng_hip has no CPU fallback)");
+    if (dev < 0) {  // (the host form: the library's own device)
+        if (usable_devices() < 1) return fail("no usable HIP device (libxpng_hip has no CPU fallback)");
+        dev = base_device();
+    }
     DevGuard guard;
-    HIPCHK(hipSetDevice(base_device()));
+    HIPCHK(hipSetDevice(dev));
     xpnghip_images *h = new xpnghip_images();
-    h->dev = base_device(); h->n = nimg;
+    h->dev = dev; h->n = nimg;
     h->dims.assign(dims, dims + 2ull * nimg);
     h->px_in.assign(pxsz_in, pxsz_in + nimg);
     h->px = h->px_in;
@@ -1030,10 +1036,10 @@ static int images_begin_impl(xpnghip_images **out, uint32_t nimg, const uint8_t 
         for (uint32_t i = 0; i < nimg; i++) {
             const uint64_t npx = dims[2ull * i] * dims[2ull * i + 1];
             rec[i] = ImgRec{h->d_in + off_in[i], pxsz_in[i] == 4 ? h->d_norm + off_norm[i] : nullptr, npx, pxsz_in[i], 0};
-            HIPCHK(hipMemcpyAsync(rec[i].in, rasters[i], npx * pxsz_in[i], hipMemcpyHostToDevice, h->stream));
         }
         HIPCHK(hipMemcpyAsync(h->d_rec, rec.data(), (uint64_t)nimg * sizeof(ImgRec), hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipMemsetAsync(h->d_flags, 0, (uint64_t)nimg * IMG_FLAGS * 4, h->stream));
+        if (fill(h, rec)) return 1;
         h->h_flags.assign((size_t)nimg * IMG_FLAGS, 0);
         if (off_norm[nimg]) {  // (some image is RGBA)
             k_norm_flags_batch<<<dim3(h->blocks, nimg), 256, 0, h->stream>>>(h->d_rec, h->d_flags);
@@ -1055,6 +1061,70 @@ static int images_begin_impl(xpnghip_images **out, uint32_t nimg, const uint8_t 
     memcpy(pxsz_out, h->px.data(), nimg);
     *out = h;
     return 0;
+}
+static int images_begin_impl(xpnghip_images **out, uint32_t nimg, const uint8_t *const *rasters, const uint64_t *dims, const uint8_t *pxsz_in, uint8_t *pxsz_out) {
+    if (!out) return fail("null argument");
+    *out = nullptr;
+    if (!rasters || !dims || !pxsz_in || !pxsz_out) return fail("null argument");
+    if (nimg < 1 || nimg > 4096) return fail("a staged batch holds 1 .. 4096 images");
+    return images_begin_common(out, -1, nimg, reinterpret_cast<const void *const *>(rasters), dims, pxsz_in, pxsz_out,
+                               [&](xpnghip_images *h, const std::vector<ImgRec> &rec) -> int {
+        for (uint32_t i = 0; i < nimg; i++) HIPCHK(hipMemcpyAsync(rec[i].in, rasters[i], rec[i].npx * pxsz_in[i], hipMemcpyHostToDevice, h->stream));
+        return 0;
+    });
+}
+// xpnghip_images_begin with the upload replaced by k_images_stage_from (stage_from.hpp): the rasters are filled from the caller's
+// device buffers by one launch per channel count present, queued on the CALLER's stream - behind whatever produced the buffers -
+// between two events: the first lets that stream wait for the tables the kernel reads (they go up on the handle's stream), the
+// second lets the handle's stream wait for the kernel.  Everything is checked before anything reaches the device.
+static int images_begin_device_impl(xpnghip_images **out, int device, uint32_t nimg, const void *const *d_bufs, const uint64_t *dims, const uint8_t *channels,
+                                    uint32_t layout, uint32_t dtype, const float *scale, const float *bias, void *stream, uint8_t *pxsz_out) {
+    if (!out) return fail("null argument");
+    *out = nullptr;
+    if (!d_bufs || !dims || !channels || !pxsz_out) return fail("null argument");
+    if (nimg < 1 || nimg > 4096) return fail("a staged batch holds 1 .. 4096 images, not " + std::to_string(nimg));
+    std::string why;
+    if (!stage_layout_ok(layout, why)) return fail(why);
+    if (!stage_dtype_ok(dtype, scale, bias, why)) return fail(why);
+    FloatConsts k;
+    if (!float_consts(4, scale, bias, k, why)) return fail(why);
+    const uint64_t es = dtype ? (uint64_t)xpnghip_dtype_bytes(dtype) : 1;
+    bool have[2] = {false, false};  // some image of 3 / of 4 channels
+    for (uint32_t i = 0; i < nimg; i++) {
+        const uint64_t w = dims[2ull * i], hh = dims[2ull * i + 1];
+        if (!w || !hh || w > (1u << 24) || hh > (1u << 24))
+            return fail("bad size of image " + std::to_string(i) + ": " + std::to_string(w) + " x " + std::to_string(hh) + " (each side must be 1 .. 16777216)");
+        if (channels[i] != 3 && channels[i] != 4) return fail("image " + std::to_string(i) + " has " + std::to_string(channels[i]) + " channels, not 3 or 4");
+        if (!d_bufs[i]) return fail("null buffer of image " + std::to_string(i));
+        if ((uintptr_t)d_bufs[i] & (uintptr_t)(es - 1)) {
+            char b[32];
+            snprintf(b, sizeof b, "%p", d_bufs[i]);
+            return fail("buffer " + std::string(b) + " of image " + std::to_string(i) + " is not aligned to its " + std::to_string(es) + "-byte elements");
+        }
+        have[channels[i] - 3] = true;
+    }
+    if (device < 0 || device >= xpnghip_device_count()) return fail("no usable HIP device " + std::to_string(device) + " (libxpng_hip has no CPU fallback)");
+    const hipStream_t s = (hipStream_t)stream;
+    return images_begin_common(out, device, nimg, d_bufs, dims, channels, pxsz_out, [&](xpnghip_images *h, const std::vector<ImgRec> &) -> int {
+        struct Events {
+            hipEvent_t up = nullptr, done = nullptr;
+            ~Events() { for (hipEvent_t e : {up, done}) if (e) (void)hipEventDestroy(e); }
+        } ev;
+        HIPCHK(hipEventCreateWithFlags(&ev.up, hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&ev.done, hipEventDisableTiming));
+        HIPCHK(hipMalloc((void **)&h->d_src, (uint64_t)nimg * sizeof(void *)));
+        HIPCHK(hipMemcpyAsync(h->d_src, d_bufs, (uint64_t)nimg * sizeof(void *), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipEventRecord(ev.up, h->stream));
+        HIPCHK(hipStreamWaitEvent(s, ev.up, 0));
+        XPNG_REQUIRE(h->d_rec, h->d_src, h->d_in);
+        const dim3 grid(h->blocks, nimg);
+        if (have[0]) launch_stage_from<3>(h->d_rec, h->d_src, grid, layout, dtype, k, s);
+        if (have[1]) launch_stage_from<4>(h->d_rec, h->d_src, grid, layout, dtype, k, s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ev.done, s));
+        HIPCHK(hipStreamWaitEvent(h->stream, ev.done, 0));
+        return 0;
+    });
 }
 static int images_single_colour_impl(xpnghip_images *h, uint8_t *single) {
     if (!h || !single) return fail("no staged batch");
@@ -1158,6 +1228,10 @@ extern "C" int xpnghip_batch_cuts(uint32_t n, const uint64_t *dims, const uint8_
 }
 extern "C" int xpnghip_images_begin(xpnghip_images **h, uint32_t nimg, const uint8_t *const *rasters, const uint64_t *dims, const uint8_t *pxsz_in, uint8_t *pxsz_out) {
     XPNG_GUARDED(images_begin_impl(h, nimg, rasters, dims, pxsz_in, pxsz_out))
+}
+extern "C" int xpnghip_images_begin_device(xpnghip_images **h, int device, uint32_t nimg, const void *const *d_bufs, const uint64_t *dims, const uint8_t *channels,
+                                           uint32_t layout, uint32_t dtype, const float *scale, const float *bias, void *stream, uint8_t *pxsz_out) {
+    XPNG_GUARDED(images_begin_device_impl(h, device, nimg, d_bufs, dims, channels, layout, dtype, scale, bias, stream, pxsz_out))
 }
 extern "C" int xpnghip_images_single_colour(xpnghip_images *h, uint8_t *single) { XPNG_GUARDED(images_single_colour_impl(h, single)) }
 extern "C" int xpnghip_images_encode(xpnghip_images *h, const uint8_t *modes, uint8_t **blobs, uint64_t *lens) { XPNG_GUARDED(images_encode_impl(h, modes, blobs, lens)) }

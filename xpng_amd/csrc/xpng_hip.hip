@@ -31,6 +31,7 @@
 #include "mixed.hpp"
 #include "mixed_float.hpp"
 #include "mixed_resize.hpp"
+#include "stage_from.hpp"
 
 using namespace xpng;
 
@@ -1120,6 +1121,89 @@ static int resize_host_impl(int pxsz, const uint8_t *raster, uint64_t w, uint64_
 extern "C" int xpnghip_resize_host(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip, uint32_t out_w, uint32_t out_h,
                                    uint32_t layout, uint32_t dtype, const float *scale, const float *bias, void *out) {
     XPNG_GUARDED(resize_host_impl(pxsz, raster, w, h, rect, flip, out_w, out_h, layout, dtype, scale, bias, out))
+}
+// ---- staging from tensors (stage_from.hpp) ---------------------------------------------------------------------
+// the layout word of a call whose channel count is per image: the PLANAR and BGR bits and nothing else
+static bool stage_layout_ok(uint32_t layout, std::string &why) {
+    if (!(layout & ~(XPNGHIP_LAYOUT_PLANAR | XPNGHIP_LAYOUT_BGR))) return true;
+    why = "bad layout word " + layout_hex(layout) + " (XPNGHIP_LAYOUT_PLANAR | XPNGHIP_LAYOUT_BGR only: the channel count is an argument of its own)";
+    return false;
+}
+// dtype 0 (uint8) takes no constants; 1 .. 3 as in the float call
+static bool stage_dtype_ok(uint32_t dtype, const float *scale, const float *bias, std::string &why) {
+    if (dtype > XPNGHIP_DTYPE_F32) { why = "bad dtype " + std::to_string(dtype) + " (0 = uint8, XPNGHIP_DTYPE_F16 = 1, _BF16 = 2, _F32 = 3)"; return false; }
+    if (dtype == 0 && (scale || bias)) { why = std::string(scale ? "scale" : "bias") + " given with dtype 0: a uint8 buffer is stored as it is"; return false; }
+    return true;
+}
+// the bits of an f16 widened to fp32: exact, subnormals kept (what v_cvt_f32_f16 gives on the device)
+static float f16_bits_to_f32(uint16_t hb) {
+    const uint32_t sign = (uint32_t)(hb & 0x8000u) << 16, e = (hb >> 10) & 0x1Fu, m = hb & 0x3FFu;
+    uint32_t x;
+    if (e == 0x1F) x = sign | 0x7F800000u | (m << 13);
+    else if (e) x = sign | ((e + 112u) << 23) | (m << 13);
+    else if (!m) x = sign;
+    else {  // subnormal: m * 2^-24
+        uint32_t k = m, sh = 0;
+        while (!(k & 0x400u)) { k <<= 1; sh++; }
+        x = sign | ((113u - sh) << 23) | ((k & 0x3FFu) << 13);
+    }
+    float f;
+    memcpy(&f, &x, 4);
+    return f;
+}
+// The twin of k_images_stage_from's arithmetic on the host: the same operations in the same order, the multiply-add an explicit
+// fmaf(), contraction off on top of that.
+static uint8_t quantize_one_host(uint32_t dtype, const uint8_t *p, float s, float b) {
+#pragma clang fp contract(off)
+    float x;
+    if (dtype == XPNGHIP_DTYPE_F32) memcpy(&x, p, 4);
+    else {
+        uint16_t hb;
+        memcpy(&hb, p, 2);
+        if (dtype == XPNGHIP_DTYPE_F16) x = f16_bits_to_f32(hb);
+        else { const uint32_t w = (uint32_t)hb << 16; memcpy(&x, &w, 4); }
+    }
+    const float y = fmaf(x, s, b);
+    if (!(y > 0.0f)) return 0;  // NaN, -0, -inf
+    if (y >= 255.0f) return 255;
+    return (uint8_t)nearbyintf(y);  // (the default rounding mode: half to even)
+}
+static int quantize_host_impl(uint32_t layout, uint32_t dtype, int C, const void *src, uint64_t npx, const float *scale, const float *bias, uint8_t *out) {
+    std::string why;
+    if (!stage_layout_ok(layout, why)) return fail(why);
+    if (!stage_dtype_ok(dtype, scale, bias, why)) return fail(why);
+    if (C != 3 && C != 4) return fail("xpnghip_quantize_host: C is " + std::to_string(C) + ", not 3 or 4");
+    FloatConsts k;
+    if (!float_consts(C, scale, bias, k, why)) return fail(why);
+    if (!src || !out) return fail("xpnghip_quantize_host: null source or output buffer");
+    if (npx > (1ull << 48)) return fail("xpnghip_quantize_host: npx is " + std::to_string(npx) + ", more than 2^48");
+    const bool planar = layout & XPNGHIP_LAYOUT_PLANAR, bgr = layout & XPNGHIP_LAYOUT_BGR;
+    const uint64_t es = dtype ? (uint64_t)xpnghip_dtype_bytes(dtype) : 1;
+    const uint8_t *s = static_cast<const uint8_t *>(src);
+    for (uint64_t p = 0; p < npx; p++)
+        for (int c = 0; c < C; c++) {
+            const int cc = bgr && c < 3 ? 2 - c : c;  // the channel's position in the caller's buffer
+            const uint64_t e = planar ? (uint64_t)cc * npx + p : p * C + cc;
+            out[p * C + c] = dtype ? quantize_one_host(dtype, s + e * es, k.scale[cc], k.bias[cc]) : s[e];
+        }
+    return 0;
+}
+extern "C" int xpnghip_quantize_host(uint32_t layout, uint32_t dtype, int C, const void *src, uint64_t npx, const float *scale, const float *bias, uint8_t *out) {
+    XPNG_GUARDED(quantize_host_impl(layout, dtype, C, src, npx, scale, bias, out))
+}
+template <int C, class T>
+static void launch_stage_from(const ImgRec *rec, const uint8_t *const *srcs, dim3 grid, uint32_t layout, const FloatConsts &k, hipStream_t s) {
+    const uint32_t bgr = layout & XPNGHIP_LAYOUT_BGR;
+    if (layout & XPNGHIP_LAYOUT_PLANAR) k_images_stage_from<C, true, T><<<grid, 256, 0, s>>>(rec, srcs, bgr, k);
+    else k_images_stage_from<C, false, T><<<grid, 256, 0, s>>>(rec, srcs, bgr, k);
+}
+// one launch for the images of C channels of a staged batch
+template <int C>
+static void launch_stage_from(const ImgRec *rec, const uint8_t *const *srcs, dim3 grid, uint32_t layout, uint32_t dtype, const FloatConsts &k, hipStream_t s) {
+    if (dtype == 0) launch_stage_from<C, uint8_t>(rec, srcs, grid, layout, k, s);
+    else if (dtype == XPNGHIP_DTYPE_F16) launch_stage_from<C, f16_t>(rec, srcs, grid, layout, k, s);
+    else if (dtype == XPNGHIP_DTYPE_BF16) launch_stage_from<C, bf16_t>(rec, srcs, grid, layout, k, s);
+    else launch_stage_from<C, float>(rec, srcs, grid, layout, k, s);
 }
 template <int PX, class T>
 static void launch_resize(const xpnghip_ctx *c, uint32_t layout, int C, uint64_t bpr, const ResizeCall &rz, const FloatConsts &k, hipStream_t s) {

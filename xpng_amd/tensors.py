@@ -1,4 +1,5 @@
-"""torch front end: .xpng files -> device tensors in the layout and the data type a model reads, the pixels never leaving HBM.
+"""torch front end: .xpng files -> device tensors in the layout and the data type a model reads, the pixels never leaving HBM
+(load_files), and device tensors -> .xpng files the same way back (store_files).
 
 `load_files` is what `api.load_batch` is for host arrays.  The files that reach the tile codec are grouped by (tile mode, bytes per
 pixel) and every group is decoded by mixed-size device calls straight into tensors of the final layout
@@ -282,3 +283,103 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
             for (i, _, _, _), t in zip(part, outs):
                 out[i] = t
     return whole if whole is not None else out
+
+
+def _inverse_scale_bias(mean, std, present):
+    """load_files' y = (v / 255 - mean) / std inverted: v = y * (255 std) + 255 mean, as four (scale, bias) values computed in
+    Python doubles and rounded once to fp32.  `present` = the channel counts among the tensors: a per-channel mean or std must have
+    exactly that many values, so it cannot serve a list that mixes 3 and 4 channels."""
+    def four(name, value, default):
+        if value is None:
+            return [default] * 4
+        if isinstance(value, torch.Tensor):
+            value = value.tolist()
+        if not isinstance(value, (list, tuple)):
+            return [float(value)] * 4
+        vals = [float(v) for v in value]
+        for C in sorted(present):
+            if len(vals) != C:
+                raise XpngError(f"store_files: {name} has {len(vals)} values, a tensor has {C} channels")
+        return vals + [default] * (4 - len(vals))
+    m, s = four("mean", mean, 0.0), four("std", std, 1.0)
+    f32 = lambda x: torch.tensor(x, dtype=torch.float64).to(torch.float32).item()   # noqa: E731  (round to nearest fp32)
+    return [f32(255.0 * x) for x in s], [f32(255.0 * x) for x in m]
+
+
+def store_files(tensors, paths, level: int = 1, layout: str = "chw", bgr: bool = False, mean=None, std=None):
+    """Writes one .xpng file per tensor at `level` (1, 2 or 7): the inverse of load_files.  `tensors` is a list of tensors of any
+    sizes, each (C, h, w) for layout "chw" or (h, w, C) for "hwc" with C = 3 or 4 per tensor, or one stacked (N, ...) tensor; all
+    on ONE cuda device, contiguous, of ONE dtype among torch.uint8, float16, bfloat16 and float32.  bgr=True reads the colours as
+    B, G, R (alpha stays last).  Anything else raises XpngError naming the first offender; nothing is ever copied or converted
+    silently, and no file is written unless all can be.
+
+    A uint8 tensor holds the bytes to store; mean or std with it is an error.  A float tensor holds what load_files returns for the
+    same mean and std, y = (v / 255 - mean[c]) / std[c], and is stored as v = fmaf(y, scale[c], bias[c]) rounded half to even and
+    clamped to 0 .. 255 (NaN gives 0), with scale[c] = float32(255 * std[c]) and bias[c] = float32(255 * mean[c]) computed here in
+    Python doubles and rounded once; mean and std are a number or one number per channel position of the tensors, default 0 and 1
+    (a model that writes 0 .. 1 needs neither).  The rule is written down in include/xpng_hip.h (xpnghip_images_begin_device).
+
+    The pixels stay on the device: one staging kernel, queued behind the current torch stream, quantises and rearranges every
+    tensor of the list into a staged batch, and file i is byte for byte what api.store(level, raster_i, paths[i]) writes for the
+    quantised (h, w, C) raster - normalisation of RGBA, the single colour of level 2 and the raw fallbacks included
+    (api.store_tensors, include/xpng_store_tensors.h).  When the call returns the tensors are free again.
+
+    CPU tensors are accepted with level=7 only: they are quantised by api.quantize_host, the same arithmetic on the host, and
+    written through api.store_batch, which needs no device at that level."""
+    if layout not in ("chw", "hwc"):
+        raise XpngError(f"store_files: layout must be 'chw' or 'hwc', not {layout!r}")
+    if level not in (1, 2, 7):
+        raise XpngError(f"store_files: level must be 1, 2 or 7, not {level!r}")
+    if isinstance(tensors, torch.Tensor):
+        if tensors.dim() != 4:
+            raise XpngError(f"store_files: a stacked tensor is (N, ...) with four dimensions, not {tuple(tensors.shape)}")
+        if not tensors.is_contiguous():
+            raise XpngError("store_files: the stacked tensor is not contiguous")
+        tensors = list(tensors.unbind(0))
+    else:
+        tensors = list(tensors)
+    paths = [os.fspath(p) for p in paths]
+    if len(tensors) != len(paths):
+        raise XpngError(f"store_files: {len(tensors)} tensors and {len(paths)} paths")
+    if not tensors:
+        raise XpngError("store_files: empty list")
+    first = tensors[0]
+    dims, chans = [], []
+    for i, t in enumerate(tensors):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3:
+            raise XpngError(f"store_files: tensor {i} is not a tensor of three dimensions")
+        if t.dtype != torch.uint8 and t.dtype not in _DTYPES:
+            raise XpngError(f"store_files: tensor {i} has dtype {t.dtype}; torch.uint8, float16, bfloat16 or float32 are stored")
+        if t.dtype != first.dtype:
+            raise XpngError(f"store_files: tensor {i} has dtype {t.dtype}, the first has {first.dtype}: one dtype per call")
+        if t.device != first.device:
+            raise XpngError(f"store_files: tensor {i} is on {t.device}, the first on {first.device}: one device per call")
+        if not t.is_contiguous():
+            raise XpngError(f"store_files: tensor {i} is not contiguous (call .contiguous() yourself: nothing is copied silently)")
+        C, h, w = (t.shape[0], t.shape[1], t.shape[2]) if layout == "chw" else (t.shape[2], t.shape[0], t.shape[1])
+        if C not in (3, 4):
+            raise XpngError(f"store_files: tensor {i} has {C} channels in layout {layout!r}, not 3 or 4")
+        if not (1 <= w <= 1 << 24 and 1 <= h <= 1 << 24):
+            raise XpngError(f"store_files: tensor {i} is {w} x {h}; each side must be 1 .. 16777216")
+        dims.append((w, h))
+        chans.append(C)
+    dt = _DTYPES.get(first.dtype, 0)
+    if not dt and (mean is not None or std is not None):
+        raise XpngError("store_files: mean and std need a float dtype (a torch.uint8 tensor holds the bytes to store)")
+    scale = bias = None
+    if dt:
+        scale, bias = _inverse_scale_bias(mean, std, set(chans))
+        if not all(math.isfinite(v) for v in scale + bias):
+            raise XpngError("store_files: mean and std must be finite")
+    word = api.layout(planar=layout == "chw", bgr=bgr)
+    if first.device.type == "cpu":
+        if level != 7:
+            raise XpngError("store_files: CPU tensors are stored at level 7 only; levels 1 and 2 run on a GPU (there is no CPU fallback)")
+        rasters = [api.quantize_host(t.data_ptr(), w * h, C, word, dt, scale, bias).reshape(h, w, C) for t, (w, h), C in zip(tensors, dims, chans)]
+        api.store_batch(7, rasters, paths)
+        return
+    if first.device.type != "cuda":
+        raise XpngError(f"store_files: tensors on {first.device} cannot be stored (cuda, or cpu with level=7)")
+    index = first.device.index if first.device.index is not None else torch.cuda.current_device()
+    stream = torch.cuda.current_stream(index).cuda_stream      # the staging kernel runs behind whatever produced the tensors there
+    api.store_tensors(level, [t.data_ptr() for t in tensors], dims, chans, word, dt, paths, scale, bias, device=index, stream=stream)
