@@ -9,7 +9,8 @@ tests/_resize.py does for the resized decode.  fmaf is never replaced by float64
 """
 import numpy as np
 
-from _resize import BF16, F16, F32, f32, fmaf  # noqa: F401  (the dtype codes of the library and libm's fmaf)
+from _kit import BF16, F16, F32  # noqa: F401  (the dtype codes of the library)
+from _resize import f32, fmaf  # (libm's fmaf)
 
 U8 = 0
 DTYPES = [U8, F16, BF16, F32]

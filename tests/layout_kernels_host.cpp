@@ -3,28 +3,7 @@
 // rule (every aligned dword it loads holds a byte of an allowed range); the staging raster is a heap block of its exact size, so
 // AddressSanitizer sees any other access outside it.
 // Built and run by tests/test_layout_kernels_host.py: g++ -fsanitize=address -static-libasan -DKERNEL_TEXT=\"...\".
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-#include <algorithm>
-struct D3 { uint32_t x, y, z; };
-static D3 blockIdx, threadIdx;
-#define __global__
-#define __launch_bounds__(x)
-#define __restrict__
-struct uint4 { uint32_t x, y, z, w; };
-static uint32_t bperm(uint32_t a, uint32_t b, uint32_t sel) {
-    uint64_t in = ((uint64_t)a << 32) | b; uint32_t o = 0;
-    for (int i = 0; i < 4; i++) { uint32_t s = (sel >> (8 * i)) & 0xff, v;
-        if (s < 8) v = (in >> (8 * s)) & 0xff; else if (s == 0x0c) v = 0; else if (s >= 0x0d) v = 0xff; else { puts("sign selector"); abort(); }
-        o |= v << (8 * i); }
-    return o;
-}
-#define __builtin_amdgcn_perm bperm
-static uint32_t balign(uint32_t hi, uint32_t lo, uint32_t sh) { return (uint32_t)(((((uint64_t)hi) << 32) | lo) >> (8 * (sh & 3))); }
-#define __builtin_amdgcn_alignbyte balign
+#include "kernel_host.hpp"  // the launch shim, v_perm and v_alignbyte
 // allowed read ranges for ld32u: every aligned dword it loads must hold a byte of one of them
 static std::vector<std::pair<uintptr_t, uintptr_t>> g_ok;
 static void chk(uintptr_t q) { for (auto &r : g_ok) if (q + 4 > r.first && q < r.second) return; printf("ld32u outside: %lx\n", (unsigned long)q); abort(); }
@@ -33,11 +12,6 @@ static uint32_t ld32u(const uint8_t *p) {
     chk((uintptr_t)q); uint32_t lo = q[0]; if (!sh) return lo; chk((uintptr_t)(q + 1)); return (lo >> sh) | (q[1] << (32 - sh));
 }
 #include KERNEL_TEXT  // the four kernels, their record and MC_ROWS, cut out of xpng_amd/csrc/mixed.hpp by the test
-static uint64_t rup(uint64_t a, uint64_t b) { return (a + b - 1) / b * b; }
-template <class F> static void launch(uint32_t gx, uint32_t gy, F f) {
-    for (uint32_t y = 0; y < gy; y++) for (uint32_t x = 0; x < gx; x++) for (uint32_t t = 0; t < 256; t++) { blockIdx = {x, y, 0}; threadIdx = {t, 0, 0}; f(); }
-}
-static int errors = 0;
 // caller's byte (img, y, x, c) of layout from an interleaved raster of px bytes
 static uint8_t want(const uint8_t *ras, uint32_t w, int px, int C, bool bgr, uint32_t y, uint32_t x, int c) {
     if (c == 3) return px == 4 ? ras[((uint64_t)y * w + x) * px + 3] : 0xFF;

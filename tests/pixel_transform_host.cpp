@@ -5,10 +5,7 @@
 // ((3L + 3U - 2UL) + 2) >> 2 leaves 0..255: 383 at (255, 255, 0), -127 at (0, 0, 255)), a different triple in each channel so that a
 // carry between the lanes shows, 64 current pixels each, the four predictors, column 0 and interior, alpha 0 / 1 / 255.
 // Built and run by tests/test_pixel_transform_host.py: g++ -fsanitize=undefined,address -DKERNEL_TEXT=\"...\".
-#include <cstdint>
-#include <cstdio>
-#define __device__
-#define __forceinline__ inline
+#include "kernel_host.hpp"  // __device__ and __forceinline__
 constexpr uint32_t NL_NONE = 0xFFu;
 static inline int bit_width(uint32_t v) { return v ? 32 - __builtin_clz(v) : 0; }
 static inline uint32_t times3(uint32_t x) { return x + (x << 1); }

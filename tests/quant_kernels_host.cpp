@@ -6,33 +6,8 @@
 // AddressSanitizer sees anything else.  The widening and the quantisation shims are this file's own; the expected value of every
 // byte is the rule of include/xpng_hip.h computed with fmaf().
 // Built and run by tests/test_quant_kernels_host.py: g++ -fsanitize=address -static-libasan -DKERNEL_TEXT=\"...\".
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-struct D3 { uint32_t x, y, z; };
-static D3 blockIdx, threadIdx, gridDim, blockDim;
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __launch_bounds__(x)
-#define __restrict__
-struct uint2 { uint32_t x, y; };
-struct uint4 { uint32_t x, y, z, w; };
+#include "kernel_host.hpp"  // the launch shim, v_alignbyte, fma_f32; TYPES_TEXT: FloatConsts, the element types and pick4 (mixed_float.hpp)
 struct ImgRec { uint8_t *in; uint8_t *norm; uint64_t npx; uint32_t pxsz_in, spare; };
-struct FloatConsts { float scale[4], bias[4]; };
-struct f16_t { uint16_t bits; };
-struct bf16_t { uint16_t bits; };
-template <class T> struct FloatElem { static constexpr int KIND = 3; };
-template <> struct FloatElem<f16_t> { static constexpr int KIND = 1; };
-template <> struct FloatElem<bf16_t> { static constexpr int KIND = 2; };
-static float pick4(const float (&a)[4], uint32_t i) { return i == 0 ? a[0] : i == 1 ? a[1] : i == 2 ? a[2] : a[3]; }
-static int errors = 0;
-static void bad(const char *what, long a, long b) { if (errors++ < 20) printf("%s %ld %ld\n", what, a, b); }
-static uint32_t balign(uint32_t hi, uint32_t lo, uint32_t sh) { return (uint32_t)(((((uint64_t)hi) << 32) | lo) >> (8 * (sh & 3))); }
-#define __builtin_amdgcn_alignbyte balign
 
 // ---- the images of the launch: the shims look the running image up by blockIdx.y
 struct Img { const uint8_t *src; uint64_t src_bytes; uint8_t *dst; uint64_t dst_bytes; };
@@ -57,7 +32,6 @@ static void stg_st128(uint8_t *p, uint4 v) { chk_store(p, 16, 4); memcpy(p, &v, 
 static void stg_st96(uint8_t *p, uint32_t a, uint32_t b, uint32_t c) { chk_store(p, 12, 4); const uint32_t v[3] = {a, b, c}; memcpy(p, v, 12); }
 static void stg_st8(uint8_t *p, uint32_t v) { chk_store(p, 1, 1); *p = (uint8_t)v; }
 // ---- arithmetic, written out on the bits
-static float fma_f32(float v, float s, float b) { return fmaf(v, s, b); }
 static float cvt_f32_f16(uint32_t h) {  // by value: sign * m * 2^e in double, exact, then to float (exact too)
     const int e = (h >> 10) & 31, m = h & 1023;
     double v;
@@ -78,11 +52,6 @@ static uint32_t quant_u8(float y) {
 
 #include KERNEL_TEXT  // the kernel and its helpers, cut out of xpng_amd/csrc/stage_from.hpp by the test
 
-static uint64_t rup(uint64_t a, uint64_t b) { return (a + b - 1) / b * b; }
-template <class F> static void launch(uint32_t gx, uint32_t gy, F f) {
-    gridDim = {gx, gy, 1}; blockDim = {256, 1, 1};
-    for (uint32_t y = 0; y < gy; y++) for (uint32_t x = 0; x < gx; x++) for (uint32_t t = 0; t < 256; t++) { blockIdx = {x, y, 0}; threadIdx = {t, 0, 0}; f(); }
-}
 static const FloatConsts K = {{0.5f, 2.0f, 1.0f, 1.25f}, {0.5f, -3.0f, 0.25f, -1.0f}};
 static const FloatConsts ONE = {{1.0f, 1.0f, 1.0f, 1.0f}, {0.0f, 0.0f, 0.0f, 0.0f}};
 static uint32_t rnd() { static uint64_t s = 88172645463325252ull; s ^= s << 13; s ^= s >> 7; s ^= s << 17; return (uint32_t)(s >> 16); }

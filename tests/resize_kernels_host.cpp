@@ -7,38 +7,8 @@
 // blocks, so AddressSanitizer sees anything else.  The expected value of every element is this file's own plain statement of the
 // rule: fmaf() and its own round-to-nearest-even conversions.
 // Built and run by tests/test_resize_kernels_host.py: g++ -ffp-contract=off -fsanitize=address -static-libasan -DFLOAT_TEXT=.. -DKERNEL_TEXT=..
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-#include <algorithm>
-struct D3 { uint32_t x, y, z; };
-static D3 blockIdx, threadIdx;
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __launch_bounds__(x)
-#define __restrict__
-struct uint4 { uint32_t x, y, z, w; };
-struct Dw4 { uint32_t x, y, z, w; };
-struct Dw3 { uint32_t x, y, z; };
-struct MixedLayout { uint64_t stage; uint8_t *buf; uint32_t w, h; };
-constexpr uint32_t MC_ROWS = 8;
-static int errors = 0;
-static void bad(const char *what, long a, long b) { if (errors++ < 20) printf("%s %ld %ld\n", what, a, b); }
-
-static uint32_t bperm(uint32_t a, uint32_t b, uint32_t sel) {
-    uint64_t in = ((uint64_t)a << 32) | b; uint32_t o = 0;
-    for (int i = 0; i < 4; i++) { uint32_t s = (sel >> (8 * i)) & 0xff, v;
-        if (s < 8) v = (in >> (8 * s)) & 0xff; else if (s == 0x0c) v = 0; else if (s >= 0x0d) v = 0xff; else { puts("sign selector"); abort(); }
-        o |= v << (8 * i); }
-    return o;
-}
-#define __builtin_amdgcn_perm bperm
-static uint32_t balign(uint32_t hi, uint32_t lo, uint32_t sh) { return (uint32_t)(((((uint64_t)hi) << 32) | lo) >> (8 * (sh & 3))); }
-#define __builtin_amdgcn_alignbyte balign
+#define KERNEL_HOST_FLOAT_OPS
+#include "kernel_host.hpp"  // the launch shim, v_perm / v_alignbyte, the checked loads and stores, the narrowing; TYPES_TEXT: MixedLayout, MC_ROWS, Dw4, Dw3
 
 // ---- the staging raster, the read rule and the rectangles
 static const uint8_t *g_stage; static uint64_t g_bpr, g_need; static int g_px;
@@ -58,52 +28,10 @@ static void chk_read(const uint8_t *p, uint32_t n, uint32_t align) {
     }
     bad("staging read outside every slot", (long)o, n);
 }
-static Dw4 stage_ld128(const uint8_t *p) { chk_read(p, 16, 4); Dw4 v; memcpy(&v, p, 16); return v; }
-static Dw3 stage_ld96(const uint8_t *p) { chk_read(p, 12, 4); Dw3 v; memcpy(&v, p, 12); return v; }
-static uint32_t stage_ld32(const uint8_t *p) { chk_read(p, 4, 4); uint32_t v; memcpy(&v, p, 4); return v; }
-static uint32_t stage_ld8(const uint8_t *p) { chk_read(p, 1, 1); return *p; }
-static uint32_t ld32u(const uint8_t *p) {
-    uintptr_t a = (uintptr_t)p; const uint8_t *q = (const uint8_t *)(a & ~(uintptr_t)3); uint32_t sh = (a & 3) * 8;
-    uint32_t lo = stage_ld32(q); if (!sh) return lo; return (lo >> sh) | (stage_ld32(q + 4) << (32 - sh));
-}
-// ---- the caller's buffers: a store must lie inside one of them and be aligned to its width
-static std::vector<std::pair<uint8_t *, uint8_t *>> g_out;
-static void chk_store(uint8_t *p, uint32_t n) {
-    if ((uintptr_t)p % n) bad("misaligned store", (long)((uintptr_t)p & 15), n);
-    for (auto &r : g_out) if (p >= r.first && p + n <= r.second) return;
-    bad("store outside every buffer", 0, n); abort();
-}
-static void out_st128(uint8_t *p, uint4 v) { chk_store(p, 16); memcpy(p, &v, 16); }
-static void out_st32(uint8_t *p, uint32_t v) { chk_store(p, 4); memcpy(p, &v, 4); }
-static void out_st16(uint8_t *p, uint32_t v) { chk_store(p, 2); uint16_t h = (uint16_t)v; memcpy(p, &h, 2); }
-// ---- arithmetic: fmaf and round-to-nearest-even conversions, written out on the bits
-static float fma_f32(float v, float s, float b) { return fmaf(v, s, b); }
-static uint16_t to_bf16(float f) {
-    uint32_t x; memcpy(&x, &f, 4);
-    if ((x & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((x >> 16) | 0x40);
-    return (uint16_t)((x + 0x7fffu + ((x >> 16) & 1)) >> 16);
-}
-static uint16_t to_f16(float f) {  // by value: scale into the f16 grid with exact double arithmetic, round with nearbyint (ties to even)
-    uint32_t x; memcpy(&x, &f, 4);
-    const uint16_t sign = (x >> 16) & 0x8000u;
-    const double a = fabs((double)f);
-    if (std::isnan(f)) return sign | 0x7e00;
-    if (a >= 65520.0) return sign | 0x7c00;
-    if (a < 6.103515625e-05) return sign | (uint16_t)nearbyint(a * 16777216.0);
-    int e; frexp(a, &e);
-    const double q = nearbyint(ldexp(a, 11 - e));
-    return sign | (uint16_t)(((e - 1 + 15) << 10) + ((int)q - 1024));
-}
-static uint32_t cvt_pk_f16_rne(float lo, float hi) { return to_f16(lo) | ((uint32_t)to_f16(hi) << 16); }
-static uint32_t cvt_pk_bf16_rne(float lo, float hi) { return to_bf16(lo) | ((uint32_t)to_bf16(hi) << 16); }
 
 #include FLOAT_TEXT   // FloatConsts, the element types, pick4, narrow2, store1, float_chunk (and the float kernel): mixed_float.hpp
 #include KERNEL_TEXT  // ResizeRec, resize_tap and the kernel, cut out of xpng_amd/csrc/mixed_resize.hpp by the test
 
-static uint64_t rup(uint64_t a, uint64_t b) { return (a + b - 1) / b * b; }
-template <class F> static void launch(uint32_t gx, uint32_t gy, F f) {
-    for (uint32_t y = 0; y < gy; y++) for (uint32_t x = 0; x < gx; x++) for (uint32_t t = 0; t < 256; t++) { blockIdx = {x, y, 0}; threadIdx = {t, 0, 0}; f(); }
-}
 template <class T> static uint32_t elem_bits(float y) {
     if (sizeof(T) == 4) { uint32_t b; memcpy(&b, &y, 4); return b; }
     return FloatElem<T>::KIND == 1 ? to_f16(y) : to_bf16(y);

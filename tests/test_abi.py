@@ -5,25 +5,10 @@ import subprocess
 
 import pytest
 
+from _kit import built_with_probes as built, declared, exported
 from xpng_amd import api
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module", autouse=True)
-def built():
-    api.build_native(("hip", "probes", "host"))
-
-
-def declared(header, prefix):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(" + prefix + r"\w*)\s*\(", txt)))
-
-
-def exported(so):
-    out = subprocess.check_output(["nm", "-D", "--defined-only", so], text=True)
-    return {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
 
 
 def test_hip_library_exports_every_declared_symbol():

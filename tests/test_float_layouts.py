@@ -4,14 +4,13 @@ xpnghip_decode_varsize_device_batch_as_float, xpnghip_float_table; xpng_amd/tens
 The rule: element = (T) fmaf((float)byte, scale[c], bias[c]), T rounded to nearest even, c the channel's position in the caller's
 buffer.  The checker is independent of the code under test: a 256-entry table per (dtype, scale, bias, c) made with the C library's
 fmaf through ctypes and numpy's astype(float16) / torch's CPU .to(bfloat16), indexed by the oracle's raster after the numpy
-rearrangement of tests/test_layouts.py (a copy of it is below).  Every comparison is on the bits.
+rearrangement of tests/_kit.py (arrange; table and expect are there too).  Every comparison is on the bits.
 CPU: the symbols, xpnghip_dtype_bytes, xpnghip_float_table against the checker (1/255, ImageNet, exact rounding ties, f16
 subnormals, overflow to inf) and its refusals, load_files on the host-answered kinds in every layout and dtype, stack, misuse.
 GPU (-m gpu): every layout word x dtype on batches whose widths put every row and plane-row start at every multiple of the
 element size modulo 16 bytes, inside sentinel-filled buffers; the uint8 layout call as a second reference; a rejected tile and
 misuse; load_files on reference-written goldens."""
 import ctypes as C
-import ctypes.util
 import os
 import re
 import subprocess
@@ -19,102 +18,22 @@ import subprocess
 import numpy as np
 import pytest
 
+from _kit import (built, Arena, arrange, BF16, BITS, _bits, consts_from, DTYPES, ES, expect, F16, F32, f32_of, FORMATS, gpu,
+                  IMAGENET_MEAN, IMAGENET_STD, mixed_consts, _offsets, po, table, _torch_dtype, _upload)
 from xpng_amd import api
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
-SENTINEL = 0xA5
-LEAD, GUARD = 64, 256                                           # output i starts LEAD + es * (i % 8) bytes into its region; GUARD bytes behind it
 NEW = ["xpnghip_dtype_bytes", "xpnghip_float_table", "xpnghip_decode_varsize_device_batch_as_float"]
-F16, BF16, F32 = 1, 2, 3
-DTYPES = [F16, BF16, F32]
-ES = {F16: 2, BF16: 2, F32: 4}
-BITS = {F16: np.uint16, BF16: np.uint16, F32: np.uint32}
 COMMON_DIMS = [(17, 4), (64, 64), (445, 444), (889, 445), (100, 1100), (701, 300)]
 RGB_DIMS = [(w, h) for w in range(1, 18) for h in range(1, 4)] + COMMON_DIMS
 RGBA_DIMS = [(4, 4), (5, 7), (6, 5), (7, 4), (9, 5), (13, 4)] + COMMON_DIMS
-FORMATS = [(1, False), (2, False), (1, True)]
 WORDS = [api.layout(planar=p, bgr=b, channels=c) for c in (0, 3, 4) for p in (False, True) for b in (False, True)]
-IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def built():
-    api.build_native(("hip", "host"))
-
-
-@pytest.fixture(scope="module")
-def po():
-    from oracle import pyoracle
-    return pyoracle
 
 
 # ---- the checker ------------------------------------------------------------------------------------------------------
-_libm = C.CDLL(ctypes.util.find_library("m") or "libm.so.6")
-_libm.fmaf.restype = C.c_float
-_libm.fmaf.argtypes = [C.c_float, C.c_float, C.c_float]
-
-
-def f32(x):
-    """a Python double rounded once to fp32 (and back to a Python float)"""
-    return float(np.float32(x))
-
-
-def consts_from(mean, std):
-    """load_files' formula: scale = float32(1 / (255 std)), bias = float32(-mean / std), in Python doubles rounded once"""
-    return [f32(1.0 / (255.0 * s)) for s in std], [f32(-m / s) for m, s in zip(mean, std)]
-
-
-def table(dtype, scale, bias):
-    """(C, 256) bit patterns of the expected elements: libm's fmaf, then numpy's / torch's round-to-nearest-even narrowing"""
-    import torch
-    y = np.array([[_libm.fmaf(float(v), s, b) for v in range(256)] for s, b in zip(scale, bias)], dtype=np.float32)
-    if dtype == F32:
-        return y.view(np.uint32)
-    if dtype == F16:
-        with np.errstate(over="ignore"):
-            return y.astype(np.float16).view(np.uint16)
-    return torch.from_numpy(y).to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
-
-
-def arrange(r, planar, bgr, ch):
-    """(h, w, 3|4) in the file's form -> the bytes of a buffer of that layout (the rearrangement of tests/test_layouts.py)"""
-    px = r.shape[2]
-    if ch == 4 and px == 3:
-        r = np.concatenate([r, np.full(r.shape[:2] + (1,), 255, np.uint8)], axis=2)
-    elif ch == 3 and px == 4:
-        r = r[..., :3]
-    if bgr:
-        r = r[..., [2, 1, 0] + ([3] if r.shape[2] == 4 else [])]
-    return np.ascontiguousarray(r.transpose(2, 0, 1) if planar else r)
-
-
-def expect(r, planar, bgr, ch, tab):
-    """the bit patterns of the float buffer of raster r: tab[c][byte] at every element"""
-    a = arrange(r, planar, bgr, ch)
-    out = np.empty(a.shape, tab.dtype)
-    for c in range(ch):
-        if planar:
-            out[c] = tab[c][a[c]]
-        else:
-            out[..., c] = tab[c][a[..., c]]
-    return out
-
-
 def expect_word(r, word, tab):
     return expect(r, bool(word & 1), bool(word & 2), (word >> 8) or r.shape[2], tab)
-
-
-def probes(dtype):
-    """two scales whose products with v = 1 and v = 2 are exact ties of the narrow type, one rounding down to even, one up"""
-    return (257.0 / 256.0, 259.0 / 256.0) if dtype == BF16 else (2049.0 / 2048.0, 2051.0 / 2048.0)
-
-
-def mixed_consts(dtype):
-    """four different (scale, bias) pairs, one per channel position: ImageNet's on 0 and 2, the rounding probes on 1 and 3"""
-    s, b = consts_from(IMAGENET_MEAN, IMAGENET_STD)
-    p = probes(dtype)
-    return [s[0], p[0], s[2], p[1]], [b[0], 0.0, b[2], 0.0]
 
 
 def lib_table(dtype, scale, bias):
@@ -151,7 +70,7 @@ def test_dtype_bytes():
 
 
 CONSTANT_SETS = {
-    "unit": ([f32(1.0 / 255.0)] * 4, [0.0] * 4),
+    "unit": ([f32_of(1.0 / 255.0)] * 4, [0.0] * 4),
     "imagenet": consts_from(IMAGENET_MEAN + (0.5,), IMAGENET_STD + (0.25,)),
     "ties_f16": ([2049.0 / 2048.0, 2051.0 / 2048.0], [0.0, 0.0]),
     "ties_bf16": ([257.0 / 256.0, 259.0 / 256.0], [0.0, 0.0]),
@@ -228,18 +147,6 @@ def _host_files(po, tmp_path):
     return paths, [po.decode_image(open(p, "rb").read()) for p in paths]
 
 
-def _torch_dtype(dtype):
-    import torch
-    return {F16: torch.float16, BF16: torch.bfloat16, F32: torch.float32}[dtype]
-
-
-def _bits(t, dtype):
-    """a torch tensor of a float dtype as the numpy array of its bit patterns"""
-    import torch
-    t = t.cpu().contiguous()
-    return t.view(torch.int16 if ES[dtype] == 2 else torch.int32).numpy().view(BITS[dtype])
-
-
 def test_load_files_float_answers_host_kinds_without_a_gpu(po, tmp_path):
     from xpng_amd import tensors
     paths, want = _host_files(po, tmp_path)
@@ -265,7 +172,7 @@ def test_load_files_float_answers_host_kinds_without_a_gpu(po, tmp_path):
                         assert np.array_equal(_bits(g, dtype), w), (dtype, lay, ch, bgr, r.shape)
     # the defaults: mean 0, std 1 is v / 255 as one FMA with scale float32(1 / 255)
     got = tensors.load_files(paths[:1], device="cpu", dtype=_torch_dtype(F32))
-    assert np.array_equal(_bits(got[0], F32), expect(want[0], True, False, 3, table(F32, [f32(1 / 255.0)] * 3, [0.0] * 3)))
+    assert np.array_equal(_bits(got[0], F32), expect(want[0], True, False, 3, table(F32, [f32_of(1 / 255.0)] * 3, [0.0] * 3)))
     # uint8 stays what it was
     import torch
     got = tensors.load_files(paths, layout="hwc", device="cpu")
@@ -317,15 +224,6 @@ def test_load_files_stack_and_misuse_without_a_gpu(po, tmp_path):
 
 # ---- GPU ----------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def gpu():
-    import torch
-    import xpng_amd
-    if not torch.cuda.is_available() or xpng_amd.device_count() < 1:
-        pytest.fail("GPU tests need a HIP device; the product has no CPU fallback")
-    return xpng_amd
-
-
-@pytest.fixture(scope="module")
 def batches(po):
     """per (mode, alpha): dims, the rasters and the oracle's tile blobs - computed once, never changed"""
     from xpng_amd.synth import synth_raster
@@ -345,56 +243,6 @@ def batches(po):
             assert np.array_equal(po.decode_tiles(mode, b, w, h, r.shape[2]), r)
         out[(mode, alpha)] = (dims, rasters, blobs)
     return out
-
-
-class Arena:
-    """one sentinel-filled device tensor holding a region per image: LEAD + es * (i % 8) sentinel bytes (so the buffers start at
-    every multiple of the element size modulo 16), room for `sizes[i]` bytes, GUARD sentinel bytes"""
-
-    def __init__(self, sizes, es):
-        import torch
-        self.sizes, self.off, total = sizes, [], 0
-        for i, n in enumerate(sizes):
-            self.off.append(total + LEAD + es * (i % 8))
-            total += -(-(LEAD + 8 * es + n + GUARD) // 16) * 16
-        self.host0 = np.full(total, SENTINEL, np.uint8)
-        self.t = torch.from_numpy(self.host0.copy()).cuda()
-        assert self.t.data_ptr() % 16 == 0
-        self.ptrs = [self.t.data_ptr() + o for o in self.off]
-
-    def refill(self):
-        self.t.fill_(SENTINEL)
-
-    def fetch(self, sizes=None):
-        """the first sizes[i] bytes of every image, after checking that every other byte still holds the sentinel"""
-        import torch
-        torch.cuda.synchronize()
-        got = self.t.cpu().numpy()
-        sizes = sizes or self.sizes
-        mask = np.ones(got.size, bool)
-        for o, n in zip(self.off, sizes):
-            mask[o:o + n] = False
-        assert (got[mask] == SENTINEL).all(), "a byte before or behind an image was written"
-        return [got[o:o + n] for o, n in zip(self.off, sizes)]
-
-    def untouched(self):
-        import torch
-        torch.cuda.synchronize()
-        return np.array_equal(self.t.cpu().numpy(), self.host0)
-
-
-def _upload(blobs):
-    import torch
-    return [torch.from_numpy(np.frombuffer(b + b"\0" * 64, dtype=np.uint8).copy()).cuda() for b in blobs]
-
-
-def _offsets(blobs, ctx):
-    offs = []
-    for i, b in enumerate(blobs):
-        off, end = api.walk_tile_offsets(b, ctx.first_tile[i + 1] - ctx.first_tile[i])
-        assert end == len(b)
-        offs.append(off)
-    return offs
 
 
 def _decode_float(ctx, mode, d_b, lens, word, dtype, scale, bias, offs=None, expect_status=0, arena=None):

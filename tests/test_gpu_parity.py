@@ -1,34 +1,15 @@
 """GPU parity tests (run with -m gpu on an MI355X).  Everything goes through the C-ABI (libxpng_hip.so /
 libxpng.so via ctypes); the oracle and the reference-generated goldens are only the checker."""
-import hashlib
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
+from _kit import gpu, md5, po
 from conftest import GOLD, corpus_entries, corpus_raster, golden_raster, small_entries
 
 pytestmark = pytest.mark.gpu
-
-
-def md5(b):
-    return hashlib.md5(b).hexdigest()
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    import xpng_amd
-    if not torch.cuda.is_available() or xpng_amd.device_count() < 1:
-        pytest.fail("GPU tests need a HIP device; the product has no CPU fallback")
-    return xpng_amd
-
-
-@pytest.fixture(scope="module")
-def po():
-    from oracle import pyoracle
-    return pyoracle
 
 
 def test_native_library_is_the_one_loaded(gpu):

@@ -11,22 +11,9 @@ import pytest
 
 import _rans_tables as rt
 
+from _kit import gpu, po
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    import xpng_amd
-    if not torch.cuda.is_available() or xpng_amd.device_count() < 1:
-        pytest.fail("GPU tests need a HIP device; the product has no CPU fallback")
-    return xpng_amd
-
-
-@pytest.fixture(scope="module")
-def po():
-    from oracle import pyoracle
-    return pyoracle
 
 
 def _load_both_ways(gpu, monkeypatch, path, want, what):

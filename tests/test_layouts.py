@@ -7,6 +7,7 @@ of file it answers from the host bytes.  GPU (-m gpu): every layout word on batc
 alignment, inside sentinel-filled buffers at shifted offsets; the decode status; the encode from every layout; a round trip in
 both orders; misuse; load_files on the reference-written goldens."""
 import ctypes as C
+import functools
 import os
 import re
 import subprocess
@@ -14,42 +15,19 @@ import subprocess
 import numpy as np
 import pytest
 
+import _kit
+from _kit import FORMATS, GUARD, SENTINEL, _offsets, _upload, arrange, built, gpu, po
 from xpng_amd import api
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
-SENTINEL = 0xA5
-LEAD, GUARD = 64, 256                                           # output i starts LEAD + i % 4 bytes into its region; GUARD bytes behind it
 NEW = ["xpnghip_layout_channels", "xpnghip_decode_varsize_device_batch_as", "xpnghip_encode_varsize_device_batch_from"]
 # one tile across and two (445 x 444, 889 x 445), a tall and a wide image; 701 x 300 makes the staging pitch wider than every other row
 COMMON_DIMS = [(17, 4), (64, 64), (445, 444), (889, 445), (100, 1100), (701, 300)]
 RGB_DIMS = [(w, h) for w in range(1, 9) for h in range(1, 10)] + COMMON_DIMS   # rows and plane rows at every alignment, shorter than a dword
 RGBA_DIMS = [(4, 4), (5, 7), (6, 5), (7, 4)] + COMMON_DIMS
-FORMATS = [(1, False), (2, False), (1, True)]
 WORDS = [api.layout(planar=p, bgr=b, channels=c) for c in (0, 3, 4) for p in (False, True) for b in (False, True)]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def built():
-    api.build_native(("hip", "host"))
-
-
-@pytest.fixture(scope="module")
-def po():
-    from oracle import pyoracle
-    return pyoracle
-
-
-def arrange(r, planar, bgr, ch):
-    """(h, w, 3|4) in the file's form -> the bytes of a buffer of that layout: the checker's rearrangement"""
-    px = r.shape[2]
-    if ch == 4 and px == 3:
-        r = np.concatenate([r, np.full(r.shape[:2] + (1,), 255, np.uint8)], axis=2)
-    elif ch == 3 and px == 4:
-        r = r[..., :3]
-    if bgr:
-        r = r[..., [2, 1, 0] + ([3] if r.shape[2] == 4 else [])]
-    return np.ascontiguousarray(r.transpose(2, 0, 1) if planar else r)
+Arena = functools.partial(_kit.Arena, phases=4)                  # buffer i starts LEAD + i % 4 bytes into its region; GUARD bytes behind it
 
 
 def arrange_word(r, word):
@@ -147,15 +125,6 @@ def test_load_files_answers_host_kinds_without_a_gpu(po, tmp_path):
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def gpu():
-    import torch
-    import xpng_amd
-    if not torch.cuda.is_available() or xpng_amd.device_count() < 1:
-        pytest.fail("GPU tests need a HIP device; the product has no CPU fallback")
-    return xpng_amd
-
-
-@pytest.fixture(scope="module")
 def batches(po):
     """per (mode, alpha): dims, the rasters and the oracle's tile blobs - computed once, never changed"""
     from xpng_amd.synth import synth_raster
@@ -172,55 +141,6 @@ def batches(po):
             assert np.array_equal(po.decode_tiles(mode, b, w, h, r.shape[2]), r)
         out[(mode, alpha)] = (dims, rasters, blobs)
     return out
-
-
-class Arena:
-    """one sentinel-filled device tensor holding a region per image: LEAD + i % 4 sentinel bytes, the image's `sizes[i]` bytes,
-    GUARD sentinel bytes"""
-
-    def __init__(self, sizes, fill=None):
-        import torch
-        self.sizes, self.off, total = sizes, [], 0
-        for i, n in enumerate(sizes):
-            self.off.append(total + LEAD + i % 4)
-            total += -(-(LEAD + 4 + n + GUARD) // 16) * 16
-        host = np.full(total, SENTINEL, np.uint8)
-        if fill is not None:
-            for o, n, data in zip(self.off, sizes, fill):
-                host[o:o + n] = np.frombuffer(data, np.uint8) if isinstance(data, bytes) else data.reshape(-1)
-        self.host0 = host
-        self.t = torch.from_numpy(host.copy()).cuda()
-        self.ptrs = [self.t.data_ptr() + o for o in self.off]
-
-    def fetch(self):
-        """the images' bytes, after checking that every byte outside them still holds the sentinel"""
-        import torch
-        torch.cuda.synchronize()
-        got = self.t.cpu().numpy()
-        mask = np.ones(got.size, bool)
-        for o, n in zip(self.off, self.sizes):
-            mask[o:o + n] = False
-        assert (got[mask] == SENTINEL).all(), "a byte before or behind an image was written"
-        return [got[o:o + n] for o, n in zip(self.off, self.sizes)]
-
-    def untouched(self):
-        import torch
-        torch.cuda.synchronize()
-        return np.array_equal(self.t.cpu().numpy(), self.host0)
-
-
-def _upload(blobs):
-    import torch
-    return [torch.from_numpy(np.frombuffer(b + b"\0" * 64, dtype=np.uint8).copy()).cuda() for b in blobs]
-
-
-def _offsets(blobs, ctx):
-    offs = []
-    for i, b in enumerate(blobs):
-        off, end = api.walk_tile_offsets(b, ctx.first_tile[i + 1] - ctx.first_tile[i])
-        assert end == len(b)
-        offs.append(off)
-    return offs
 
 
 def _decode_as(ctx, mode, d_b, lens, word, offs=None, expect_status=0):

@@ -4,14 +4,9 @@ decode has to accept them on every path: the ordinary context, the host-buffer c
 import numpy as np
 import pytest
 
-from xpng_amd import api
+from _kit import built
 
 SHAPES = [(1, 3), (3, 1), (1, 2), (2, 1)]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def built():
-    api.build_native(("hip", "host"))
 
 
 def _gray(w, h):

@@ -10,40 +10,17 @@ bit-exact."""
 import ctypes as C
 import os
 import random
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from _kit import built_with_probes as built, declared, exported, gpu, _offsets, po, SENTINEL, _upload
 from xpng_amd import api
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SENTINEL = 0xA5
 # geometries every synthetic batch holds: one tile (100 x 100, 444 x 444), the two-tile split (445 x 444, 889 x 445), the
 # narrow-image tile shapes (300 x 4000, 4000 x 300)
 FIXED_DIMS = [(100, 100), (445, 444), (889, 445), (300, 4000), (4000, 300), (444, 444)]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def built():
-    api.build_native(("hip", "probes", "host"))
-
-
-@pytest.fixture(scope="module")
-def po():
-    from oracle import pyoracle
-    return pyoracle
-
-
-def declared(header, prefix):
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(" + prefix + r"\w*)\s*\(", txt)))
-
-
-def exported(so):
-    out = subprocess.check_output(["nm", "-D", "--defined-only", so], text=True)
-    return {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
 
 
 # ---- CPU ------------------------------------------------------------------------------------------------------------
@@ -146,30 +123,6 @@ def test_decode_mixed_rejects_bad_input_before_device_work(po):
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    import xpng_amd
-    if not torch.cuda.is_available() or xpng_amd.device_count() < 1:
-        pytest.fail("GPU tests need a HIP device; the product has no CPU fallback")
-    return xpng_amd
-
-
-def _upload(blobs):
-    import torch
-    return [torch.from_numpy(np.frombuffer(b + b"\0" * 64, dtype=np.uint8).copy()).cuda() for b in blobs]
-
-
-def _offsets(blobs, ctx):
-    from xpng_amd.api import walk_tile_offsets
-    offs = []
-    for i, b in enumerate(blobs):
-        off, end = walk_tile_offsets(b, ctx.first_tile[i + 1] - ctx.first_tile[i])
-        assert end == len(b)
-        offs.append(off)
-    return offs
-
-
 def _decode_padded(ctx, mode, d_b, lens, pad, offs=None, expect_status=0):
     """padded form at a pitch `pad` bytes beyond the widest row, `extra` sentinel rows behind every image: returns the rasters
     after checking that every byte outside [0, w * pxsz) of rows < h, and every row >= h, still holds the sentinel"""

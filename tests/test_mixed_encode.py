@@ -10,45 +10,21 @@ xpng_store_batch against xpng_store and the oracle's files.  Every comparison is
 import ctypes as C
 import os
 import random
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from _kit import built_with_probes as built, declared, exported, FORMATS, gpu, po, SENTINEL, _upload
 from xpng_amd import api
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SENTINEL = 0xA5
 GUARD = 256
 # one tile (100 x 100, 444 x 444), two tiles (889 x 445), nine tiles whose widest is 612 px (1500 x 1200), six tiles 715 tall
 # (300 x 4000), the smallest RGBA the codec accepts (4 x 4), an odd small size (17 x 4)
 STRIP_DIMS = [(100, 100), (444, 444), (889, 445), (1500, 1200), (300, 4000), (4, 4), (17, 4)]
 WIDE_DIMS = [(673, 10), (2000, 100)]                             # one tile wider than TR_MAXW = 672: the generic transform for the call
 RGB_SMALL = [(1, 7), (2, 1), (3, 3), (5, 7)]                     # rows shorter than a dword; tight RGB rows at all four alignments
-FORMATS = [(1, False), (2, False), (1, True)]
 FORMS = ["XPNG_WIDE_RANS", "XPNG_NARROW_RANS"]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def built():
-    api.build_native(("hip", "probes", "host"))
-
-
-@pytest.fixture(scope="module")
-def po():
-    from oracle import pyoracle
-    return pyoracle
-
-
-def declared(header, prefix):
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(" + prefix + r"\w*)\s*\(", txt)))
-
-
-def exported(so):
-    out = subprocess.check_output(["nm", "-D", "--defined-only", so], text=True)
-    return {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
 
 
 NEW_HIP = ["xpnghip_encode_varsize_device_batch", "xpnghip_images_begin", "xpnghip_images_single_colour", "xpnghip_images_encode",
@@ -178,15 +154,6 @@ def test_device_entry_points_refuse_bad_arguments():
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    import xpng_amd
-    if not torch.cuda.is_available() or xpng_amd.device_count() < 1:
-        pytest.fail("GPU tests need a HIP device; the product has no CPU fallback")
-    return xpng_amd
-
-
 _BATCHES = {}
 
 
@@ -305,11 +272,6 @@ def _decode_tight(ctx, mode, d_b, lens):
         assert (got[h * w * ch:] == SENTINEL).all()
         out.append(got[: h * w * ch].reshape(h, w, ch))
     return out
-
-
-def _upload(blobs):
-    import torch
-    return [torch.from_numpy(np.frombuffer(b + b"\0" * 64, dtype=np.uint8).copy()).cuda() for b in blobs]
 
 
 @pytest.mark.gpu

@@ -3,8 +3,8 @@ pointers (xpng_amd/csrc/xpng_hip.hip mixed_records; DESIGN.md 13 "The record tab
 stale, or wrongly believed current, when the form or the buffers change between calls - so this runs the forms of each direction
 in a fixed order over two buffer sets A and B on one context per format, and checks every byte of both sets after every call.
 
-The checker is the oracle (blobs and rasters) and the rearrangement / float table of tests/test_layouts.py and
-tests/test_float_layouts.py; every comparison is bit-exact.  Both sets are kept as a host model of their whole device tensor: a
+The checker is the oracle (blobs and rasters) and the rearrangement / float table of tests/_kit.py (those of
+tests/test_layouts.py and tests/test_float_layouts.py); every comparison is bit-exact.  Both sets are kept as a host model of their whole device tensor: a
 step writes its expectation into the model of its set, and afterwards BOTH device tensors must equal their models - the image
 bytes, what earlier steps left beside them, the sentinels around every buffer, and the set the step did not touch.
 
@@ -13,30 +13,13 @@ images beside a 700 px wide one), so the same pointers carry every form.  GPU on
 import numpy as np
 import pytest
 
-from test_float_layouts import F16, F32, expect, mixed_consts, table
-from test_layouts import FORMATS, arrange
+from _kit import F16, F32, FORMATS, GUARD, LEAD, SENTINEL, _upload, arrange, built, expect, gpu, mixed_consts, table
 from xpng_amd import api
 
-SENTINEL = 0xA5
-LEAD, GUARD = 64, 256
 # rows shorter than a dword, rows and plane rows at every alignment, more than one block of rows, and one image of two tiles
 RGB_DIMS = [(1, 1), (2, 1), (3, 3), (5, 7), (9, 4), (17, 4), (64, 64), (257, 17), (700, 500)]
 RGBA_DIMS = [d for d in RGB_DIMS if min(d) >= 4]               # (RGBA under 4 px on a side is undefined in the reference)
 PAD = 52                                                        # the padded step's pitch: the widest row and this
-
-
-@pytest.fixture(scope="module", autouse=True)
-def built():
-    api.build_native(("hip", "host"))
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    import xpng_amd
-    if not torch.cuda.is_available() or xpng_amd.device_count() < 1:
-        pytest.fail("GPU tests need a HIP device; the product has no CPU fallback")
-    return xpng_amd
 
 
 @pytest.fixture(scope="module")
@@ -104,11 +87,6 @@ class BufferSet:
         import torch
         torch.cuda.synchronize()
         return np.array_equal(self.t.cpu().numpy(), self.model)
-
-
-def _upload(blobs):
-    import torch
-    return [torch.from_numpy(np.frombuffer(b + b"\0" * 64, dtype=np.uint8).copy()).cuda() for b in blobs]
 
 
 @pytest.mark.gpu

@@ -4,19 +4,15 @@ Pins the oracle: every manifest entry whose input can be rebuilt here (committed
 generator) must encode to the byte-identical .xpng the compiled reference produced (size + md5, and
 the stored file where present) and decode back to the reference's decoded .7.
 """
-import hashlib
 import os
 
 import numpy as np
 import pytest
 
+from _kit import md5
 from conftest import GOLD, corpus_entries, corpus_raster, golden_raster, small_entries
 from oracle import pyoracle as po
 from xpng_amd.synth import to_seven_bytes
-
-
-def md5(b):
-    return hashlib.md5(b).hexdigest()
 
 
 def test_manifest_has_corpus_and_edges(manifest):

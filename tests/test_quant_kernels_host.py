@@ -7,31 +7,10 @@ one after another for all 16 instances and both colour orders on npx = 1 .. 9 wi
 sentinel-framed arena, on a size above one grid pass and on several images per launch that mix 3 and 4 channels, and checks every
 byte against the rule computed with fmaf(), that every store is dword-aligned (the tail: single bytes) and inside the image's slot,
 that no read leaves the aligned dwords the buffer occupies, and the sentinels."""
-import os
-import shutil
-import subprocess
-
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _kit as K
 
 
 def test_quant_kernels_on_the_host(tmp_path):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if not cxx:
-        pytest.fail("no C++ compiler for the host run of the staging kernel")
-    src = open(os.path.join(ROOT, "xpng_amd", "csrc", "stage_from.hpp")).read()
-    a, b = src.index("// ---- staging from tensors"), src.rindex("}  // namespace xpng")
-    text = src[a:b]
+    text = K.cut("stage_from.hpp", "// ---- staging from tensors")
     assert "k_images_stage_from" in text and "asm" not in text and "address_space" not in text
-    inc = tmp_path / "quant_kernels.inc"
-    inc.write_text(text)
-    exe = tmp_path / "quant_kernels_host"
-    cmd = [cxx, "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", '-DKERNEL_TEXT="%s"' % inc,
-           os.path.join(ROOT, "tests", "quant_kernels_host.cpp"), "-o", str(exe)]
-    # the sanitizer's runtime is linked statically, so the program runs in whatever environment the suite runs in; where the
-    # toolchain has no static runtime the program is built plain and its own range checks and sentinels are what is checked
-    if subprocess.run(cmd + ["-fsanitize=address", "-static-libasan"], capture_output=True).returncode != 0:
-        subprocess.check_call(cmd)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and r.stdout.strip().endswith("errors: 0"), (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    K.run_kernels_on_host(tmp_path, "quant_kernels_host", {"TYPES_TEXT": K.product_types("float"), "KERNEL_TEXT": text})

@@ -7,12 +7,7 @@ import numpy as np
 import pytest
 
 import _rans_tables as rt
-
-
-@pytest.fixture(scope="module")
-def po():
-    from oracle import pyoracle
-    return pyoracle
+from _kit import po
 
 
 def catalogue(pb):

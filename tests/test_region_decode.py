@@ -12,21 +12,11 @@ import subprocess
 import numpy as np
 import pytest
 
+from _kit import built, gpu, po
 from xpng_amd import api
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GEOMETRIES = [(4096, 4096), (16384, 16384), (1500, 1200), (445, 444), (300, 4000), (3799, 1927), (100, 100)]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def built():
-    api.build_native(("hip", "host"))
-
-
-@pytest.fixture(scope="module")
-def po():
-    from oracle import pyoracle
-    return pyoracle
 
 
 def rect_set(W, H, tiles, seed=0, n_random=24):
@@ -152,15 +142,6 @@ def test_decode_region_rejects_invalid_rects_before_device_work(po):
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    import xpng_amd
-    if not torch.cuda.is_available() or xpng_amd.device_count() < 1:
-        pytest.fail("GPU tests need a HIP device; the product has no CPU fallback")
-    return xpng_amd
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("form", ["XPNG_WIDE_RANS", "XPNG_NARROW_RANS"])
 def test_corpus_regions_equal_the_oracle_crop(gpu, po, manifest, monkeypatch, form):

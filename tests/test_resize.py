@@ -17,15 +17,15 @@ import subprocess
 import numpy as np
 import pytest
 
-import _resize as R
-from _resize import BF16, BITS, DTYPES, ES, F16, F32, Arena, Resized, mixed_consts
+from _kit import (BF16, BITS, DTYPES, ES, F16, F32, FORMATS, IMAGENET_MEAN, IMAGENET_STD, Arena, _bits, _offsets, _torch_dtype, _upload,
+                  arrange, built, consts_from, f32_of, gpu, mixed_consts, po)
+from _resize import Resized
 from xpng_amd import api
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
 NEW = ["xpnghip_decode_varsize_device_batch_resized", "xpnghip_resize_host"]
 WORDS = [api.layout(planar=p, bgr=b, channels=c) for c in (0, 3, 4) for p in (False, True) for b in (False, True)]
-FORMATS = [(1, False), (2, False), (1, True)]
 RGB_DIMS = [(1, 1), (2, 1), (1, 2), (3, 3), (17, 4), (64, 64), (445, 444), (889, 445), (100, 1100)]
 RGBA_DIMS = [(4, 4), (5, 7), (13, 4), (64, 64), (445, 444), (889, 445)]
 GPU_SIZES = [(3, 5), (37, 29)]                                    # (OW, OH): rows narrower than one 16-byte store; an odd width
@@ -36,46 +36,11 @@ RGB_RECTS = [(0, 0, 1, 1), (1, 0, 1, 1), (0, 0, 1, 2), (2, 0, 1, 3), (0, 3, 17, 
 RGBA_RECTS = [(0, 0, 4, 4), (4, 6, 1, 1), (12, 0, 1, 4), (0, 63, 64, 1), (430, 431, 2, 4), (440, 0, 9, 445)]
 
 
-@pytest.fixture(scope="module", autouse=True)
-def built():
-    api.build_native(("hip", "host"))
-
-
-@pytest.fixture(scope="module")
-def po():
-    from oracle import pyoracle
-    return pyoracle
-
-
-def _torch_dtype(dtype):
-    import torch
-    return {F16: torch.float16, BF16: torch.bfloat16, F32: torch.float32}[dtype]
-
-
-def _bits(t, dtype):
-    """a torch tensor of a float dtype as the numpy array of its bit patterns"""
-    import torch
-    t = t.cpu().contiguous()
-    return t.view(torch.int16 if ES[dtype] == 2 else torch.int32).numpy().view(BITS[dtype])
-
-
 def _lib_resize(r, rect, flip, OW, OH, word, dtype, scale, bias):
     ch = (word >> 8) or r.shape[2]
     raw = api.resize_host(r, (OH, OW), word, dtype, scale[:ch], bias[:ch], rect=rect, flip=flip)
     shape = (ch, OH, OW) if word & 1 else (OH, OW, ch)
     return np.frombuffer(raw, BITS[dtype]).reshape(shape)
-
-
-def _arrange(r, planar, bgr, ch):
-    """(h, w, 3|4) in the file's form -> the bytes of a buffer of that layout (the rearrangement of tests/test_layouts.py)"""
-    px = r.shape[2]
-    if ch == 4 and px == 3:
-        r = np.concatenate([r, np.full(r.shape[:2] + (1,), 255, np.uint8)], axis=2)
-    elif ch == 3 and px == 4:
-        r = r[..., :3]
-    if bgr:
-        r = r[..., [2, 1, 0] + ([3] if r.shape[2] == 4 else [])]
-    return np.ascontiguousarray(r.transpose(2, 0, 1) if planar else r)
 
 
 # ---- CPU ----------------------------------------------------------------------------------------------------------------
@@ -128,7 +93,7 @@ def test_resize_host_equals_the_checker(px):
                         if rect is not None and rect[2:] == (OW, OH):
                             ch = (word >> 8) or px
                             tab = np.frombuffer(api.float_table(dtype, scale[:ch], bias[:ch]), BITS[dtype]).reshape(ch, 256)
-                            a = _arrange(r[rect[1]:rect[1] + OH, rect[0]:rect[0] + OW], bool(word & 1), bool(word & 2), ch)
+                            a = arrange(r[rect[1]:rect[1] + OH, rect[0]:rect[0] + OW], bool(word & 1), bool(word & 2), ch)
                             look = np.stack([tab[c][a[c] if word & 1 else a[..., c]] for c in range(ch)], axis=0 if word & 1 else 2)
                             assert np.array_equal(got[0], look), ("identity", (w, h), rect, dtype, hex(word))
                             identities += 1
@@ -231,12 +196,12 @@ def test_load_files_size_answers_host_kinds_without_a_gpu(po, tmp_path):
     paths, want = _host_files(po, tmp_path)
     assert [r.shape for r in want] == [(7, 5, 3), (1000, 1000, 3), (6, 9, 4)]
     crops, flips = [(1, 2, 3, 4), None, (2, 0, 7, 5)], [True, False, True]
-    mean, std = R.IMAGENET_MEAN + (0.5,), R.IMAGENET_STD + (0.25,)
+    mean, std = IMAGENET_MEAN + (0.5,), IMAGENET_STD + (0.25,)
     OH, OW = 6, 5
     zs = [Resized(r, c, f, OH, OW) for r, c, f in zip(want, crops, flips)]
     for dtype in DTYPES:
         for ch in (3, 4):
-            scale, bias = R.consts_from(mean[:ch], std[:ch])
+            scale, bias = consts_from(mean[:ch], std[:ch])
             for lay in ("chw", "hwc"):
                 for bgr in (False, True):
                     word = api.layout(planar=lay == "chw", bgr=bgr, channels=ch)
@@ -255,7 +220,7 @@ def test_load_files_size_answers_host_kinds_without_a_gpu(po, tmp_path):
     got = tensors.load_files(paths, device="cpu", dtype=torch.float32, size=(4, 3))
     for g, r in zip(got, want):
         px = r.shape[2]
-        exp = Resized(r, None, False, 4, 3).bits(api.layout(planar=True), F32, [R.f32_of(1 / 255.0)] * px, [0.0] * px)
+        exp = Resized(r, None, False, 4, 3).bits(api.layout(planar=True), F32, [f32_of(1 / 255.0)] * px, [0.0] * px)
         assert tuple(g.shape) == (px, 4, 3) and np.array_equal(_bits(g, F32), exp)
     # misuse
     for bad in (dict(size=(4, 4)),                                               # uint8
@@ -302,15 +267,6 @@ def test_random_resized_crops():
 
 # ---- GPU ----------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def gpu():
-    import torch
-    import xpng_amd
-    if not torch.cuda.is_available() or xpng_amd.device_count() < 1:
-        pytest.fail("GPU tests need a HIP device; the product has no CPU fallback")
-    return xpng_amd
-
-
-@pytest.fixture(scope="module")
 def batches(po):
     """per (mode, alpha): dims, rectangles, the rasters and the oracle's tile blobs - computed once, never changed"""
     from xpng_amd.synth import synth_raster
@@ -334,20 +290,6 @@ def checked(key, i, raster, rect, flip, OW, OH):
     if k not in _CHECK:
         _CHECK[k] = Resized(raster, rect, bool(flip), OH, OW)
     return _CHECK[k]
-
-
-def _upload(blobs):
-    import torch
-    return [torch.from_numpy(np.frombuffer(b + b"\0" * 64, dtype=np.uint8).copy()).cuda() for b in blobs]
-
-
-def _offsets(blobs, ctx):
-    offs = []
-    for i, b in enumerate(blobs):
-        off, end = api.walk_tile_offsets(b, ctx.first_tile[i + 1] - ctx.first_tile[i])
-        assert end == len(b)
-        offs.append(off)
-    return offs
 
 
 def _decode_resized(ctx, mode, d_b, lens, word, dtype, size, scale, bias, rects, flips, offs=None, expect_status=0, arena=None):
@@ -523,10 +465,10 @@ def test_load_files_size_and_stack_on_goldens(gpu, manifest):
     crops = tensors.random_resized_crops(dims, generator=torch.Generator().manual_seed(3))
     crops[0] = None
     flips = [i % 2 == 1 for i in range(len(paths))]
-    scale, bias = R.consts_from(R.IMAGENET_MEAN, R.IMAGENET_STD)
+    scale, bias = consts_from(IMAGENET_MEAN, IMAGENET_STD)
     OH, OW = 24, 21
     for lay, bgr, dtype in (("chw", False, F16), ("hwc", True, F32)):
-        t = tensors.load_files(paths, layout=lay, channels=3, bgr=bgr, dtype=_torch_dtype(dtype), mean=R.IMAGENET_MEAN, std=R.IMAGENET_STD,
+        t = tensors.load_files(paths, layout=lay, channels=3, bgr=bgr, dtype=_torch_dtype(dtype), mean=IMAGENET_MEAN, std=IMAGENET_STD,
                                size=(OH, OW), crops=crops, flips=flips, stack=True)
         assert isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == _torch_dtype(dtype)
         assert tuple(t.shape) == (len(paths),) + ((3, OH, OW) if lay == "chw" else (OH, OW, 3))
@@ -534,7 +476,7 @@ def test_load_files_size_and_stack_on_goldens(gpu, manifest):
         for i, r in enumerate(want):
             exp = Resized(r, crops[i], flips[i], OH, OW).bits(word, dtype, scale, bias)
             assert np.array_equal(_bits(t[i], dtype), exp), (lay, i, paths[i])
-    lst = tensors.load_files(paths[:3], channels=3, dtype=torch.float16, mean=R.IMAGENET_MEAN, std=R.IMAGENET_STD, size=(OH, OW))
+    lst = tensors.load_files(paths[:3], channels=3, dtype=torch.float16, mean=IMAGENET_MEAN, std=IMAGENET_STD, size=(OH, OW))
     assert isinstance(lst, list) and all(tuple(g.shape) == (3, OH, OW) and g.is_cuda for g in lst)
     for i, g in enumerate(lst):
         assert np.array_equal(_bits(g, F16), Resized(want[i], None, False, OH, OW).bits(api.layout(planar=True, channels=3), F16, scale, bias)), i

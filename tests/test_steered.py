@@ -4,7 +4,6 @@ The CPU part (not marked gpu) is a census: it walks the oracle's tile blobs and 
 the format the encoder can write, and pins the rasters to the compiled reference through tests/golden/steered.json
 (oracle/make_steered_golden.py).  The GPU part runs the same rasters through the device entry points, bit-exact against the
 oracle.  No timing and no tolerance anywhere: every comparison is on bytes."""
-import hashlib
 import json
 import os
 
@@ -12,17 +11,8 @@ import numpy as np
 import pytest
 
 import _steered as S
+from _kit import gpu, md5, po
 from conftest import GOLD
-
-
-def md5(b):
-    return hashlib.md5(b).hexdigest()
-
-
-@pytest.fixture(scope="module")
-def po():
-    from oracle import pyoracle
-    return pyoracle
 
 
 @pytest.fixture(scope="module")
@@ -229,15 +219,6 @@ def _blobs(po, name, level):
     if (name, level) not in _ORACLE:
         _ORACLE[(name, level)] = po.encode_tiles(level, S.raster(name))
     return _ORACLE[(name, level)]
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    import xpng_amd
-    if not torch.cuda.is_available() or xpng_amd.device_count() < 1:
-        pytest.fail("GPU tests need a HIP device; the product has no CPU fallback")
-    return xpng_amd
 
 
 def _encode_then_decode(gpu, raster, want, level, what, shifts=(0,)):

@@ -8,11 +8,11 @@ patterns, the refusals, the round trip of api.float_table, and store_files at le
 files at every level, the round trip through load_files, and the order behind a side stream."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from _kit import built_with_probes as built, declared, exported, gpu, po
 import _quant as Q
 from xpng_amd import api
 
@@ -23,27 +23,6 @@ CONST_SETS = {"imagenet": IMAGENET, "unit": ((0.0, 0.0, 0.0), (1.0, 1.0, 1.0)), 
 # four different pairs, one per channel position of the caller's buffer; position 3 (alpha) passes 0 and 255 through
 MIXED = ([0.5, 2.0, 1.0, 1.0], [0.5, -3.0, 0.25, 0.0])
 WORDS = [0, Q.PLANAR, Q.BGR, Q.PLANAR | Q.BGR]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def built():
-    api.build_native(("hip", "probes", "host"))
-
-
-@pytest.fixture(scope="module")
-def po():
-    from oracle import pyoracle
-    return pyoracle
-
-
-def declared(header, prefix):
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(" + prefix + r"\w*)\s*\(", txt)))
-
-
-def exported(so):
-    out = subprocess.check_output(["nm", "-D", "--defined-only", so], text=True)
-    return {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
 
 
 # ---- CPU ------------------------------------------------------------------------------------------------------------
@@ -318,15 +297,6 @@ def test_store_files_level_7_on_cpu_tensors(po, tmp_path):
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    import xpng_amd
-    if not torch.cuda.is_available() or xpng_amd.device_count() < 1:
-        pytest.fail("GPU tests need a HIP device; the product has no CPU fallback")
-    return xpng_amd
-
-
 _RASTERS = {}
 
 

@@ -6,17 +6,13 @@ import subprocess
 import numpy as np
 import pytest
 
+from _kit import built
 from xpng_amd import api
 from xpng_amd.synth import load_seven, synth_raster, to_seven_bytes
 
 TOOL = os.path.join(os.path.dirname(api.CLI), "tool")
 NP = {"mv": lambda r: r[::-1], "mh": lambda r: r[:, ::-1], "mvh": lambda r: r[::-1, ::-1],
       "r90": lambda r: np.rot90(r, k=-1), "r270": lambda r: np.rot90(r, k=1), "tl": lambda r: r, "tr": lambda r: r}
-
-
-@pytest.fixture(scope="module", autouse=True)
-def built():
-    api.build_native(("hip", "host"))
 
 
 def run(op, src, dst):

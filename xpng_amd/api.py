@@ -512,6 +512,12 @@ def _floats(name, values, n=None):
     return (C.c_float * len(vals))(*vals)
 
 
+def _scale_bias(layout, pxsz, scale, bias):
+    """scale and bias of a float call, one value per channel of a buffer of this layout (a bad layout is the library's to refuse)"""
+    ch = hip_lib().xpnghip_layout_channels(layout, pxsz)
+    return _floats("scale", scale, ch if ch > 0 else None), _floats("bias", bias, ch if ch > 0 else None), ch
+
+
 def float_table(dtype: int, scale, bias) -> bytes:
     """The outputs of the float decode for every byte value: len(scale) * 256 elements of `dtype` as raw bytes, element
     c * 256 + v being the conversion of fmaf(v, scale[c], bias[c]) (xpnghip_float_table; host-only, needs no device).  Bit for
@@ -550,8 +556,7 @@ def resize_host(raster, size, layout: int, dtype: int, scale=None, bias=None, re
     except (TypeError, ValueError):
         raise XpngError(f"resize_host: size must be (OH, OW), not {size!r}") from None
     px = r.shape[2]
-    ch = hip_lib().xpnghip_layout_channels(layout, px)
-    sc, bi = _floats("scale", scale, ch if ch > 0 else None), _floats("bias", bias, ch if ch > 0 else None)
+    sc, bi, ch = _scale_bias(layout, px, scale, bias)
     ra = _rect_array("resize_host", None if rect is None else [rect], 1)
     ok = ch > 0 and 1 <= oh <= 16384 and 1 <= ow <= 16384          # (anything else the library refuses, naming the value)
     buf = np.empty(ch * oh * ow if ok else 1, dtype=np.uint32)     # 4-byte aligned, room for the widest element
@@ -715,19 +720,8 @@ def normalize_device(d_rgba: int, npx: int, d_out: int, stream=0):
     return pxsz.value, bool(rew.value)
 
 
-class Context:
-    """xpnghip_ctx: tile table + device workspace for one raster geometry on one GPU.  Device pointers are
-    plain integers (e.g. torch.Tensor.data_ptr()); `stream` is a hipStream_t handle or 0."""
-
-    FETCH = {"pr": 0, "nl": 1, "r": 2, "g": 3, "b": 4, "a": 5, "k": 19, "sums": 30}
-
-    def __init__(self, w: int, h: int, pxsz: int, device: int = 0, batch: int = 1, tile_range=None):
-        self.w, self.h, self.pxsz, self.device, self.batch = w, h, pxsz, device, batch
-        self._h = C.c_void_p()
-        r0, r1 = tile_range if tile_range else (0, (1 << 64) - 1)
-        if hip_lib().xpnghip_ctx_create_range(C.byref(self._h), device, w, h, pxsz, batch, r0, r1):
-            raise XpngError("xpnghip_ctx_create_range: " + _err())
-        self.n_tiles = hip_lib().xpnghip_ctx_tile_count(self._h)
+class _Handle:
+    """What both kinds of context do with their xpnghip_ctx handle (self._h)."""
 
     def close(self):
         if self._h:
@@ -746,14 +740,33 @@ class Context:
             raise IndexError(i)
         return tuple(a)
 
+    def workspace_bytes(self) -> int:
+        return hip_lib().xpnghip_ctx_workspace_bytes(self._h)
+
+    def decode_status(self, stream=0) -> int:
+        """Synchronise and report whether the last decode accepted every tile header (0) or rejected some (1)."""
+        return hip_lib().xpnghip_ctx_decode_status(self._h, stream)
+
+
+class Context(_Handle):
+    """xpnghip_ctx: tile table + device workspace for one raster geometry on one GPU.  Device pointers are
+    plain integers (e.g. torch.Tensor.data_ptr()); `stream` is a hipStream_t handle or 0."""
+
+    FETCH = {"pr": 0, "nl": 1, "r": 2, "g": 3, "b": 4, "a": 5, "k": 19, "sums": 30}
+
+    def __init__(self, w: int, h: int, pxsz: int, device: int = 0, batch: int = 1, tile_range=None):
+        self.w, self.h, self.pxsz, self.device, self.batch = w, h, pxsz, device, batch
+        self._h = C.c_void_p()
+        r0, r1 = tile_range if tile_range else (0, (1 << 64) - 1)
+        if hip_lib().xpnghip_ctx_create_range(C.byref(self._h), device, w, h, pxsz, batch, r0, r1):
+            raise XpngError("xpnghip_ctx_create_range: " + _err())
+        self.n_tiles = hip_lib().xpnghip_ctx_tile_count(self._h)
+
     def tiles(self):
         return [self.tile(i) for i in range(self.n_tiles)]
 
     def blob_bound(self, t0=0, t1=None) -> int:
         return hip_lib().xpnghip_ctx_blob_bound(self._h, t0, self.n_tiles if t1 is None else t1)
-
-    def workspace_bytes(self) -> int:
-        return hip_lib().xpnghip_ctx_workspace_bytes(self._h)
 
     def encode_device(self, mode, d_raster: int, d_blobs: int, t0=0, t1=None, stream=0, sync=True) -> int:
         n = C.c_uint64()
@@ -773,10 +786,6 @@ class Context:
         if rc:
             raise XpngError("xpnghip_encode_device_batch: " + _err())
         return list(lens) if sync else None
-
-    def decode_status(self, stream=0) -> int:
-        """Synchronise and report whether the last decode accepted every tile header (0) or rejected some (1)."""
-        return hip_lib().xpnghip_ctx_decode_status(self._h, stream)
 
     def decode_device_batch(self, mode, d_blobs, blob_lens, tile_offs, d_rasters, t0=0, t1=None, stream=0):
         """blob_lens: bytes of each blob buffer; tile_offs: per image, the blob start offsets of tiles [t0, t1)."""
@@ -839,7 +848,7 @@ class Context:
         return buf[:n].copy()
 
 
-class MixedContext:
+class MixedContext(_Handle):
     """A mixed-size context (xpnghip_ctx_create_mixed): images of different sizes, dims[i] = (w, h), one pixel size, decoded or
     encoded by ONE device call.  Device pointers are plain integers; `stream` is a hipStream_t handle or 0."""
 
@@ -853,30 +862,6 @@ class MixedContext:
         self.n_tiles = hip_lib().xpnghip_ctx_tile_count(self._h)
         self.first_tile = [hip_lib().xpnghip_ctx_mixed_first_tile(self._h, i) for i in range(self.nimg + 1)]
 
-    def close(self):
-        if self._h:
-            hip_lib().xpnghip_ctx_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def tile(self, i: int):
-        a = (C.c_uint64 * 4)()
-        if hip_lib().xpnghip_ctx_tile(self._h, i, a):
-            raise IndexError(i)
-        return tuple(a)
-
-    def workspace_bytes(self) -> int:
-        return hip_lib().xpnghip_ctx_workspace_bytes(self._h)
-
-    def decode_status(self, stream=0) -> int:
-        """Synchronise and report whether the last decode accepted every tile header (0) or rejected some (1)."""
-        return hip_lib().xpnghip_ctx_decode_status(self._h, stream)
-
     def blob_bound(self, i: int) -> int:
         """Capacity the blob buffer of image i needs (xpnghip_ctx_blob_bound over the image's span of the concatenated table)."""
         return hip_lib().xpnghip_ctx_blob_bound(self._h, self.first_tile[i], self.first_tile[i + 1])
@@ -885,10 +870,14 @@ class MixedContext:
         """One launch sequence over every tile of every image (xpnghip_encode_varsize_device_batch).  in_bpr != 0: every
         d_rasters[i] holds its rows at this pitch; 0: tight rasters.  Returns the list of blob lengths (sync=True) or None (read
         them with last_blobs_len_at after synchronising)."""
+        return self._encode("xpnghip_encode_varsize_device_batch", mode, d_rasters, in_bpr, d_blobs, stream, sync)
+
+    def _encode(self, symbol, mode, d_rasters, form, d_blobs, stream, sync):
+        """the marshalling of both encode calls; form = the row pitch or the layout word, the argument in which they differ"""
         k = len(d_rasters)
         ins, outs, lens = (C.c_void_p * k)(*d_rasters), (C.c_void_p * len(d_blobs))(*d_blobs), (C.c_uint64 * max(k, 1))()
-        if hip_lib().xpnghip_encode_varsize_device_batch(self._h, mode, ins, in_bpr, k, outs, lens if sync else None, stream):
-            raise XpngError("xpnghip_encode_varsize_device_batch: " + _err())
+        if getattr(hip_lib(), symbol)(self._h, mode, ins, form, k, outs, lens if sync else None, stream):
+            raise XpngError(symbol + ": " + _err())
         return list(lens)[:k] if sync else None
 
     def last_blobs_len_at(self, i: int) -> int:
@@ -898,6 +887,10 @@ class MixedContext:
         """One launch over every tile of every image (xpnghip_decode_mixed_device_batch).  out_bpr != 0: every d_outs[i] is
         written at this row pitch; 0: tight rasters.  tile_offs None: the size walk runs on the device; else per image the blob
         offsets of its tiles."""
+        self._decode("xpnghip_decode_mixed_device_batch", mode, d_blobs, lens, d_outs, tile_offs, stream, out_bpr)
+
+    def _decode(self, symbol, mode, d_blobs, lens, d_outs, tile_offs, stream, *between):
+        """the marshalling of every decode call; between = the arguments of this form, which sit between d_outs and stream"""
         k = len(d_blobs)
         off_arr = None
         if tile_offs is not None:
@@ -905,38 +898,20 @@ class MixedContext:
             assert len(flat) == self.n_tiles
             off_arr = (C.c_uint64 * len(flat))(*flat)
         ins, outs, ln = (C.c_void_p * k)(*d_blobs), (C.c_void_p * len(d_outs))(*d_outs), (C.c_uint64 * len(lens))(*lens)
-        if hip_lib().xpnghip_decode_mixed_device_batch(self._h, mode, ins, ln, k, off_arr, outs, out_bpr, stream):
-            raise XpngError("xpnghip_decode_mixed_device_batch: " + _err())
-
+        if getattr(hip_lib(), symbol)(self._h, mode, ins, ln, k, off_arr, outs, *between, stream):
+            raise XpngError(symbol + ": " + _err())
 
     def decode_batch_as(self, mode, d_blobs, lens, d_outs, layout, tile_offs=None, stream=0):
         """decode_batch in its tight form, with every d_outs[i] written in `layout` (api.layout(); C * w * h bytes at any
         alignment): xpnghip_decode_varsize_device_batch_as."""
-        k = len(d_blobs)
-        off_arr = None
-        if tile_offs is not None:
-            flat = [o for offs in tile_offs for o in offs]
-            assert len(flat) == self.n_tiles
-            off_arr = (C.c_uint64 * len(flat))(*flat)
-        ins, outs, ln = (C.c_void_p * k)(*d_blobs), (C.c_void_p * len(d_outs))(*d_outs), (C.c_uint64 * len(lens))(*lens)
-        if hip_lib().xpnghip_decode_varsize_device_batch_as(self._h, mode, ins, ln, k, off_arr, outs, layout, stream):
-            raise XpngError("xpnghip_decode_varsize_device_batch_as: " + _err())
+        self._decode("xpnghip_decode_varsize_device_batch_as", mode, d_blobs, lens, d_outs, tile_offs, stream, layout)
 
     def decode_batch_as_float(self, mode, d_blobs, lens, d_outs, layout, dtype, scale=None, bias=None, tile_offs=None, stream=0):
         """decode_batch_as with every d_outs[i] written as C * w * h elements of `dtype` (DTYPE_F16, DTYPE_BF16, DTYPE_F32), aligned
         to the element: element = fmaf(byte, scale[c], bias[c]) rounded to nearest even, c the channel's position in the buffer.
         scale / bias: one number per channel of the buffers or None (ones / zeros): xpnghip_decode_varsize_device_batch_as_float."""
-        k = len(d_blobs)
-        off_arr = None
-        if tile_offs is not None:
-            flat = [o for offs in tile_offs for o in offs]
-            assert len(flat) == self.n_tiles
-            off_arr = (C.c_uint64 * len(flat))(*flat)
-        ch = hip_lib().xpnghip_layout_channels(layout, self.pxsz)
-        sc, bi = _floats("scale", scale, ch if ch > 0 else None), _floats("bias", bias, ch if ch > 0 else None)
-        ins, outs, ln = (C.c_void_p * k)(*d_blobs), (C.c_void_p * len(d_outs))(*d_outs), (C.c_uint64 * len(lens))(*lens)
-        if hip_lib().xpnghip_decode_varsize_device_batch_as_float(self._h, mode, ins, ln, k, off_arr, outs, layout, dtype, sc, bi, stream):
-            raise XpngError("xpnghip_decode_varsize_device_batch_as_float: " + _err())
+        sc, bi, _ = _scale_bias(layout, self.pxsz, scale, bias)
+        self._decode("xpnghip_decode_varsize_device_batch_as_float", mode, d_blobs, lens, d_outs, tile_offs, stream, layout, dtype, sc, bi)
 
     def decode_batch_resized(self, mode, d_blobs, lens, d_outs, layout, dtype, size, scale=None, bias=None, rects=None, flips=None,
                              tile_offs=None, stream=0):
@@ -944,17 +919,11 @@ class MixedContext:
         C * OH * OW elements of `dtype`, size = (OH, OW), the resampling of rects[i] = (x, y, w, h) of image i (None: every whole
         image), mirrored where flips[i] is true (None: none): xpnghip_decode_varsize_device_batch_resized."""
         k = len(d_blobs)
-        off_arr = None
-        if tile_offs is not None:
-            flat = [o for offs in tile_offs for o in offs]
-            assert len(flat) == self.n_tiles
-            off_arr = (C.c_uint64 * len(flat))(*flat)
         try:
             oh, ow = (int(v) & 0xFFFFFFFF for v in size)
         except (TypeError, ValueError):
             raise XpngError(f"decode_batch_resized: size must be (OH, OW), not {size!r}") from None
-        ch = hip_lib().xpnghip_layout_channels(layout, self.pxsz)
-        sc, bi = _floats("scale", scale, ch if ch > 0 else None), _floats("bias", bias, ch if ch > 0 else None)
+        sc, bi, _ = _scale_bias(layout, self.pxsz, scale, bias)
         ra = _rect_array("decode_batch_resized", rects, k)
         fl = None
         if flips is not None:
@@ -962,18 +931,12 @@ class MixedContext:
             if len(flips) != k:
                 raise XpngError(f"decode_batch_resized: flips has {len(flips)} entries for {k} images")
             fl = (C.c_uint8 * max(k, 1))(*[int(f) & 0xFF for f in flips])
-        ins, outs, ln = (C.c_void_p * k)(*d_blobs), (C.c_void_p * len(d_outs))(*d_outs), (C.c_uint64 * len(lens))(*lens)
-        if hip_lib().xpnghip_decode_varsize_device_batch_resized(self._h, mode, ins, ln, k, off_arr, outs, layout, dtype, sc, bi, ra, fl, ow, oh, stream):
-            raise XpngError("xpnghip_decode_varsize_device_batch_resized: " + _err())
+        self._decode("xpnghip_decode_varsize_device_batch_resized", mode, d_blobs, lens, d_outs, tile_offs, stream, layout, dtype, sc, bi, ra, fl, ow, oh)
 
     def encode_batch_from(self, mode, d_rasters, layout, d_blobs, stream=0, sync=True):
         """encode_batch in its tight form, with every d_rasters[i] read in `layout` (api.layout(); its channels must be the
         context's): xpnghip_encode_varsize_device_batch_from.  Returns the list of blob lengths (sync=True) or None."""
-        k = len(d_rasters)
-        ins, outs, lens = (C.c_void_p * k)(*d_rasters), (C.c_void_p * len(d_blobs))(*d_blobs), (C.c_uint64 * max(k, 1))()
-        if hip_lib().xpnghip_encode_varsize_device_batch_from(self._h, mode, ins, layout, k, outs, lens if sync else None, stream):
-            raise XpngError("xpnghip_encode_varsize_device_batch_from: " + _err())
-        return list(lens)[:k] if sync else None
+        return self._encode("xpnghip_encode_varsize_device_batch_from", mode, d_rasters, layout, d_blobs, stream, sync)
 
 
 def walk_tile_offsets(blobs: bytes, n_tiles: int):

@@ -14,6 +14,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "common.hpp"
@@ -480,16 +481,6 @@ static int launch_transform(xpnghip_ctx *c, const EncSpan &e, hipStream_t s, siz
     return 0;
 }
 
-extern "C" int xpnghip_m1_transform_device(xpnghip_ctx *c, const void *d_raster, uint64_t t0, uint64_t t1, void *stream) {
-    if (check_range(c, t0, t1)) return 1;
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(c);
-    void *dummy = c->d_out_ptrs;  // no output buffer in this stage
-    if (set_ptrs(c, &d_raster, &dummy, 1, s)) return 1;
-    const EncSpan e = enc_span(c, 1, (uint32_t)t0, (uint32_t)t1);
-    return c->pxsz == 4 ? launch_transform<4>(c, e, s, 0, true) : launch_transform<3>(c, e, s, 0, true);  // (with the nl histogram: the kernel the encode runs)
-}
-
 extern "C" int xpnghip_m1_transform_device_batch(xpnghip_ctx *c, const void *const *d_rasters, uint32_t nimg, uint64_t t0, uint64_t t1, void *stream) {
     if (check_range(c, t0, t1)) return 1;
     HIPCHK(hipSetDevice(c->device));
@@ -497,7 +488,10 @@ extern "C" int xpnghip_m1_transform_device_batch(xpnghip_ctx *c, const void *con
     std::vector<void *> dummy(nimg, (void *)c->d_out_ptrs);  // no output buffers in this stage
     if (set_ptrs(c, d_rasters, dummy.data(), nimg, s)) return 1;
     const EncSpan e = enc_span(c, nimg, (uint32_t)t0, (uint32_t)t1);
-    return c->pxsz == 4 ? launch_transform<4>(c, e, s, 0, true) : launch_transform<3>(c, e, s, 0, true);
+    return c->pxsz == 4 ? launch_transform<4>(c, e, s, 0, true) : launch_transform<3>(c, e, s, 0, true);  // (with the nl histogram: the kernel the encode runs)
+}
+extern "C" int xpnghip_m1_transform_device(xpnghip_ctx *c, const void *d_raster, uint64_t t0, uint64_t t1, void *stream) {
+    return xpnghip_m1_transform_device_batch(c, &d_raster, 1, t0, t1, stream);
 }
 
 template <int PXSZ>
@@ -630,6 +624,16 @@ static int launch_encode_m2(xpnghip_ctx *c, const EncSpan &e, hipStream_t s) {
     return 0;
 }
 
+// The end of every encode call: the launch sequence of the mode and pixel size, and the blob lengths for a caller that waits for them.
+static int enc_finish(xpnghip_ctx *c, int mode, const EncSpan &e, uint32_t nimg, uint64_t *blobs_len, hipStream_t s) {
+    const int rc = mode == 2 ? launch_encode_m2(c, e, s) : c->pxsz == 4 ? launch_encode_m1<4>(c, e, s) : launch_encode_m1<3>(c, e, s);
+    if (rc) return rc;
+    if (blobs_len) {
+        HIPCHK(hipStreamSynchronize(s));
+        for (uint32_t b = 0; b < nimg; b++) blobs_len[b] = c->h_total[b];
+    }
+    return 0;
+}
 extern "C" int xpnghip_encode_device_batch(xpnghip_ctx *c, int mode, const void *const *d_rasters, uint32_t nimg, uint64_t t0,
                                            uint64_t t1, void *const *d_blobs, uint64_t *blobs_len, void *stream) {
     if (check_range(c, t0, t1)) return 1;
@@ -642,13 +646,7 @@ extern "C" int xpnghip_encode_device_batch(xpnghip_ctx *c, int mode, const void 
     hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(c);
     if (set_ptrs(c, d_rasters, d_blobs, nimg, s)) return 1;
     const EncSpan e = enc_span(c, nimg, (uint32_t)t0, (uint32_t)t1);
-    const int rc = mode == 2 ? launch_encode_m2(c, e, s) : c->pxsz == 4 ? launch_encode_m1<4>(c, e, s) : launch_encode_m1<3>(c, e, s);
-    if (rc) return rc;
-    if (blobs_len) {
-        HIPCHK(hipStreamSynchronize(s));
-        for (uint32_t b = 0; b < nimg; b++) blobs_len[b] = c->h_total[b];
-    }
-    return 0;
+    return enc_finish(c, mode, e, nimg, blobs_len, s);
 }
 extern "C" int xpnghip_encode_device(xpnghip_ctx *c, int mode, const void *d_raster, uint64_t t0, uint64_t t1,
                                      void *d_blobs, uint64_t *blobs_len, void *stream) {
@@ -930,26 +928,11 @@ static int mixed_records(xpnghip_ctx *c, MixedLayout *&table, std::vector<const 
     cache.assign(bufs, bufs + nimg);
     return 0;
 }
-template <int PX>
-static void launch_copy_as(const xpnghip_ctx *c, uint32_t layout, int C, uint64_t bpr, hipStream_t s) {
-    const dim3 grid((uint32_t)((c->m_max_h + MC_ROWS - 1) / MC_ROWS), c->B);
-    const uint32_t bgr = layout & XPNGHIP_LAYOUT_BGR;
-    if (layout & XPNGHIP_LAYOUT_PLANAR) {
-        if (C == 3) k_mixed_copy_as<PX, 3, true><<<grid, 256, 0, s>>>(c->d_m_out, c->d_m_stage, bpr, bgr);
-        else k_mixed_copy_as<PX, 4, true><<<grid, 256, 0, s>>>(c->d_m_out, c->d_m_stage, bpr, bgr);
-    } else {
-        if (C == 3) k_mixed_copy_as<PX, 3, false><<<grid, 256, 0, s>>>(c->d_m_out, c->d_m_stage, bpr, bgr);
-        else k_mixed_copy_as<PX, 4, false><<<grid, 256, 0, s>>>(c->d_m_out, c->d_m_stage, bpr, bgr);
-    }
-}
-template <int PX>
-static void launch_pack_from(const xpnghip_ctx *c, uint32_t layout, uint64_t bpr, hipStream_t s) {
-    const dim3 grid((uint32_t)((c->m_max_h + MC_ROWS - 1) / MC_ROWS), c->B);
-    const uint32_t bgr = layout & XPNGHIP_LAYOUT_BGR;
-    if (layout & XPNGHIP_LAYOUT_PLANAR) k_mixed_pack_from<PX, true><<<grid, 256, 0, s>>>(c->d_m_in, c->d_m_stage, bpr, bgr);
-    else k_mixed_pack_from<PX, false><<<grid, 256, 0, s>>>(c->d_m_in, c->d_m_stage, bpr, bgr);
-}
-
+// The compile-time form of a copy-out / staging kernel from the run-time words of a call: each of these hands its callable a
+// value whose TYPE carries the choice (3 | 4, planar or not, the element type), and the one place that names a kernel nests them.
+template <class F> static void with_3or4(int n, F f) { if (n == 3) f(std::integral_constant<int, 3>{}); else f(std::integral_constant<int, 4>{}); }
+template <class F> static void with_planar(uint32_t layout, F f) { if (layout & XPNGHIP_LAYOUT_PLANAR) f(std::true_type{}); else f(std::false_type{}); }
+static dim3 mixed_grid(const xpnghip_ctx *c, uint64_t rows) { return dim3((uint32_t)((rows + MC_ROWS - 1) / MC_ROWS), c->B); }
 // ---- float layouts (XPNGHIP_DTYPE_*; mixed_float.hpp) -----------------------------------------------------
 extern "C" int xpnghip_dtype_bytes(uint32_t dtype) {
     return dtype == XPNGHIP_DTYPE_F16 || dtype == XPNGHIP_DTYPE_BF16 ? 2 : dtype == XPNGHIP_DTYPE_F32 ? 4 : -1;
@@ -1010,23 +993,8 @@ struct FloatCall {
     uint32_t dtype;
     const float *scale, *bias;
 };
-template <int PX, class T>
-static void launch_copy_as_float(const xpnghip_ctx *c, uint32_t layout, int C, uint64_t bpr, const FloatConsts &k, hipStream_t s) {
-    const dim3 grid((uint32_t)((c->m_max_h + MC_ROWS - 1) / MC_ROWS), c->B);
-    const uint32_t bgr = layout & XPNGHIP_LAYOUT_BGR;
-    if (layout & XPNGHIP_LAYOUT_PLANAR) {
-        if (C == 3) k_mixed_copy_as_float<PX, 3, true, T><<<grid, 256, 0, s>>>(c->d_m_out, c->d_m_stage, bpr, bgr, k);
-        else k_mixed_copy_as_float<PX, 4, true, T><<<grid, 256, 0, s>>>(c->d_m_out, c->d_m_stage, bpr, bgr, k);
-    } else {
-        if (C == 3) k_mixed_copy_as_float<PX, 3, false, T><<<grid, 256, 0, s>>>(c->d_m_out, c->d_m_stage, bpr, bgr, k);
-        else k_mixed_copy_as_float<PX, 4, false, T><<<grid, 256, 0, s>>>(c->d_m_out, c->d_m_stage, bpr, bgr, k);
-    }
-}
-template <int PX>
-static void launch_copy_as_float(const xpnghip_ctx *c, uint32_t layout, int C, uint64_t bpr, uint32_t dtype, const FloatConsts &k, hipStream_t s) {
-    if (dtype == XPNGHIP_DTYPE_F16) launch_copy_as_float<PX, f16_t>(c, layout, C, bpr, k, s);
-    else if (dtype == XPNGHIP_DTYPE_BF16) launch_copy_as_float<PX, bf16_t>(c, layout, C, bpr, k, s);
-    else launch_copy_as_float<PX, float>(c, layout, C, bpr, k, s);
+template <class F> static void with_float(uint32_t dtype, F f) {
+    if (dtype == XPNGHIP_DTYPE_F16) f(f16_t{}); else if (dtype == XPNGHIP_DTYPE_BF16) f(bf16_t{}); else f(float{});
 }
 
 // ---- crop, resize and flip in the copy-out (mixed_resize.hpp) ------------------------------------------------
@@ -1191,37 +1159,15 @@ static int quantize_host_impl(uint32_t layout, uint32_t dtype, int C, const void
 extern "C" int xpnghip_quantize_host(uint32_t layout, uint32_t dtype, int C, const void *src, uint64_t npx, const float *scale, const float *bias, uint8_t *out) {
     XPNG_GUARDED(quantize_host_impl(layout, dtype, C, src, npx, scale, bias, out))
 }
-template <int C, class T>
-static void launch_stage_from(const ImgRec *rec, const uint8_t *const *srcs, dim3 grid, uint32_t layout, const FloatConsts &k, hipStream_t s) {
-    const uint32_t bgr = layout & XPNGHIP_LAYOUT_BGR;
-    if (layout & XPNGHIP_LAYOUT_PLANAR) k_images_stage_from<C, true, T><<<grid, 256, 0, s>>>(rec, srcs, bgr, k);
-    else k_images_stage_from<C, false, T><<<grid, 256, 0, s>>>(rec, srcs, bgr, k);
-}
 // one launch for the images of C channels of a staged batch
 template <int C>
 static void launch_stage_from(const ImgRec *rec, const uint8_t *const *srcs, dim3 grid, uint32_t layout, uint32_t dtype, const FloatConsts &k, hipStream_t s) {
-    if (dtype == 0) launch_stage_from<C, uint8_t>(rec, srcs, grid, layout, k, s);
-    else if (dtype == XPNGHIP_DTYPE_F16) launch_stage_from<C, f16_t>(rec, srcs, grid, layout, k, s);
-    else if (dtype == XPNGHIP_DTYPE_BF16) launch_stage_from<C, bf16_t>(rec, srcs, grid, layout, k, s);
-    else launch_stage_from<C, float>(rec, srcs, grid, layout, k, s);
-}
-template <int PX, class T>
-static void launch_resize(const xpnghip_ctx *c, uint32_t layout, int C, uint64_t bpr, const ResizeCall &rz, const FloatConsts &k, hipStream_t s) {
-    const dim3 grid((rz.out_h + MC_ROWS - 1) / MC_ROWS, c->B);
     const uint32_t bgr = layout & XPNGHIP_LAYOUT_BGR;
-    if (layout & XPNGHIP_LAYOUT_PLANAR) {
-        if (C == 3) k_mixed_resize_as_float<PX, 3, true, T><<<grid, 256, 0, s>>>(c->d_m_out, c->d_m_rect, c->d_m_stage, bpr, bgr, rz.out_w, rz.out_h, k);
-        else k_mixed_resize_as_float<PX, 4, true, T><<<grid, 256, 0, s>>>(c->d_m_out, c->d_m_rect, c->d_m_stage, bpr, bgr, rz.out_w, rz.out_h, k);
-    } else {
-        if (C == 3) k_mixed_resize_as_float<PX, 3, false, T><<<grid, 256, 0, s>>>(c->d_m_out, c->d_m_rect, c->d_m_stage, bpr, bgr, rz.out_w, rz.out_h, k);
-        else k_mixed_resize_as_float<PX, 4, false, T><<<grid, 256, 0, s>>>(c->d_m_out, c->d_m_rect, c->d_m_stage, bpr, bgr, rz.out_w, rz.out_h, k);
-    }
-}
-template <int PX>
-static void launch_resize(const xpnghip_ctx *c, uint32_t layout, int C, uint64_t bpr, uint32_t dtype, const ResizeCall &rz, const FloatConsts &k, hipStream_t s) {
-    if (dtype == XPNGHIP_DTYPE_F16) launch_resize<PX, f16_t>(c, layout, C, bpr, rz, k, s);
-    else if (dtype == XPNGHIP_DTYPE_BF16) launch_resize<PX, bf16_t>(c, layout, C, bpr, rz, k, s);
-    else launch_resize<PX, float>(c, layout, C, bpr, rz, k, s);
+    with_planar(layout, [&](auto PL) {
+        constexpr bool P = decltype(PL)::value;
+        if (dtype == 0) k_images_stage_from<C, P, uint8_t><<<grid, 256, 0, s>>>(rec, srcs, bgr, k);
+        else with_float(dtype, [&](auto t) { k_images_stage_from<C, P, decltype(t)><<<grid, 256, 0, s>>>(rec, srcs, bgr, k); });
+    });
 }
 // The rectangle table of a resized call: allocated on first use, uploaded by EVERY call (rectangles change with every batch, so
 // there is nothing to cache).  The records are in pageable host memory that dies with this call, so the stream is synchronised
@@ -1317,24 +1263,27 @@ static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *
     XPNG_REQUIRE(c->d_m_first, c->d_m_list);
     const int rc = dec_launch(c, mode, nimg, c->m_max_w, tile_off, s, 0, (uint32_t)c->tiles.size(), &c->m_list, c->d_m_list, bpr);
     if (rc) return rc;
-    if (rz) {
-        XPNG_REQUIRE(c->d_m_stage, c->d_m_out, c->d_m_rect);
-        if (c->pxsz == 4) launch_resize<4>(c, *layout, C, bpr, fc->dtype, *rz, fk, s);
-        else launch_resize<3>(c, *layout, C, bpr, fc->dtype, *rz, fk, s);
-        HIPCHK(hipGetLastError());
-    } else if (fc) {
+    if (rz || fc || as) {
         XPNG_REQUIRE(c->d_m_stage, c->d_m_out);
-        if (c->pxsz == 4) launch_copy_as_float<4>(c, *layout, C, bpr, fc->dtype, fk, s);
-        else launch_copy_as_float<3>(c, *layout, C, bpr, fc->dtype, fk, s);
-        HIPCHK(hipGetLastError());
-    } else if (as) {
-        XPNG_REQUIRE(c->d_m_stage, c->d_m_out);
-        if (c->pxsz == 4) launch_copy_as<4>(c, *layout, C, bpr, s);
-        else launch_copy_as<3>(c, *layout, C, bpr, s);
+        if (rz) XPNG_REQUIRE(c->d_m_rect);
+        const uint32_t bgr = *layout & XPNGHIP_LAYOUT_BGR;
+        with_3or4(c->pxsz, [&](auto PXc) { with_3or4(C, [&](auto Cc) { with_planar(*layout, [&](auto PL) {
+            constexpr int PX = decltype(PXc)::value, CH = decltype(Cc)::value;
+            constexpr bool P = decltype(PL)::value;
+            if (rz) {
+                with_float(fc->dtype, [&](auto t) {
+                    k_mixed_resize_as_float<PX, CH, P, decltype(t)><<<mixed_grid(c, rz->out_h), 256, 0, s>>>(c->d_m_out, c->d_m_rect, c->d_m_stage, bpr, bgr, rz->out_w, rz->out_h, fk);
+                });
+            } else if (fc) {
+                with_float(fc->dtype, [&](auto t) {
+                    k_mixed_copy_as_float<PX, CH, P, decltype(t)><<<mixed_grid(c, c->m_max_h), 256, 0, s>>>(c->d_m_out, c->d_m_stage, bpr, bgr, fk);
+                });
+            } else k_mixed_copy_as<PX, CH, P><<<mixed_grid(c, c->m_max_h), 256, 0, s>>>(c->d_m_out, c->d_m_stage, bpr, bgr);
+        }); }); });
         HIPCHK(hipGetLastError());
     } else if (!out_bpr) {
         XPNG_REQUIRE(c->d_m_stage, c->d_m_out);
-        k_mixed_copy<<<dim3((uint32_t)((c->m_max_h + MC_ROWS - 1) / MC_ROWS), nimg), 256, 0, s>>>(c->d_m_out, c->d_m_stage, bpr, (uint32_t)px);
+        k_mixed_copy<<<mixed_grid(c, c->m_max_h), 256, 0, s>>>(c->d_m_out, c->d_m_stage, bpr, (uint32_t)px);
         HIPCHK(hipGetLastError());
     }
     return 0;
@@ -1429,22 +1378,18 @@ static int encode_varsize_impl(xpnghip_ctx *c, int mode, const void *const *d_ra
     XPNG_REQUIRE(c->d_m_first, c->d_m_list);
     if (from) {
         XPNG_REQUIRE(c->d_m_stage, c->d_m_in);
-        if (c->pxsz == 4) launch_pack_from<4>(c, *layout, bpr, s);
-        else launch_pack_from<3>(c, *layout, bpr, s);
+        const uint32_t bgr = *layout & XPNGHIP_LAYOUT_BGR;
+        with_3or4(c->pxsz, [&](auto PXc) { with_planar(*layout, [&](auto PL) {
+            k_mixed_pack_from<decltype(PXc)::value, decltype(PL)::value><<<mixed_grid(c, c->m_max_h), 256, 0, s>>>(c->d_m_in, c->d_m_stage, bpr, bgr);
+        }); });
         HIPCHK(hipGetLastError());
     } else if (!in_bpr) {
         XPNG_REQUIRE(c->d_m_stage, c->d_m_in);
-        k_mixed_pack<<<dim3((uint32_t)((c->m_max_h + MC_ROWS - 1) / MC_ROWS), nimg), 256, 0, s>>>(c->d_m_in, c->d_m_stage, bpr, (uint32_t)px);
+        k_mixed_pack<<<mixed_grid(c, c->m_max_h), 256, 0, s>>>(c->d_m_in, c->d_m_stage, bpr, (uint32_t)px);
         HIPCHK(hipGetLastError());
     }
     const EncSpan e = enc_span_mixed(c, bpr);
-    const int rc = mode == 2 ? launch_encode_m2(c, e, s) : c->pxsz == 4 ? launch_encode_m1<4>(c, e, s) : launch_encode_m1<3>(c, e, s);
-    if (rc) return rc;
-    if (blobs_len) {
-        HIPCHK(hipStreamSynchronize(s));
-        for (uint32_t b = 0; b < nimg; b++) blobs_len[b] = c->h_total[b];
-    }
-    return 0;
+    return enc_finish(c, mode, e, nimg, blobs_len, s);
 }
 extern "C" int xpnghip_encode_varsize_device_batch(xpnghip_ctx *c, int mode, const void *const *d_rasters, uint64_t in_bpr, uint32_t nimg,
                                                    void *const *d_blobs, uint64_t *blobs_len, void *stream) {
