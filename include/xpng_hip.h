@@ -161,6 +161,8 @@ int xpnghip_ctx_tile(const xpnghip_ctx *ctx, uint64_t i, uint64_t xywh[4]);
 /* upper bound of the concatenated blobs of tiles [t0, t1) (raw fallback bound: sum(w*h*pxsz + 4)).  On a mixed context t0 and t1
  * index the concatenated table: image i's blob buffer needs blob_bound(first_tile(i), first_tile(i + 1)). */
 uint64_t xpnghip_ctx_blob_bound(const xpnghip_ctx *ctx, uint64_t t0, uint64_t t1);
+/* the sum of all device memory the context holds now: what it was created with and everything its calls have allocated since -
+ * planes and scratch, the level-2 and wide-form tables, the decode tables, staging rasters, the host wrappers' buffers */
 uint64_t xpnghip_ctx_workspace_bytes(const xpnghip_ctx *ctx);
 
 /* Encode tiles [t0, t1) of the device raster `d_raster` (full w*h*pxsz image, device pointer) into

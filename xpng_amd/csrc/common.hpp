@@ -6,6 +6,7 @@
 #include <atomic>
 #include <stdlib.h>
 #include <string.h>
+#include <vector>
 
 namespace xpng {
 
@@ -318,5 +319,33 @@ __device__ __forceinline__ uint32_t wave_scan_max(uint32_t v) {  // inclusive ru
 // force a wave-uniform value into an SGPR (loop cursors derived from ballots stay scalar: SALU arithmetic and
 // s_cbranch instead of VALU + exec-mask branches)
 __device__ __forceinline__ uint32_t sgpr(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
+// ---- workspace table (host only) ---------------------------------------------------------------------------------------
+// The device memory of one context: (address of the pointer member, bytes) for every live allocation, and their sum.  The members
+// stay plain typed pointers of xpnghip_ctx / DecodeWs (a context lives on the heap and never moves, so their addresses hold); the
+// table is what allocates, counts and frees them, so a buffer is added by one get() and nothing else.
+struct WsTable {
+    struct Entry { void **slot; uint64_t bytes; };
+    std::vector<Entry> live;
+    uint64_t total = 0;
+    hipError_t get(void **slot, uint64_t bytes) {  // a filled slot is left alone: the later calls of a lazy group, the retry after a failure
+        if (*slot) return hipSuccess;
+        const hipError_t e = hipMalloc(slot, bytes);
+        if (e == hipSuccess) { live.push_back(Entry{slot, bytes}); total += bytes; }
+        return e;
+    }
+    void drop(void **slot) {  // (a grow path: drop, then get)
+        for (size_t i = 0; *slot && i < live.size(); i++)
+            if (live[i].slot == slot) {
+                (void)hipFree(*slot);
+                *slot = nullptr; total -= live[i].bytes;
+                live.erase(live.begin() + (long)i);
+            }
+    }
+    void free_all() {
+        for (const Entry &e : live) { (void)hipFree(*e.slot); *e.slot = nullptr; }
+        live.clear(); total = 0;
+    }
+};
 
 }  // namespace xpng

@@ -34,8 +34,8 @@ struct WDec;  // rans2_wide_dec.hpp
 
 // The decode workspace of one context.  It BORROWS the context's side stream and its stream scratch (`arena`: the five symbol /
 // residual planes, 8 B per pixel, are carved out of it - no decode kernel reads the encode's intermediates and no encode kernel runs
-// while a decode of the same context does); dec_prepare (xpng_hip.hip) lends both before every launch.  It OWNS the per-tile
-// tables, which grow on demand, and its events.
+// while a decode of the same context does); dec_prepare (xpng_hip.hip) lends both before every launch.  Its per-tile tables grow on
+// demand inside the context's workspace table (WsTable, common.hpp), which frees them; it OWNS its events only.
 struct DecodeWs {
     uint64_t cap_tiles = 0, cap_plane = 0;
     WDec *d_wdec = nullptr;              // wide rANS decode: per (tile, stream) descriptors and decode tables
@@ -55,8 +55,6 @@ struct DecodeWs {
     uint64_t arena_bytes = 0;
 };
 inline void decode_ws_free(DecodeWs &w) {
-    void *p[] = {w.d_info, w.d_off, w.d_wdec, w.d_dtab, w.d_wdec2, w.d_dtab2};
-    for (void *q : p) if (q) (void)hipFree(q);
     for (hipEvent_t e : {w.ev_fork, w.ev_join, w.ev_ctx, w.ev_small}) if (e) (void)hipEventDestroy(e);
     w = DecodeWs();
 }
@@ -1588,27 +1586,26 @@ struct DecodeJob {
 };
 
 // (re)allocate the per-tile tables, place the five planes in the arena and bring the tile offsets to the device
-inline int decode_ws_prepare(DecodeWs &ws, const DecodeJob &j, std::string &err) {
+inline int decode_ws_prepare(DecodeWs &ws, WsTable &tab, const DecodeJob &j, std::string &err) {
     auto bad = [&](const char *m) { err = m; return 1; };
     const uint64_t vn = (uint64_t)j.B * j.n_tiles, plane = j.plane;
     const uint32_t total = j.list ? (uint32_t)vn : j.total();  // offsets to bring
     if (ws.cap_tiles < vn || ws.cap_plane < plane) {
-        for (void *q : {(void *)ws.d_info, (void *)ws.d_off, (void *)ws.d_wdec, (void *)ws.d_dtab}) if (q) (void)hipFree(q);
-        ws.d_info = nullptr; ws.d_off = nullptr; ws.d_wdec = nullptr; ws.d_dtab = nullptr;
+        for (void **q : {(void **)&ws.d_info, (void **)&ws.d_off, (void **)&ws.d_wdec, (void **)&ws.d_dtab}) tab.drop(q);
         ws.cap_tiles = ws.cap_plane = 0;
         ws.last_off.clear();
         // (the context symbol area carries one largest tile of slack: a corrupt payload can make the walk pop one queue for all
         //  of a tile's steps, i.e. read up to a tile's pixel count past that queue's start)
         const uint64_t sz[5] = {rup(plane + 8192 + 450000, 256), rup(plane + 64, 256), rup(plane + 64, 256), rup(plane + 64, 256), rup(4 * plane + 1024, 256)};
-        // (a hipMalloc fallback for the planes existed behind a probe switch; the context's arena always has the room, so it could never run)
+        // (an allocation of their own as a fallback for the planes existed behind a probe switch; the context's arena always has the room, so it could never run)
         if (!ws.arena || ws.arena_bytes < sz[0] + sz[1] + sz[2] + sz[3] + sz[4] + 256) return bad("internal error: the decode arena is too small for the symbol planes of this batch");
         uint8_t *pl[5], *q = reinterpret_cast<uint8_t *>(rup(reinterpret_cast<uintptr_t>(ws.arena), 256));
         for (int i = 0; i < 5; i++) { pl[i] = q; q += sz[i]; }
         ws.d_ctxsym = pl[0]; ws.d_asym = pl[1]; ws.d_alpha = pl[2]; ws.d_nlseq = pl[3];
         ws.d_resid = reinterpret_cast<uint32_t *>(pl[4]) + 16;
-        if (hipMalloc((void **)&ws.d_info, vn * sizeof(DecTile)) != hipSuccess || hipMalloc((void **)&ws.d_off, vn * 8) != hipSuccess ||
-            hipMalloc((void **)&ws.d_wdec, vn * 10 * sizeof(WDec)) != hipSuccess ||
-            hipMalloc((void **)&ws.d_dtab, vn * 10 * WD_TAB_MAX) != hipSuccess)
+        if (tab.get((void **)&ws.d_info, vn * sizeof(DecTile)) != hipSuccess || tab.get((void **)&ws.d_off, vn * 8) != hipSuccess ||
+            tab.get((void **)&ws.d_wdec, vn * 10 * sizeof(WDec)) != hipSuccess ||
+            tab.get((void **)&ws.d_dtab, vn * 10 * WD_TAB_MAX) != hipSuccess)
             return bad("hipMalloc failed (decode workspace)");
         ws.cap_tiles = vn; ws.cap_plane = plane;
     }
@@ -1701,7 +1698,7 @@ inline void dec_tail(const DecodeWs &ws, const DecodeJob &j, const DecodePlan &p
 }
 
 // Launch the whole level-1 decode of a job.
-inline int decode_m1_launch(DecodeWs &ws, const DecodeJob &j, std::string &err) {
+inline int decode_m1_launch(DecodeWs &ws, WsTable &tab, const DecodeJob &j, std::string &err) {
     auto bad = [&](const char *m) { err = m; return 1; };
     const DecodePlan p = decode_m1_plan(j);
     const TileSel sel = j.sel();
@@ -1710,7 +1707,7 @@ inline int decode_m1_launch(DecodeWs &ws, const DecodeJob &j, std::string &err) 
     const bool rgba = j.pxsz == 4;
     const auto tail = rgba ? &dec_tail<4> : &dec_tail<3>;
     dbg_count_sequence();
-    if (decode_ws_prepare(ws, j, err)) return 1;
+    if (decode_ws_prepare(ws, tab, j, err)) return 1;
     // (a null workspace pointer handed to a kernel is a GPU fault, i.e. abort(): refuse to launch instead)
     if (!ws.d_info || !ws.d_off || !ws.d_wdec || !ws.d_dtab || !ws.d_ctxsym || !ws.d_asym || !ws.d_alpha || !ws.d_nlseq || !ws.d_resid || !j.tiles || !j.blobs || !j.rasters)
         return bad("internal error: a decode workspace buffer was never allocated");

@@ -498,15 +498,15 @@ __global__ __launch_bounds__(64) void k_m2_dec_recon_band(const M2DecTile *__res
 // the level-2 buffers of a decode job (the context's; DecodeJob has the rest)
 struct M2DecBufs { M2DecTile *info2; M2Blk *blk2; uint16_t *tabs2; uint8_t *scratch2; const uint64_t *sbase2; uint32_t *stream_n2; };
 
-inline int m2_wide_decode(DecodeWs &ws, const DecodeJob &j, const M2DecBufs &m, const TileSel &sel, std::string &err);  // rans1_wide_dec.hpp
+inline int m2_wide_decode(DecodeWs &ws, WsTable &tab, const DecodeJob &j, const M2DecBufs &m, const TileSel &sel, std::string &err);  // rans1_wide_dec.hpp
 
 // Launch the level-2 decode of a job (RGB only).
-inline int decode_m2_launch(DecodeWs &ws, const DecodeJob &j, const M2DecBufs &m, std::string &err) {
+inline int decode_m2_launch(DecodeWs &ws, WsTable &tab, const DecodeJob &j, const M2DecBufs &m, std::string &err) {
     const uint32_t cnt = j.cnt(), total = j.total();
     const hipStream_t s = j.s;
     TileSel sel = j.sel();
     sel.order = nullptr;  // (level 2 enumerates image-major)
-    if (decode_ws_prepare(ws, j, err)) return 1;
+    if (decode_ws_prepare(ws, tab, j, err)) return 1;
     if (!ws.d_off || !ws.d_nlseq || !ws.d_resid || !ws.side || !m.info2 || !m.blk2 || !m.tabs2 || !m.scratch2 || !m.sbase2 || !m.stream_n2 || !j.tiles || !j.blobs || !j.rasters) {
         err = "internal error: a mode-2 decode workspace buffer was never allocated";  // (a null pointer in a kernel is a GPU fault = abort())
         return 1;
@@ -518,7 +518,7 @@ inline int decode_m2_launch(DecodeWs &ws, const DecodeJob &j, const M2DecBufs &m
     if (!wide) {
         k_rans1_decode<14><<<total * M2_STREAMS, 64, 0, s>>>(m.info2, j.tiles, sel, 0, M2_STREAMS, m.blk2, m.tabs2, m.scratch2, m.sbase2, m.stream_n2);
         k_rans1_decode<15><<<total, 64, 0, s>>>(m.info2, j.tiles, sel, 17, 1, m.blk2, m.tabs2, m.scratch2, m.sbase2, m.stream_n2);  // gray tiles
-    } else if (m2_wide_decode(ws, j, m, sel, err)) return 1;
+    } else if (m2_wide_decode(ws, tab, j, m, sel, err)) return 1;
     k_m2_dec_walk<<<total, 64, 0, s>>>(m.info2, j.tiles, sel, m.scratch2, m.sbase2, m.stream_n2, ws.d_nlseq);
     if (small_blocks(items)) k_m2_dec_resid<256><<<total, 256, 0, s>>>(m.info2, j.tiles, sel, m.scratch2, m.sbase2, m.stream_n2, ws.d_nlseq, ws.d_resid);
     else k_m2_dec_resid<1024><<<total, 1024, 0, s>>>(m.info2, j.tiles, sel, m.scratch2, m.sbase2, m.stream_n2, ws.d_nlseq, ws.d_resid);

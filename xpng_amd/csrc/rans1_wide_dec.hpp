@@ -306,15 +306,14 @@ __global__ __launch_bounds__(64) void k_rans1_dec_chain(const M2DecTile *__restr
     }
 }
 
-inline int m2_wide_decode(DecodeWs &ws, const DecodeJob &j, const M2DecBufs &m, const TileSel &sel, std::string &err) {
+inline int m2_wide_decode(DecodeWs &ws, WsTable &tab, const DecodeJob &j, const M2DecBufs &m, const TileSel &sel, std::string &err) {
     const uint64_t need = (uint64_t)j.B * j.n_tiles * M2_SLOTS;
     const uint32_t total = j.total();
     const hipStream_t s = j.s;
     if (ws.cap2 < need) {
-        if (ws.d_wdec2) (void)hipFree(ws.d_wdec2);
-        if (ws.d_dtab2) (void)hipFree(ws.d_dtab2);
-        ws.d_wdec2 = nullptr; ws.d_dtab2 = nullptr; ws.cap2 = 0;
-        if (hipMalloc((void **)&ws.d_wdec2, need * sizeof(WDec)) != hipSuccess || hipMalloc((void **)&ws.d_dtab2, need * WD_TAB_MAX) != hipSuccess) {
+        tab.drop((void **)&ws.d_wdec2); tab.drop((void **)&ws.d_dtab2);
+        ws.cap2 = 0;
+        if (tab.get((void **)&ws.d_wdec2, need * sizeof(WDec)) != hipSuccess || tab.get((void **)&ws.d_dtab2, need * WD_TAB_MAX) != hipSuccess) {
             err = "hipMalloc failed (mode-2 wide decode workspace)";
             return 1;
         }

@@ -71,7 +71,7 @@ static std::vector<xpnghip_ctx *> pool_trim_locked(size_t keep, uint64_t keep_by
     std::vector<xpnghip_ctx *> kept, victims;
     uint64_t sum = 0;
     for (xpnghip_ctx *c : g_idle) {
-        sum += c->ws_bytes + c->cap_raster + c->cap_blobs + c->cap_blob_in;
+        sum += c->ws.total;
         if (kept.size() < keep && sum <= keep_bytes) kept.push_back(c); else victims.push_back(c);
     }
     g_idle.swap(kept);
@@ -133,11 +133,19 @@ struct CtxLease {  // a context for the duration of one call
     ~CtxLease() { ctx_quiesce(c); ctx_checkin(c); }
 };
 
-static int ensure_buf(uint8_t *&p, uint64_t &cap, uint64_t need) {
+static int ensure_buf(uint8_t *&p, uint64_t &cap, uint64_t need) {  // (a staging buffer of an image handle)
     if (cap >= need && p) return 0;
     if (p) (void)hipFree(p);
     p = nullptr; cap = 0;
     HIPCHK(hipMalloc((void **)&p, need + 64));
+    cap = need;
+    return 0;
+}
+// the same for a context's d_raster, d_blobs and d_blob_in, which its workspace table holds
+static int ctx_buf(xpnghip_ctx *c, uint8_t *&p, uint64_t &cap, uint64_t need) {
+    if (cap >= need && p) return 0;
+    c->ws.drop((void **)&p); cap = 0;
+    WS_GET(p, need + 64);
     cap = need;
     return 0;
 }
@@ -339,8 +347,8 @@ static int encode_multi(std::vector<Shard> sh, const std::vector<TileDesc> &tile
         leases.emplace_back(s.c);
         xpnghip_ctx *c = s.c;
         const uint64_t band = (uint64_t)(s.y1 - s.y0) * bpr;
-        if (ensure_buf(c->d_raster, c->cap_raster, band + 16)) return 1;
-        if (ensure_buf(c->d_blobs, c->cap_blobs, k == 0 ? whole_bound : xpnghip_ctx_blob_bound(c, s.r0, s.r1))) return 1;
+        if (ctx_buf(c, c->d_raster, c->cap_raster, band + 16)) return 1;
+        if (ctx_buf(c, c->d_blobs, c->cap_blobs, k == 0 ? whole_bound : xpnghip_ctx_blob_bound(c, s.r0, s.r1))) return 1;
         // kernels address rows absolutely: the band is handed over as if the whole raster were there (only rows [y0, y1) are
         // touched); it starts at the 16-byte phase row y0 has in the whole raster, so the virtual base stays 16-byte aligned
         uint8_t *bandp = c->d_raster + (((uint64_t)s.y0 * bpr) & 15);
@@ -407,7 +415,7 @@ static int encode_tiles_impl(uint64_t T, int mode, const uint8_t *raster, uint64
     CtxLease lease(ctx_checkout(base_device(), w, h, pxsz));
     xpnghip_ctx *c = lease.c;
     if (!c) return 1;
-    if (ensure_buf(c->d_raster, c->cap_raster, s) || ensure_buf(c->d_blobs, c->cap_blobs, xpnghip_ctx_blob_bound(c, 0, N))) return 1;
+    if (ctx_buf(c, c->d_raster, c->cap_raster, s) || ctx_buf(c, c->d_blobs, c->cap_blobs, xpnghip_ctx_blob_bound(c, 0, N))) return 1;
     HIPCHK(hipMemcpyAsync(c->d_raster, raster, s, hipMemcpyHostToDevice, ctx_stream(c)));
     uint64_t len = 0;
     if (xpnghip_encode_device(c, mode, c->d_raster, 0, N, c->d_blobs, &len, nullptr)) return 1;
@@ -434,7 +442,7 @@ static int decode_multi(std::vector<Shard> sh, const std::vector<TileDesc> &tile
         xpnghip_ctx *c = s.c;
         s.off = off[s.r0]; s.len = off[s.r1] - off[s.r0];
         const uint64_t band = (uint64_t)(s.y1 - s.y0) * bpr;
-        if (ensure_buf(c->d_raster, c->cap_raster, band + 16) || ensure_buf(c->d_blob_in, c->cap_blob_in, s.len)) return 1;
+        if (ctx_buf(c, c->d_raster, c->cap_raster, band + 16) || ctx_buf(c, c->d_blob_in, c->cap_blob_in, s.len)) return 1;
         HIPCHK(hipMemcpyAsync(c->d_blob_in, blobs + s.off, s.len, hipMemcpyHostToDevice, ctx_stream(c)));
         rel.assign(off.begin() + (long)s.r0, off.begin() + (long)s.r1);
         for (uint64_t &o : rel) o -= s.off;
@@ -514,7 +522,7 @@ static int decode_tiles_impl(uint64_t T, int mode, const uint8_t *blobs, uint64_
     CtxLease lease(ctx_checkout(base_device(), w, h, pxsz));
     xpnghip_ctx *c = lease.c;
     if (!c) return 1;
-    if (ensure_buf(c->d_raster, c->cap_raster, s) || ensure_buf(c->d_blob_in, c->cap_blob_in, blobs_len)) return 1;
+    if (ctx_buf(c, c->d_raster, c->cap_raster, s) || ctx_buf(c, c->d_blob_in, c->cap_blob_in, blobs_len)) return 1;
     HIPCHK(hipMemcpyAsync(c->d_blob_in, blobs, blobs_len, hipMemcpyHostToDevice, ctx_stream(c)));
     if (xpnghip_decode_device(c, mode, c->d_blob_in, blobs_len, off.data(), 0, N, c->d_raster, nullptr)) return 1;
     Prefault pf;
@@ -562,7 +570,7 @@ static int decode_region_impl(int mode, const uint8_t *blobs, uint64_t blobs_len
     xpnghip_ctx *c = lease.c;
     if (!c) return 1;
     const uint64_t crop = rect[2] * rect[3] * (uint64_t)pxsz;
-    if (ensure_buf(c->d_raster, c->cap_raster, crop) || ensure_buf(c->d_blob_in, c->cap_blob_in, span)) return 1;
+    if (ctx_buf(c, c->d_raster, c->cap_raster, crop) || ctx_buf(c, c->d_blob_in, c->cap_blob_in, span)) return 1;
     HIPCHK(hipMemcpyAsync(c->d_blob_in, blobs + first, span, hipMemcpyHostToDevice, ctx_stream(c)));
     const void *bp = c->d_blob_in;
     void *op = c->d_raster;
@@ -630,7 +638,7 @@ static int decode_mixed_host_impl(int mode, int pxsz, uint32_t nimg, const uint8
     if (xpnghip_ctx_create_mixed(&own.c, base_device(), dims, nimg, pxsz)) return 1;
     xpnghip_ctx *c = own.c;
     if (off.size() != c->tiles.size()) return fail("internal error: tile count of the mixed table");
-    if (ensure_buf(c->d_raster, c->cap_raster, roff[nimg]) || ensure_buf(c->d_blob_in, c->cap_blob_in, boff[nimg])) return 1;
+    if (ctx_buf(c, c->d_raster, c->cap_raster, roff[nimg]) || ctx_buf(c, c->d_blob_in, c->cap_blob_in, boff[nimg])) return 1;
     hipStream_t s = ctx_stream(c);
     std::vector<const void *> bp(nimg);
     std::vector<void *> op(nimg);
@@ -903,7 +911,7 @@ static int image_encode_banded(xpnghip_image *im, std::vector<Shard> &sh, const 
         if (image_issue_band(im, k)) return 1;
         if (!(s.c = ctx_checkout(im->dev, im->w, im->h, im->pxsz, s.r0, s.r1))) return 1;
         leases.emplace_back(s.c);
-        if (ensure_buf(s.c->d_blobs, s.c->cap_blobs, k == 0 ? whole_bound : xpnghip_ctx_blob_bound(s.c, s.r0, s.r1))) return 1;
+        if (ctx_buf(s.c, s.c->d_blobs, s.c->cap_blobs, k == 0 ? whole_bound : xpnghip_ctx_blob_bound(s.c, s.r0, s.r1))) return 1;
         // (kernels address rows absolutely and touch only the rows of their tiles: the staged raster is handed over whole)
         if (xpnghip_encode_device(s.c, mode, im->cur, s.r0, s.r1, s.c->d_blobs, nullptr, im->bs[k])) return 1;
         tr.mark("encode launched, band", (int)k);
@@ -951,7 +959,7 @@ static int image_encode_impl(xpnghip_image *im, uint64_t T, int mode, uint8_t **
     CtxLease lease(ctx_checkout(im->dev, im->w, im->h, im->pxsz));
     xpnghip_ctx *c = lease.c;
     if (!c) return 1;
-    if (ensure_buf(c->d_blobs, c->cap_blobs, xpnghip_ctx_blob_bound(c, 0, N))) return 1;
+    if (ctx_buf(c, c->d_blobs, c->cap_blobs, xpnghip_ctx_blob_bound(c, 0, N))) return 1;
     uint64_t len = 0;
     // on the image's stream: ordered behind the upload and the normalisation without a device-wide synchronisation
     if (xpnghip_encode_device(c, mode, im->cur, 0, N, c->d_blobs, &len, im->stream)) { (void)hipStreamSynchronize(im->stream); return 1; }

@@ -44,6 +44,13 @@ static int fail(const std::string &m) { g_err = m; return 1; }
         if (e_ != hipSuccess) return fail(std::string(#call) + ": " + hipGetErrorString(e_));          \
     } while (0)
 
+// One table of the context's workspace (WsTable, common.hpp): allocated, recorded and counted, or left alone when it exists.  The
+// text of a failure is the one HIPCHK gave around the runtime's own allocation call with these arguments.
+#define WS_GET(ptr, bytes)                                                                                                        \
+    do {                                                                                                                         \
+        if (hipError_t e_ = c->ws.get((void **)&(ptr), (bytes))) return fail(std::string("hipMalloc" "((void **)&" #ptr ", " #bytes "): ") + hipGetErrorString(e_)); \
+    } while (0)
+
 // extern "C" must not leak C++ exceptions (std::bad_alloc from a header that claims an absurd geometry)
 #define XPNG_GUARDED(expr)                                               \
     try { return (expr); }                                               \
@@ -122,7 +129,8 @@ struct xpnghip_ctx {
     uint64_t r0 = 0, r1 = 0;  // tile range this context has workspace for
     uint32_t spt = 0;  // streams per tile: 9 (+1 alpha)
     std::vector<TileDesc> tiles;  // the N tiles of ONE image (host copy); the device table has B * N entries
-    uint64_t plane_img = 0, plane_stride = 0, scratch_img = 0, ws_bytes = 0;
+    uint64_t plane_img = 0, plane_stride = 0, scratch_img = 0;
+    WsTable ws;  // every device allocation of the context, the decode workspace's and the host wrappers' included: ws.total is xpnghip_ctx_workspace_bytes
     TileDesc *d_tiles = nullptr;
     uint8_t *d_planes = nullptr, *d_scratch = nullptr;  // d_planes (4 or 5 symbol planes) and d_scratch (level-1 stream scratch = the decode's planes): allocated on first use
     uint32_t *d_sums = nullptr, *d_nlh = nullptr, *d_ctx_n = nullptr, *d_k_n = nullptr, *d_blk_sz = nullptr, *d_tile_sz = nullptr, *d_tile_hdr = nullptr;
@@ -152,6 +160,7 @@ struct xpnghip_ctx {
     uint32_t n_big = 0;  // tiles of the biggest size class (>= 3/4 of the largest pixel count)
     uint16_t *d_wF = nullptr;
     // mode 2 (RGB slow level): allocated on first use
+    bool m2_ready = false;                // ensure_m2 has allocated all of them and uploaded d_sbase2
     uint8_t *d_scratch2 = nullptr;
     uint64_t *d_sbase2 = nullptr;
     uint32_t *d_flags2 = nullptr, *d_stream_n2 = nullptr;
@@ -215,18 +224,32 @@ extern "C" void xpnghip_ctx_destroy(xpnghip_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    void *ptrs[] = {c->d_tiles, c->d_planes, c->d_scratch, c->d_sums, c->d_nlh, c->d_ctx_n, c->d_k_n, c->d_blk_sz, c->d_tile_sz,
-                    c->d_tile_hdr, c->d_off, c->d_totals, c->d_raster, c->d_blobs, c->d_blob_in, c->d_dbg, (void *)c->d_in_ptrs, (void *)c->d_out_ptrs, (void *)c->d_dec_in_ptrs, (void *)c->d_dec_out_ptrs, (void *)c->d_order,
-                    c->d_wprep, c->d_wtab, c->d_wF, c->d_blob_len, c->d_status, c->d_scratch2, c->d_sbase2, c->d_flags2, c->d_stream_n2, c->d_blk2, c->d_mt2, c->d_info2, c->d_tabs2, c->d_w1prep, c->d_w1tab, c->d_w1F, c->d_region_stage, c->d_region_meta, c->d_m_first, c->d_m_stage, c->d_m_out, c->d_m_in, c->d_m_rect};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
+    c->ws.free_all();
     if (c->enc_side) (void)hipStreamDestroy(c->enc_side);
-    if (c->ev_enc_fork) (void)hipEventDestroy(c->ev_enc_fork);
-    if (c->ev_enc_join) (void)hipEventDestroy(c->ev_enc_join);
+    for (hipEvent_t e : {c->ev_enc_fork, c->ev_enc_join}) if (e) (void)hipEventDestroy(e);
     decode_ws_free(c->dec);
     if (c->h_total) (void)hipHostFree(c->h_total);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
+}
+
+// The encode workspace, the one statement of its 14 tables and their sizes: `entries` entries of the device tile table (B * N of an
+// ordinary context, which allocates it when it is created; the M of a mixed one, which does with its first encode), `images` rasters
+// per launch.  A table that exists is left alone.  Returns the name of the table whose allocation failed, or nullptr.
+static const char *encode_tables(xpnghip_ctx *c, uint64_t entries, uint64_t images) {
+    for (uint64_t i = c->r0; i < c->r1; i++) c->nlh_slots = std::max({c->nlh_slots, nlh_records(c->tiles[i].w, c->tiles[i].h, false), nlh_records(c->tiles[i].w, c->tiles[i].h, true)});
+#define TABLE(ptr, bytes) {(void **)&c->ptr, (bytes), "c->" #ptr}
+    const struct { void **slot; uint64_t bytes; const char *name; } tables[] = {
+        TABLE(d_sums, entries * 16),
+        TABLE(d_nlh, entries * c->nlh_slots * NLH_STRIDE * 4 + 64),  // nl histogram + last coded pixel of every transform workgroup (m1_encode.hpp)
+        TABLE(d_ctx_n, entries * 9 * 4), TABLE(d_k_n, entries * 4), TABLE(d_blk_sz, entries * 10 * 4), TABLE(d_tile_sz, entries * 4),
+        TABLE(d_tile_hdr, entries * 4), TABLE(d_off, (entries + images) * 8), TABLE(d_totals, images * 8), TABLE(d_wprep, entries * 10 * sizeof(WPrep)),
+        TABLE(d_wtab, entries * WTAB_TILE_BYTES + 4096 + watab_bytes(entries)),  // per-tile tables, then the launch's interleaved alpha tables (rans2_wide.hpp)
+        TABLE(d_wF, entries * 10 * 512), TABLE(d_in_ptrs, images * 8), TABLE(d_out_ptrs, images * 8)};
+#undef TABLE
+    for (const auto &t : tables) if (c->ws.get(t.slot, t.bytes) != hipSuccess) return t.name;
+    return nullptr;
 }
 
 static int ctx_create_range_impl(xpnghip_ctx **out, int device, uint64_t w, uint64_t h, int pxsz, uint32_t batch, uint64_t r0, uint64_t r1);
@@ -256,38 +279,20 @@ static int ctx_create_range_impl(xpnghip_ctx **out, int device, uint64_t w, uint
         }
 #define ALLOC(ptr, bytes)                                                                          \
     do {                                                                                           \
-        if (hipMalloc((void **)&(ptr), (bytes)) != hipSuccess) {                                   \
-            xpnghip_ctx_destroy(c);                                                                \
-            return fail("hipMalloc failed for " #ptr);                                             \
-        }                                                                                          \
-        c->ws_bytes += (bytes);                                                                    \
+        if (c->ws.get((void **)&(ptr), (bytes)) != hipSuccess) { xpnghip_ctx_destroy(c); return fail("hipMalloc failed for " #ptr); } \
     } while (0)
     ALLOC(c->d_tiles, VN * sizeof(TileDesc));
     // (the stream scratch - 7.5 B/px for a level-1 encode, 8 B/px as the decode's symbol / residual planes: one buffer of the larger
     //  size - and the symbol planes, 4 or 5 B/px, are allocated by the first call that needs them: ensure_scratch, ensure_planes)
-    ALLOC(c->d_sums, VN * 16);
-    for (uint64_t i = c->r0; i < c->r1; i++) {
-        const TileDesc &t = c->tiles[i];
-        c->nlh_slots = std::max(c->nlh_slots, std::max(nlh_records(t.w, t.h, false), nlh_records(t.w, t.h, true)));
+    if (const char *name = encode_tables(c, VN, batch)) {
+        xpnghip_ctx_destroy(c);
+        return fail(std::string("hipMalloc failed for ") + name);
     }
-    ALLOC(c->d_nlh, VN * c->nlh_slots * NLH_STRIDE * 4 + 64);  // nl histogram + last coded pixel of every transform workgroup (m1_encode.hpp)
-    ALLOC(c->d_ctx_n, VN * 9 * 4);
-    ALLOC(c->d_k_n, VN * 4);
-    ALLOC(c->d_blk_sz, VN * 10 * 4);
-    ALLOC(c->d_tile_sz, VN * 4);
-    ALLOC(c->d_tile_hdr, VN * 4);
-    ALLOC(c->d_off, (VN + batch) * 8);
-    ALLOC(c->d_totals, (uint64_t)batch * 8);
 #ifdef XPNG_PROBES
     ALLOC(c->d_dbg, VN * 10 * 8 * 8 * 2);  // phase stamps of the chain kernels (XPNG_STAMPS)
 #endif
-    ALLOC(c->d_wprep, VN * 10 * sizeof(WPrep));
-    ALLOC(c->d_wtab, VN * WTAB_TILE_BYTES + 4096 + watab_bytes(VN));  // per-tile tables, then the launch's interleaved alpha tables (rans2_wide.hpp)
-    ALLOC(c->d_wF, VN * 10 * 512);
     ALLOC(c->d_blob_len, (uint64_t)batch * 8);
     ALLOC(c->d_status, 64);
-    ALLOC(c->d_in_ptrs, (uint64_t)batch * 8);
-    ALLOC(c->d_out_ptrs, (uint64_t)batch * 8);
     ALLOC(c->d_dec_in_ptrs, (uint64_t)batch * 8);
     ALLOC(c->d_dec_out_ptrs, (uint64_t)batch * 8);
     ALLOC(c->d_order, (c->r1 - c->r0) * 4);
@@ -338,7 +343,7 @@ extern "C" uint64_t xpnghip_ctx_blob_bound(const xpnghip_ctx *c, uint64_t t0, ui
     for (uint64_t i = t0; c && i < t1 && i < c->tiles.size(); i++) b += (uint64_t)c->tiles[i].n * c->pxsz + 4;
     return b + 16;
 }
-extern "C" uint64_t xpnghip_ctx_workspace_bytes(const xpnghip_ctx *c) { return c ? c->ws_bytes : 0; }
+extern "C" uint64_t xpnghip_ctx_workspace_bytes(const xpnghip_ctx *c) { return c ? c->ws.total : 0; }
 
 static int check_range(const xpnghip_ctx *c, uint64_t t0, uint64_t t1) {
     if (!c) return fail("null context");
@@ -387,14 +392,11 @@ static int ensure_scratch(xpnghip_ctx *c, hipStream_t s = nullptr) {
         // The context is a single-queue object: its earlier work is on the call's stream, its own stream or its side stream.
         // (hipFree itself may still wait for the device: xpng_hip.h says so.)
         for (hipStream_t q : {s, c->stream, c->enc_side}) if (q) HIPCHK(hipStreamSynchronize(q));
-        HIPCHK(hipFree(c->d_scratch));
-        c->ws_bytes -= c->cap_scratch;
-        c->d_scratch = nullptr; c->cap_scratch = 0;
+        c->ws.drop((void **)&c->d_scratch); c->cap_scratch = 0;
         c->dec.arena = nullptr; c->dec.arena_bytes = 0; c->dec.cap_plane = 0;
     }
-    HIPCHK(hipMalloc((void **)&c->d_scratch, bytes));
+    WS_GET(c->d_scratch, bytes);
     c->cap_scratch = bytes;
-    c->ws_bytes += bytes;
     return 0;
 }
 static int ensure_arena(xpnghip_ctx *c) {
@@ -405,10 +407,8 @@ static int ensure_arena(xpnghip_ctx *c) {
 }
 // the symbol planes (nl, r, g, b, + alpha symbols for RGBA): allocated on first use
 static int ensure_planes(xpnghip_ctx *c) {
-    if (c->d_planes) return 0;
     const uint64_t np = c->pxsz == 4 ? 5 : 4;  // nl, r, g, b (+ alpha symbols)
-    HIPCHK(hipMalloc((void **)&c->d_planes, np * c->plane_stride + 8192));
-    c->ws_bytes += np * c->plane_stride + 8192;
+    WS_GET(c->d_planes, np * c->plane_stride + 8192);
     return 0;
 }
 
@@ -554,19 +554,20 @@ static int launch_encode_m1(xpnghip_ctx *c, const EncSpan &e, hipStream_t s) {
 }
 
 static int ensure_m2(xpnghip_ctx *c) {
-    if (c->d_scratch2) return 0;
+    if (c->m2_ready) return 0;  // (every table and the upload: a call after a failed attempt completes the group)
     const uint64_t N = c->tiles.size(), VN = c->mixed ? N : N * c->B;  // (a mixed context's table already holds every image)
     std::vector<uint64_t> sb(VN);
     uint64_t o = 0;
     for (uint64_t v = 0; v < VN; v++) { sb[v] = o; if (v % N >= c->r0 && v % N < c->r1) o += m2_tile_scratch(c->tiles[v % N].n); }
     // (d_flags2 and d_mt2 are the encode's: a mixed context allocates them with its first level-2 encode, launch_encode_m2)
-    if (hipMalloc((void **)&c->d_scratch2, o + 8192) != hipSuccess || hipMalloc((void **)&c->d_sbase2, VN * 8) != hipSuccess ||
-        (!c->mixed && hipMalloc((void **)&c->d_flags2, VN * 4) != hipSuccess) || hipMalloc((void **)&c->d_stream_n2, VN * M2_SLOTS * 4) != hipSuccess ||
-        hipMalloc((void **)&c->d_blk2, VN * M2_SLOTS * sizeof(M2Blk)) != hipSuccess || (!c->mixed && hipMalloc((void **)&c->d_mt2, VN * sizeof(M2Tile)) != hipSuccess) ||
-        hipMalloc((void **)&c->d_info2, VN * sizeof(M2DecTile)) != hipSuccess || hipMalloc((void **)&c->d_tabs2, VN * M2_SLOTS * 512) != hipSuccess)
+    auto get = [&](void **p, uint64_t bytes) { return c->ws.get(p, bytes) == hipSuccess; };
+    if (!get((void **)&c->d_scratch2, o + 8192) || !get((void **)&c->d_sbase2, VN * 8) || (!c->mixed && !get((void **)&c->d_flags2, VN * 4)) ||
+        !get((void **)&c->d_stream_n2, VN * M2_SLOTS * 4) || !get((void **)&c->d_blk2, VN * M2_SLOTS * sizeof(M2Blk)) ||
+        (!c->mixed && !get((void **)&c->d_mt2, VN * sizeof(M2Tile))) || !get((void **)&c->d_info2, VN * sizeof(M2DecTile)) ||
+        !get((void **)&c->d_tabs2, VN * M2_SLOTS * 512))
         return fail("hipMalloc failed (mode-2 workspace)");
-    c->ws_bytes += o + 8192;
     HIPCHK(hipMemcpy(c->d_sbase2, sb.data(), VN * 8, hipMemcpyHostToDevice));
+    c->m2_ready = true;
     return 0;
 }
 
@@ -576,14 +577,8 @@ static int launch_encode_m2(xpnghip_ctx *c, const EncSpan &e, hipStream_t s) {
     const uint32_t t0 = e.t0, t1 = e.t0 + e.cnt, cnt = e.cnt, nimg = e.nimg, total = nimg * cnt;
     const TileSel sel{t0, cnt, e.N, nimg, nullptr};
     const uint64_t bpr = e.bpr, VN = e.VN;
-    if (c->mixed && !c->d_flags2) {
-        if (hipMalloc((void **)&c->d_flags2, VN * 4) != hipSuccess) return fail("hipMalloc failed (mode-2 encode workspace)");
-        c->ws_bytes += VN * 4;
-    }
-    if (c->mixed && !c->d_mt2) {
-        if (hipMalloc((void **)&c->d_mt2, VN * sizeof(M2Tile)) != hipSuccess) return fail("hipMalloc failed (mode-2 encode workspace)");
-        c->ws_bytes += VN * sizeof(M2Tile);
-    }
+    if (c->mixed && (c->ws.get((void **)&c->d_flags2, VN * 4) != hipSuccess || c->ws.get((void **)&c->d_mt2, VN * sizeof(M2Tile)) != hipSuccess))
+        return fail("hipMalloc failed (mode-2 encode workspace)");
     uint32_t max_n = 0;
     for (uint32_t i = t0; i < t1; i++) max_n = c->tiles[i].n > max_n ? c->tiles[i].n : max_n;
     XPNG_REQUIRE(c->d_scratch2, c->d_sbase2, c->d_flags2, c->d_stream_n2, c->d_blk2, c->d_mt2, c->d_in_ptrs, c->d_out_ptrs, c->d_tiles, c->d_sums, c->d_tile_sz, c->d_off,
@@ -602,12 +597,10 @@ static int launch_encode_m2(xpnghip_ctx *c, const EncSpan &e, hipStream_t s) {
     if (!wide_form((uint64_t)total * M2_STREAMS)) {
         k_rans1_encode<<<total * M2_SLOTS, 64, 0, s>>>(c->d_tiles, sel, c->d_flags2, c->d_scratch2, c->d_sbase2, c->d_stream_n2, c->d_blk2);
     } else {  // every lane a chain: prep -> chains (small and big alphabets) -> finish
-        if (!c->d_w1prep) {
-            if (hipMalloc((void **)&c->d_w1prep, VN * M2_SLOTS * sizeof(W1Prep)) != hipSuccess ||
-                hipMalloc((void **)&c->d_w1tab, VN * M2_SLOTS * W1_TAB_BYTES) != hipSuccess ||
-                hipMalloc((void **)&c->d_w1F, VN * M2_SLOTS * 512) != hipSuccess)
-                return fail("hipMalloc failed (mode-2 wide encode workspace)");
-        }
+        if (c->ws.get((void **)&c->d_w1prep, VN * M2_SLOTS * sizeof(W1Prep)) != hipSuccess ||
+            c->ws.get((void **)&c->d_w1tab, VN * M2_SLOTS * W1_TAB_BYTES) != hipSuccess ||
+            c->ws.get((void **)&c->d_w1F, VN * M2_SLOTS * 512) != hipSuccess)
+            return fail("hipMalloc failed (mode-2 wide encode workspace)");
         XPNG_REQUIRE(c->d_w1prep, c->d_w1tab, c->d_w1F);
         k_rans1_prep<<<total * M2_SLOTS, 64, 0, s>>>(c->d_tiles, sel, c->d_flags2, c->d_scratch2, c->d_sbase2, c->d_stream_n2, c->d_blk2, c->d_w1prep, c->d_w1tab, c->d_w1F);
         k_rans1_chain<true><<<((total + 15) / 16) * W1_BIG_SLOTS, 64, rans1_chain_lds_bytes<true>(), s>>>(c->d_tiles, sel, total, c->d_scratch2, c->d_sbase2, c->d_stream_n2, c->d_w1prep, c->d_w1tab);
@@ -699,8 +692,8 @@ static int dec_launch(xpnghip_ctx *c, int mode, uint32_t nimg, uint64_t W, const
     j.tile_off = tile_off;
     j.s = s;
     j.stamps = c->stamps && !list ? c->d_dbg + N * c->B * 80 : nullptr;
-    if (mode == 2) return decode_m2_launch(c->dec, j, M2DecBufs{c->d_info2, c->d_blk2, c->d_tabs2, c->d_scratch2, c->d_sbase2, c->d_stream_n2}, g_err);
-    return decode_m1_launch(c->dec, j, g_err);
+    if (mode == 2) return decode_m2_launch(c->dec, c->ws, j, M2DecBufs{c->d_info2, c->d_blk2, c->d_tabs2, c->d_scratch2, c->d_sbase2, c->d_stream_n2}, g_err);
+    return decode_m1_launch(c->dec, c->ws, j, g_err);
 }
 
 extern "C" int xpnghip_decode_device_batch(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
@@ -777,20 +770,16 @@ static int region_batch_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
         if (c->d_region_stage) {
             HIPCHK(hipSetDevice(c->device));
             HIPCHK(hipDeviceSynchronize());  // (an earlier call's kernels may still use the old buffer)
-            HIPCHK(hipFree(c->d_region_stage));
-            c->ws_bytes -= c->cap_region_stage;
-            c->d_region_stage = nullptr; c->cap_region_stage = 0;
+            c->ws.drop((void **)&c->d_region_stage); c->cap_region_stage = 0;
         }
         HIPCHK(hipSetDevice(c->device));
-        HIPCHK(hipMalloc((void **)&c->d_region_stage, slot * nimg));
+        WS_GET(c->d_region_stage, slot * nimg);
         c->cap_region_stage = slot * nimg;
-        c->ws_bytes += slot * nimg;
     }
     if (!c->d_region_meta) {
         HIPCHK(hipSetDevice(c->device));
         const uint64_t bytes = rup((uint64_t)c->B * N * 4, 16) + (uint64_t)c->B * sizeof(RegionCopy);
-        HIPCHK(hipMalloc((void **)&c->d_region_meta, bytes));
-        c->ws_bytes += bytes;
+        WS_GET(c->d_region_meta, bytes);
     }
     std::vector<void *> vbase(nimg);
     std::vector<RegionCopy> rc(nimg);
@@ -871,11 +860,7 @@ static int ctx_create_mixed_impl(xpnghip_ctx **out, int device, const uint64_t *
     std::vector<uint8_t> meta(first_bytes + M * 4, 0);
     memcpy(meta.data(), c->m_first.data(), ((size_t)nimg + 1) * 4);
     memcpy(meta.data() + first_bytes, c->m_list.data(), M * 4);
-    auto alloc = [&](void **p, uint64_t bytes) {
-        if (hipMalloc(p, bytes) != hipSuccess) return false;
-        c->ws_bytes += bytes;
-        return true;
-    };
+    auto alloc = [&](void **p, uint64_t bytes) { return c->ws.get(p, bytes) == hipSuccess; };
     // what a decode needs, sized from M and nimg; planes / arena, decode tables and level-2 tables follow on first use (ensure_arena,
     // decode_ws_prepare, ensure_m2), sized from M and the summed plane lengths too.  The encode workspace: ensure_mixed_encode.
     if (!alloc((void **)&c->d_tiles, M * sizeof(TileDesc)) || !alloc((void **)&c->d_blob_len, (uint64_t)nimg * 8) || !alloc((void **)&c->d_status, 64) ||
@@ -914,10 +899,7 @@ static std::string layout_hex(uint32_t layout) {
 static int mixed_records(xpnghip_ctx *c, MixedLayout *&table, std::vector<const void *> &cache, const std::vector<uint64_t> &slot,
                          const void *const *bufs, hipStream_t s) {
     const uint32_t nimg = c->B;
-    if (!table) {
-        HIPCHK(hipMalloc((void **)&table, (uint64_t)nimg * sizeof(MixedLayout)));
-        c->ws_bytes += (uint64_t)nimg * sizeof(MixedLayout);
-    }
+    WS_GET(table, (uint64_t)nimg * sizeof(MixedLayout));
     if (cache.size() == nimg && std::equal(cache.begin(), cache.end(), bufs)) return 0;
     std::vector<MixedLayout> ml(nimg);
     for (uint32_t i = 0; i < nimg; i++)
@@ -1175,10 +1157,7 @@ static void launch_stage_from(const ImgRec *rec, const uint8_t *const *srcs, dim
 // stream earlier, never this call's work.
 static int resize_records(xpnghip_ctx *c, const std::vector<ResizeRec> &recs, hipStream_t s) {
     const uint64_t bytes = (uint64_t)c->B * sizeof(ResizeRec);
-    if (!c->d_m_rect) {
-        HIPCHK(hipMalloc((void **)&c->d_m_rect, bytes));
-        c->ws_bytes += bytes;
-    }
+    WS_GET(c->d_m_rect, bytes);
     HIPCHK(hipMemcpyAsync(c->d_m_rect, recs.data(), bytes, hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
     return 0;
@@ -1194,8 +1173,8 @@ static int mixed_stage_slots(xpnghip_ctx *c, uint64_t bpr, std::vector<uint64_t>
     const uint64_t need = slot[nimg] + 256;
     if (c->cap_m_stage >= need) return 0;
     if (c->d_m_stage) return fail("internal error: the staging raster of a mixed context was allocated for another layout");  // (bpr is a function of the context: this cannot happen)
-    HIPCHK(hipMalloc((void **)&c->d_m_stage, need));
-    c->cap_m_stage = need; c->ws_bytes += need;
+    WS_GET(c->d_m_stage, need);
+    c->cap_m_stage = need;
     return 0;
 }
 
@@ -1317,20 +1296,7 @@ extern "C" int xpnghip_decode_varsize_device_batch_resized(xpnghip_ctx *c, int m
 // launch sequences (ensure_planes, ensure_scratch, ensure_m2 / launch_encode_m2).
 static int ensure_mixed_encode(xpnghip_ctx *c) {
     if (c->m_enc) return 0;
-    const uint64_t M = c->tiles.size(), nimg = c->B;
-    for (const TileDesc &t : c->tiles) c->nlh_slots = std::max(c->nlh_slots, std::max(nlh_records(t.w, t.h, false), nlh_records(t.w, t.h, true)));
-    auto alloc = [&](void **p, uint64_t bytes) {
-        if (*p) return true;  // (an earlier attempt got this far)
-        if (hipMalloc(p, bytes) != hipSuccess) return false;
-        c->ws_bytes += bytes;
-        return true;
-    };
-    if (!alloc((void **)&c->d_sums, M * 16) || !alloc((void **)&c->d_nlh, M * c->nlh_slots * NLH_STRIDE * 4 + 64) || !alloc((void **)&c->d_ctx_n, M * 9 * 4) ||
-        !alloc((void **)&c->d_k_n, M * 4) || !alloc((void **)&c->d_blk_sz, M * 10 * 4) || !alloc((void **)&c->d_tile_sz, M * 4) ||
-        !alloc((void **)&c->d_tile_hdr, M * 4) || !alloc((void **)&c->d_off, (M + nimg) * 8) || !alloc((void **)&c->d_totals, nimg * 8) ||
-        !alloc((void **)&c->d_wprep, M * 10 * sizeof(WPrep)) || !alloc((void **)&c->d_wtab, M * WTAB_TILE_BYTES + 4096 + watab_bytes(M)) ||
-        !alloc((void **)&c->d_wF, M * 10 * 512) || !alloc((void **)&c->d_in_ptrs, nimg * 8) || !alloc((void **)&c->d_out_ptrs, nimg * 8))
-        return fail("hipMalloc failed (encode workspace of a mixed context)");
+    if (encode_tables(c, c->tiles.size(), c->B)) return fail("hipMalloc failed (encode workspace of a mixed context)");
     c->m_enc = true;  // (from here on scratch_bytes() includes the encode's share)
     return 0;
 }
