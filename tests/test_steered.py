@@ -203,14 +203,15 @@ def test_census_reaches_every_branch_the_encoder_can_write(survey):
 
 
 # ================================================================================================ GPU: bit-exact against the oracle
-# Which kernel form a geometry selects (xpng_hip.hip launch_transform; m1_decode.hpp decode_m1_plan / recon_geometry; m2_decode.hpp
-# decode_m2_launch):
+# Which kernel form a geometry selects (xpng_hip.hip launch_transform; recon.hpp recon_geometry, for m1_decode.hpp decode_m1_plan and
+# m2_decode.hpp decode_m2_launch alike):
 #   transform       tiles up to TR_MAXW = 672 px wide: the LDS-staged k_m1_transform_rgba / _rgb (m1_pixel_interior, byte-parallel);
 #                   wider (30000 x 4, 2500 x 70): k_m1_transform_generic (m1_pixel, scalar).
-#   reconstruction  narrow entropy path, or wide with a tile beyond RB_MAXW = 2048 px: k_dec_recon / k_m2_dec_recon, which run
+#   reconstruction  narrow entropy path, or wide with a tile beyond RB_MAXW = 2048 px: k_dec_recon<PXSZ, DecTile / M2DecTile>, which runs
 #                   recon_free when the tile is at most 1024 rows and its rows fit the LDS (900 x 460, 64 x 64, 2500 x 70) and
 #                   recon_wavefront otherwise (30000 x 4: rows too long; 7 x 9000: nine bands of 1024 rows with seams);
-#                   wide entropy path (XPNG_WIDE_RANS=1 or more than 2048 chains) and tiles up to 2048 px: recon_band_core.
+#                   wide entropy path (XPNG_WIDE_RANS=1 or more than 2048 chains) and tiles up to 2048 px: k_dec_recon_band<PXSZ,
+#                   DecTile / M2DecTile> (recon_band_core).
 _ORACLE = {}
 
 
@@ -350,7 +351,7 @@ def test_level2_gray_modes(gpu, po, monkeypatch, kind, force_wide):
 @pytest.mark.parametrize("force_wide", [False, True])
 def test_gray_left_and_gradient_beside_colour_tiles(gpu, po, monkeypatch, force_wide):
     """Gray "left" and gray "gradient" tiles beside a colour tile (predictor 3) and a single-colour tile in one raster: the four
-    tiles of one launch take four different branches of k_m2_dec_recon / k_m2_dec_recon_band."""
+    tiles of one launch take four different paths (recon_head, recon_fill) of k_dec_recon / k_dec_recon_band<3, M2DecTile>."""
     if force_wide:
         monkeypatch.setenv("XPNG_WIDE_RANS", "1")
     name = "mixed_gray_1000x900"
@@ -412,7 +413,7 @@ def test_level1_batch_of_all_predictors_selects_the_wide_kernels(gpu, po, fmt):
 @pytest.mark.gpu
 def test_level2_batch_with_every_gray_mode_selects_the_wide_kernels(gpu, po):
     """The same at level 2: the four predictors and the eight gray rasters, resized to the batch geometry, in one launch (the wide
-    rANS v1 kernels; k_m2_gray_syms / k_m2_select and k_m2_dec_recon_band on tiles of every kind side by side)."""
+    rANS v1 kernels; k_m2_gray_syms / k_m2_select and k_dec_recon_band<3, M2DecTile> on tiles of every kind side by side)."""
     rasters = [S.raster(f"pr{p}_rgb_900x460") for p in range(4)] + [S.gray(k, 900, 460) for k in S.GRAY]
     seen = set()
     for r in rasters:

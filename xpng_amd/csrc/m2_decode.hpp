@@ -9,10 +9,12 @@
 //                    cache / LDS tables / scalar word cursor as the v2 decoder
 //   ctx_walk_salu    the nl context chain (shared with mode 1)
 //   k_m2_dec_resid   class-stream routing back to pixels (rank by nl: packed prefix sums, four pixels per lane), zig-zag / green add-back
-//   k_m2_dec_recon   fill / raw copy / anti-diagonal wavefront (shared with mode 1); gray tiles use predictor m
+//   k_dec_recon      fill / raw copy / anti-diagonal wavefront or 64-row bands (recon.hpp, shared with mode 1; recon_head below reads
+//                    the tile record); gray tiles use predictor m
 #pragma once
 #include "common.hpp"
-#include "m1_decode.hpp"
+#include "m1_decode.hpp"  // ld32u, DecodeWs, ctx_walk_salu
+#include "recon.hpp"
 #include "m2_encode.hpp"
 
 namespace xpng {
@@ -36,6 +38,29 @@ __device__ __forceinline__ uint32_t bits_at(const uint8_t *w, uint64_t pos, uint
 }
 
 constexpr uint32_t M2_KIND_BAD = 9;  // tile failed validation: every kernel skips it (see k_dec_parse in m1_decode.hpp)
+
+// what the reconstruction (recon.hpp) takes from a tile's record
+template <int PXSZ>
+__device__ __forceinline__ ReconHead recon_head(const M2DecTile *d) {
+    ReconHead h{};
+    const uint32_t kind = d->kind;
+    h.fill = RF_SKIP;
+    if (kind == M2_KIND_BAD) return h;
+    h.fill = kind == 0 ? RF_ROWS : kind == 3 ? RF_GRAY : RF_COLOUR;  // raw rows (libxpng.c:941), raw gray (875-878), single colour (916-927)
+    h.src = d->blob + 4;
+    if (kind == 0 || kind == 3 || kind == 4) return h;
+    h.fill = RF_CODED;
+    const uint32_t w0 = ld32u(d->blob + 8);  // head of b: first pixel, MSB first
+    if (kind == 2) {
+        const uint32_t g = w0 >> 24;
+        h.first = g | (g << 8) | (g << 16);
+        h.predmode = d->m == 0 ? 2 : d->m == 1 ? 3 : d->m == 2 ? 0 : 1;  // p1x, p1y, p2a, p3a (libxpng.c:890-895)
+    } else {
+        h.first = ((w0 >> 24) & 255u) | (((w0 >> 16) & 255u) << 8) | (((w0 >> 8) & 255u) << 16);
+        h.predmode = (int)((d->m >> 1) & 1);
+    }
+    return h;
+}
 
 __global__ void k_m2_dec_parse(const uint8_t *const *__restrict__ blobs, const uint64_t *__restrict__ off,
                                const uint64_t *__restrict__ blob_len, uint32_t cnt, uint32_t total,
@@ -414,87 +439,6 @@ __global__ __launch_bounds__(THREADS) void k_m2_dec_resid(const M2DecTile *__res
     }
 }
 
-// --------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void k_m2_dec_recon(const M2DecTile *__restrict__ info, const TileDesc *__restrict__ tiles, TileSel sel,
-                                                       const uint32_t *__restrict__ resid, uint8_t *const *__restrict__ rasters,
-                                                       uint64_t bpr, uint32_t free_ew) {
-    const uint32_t j = blockIdx.x, tid = threadIdx.x;
-    const M2DecTile d = info[j];
-    const TileDesc t = tiles[vtile(sel, j)];
-    uint8_t *dst = rasters[t.img] + (uint64_t)t.y * bpr + (uint64_t)t.x * 3;
-    const uint64_t row = (uint64_t)t.w * 3;
-    if (d.kind == M2_KIND_BAD) return;
-    if (d.kind == 0) {  // raw rows (libxpng.c:941)
-        const uint8_t *src = d.blob + 4;
-        for (uint64_t b = tid; b < row * t.h; b += blockDim.x) { const uint64_t y = b / row, o = b - y * row; dst[y * bpr + o] = src[b]; }
-        return;
-    }
-    if (d.kind == 4) {  // single colour (libxpng.c:916-927)
-        const uint8_t *px = d.blob + 4;
-        for (uint64_t b = tid; b < row * t.h; b += blockDim.x) { const uint64_t y = b / row, o = b - y * row; dst[y * bpr + o] = px[o % 3]; }
-        return;
-    }
-    if (d.kind == 3) {  // raw gray (libxpng.c:875-878)
-        const uint8_t *src = d.blob + 4;
-        for (uint64_t b = tid; b < row * t.h; b += blockDim.x) { const uint64_t y = b / row, o = b - y * row; dst[y * bpr + o] = src[y * t.w + o / 3]; }
-        return;
-    }
-    const uint32_t w0 = ld32u(d.blob + 8);  // head of b: first pixel, MSB first
-    uint32_t first;
-    int predmode;
-    if (d.kind == 2) {
-        const uint32_t g = w0 >> 24;
-        first = g | (g << 8) | (g << 16);
-        predmode = d.m == 0 ? 2 : d.m == 1 ? 3 : d.m == 2 ? 0 : 1;  // p1x, p1y, p2a, p3a (libxpng.c:890-895)
-    } else {
-        first = ((w0 >> 24) & 255u) | (((w0 >> 16) & 255u) << 8) | (((w0 >> 8) & 255u) << 16);
-        predmode = (d.m >> 1) & 1;
-    }
-    if (free_ew) {
-        extern __shared__ uint32_t dyn_lds[];
-        recon_free<3>(t, dst, bpr, nullptr, resid + t.pbase, first, predmode, dyn_lds + 16, free_ew, dyn_lds);
-    } else {
-        __shared__ uint32_t s_row[2][1024];
-        recon_wavefront<3>(t, dst, bpr, nullptr, resid + t.pbase, first, predmode, s_row);
-    }
-}
-
-// The same for batches: ONE wavefront per tile sweeping 64-row bands (recon_band_core, m1_decode.hpp: lane = row, U by DPP, byte-
-// parallel predictors, 16-byte residual loads and 12-byte pixel stores), as mode 1 uses; the multi-wave form above hands rows
-// from wave to wave through LDS and progress counters, which is right for one image and 4x slower per tile in a batch.
-__global__ __launch_bounds__(64) void k_m2_dec_recon_band(const M2DecTile *__restrict__ info, const TileDesc *__restrict__ tiles, TileSel sel,
-                                                          const uint32_t *__restrict__ resid, uint8_t *const *__restrict__ rasters, uint64_t bpr) {
-    extern __shared__ uint32_t rb_lds[];  // staging rings, then the seam row (recon_band_core)
-    uint32_t *seam = rb_lds + RB_STAGE_WORDS;
-    const uint32_t j = blockIdx.x, lane = threadIdx.x & 63;
-    const M2DecTile *d = info + j;
-    const uint32_t kind = d->kind;
-    if (kind == M2_KIND_BAD) return;
-    const TileDesc t = tiles[vtile(sel, j)];
-    uint8_t *dst = rasters[t.img] + (uint64_t)t.y * bpr + (uint64_t)t.x * 3;
-    const uint64_t row = (uint64_t)t.w * 3;
-    if (kind == 0 || kind == 3 || kind == 4) {  // raw rows (libxpng.c:941), raw gray (875-878), single colour (916-927)
-        const uint8_t *src = d->blob + 4;
-        for (uint64_t b = lane; b < row * t.h; b += 64) {
-            const uint64_t y = b / row, o = b - y * row;
-            dst[y * bpr + o] = kind == 0 ? src[b] : kind == 3 ? src[y * t.w + o / 3] : src[o % 3];
-        }
-        return;
-    }
-    const uint32_t w0 = ld32u(d->blob + 8);  // head of b: first pixel, MSB first
-    uint32_t first;
-    int predmode;
-    if (kind == 2) {
-        const uint32_t g = w0 >> 24;
-        first = g | (g << 8) | (g << 16);
-        predmode = d->m == 0 ? 2 : d->m == 1 ? 3 : d->m == 2 ? 0 : 1;  // p1x, p1y, p2a, p3a (libxpng.c:890-895)
-    } else {
-        first = ((w0 >> 24) & 255u) | (((w0 >> 16) & 255u) << 8) | (((w0 >> 8) & 255u) << 16);
-        predmode = (int)((d->m >> 1) & 1);
-    }
-    recon_band_core<3>(t, dst, bpr, resid + t.pbase, first, predmode, rb_lds, seam, 0u);
-}
-
 // the level-2 buffers of a decode job (the context's; DecodeJob has the rest)
 struct M2DecBufs { M2DecTile *info2; M2Blk *blk2; uint16_t *tabs2; uint8_t *scratch2; const uint64_t *sbase2; uint32_t *stream_n2; };
 
@@ -522,10 +466,7 @@ inline int decode_m2_launch(DecodeWs &ws, WsTable &tab, const DecodeJob &j, cons
     k_m2_dec_walk<<<total, 64, 0, s>>>(m.info2, j.tiles, sel, m.scratch2, m.sbase2, m.stream_n2, ws.d_nlseq);
     if (small_blocks(items)) k_m2_dec_resid<256><<<total, 256, 0, s>>>(m.info2, j.tiles, sel, m.scratch2, m.sbase2, m.stream_n2, ws.d_nlseq, ws.d_resid);
     else k_m2_dec_resid<1024><<<total, 1024, 0, s>>>(m.info2, j.tiles, sel, m.scratch2, m.sbase2, m.stream_n2, ws.d_nlseq, ws.d_resid);
-    uint32_t free_ew, rthreads, rlds;
-    recon_geometry(j.max_w, j.max_h, free_ew, rthreads, rlds);
-    if (wide && j.max_w <= RB_MAXW && !probe_env("XPNG_WAVEFRONT_RECON")) k_m2_dec_recon_band<<<total, 64, RB_LDS_BYTES(j.max_w), s>>>(m.info2, j.tiles, sel, ws.d_resid, j.rasters, bpr);
-    else k_m2_dec_recon<<<total, rthreads, rlds, s>>>(m.info2, j.tiles, sel, ws.d_resid, j.rasters, bpr, free_ew);
+    recon_launch<3>(recon_geometry(j.max_w, j.max_h, wide), m.info2, j.tiles, sel, ws.d_resid, j.rasters, bpr, 0, total, s);
     if (hipGetLastError() != hipSuccess) { err = "mode-2 decode kernel launch failed"; return 1; }
     return 0;
 }
