@@ -3,7 +3,8 @@
 - parse_v2_block / gray_table: the frequency tables of v2 blocks (level 1) and of level-2 gray tiles, read as the reference
   decoder reads them (libxpng.c:429-493; MSB-first bit fields out of little-endian 32-bit words).
 - lookup_profile / gray_profile: which symbol-lookup route of the wide decode chains (xpng_amd/csrc/rans2_wide_dec.hpp,
-  rans1_wide_dec.hpp) a stream with a given table can take, by the rules of their prep kernels.
+  rans1_wide_dec.hpp; table layouts and wd_store_tables in rans_dec.hpp) a stream with a given table can take, by the rules of
+  their prep kernels.
 - recode_tiles: rewrite chosen v2 blocks of mode-1 tile blobs (crafted, decode-only files).
 - alpha_plane / symbol helpers: RGBA rasters whose alpha stream has a chosen symbol histogram.
 """

@@ -19,19 +19,11 @@
 #include <vector>
 
 #include "common.hpp"
+#include "rans_dec.hpp"  // DecTile, WDec, ld32u, the decode set-up
+#include "recon.hpp"
+#include "rans2_wide_dec.hpp"
 
 namespace xpng {
-
-struct DecTile {  // per-tile parse result (device)
-    const uint8_t *blob;  // the tile blob (inside its image's blob buffer)
-    uint32_t type;      // tile type byte (0 = raw rows)
-    uint32_t kbytes;    // bytes of k words
-    uint32_t blk_off[10];  // block offsets relative to the blob start
-    uint32_t blk_n[10];    // symbols per block
-    uint32_t ctx_start[10];  // 16-byte aligned start of context stream c inside the tile's symbol area (ctx_start[9] = total coded)
-};
-
-struct WDec;  // rans2_wide_dec.hpp
 
 // The decode workspace of one context.  It BORROWS the context's side stream and its stream scratch (`arena`: the five symbol /
 // residual planes, 8 B per pixel, are carved out of it - no decode kernel reads the encode's intermediates and no encode kernel runs
@@ -61,39 +53,6 @@ inline void decode_ws_free(DecodeWs &w) {
 }
 // an event of the workspace, created when a launch sequence first needs it
 inline bool decode_ws_event(hipEvent_t &e) { return e || hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess; }
-
-// unaligned-safe little-endian u32 load from global memory (tile blobs are only byte-aligned after a raw RGB tile)
-__device__ __forceinline__ uint32_t ld32u(const uint8_t *p) {
-    const uintptr_t a = (uintptr_t)p;
-    const uint32_t *q = reinterpret_cast<const uint32_t *>(a & ~(uintptr_t)3);
-    const uint32_t sh = (uint32_t)(a & 3) * 8;
-    const uint32_t lo = q[0];
-    if (sh == 0) return lo;
-    return (lo >> sh) | (q[1] << (32 - sh));
-}
-__device__ __forceinline__ uint64_t ld64u(const uint8_t *p) { return (uint64_t)ld32u(p) | ((uint64_t)ld32u(p + 4) << 32); }
-
-// MSB-first bit reader over u32 words (BITSTREAM_FILL / BITSTREAM_READ, libxpng.c:9,12); words past `end` read as 0
-struct BitR {
-    uint64_t acc;
-    uint32_t have;
-    const uint8_t *p, *end;
-    __device__ __forceinline__ uint32_t get(uint32_t c) {
-        if (have < 32) {
-            acc <<= 32; have += 32;
-            if (p < end) { acc += ld32u(p); p += 4; }
-        }
-        have -= c;
-        return (uint32_t)((acc >> have) & ((1ull << c) - 1));
-    }
-};
-
-// --------------------------------------------------------------------------------------------------
-constexpr uint32_t TILE_BAD = 0xEE;  // type value of a tile whose headers failed validation: every kernel skips it
-
-}  // namespace xpng
-#include "recon.hpp"  // (reads DecTile with ld32u, skips TILE_BAD)
-namespace xpng {
 
 // The reference decoder trusts the file ("no bounds checks on file contents"); on a GPU a wild
 // offset is a fault that can take the device down, so every length / offset / count is checked here, once, and a bad
@@ -154,10 +113,6 @@ __global__ void k_dec_parse(const uint8_t *const *__restrict__ blobs, const uint
     info[j] = d;
 }
 
-}  // namespace xpng
-#include "rans2_wide_dec.hpp"
-namespace xpng {
-
 // --------------------------------------------------------------------------------------------------
 // one v2 block -> symbols (decompress_block_v2, libxpng.c:429-493).  Single-wave workgroup per (tile, stream).
 //
@@ -201,20 +156,7 @@ __device__ __forceinline__ void rans2_decode_stream(const DecTile *__restrict__ 
     const uint8_t *end = in + csz;
     const uint32_t h1 = sgpr(ld32u(in + 4)), n = h1 & 0xFFFFFF, v2 = h1 >> 24;
     if (type <= 2 && only_over) return;
-    if (type == 1) {  // one distinct symbol
-        for (uint32_t i = lane; i < n; i += 64) out[i] = (uint8_t)v2;
-        return;
-    }
-    if (type == 2) {  // raw: v2 bits per symbol, MSB first
-        for (uint32_t i = lane; i < n; i += 64) {
-            const uint64_t b0 = (uint64_t)i * v2;
-            const uint8_t *wp = in + 8 + (b0 >> 5) * 4;
-            const uint32_t rel = (uint32_t)(b0 & 31);
-            const uint64_t two = ((uint64_t)ld32u(wp) << 32) | (wp + 4 < end ? ld32u(wp + 4) : 0u);
-            out[i] = (uint8_t)((two >> (64 - rel - v2)) & ((1u << v2) - 1));
-        }
-        return;
-    }
+    if (rans2_dec_plain(type, in, end, n, v2, out)) return;
     const uint32_t N = v2 + 2;
     const uint32_t h2 = sgpr(ld32u(in + 8));
     const int pb = (int)(h2 >> 24);
@@ -224,59 +166,22 @@ __device__ __forceinline__ void rans2_decode_stream(const DecTile *__restrict__ 
     XPNG_DSTAMP(0);
     const uint8_t *words = in + 12;
     const uint8_t *table = in + 8 + 4ull * (h2 & 0xFFFFFF);
-    if (lane == 0) {  // frequency table: <= 256 short fields, serial bit reader
-        BitR tr{0, 0, table, end};
-        for (uint32_t i = 0; i < N; i++) {
-            uint32_t F;
-            if (type == 3) F = tr.get((uint32_t)pb);
-            else F = tr.get(1) ? tr.get((uint32_t)pb) : 0;
-            Fs[i] = F;
-        }
-    }
+    rans2_dec_freqs(type, (uint32_t)pb, N, table, end, Fs);
     __syncthreads();
-    uint32_t hot0, hot1;  // (F << 8 | sym) of the two most probable symbols
-    {   // cum by 4-per-lane partial sums + wave scan; fc[i] = F | cum << 16
-        const uint32_t b = lane * 4;
-        const uint32_t f0 = b + 0 < N ? Fs[b + 0] : 0, f1 = b + 1 < N ? Fs[b + 1] : 0, f2 = b + 2 < N ? Fs[b + 2] : 0, f3 = b + 3 < N ? Fs[b + 3] : 0;
-        const uint32_t tot = f0 + f1 + f2 + f3;
-        uint32_t incl = tot;
-        incl = wave_scan_incl(incl);
-        const uint32_t c0 = incl - tot, c1 = c0 + f0, c2 = c1 + f1, c3 = c2 + f2;
-        if (b + 0 < N) fc[b + 0] = f0 | (c0 << 16);
-        if (b + 1 < N) fc[b + 1] = f1 | (c1 << 16);
-        if (b + 2 < N) fc[b + 2] = f2 | (c2 << 16);
-        if (b + 3 < N) fc[b + 3] = f3 | (c3 << 16);
-        auto wmax = [&](uint32_t v) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) { const uint32_t o = __shfl_xor(v, off); v = o > v ? o : v; }
-            return v;
-        };
-        const uint32_t k0 = (f0 << 8) | (b + 0), k1 = (f1 << 8) | (b + 1), k2 = (f2 << 8) | (b + 2), k3 = (f3 << 8) | (b + 3);
-        uint32_t m = k0 > k1 ? k0 : k1; m = k2 > m ? k2 : m; m = k3 > m ? k3 : m;
-        hot0 = wmax(m);
-        auto ex = [&](uint32_t k) { return k == hot0 ? 0u : k; };
-        uint32_t m2 = ex(k0) > ex(k1) ? ex(k0) : ex(k1); m2 = ex(k2) > m2 ? ex(k2) : m2; m2 = ex(k3) > m2 ? ex(k3) : m2;
-        hot1 = wmax(m2);
-    }
+    const uint2 hot = rans_dec_cum([&](uint32_t i) { return Fs[i]; }, N, fc);  // (F << 8 | sym) of the two most probable symbols
     __syncthreads();
-    if (COARSE) {   // coarse slot -> symbol: binary search over cum for every 8th slot (N <= 256 -> 8 probes)
+    if (COARSE) {   // coarse slot -> symbol: the owner of every 8th slot
         const uint32_t groups = 1u << (pb - 3);
         for (uint32_t g = lane; g < groups; g += 64) {
-            const uint32_t s = g << 3;
-            uint32_t lo = 0, hi = N - 1;  // largest index with cum <= s
-            while (lo < hi) {
-                const uint32_t mid = (lo + hi + 1) >> 1;
-                if ((fc[mid] >> 16) <= s) lo = mid; else hi = mid - 1;
-            }
-            while (lo > 0 && (fc[lo] & 0xFFFF) == 0) lo--;  // only reachable on corrupt tables
+            const uint32_t lo = rans_dec_owner(fc, N, g << 3);
             coarse[g] = make_uint2(fc[lo], lo);
         }
     }
     __syncthreads();
     XPNG_DSTAMP(1);
-    const uint32_t sym0 = hot0 & 255u, sym1 = hot1 & 255u;
+    const uint32_t sym0 = hot.x & 255u, sym1 = hot.y & 255u;
     const uint32_t e0 = fc[sym0], e1 = fc[sym1];
-    const uint32_t F0 = e0 & 0xFFFF, C0 = e0 >> 16, F1 = (hot1 >> 8) ? (e1 & 0xFFFF) : 0u, C1 = e1 >> 16;
+    const uint32_t F0 = e0 & 0xFFFF, C0 = e0 >> 16, F1 = e1 & 0xFFFF, C1 = e1 >> 16;
     const uint32_t mask = (1u << pb) - 1;
     const uint8_t *sp = table - 16;  // state0 at table-16, state1 at table-8
     const uint32_t nw = (uint32_t)((sp - words) >> 2);  // renormalisation words below the states
@@ -319,12 +224,7 @@ __device__ __forceinline__ void rans2_decode_stream(const DecTile *__restrict__ 
         } else {                                                                                                  \
             uint32_t e_;                                                                                          \
             if (COARSE) { const uint2 cg_ = coarse[slot_ >> 3]; sym = cg_.y; e_ = cg_.x; }                        \
-            else {  /* largest index with cum <= slot */                                                          \
-                uint32_t lo_ = 0, hi_ = N - 1;                                                                    \
-                while (lo_ < hi_) { const uint32_t mid_ = (lo_ + hi_ + 1) >> 1; if ((fc[mid_] >> 16) <= slot_) lo_ = mid_; else hi_ = mid_ - 1; } \
-                while (lo_ > 0 && (fc[lo_] & 0xFFFF) == 0) lo_--;                                                 \
-                sym = lo_; e_ = fc[lo_];                                                                          \
-            }                                                                                                     \
+            else { sym = rans_dec_owner(fc, N, slot_); e_ = fc[sym]; }                                            \
             while (slot_ - (e_ >> 16) >= (e_ & 0xFFFF) && sym + 1 < N) e_ = fc[++sym];  /* to the symbol whose [cum, cum+F) holds the slot */ \
             F_ = e_ & 0xFFFF; off_ = slot_ - (e_ >> 16);                                                          \
         }                                                                                                         \

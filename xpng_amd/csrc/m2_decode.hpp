@@ -13,7 +13,8 @@
 //                    the tile record); gray tiles use predictor m
 #pragma once
 #include "common.hpp"
-#include "m1_decode.hpp"  // ld32u, DecodeWs, ctx_walk_salu
+#include "m1_decode.hpp"  // DecodeWs, ctx_walk_salu
+#include "rans_dec.hpp"   // ld32u, bits_at, the decode set-up
 #include "recon.hpp"
 #include "m2_encode.hpp"
 
@@ -28,14 +29,6 @@ struct M2DecTile {
 };
 // M2Blk is reused per (tile, slot): type, n, cnt = byte offset of the block inside the blob, pbits = bit offset of its raw
 // symbols in b (type 2) or its single symbol (type 1).
-
-// random-access MSB-first bit read from the words at `w` (bits past `endbit` read as 0, like BITSTREAM_FILL past DP)
-__device__ __forceinline__ uint32_t bits_at(const uint8_t *w, uint64_t pos, uint32_t c, uint64_t endbit) {
-    const uint64_t wi = pos >> 5;
-    const uint32_t a = wi * 32 < endbit ? ld32u(w + wi * 4) : 0u, b = (wi + 1) * 32 < endbit ? ld32u(w + wi * 4 + 4) : 0u;
-    const uint64_t two = ((uint64_t)a << 32) | b;
-    return (uint32_t)((two >> (64 - (pos & 31) - c)) & ((1ull << c) - 1));
-}
 
 constexpr uint32_t M2_KIND_BAD = 9;  // tile failed validation: every kernel skips it (see k_dec_parse in m1_decode.hpp)
 
@@ -161,17 +154,7 @@ __global__ __launch_bounds__(64) void k_rans1_decode(const M2DecTile *__restrict
     const uint32_t Nnom = m2_nominal(slot);
     const int pb = slot >= 17 ? 15 : 14;
     if (type == 0 || n == 0) return;
-    if (type == 1) {
-        for (uint32_t i = lane; i < n; i += 64) out[i] = (uint8_t)mb.pbits;
-        return;
-    }
-    if (type == 2) {  // raw symbols from b (libxpng.c:273)
-        const uint32_t rb = (uint32_t)bit_width(Nnom - 1);
-        const uint8_t *bw = d.blob + 8;
-        const uint64_t endbit = (uint64_t)(d.bsz - 4) * 8;
-        for (uint32_t i = lane; i < n; i += 64) out[i] = (uint8_t)bits_at(bw, (uint64_t)mb.pbits + (uint64_t)i * rb, rb, endbit);
-        return;
-    }
+    if (rans1_dec_plain(type, mb.pbits, (uint32_t)bit_width(Nnom - 1), d.blob + 8, (uint64_t)(d.bsz - 4) * 8, n, out)) return;
     if (type != 3 && type != 4) return;
     const uint8_t *blkp = d.blob + mb.cnt;
     const uint32_t size = sgpr(ld32u(blkp)) & 0xFFFFFF;
@@ -179,48 +162,19 @@ __global__ __launch_bounds__(64) void k_rans1_decode(const M2DecTile *__restrict
     const uint8_t *words = blkp + 24;
     const uint32_t nw = (size - 24) >> 2;
     const uint16_t *F16 = tabs + ((uint64_t)tile * M2_SLOTS + slot) * 256;
-    uint32_t hot0, hot1;
-    {   // cum by 4-per-lane partial sums + wave scan; fc[i] = F | cum << 16
-        const uint32_t b = lane * 4;
-        const uint32_t f0 = b + 0 < Nnom ? F16[b + 0] : 0, f1 = b + 1 < Nnom ? F16[b + 1] : 0, f2 = b + 2 < Nnom ? F16[b + 2] : 0, f3 = b + 3 < Nnom ? F16[b + 3] : 0;
-        const uint32_t tot = f0 + f1 + f2 + f3;
-        uint32_t incl = tot;
-        incl = wave_scan_incl(incl);
-        const uint32_t c0 = incl - tot, c1 = c0 + f0, c2 = c1 + f1, c3 = c2 + f2;
-        if (b + 0 < Nnom) fc[b + 0] = f0 | (c0 << 16);
-        if (b + 1 < Nnom) fc[b + 1] = f1 | (c1 << 16);
-        if (b + 2 < Nnom) fc[b + 2] = f2 | (c2 << 16);
-        if (b + 3 < Nnom) fc[b + 3] = f3 | (c3 << 16);
-        auto wmax = [&](uint32_t v) {
-#pragma unroll
-            for (int o2 = 32; o2 > 0; o2 >>= 1) { const uint32_t o = __shfl_xor(v, o2); v = o > v ? o : v; }
-            return v;
-        };
-        const uint32_t k0 = (f0 << 8) | (b + 0), k1 = (f1 << 8) | (b + 1), k2 = (f2 << 8) | (b + 2), k3 = (f3 << 8) | (b + 3);
-        uint32_t m = k0 > k1 ? k0 : k1; m = k2 > m ? k2 : m; m = k3 > m ? k3 : m;
-        hot0 = wmax(m);
-        auto ex = [&](uint32_t k) { return k == hot0 ? 0u : k; };
-        uint32_t m2 = ex(k0) > ex(k1) ? ex(k0) : ex(k1); m2 = ex(k2) > m2 ? ex(k2) : m2; m2 = ex(k3) > m2 ? ex(k3) : m2;
-        hot1 = wmax(m2);
-    }
+    const uint2 hot = rans_dec_cum([&](uint32_t i) { return (uint32_t)F16[i]; }, Nnom, fc);  // (F << 8 | sym) of the two most probable symbols
     __syncthreads();
-    {   // coarse slot -> symbol: binary search over cum for every 8th slot (Nnom <= 256 -> 8 probes)
+    {   // coarse slot -> symbol: the owner of every 8th slot
         const uint32_t groups = 1u << (pb - 3);
         for (uint32_t g = lane; g < groups; g += 64) {
-            const uint32_t s = g << 3;
-            uint32_t lo = 0, hi = Nnom - 1;  // largest index with cum <= s
-            while (lo < hi) {
-                const uint32_t mid = (lo + hi + 1) >> 1;
-                if ((fc[mid] >> 16) <= s) lo = mid; else hi = mid - 1;
-            }
-            while (lo > 0 && (fc[lo] & 0xFFFF) == 0) lo--;  // only reachable on corrupt tables
+            const uint32_t lo = rans_dec_owner(fc, Nnom, g << 3);
             coarse[g] = make_uint2(fc[lo], lo);
         }
     }
     __syncthreads();
-    const uint32_t sym0 = hot0 & 255u, sym1 = hot1 & 255u;
+    const uint32_t sym0 = hot.x & 255u, sym1 = hot.y & 255u;
     const uint32_t e0 = fc[sym0], e1 = fc[sym1];
-    const uint32_t F0 = e0 & 0xFFFF, C0 = e0 >> 16, F1 = (hot1 >> 8) ? (e1 & 0xFFFF) : 0u, C1 = e1 >> 16;
+    const uint32_t F0 = e0 & 0xFFFF, C0 = e0 >> 16, F1 = e1 & 0xFFFF, C1 = e1 >> 16;
     const uint32_t mask = (1u << pb) - 1;
     uint64_t s = ld64u(blkp + 8 + 8 * par);  // state0 at +8, state1 at +16
     uint32_t rw = 0;                          // scalar cursor: next word to read is words[rw]

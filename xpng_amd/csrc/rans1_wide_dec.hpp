@@ -1,6 +1,6 @@
 // rans1_wide_dec.hpp -- throughput form of the mode-2 entropy DECODE stage (rANS v1, decompress_block, libxpng.c:262-301).
 //
-// The same split as rans2_wide_dec.hpp (it reuses its table layouts, WDec and helpers):
+// The same split as rans2_wide_dec.hpp (the table layouts, WDec and the pieces both share are in rans_dec.hpp):
 //   k_rans1_dec_prep    wave per (tile, slot): type 1 / 2 blocks are finished on the spot; for rANS blocks the decode tables
 //                       are built from the frequencies k_m2_dec_parse left in `tabs`
 //   k_rans1_dec_chain   lane = one state, a wave = ONE slot of 32 tiles.  v1 decodes FORWARDS: pair k gives symbols 2k (state0)
@@ -11,7 +11,9 @@
 #pragma once
 #include "common.hpp"
 #include "m2_decode.hpp"
-#include "rans2_wide_dec.hpp"
+#include "rans_dec.hpp"
+
+#include <type_traits>
 
 namespace xpng {
 
@@ -22,7 +24,7 @@ namespace xpng {
 #define XPNG_W1D_CBITS 9
 #endif
 struct W1dLayoutA {
-    static constexpr uint32_t CBITS = XPNG_W1D_CBITS, FCN = 256, RING = 64, REGN = 9;
+    static constexpr uint32_t CBITS = XPNG_W1D_CBITS, FCN = 256, RING = 64, REGN = 9, KIND = 2;
     static constexpr uint32_t CO_OFF = 2 * (FCN + 2), TAB = CO_OFF + (1u << CBITS);
 };
 __host__ __device__ inline bool w1d_small(uint32_t slot) { return m2_nominal(slot) <= WdLayout<false>::REGN; }
@@ -48,107 +50,45 @@ __global__ __launch_bounds__(64) void k_rans1_dec_prep(const M2DecTile *__restri
     const uint32_t Nnom = m2_nominal(slot);
     const uint32_t pb = slot >= 17 ? 15 : 14;
     if (type == 0 || n == 0) return;
-    if (type == 1) {
-        for (uint32_t i = lane; i < n; i += 64) out[i] = (uint8_t)mb.pbits;
-        return;
-    }
-    if (type == 2) {  // raw symbols from b (libxpng.c:273)
-        const uint32_t rb = (uint32_t)bit_width(Nnom - 1);
-        const uint8_t *bw = d.blob + 8;
-        const uint64_t endbit = (uint64_t)(d.bsz - 4) * 8;
-        for (uint32_t i = lane; i < n; i += 64) out[i] = (uint8_t)bits_at(bw, (uint64_t)mb.pbits + (uint64_t)i * rb, rb, endbit);
-        return;
-    }
+    if (rans1_dec_plain(type, mb.pbits, (uint32_t)bit_width(Nnom - 1), d.blob + 8, (uint64_t)(d.bsz - 4) * 8, n, out)) return;
     if (type != 3 && type != 4) return;
     const uint8_t *blkp = d.blob + mb.cnt;
     const uint32_t size = sgpr(ld32u(blkp)) & 0xFFFFFF;
     if (size < 24) return;  // libxpng.c:285
     const uint16_t *F16 = tabs + ((uint64_t)tile * M2_SLOTS + slot) * 256;
-    uint32_t hot0, hot1;
-    {   // cum by 4-per-lane partial sums + wave scan; fc[i] = F | cum << 16
-        const uint32_t b = lane * 4;
-        const uint32_t f0 = b + 0 < Nnom ? F16[b + 0] : 0, f1 = b + 1 < Nnom ? F16[b + 1] : 0, f2 = b + 2 < Nnom ? F16[b + 2] : 0, f3 = b + 3 < Nnom ? F16[b + 3] : 0;
-        const uint32_t tot = f0 + f1 + f2 + f3;
-        uint32_t incl = tot;
-        incl = wave_scan_incl(incl);
-        const uint32_t c0 = incl - tot, c1 = c0 + f0, c2 = c1 + f1, c3 = c2 + f2;
-        fc[b + 0] = b + 0 < Nnom ? f0 | (c0 << 16) : 0;
-        fc[b + 1] = b + 1 < Nnom ? f1 | (c1 << 16) : 0;
-        fc[b + 2] = b + 2 < Nnom ? f2 | (c2 << 16) : 0;
-        fc[b + 3] = b + 3 < Nnom ? f3 | (c3 << 16) : 0;
-        auto wmax = [&](uint32_t v) {
-#pragma unroll
-            for (int o2 = 32; o2 > 0; o2 >>= 1) { const uint32_t o = __shfl_xor(v, o2); v = o > v ? o : v; }
-            return v;
-        };
-        const uint32_t k0 = (f0 << 8) | (b + 0), k1 = (f1 << 8) | (b + 1), k2 = (f2 << 8) | (b + 2), k3 = (f3 << 8) | (b + 3);
-        uint32_t m = k0 > k1 ? k0 : k1; m = k2 > m ? k2 : m; m = k3 > m ? k3 : m;
-        hot0 = wmax(m);
-        auto ex = [&](uint32_t k) { return k == hot0 ? 0u : k; };
-        uint32_t m2 = ex(k0) > ex(k1) ? ex(k0) : ex(k1); m2 = ex(k2) > m2 ? ex(k2) : m2; m2 = ex(k3) > m2 ? ex(k3) : m2;
-        hot1 = wmax(m2);
-        if ((hot1 >> 8) == 0) hot1 = hot0;
-    }
+    const uint2 hot = rans_dec_cum([&](uint32_t i) { return (uint32_t)F16[i]; }, Nnom, fc);  // (F << 8 | sym) of the two most probable symbols
     __syncthreads();
     const bool small = w1d_small(slot);
     // big-alphabet slots: 16-bit cumulative counts cum[0 .. N] (cum[N] = 2^pb, 0x8000 behind it: greater than any slot) and 2^9
-    // coarse bytes - the byte layout of rans2_wide_dec.hpp's WdLayoutA, but indexed by the SLOT (residual alphabets are not
+    // coarse bytes - the byte layout of WdLayoutA, but indexed by the SLOT (residual alphabets are not
     // skewed enough for the cold-rank form to pay: measured 108 ms against 76 per 32 images).  1 KB of LDS per resident stream
     // instead of 2 KB: a chain wave holds its 32 tables for its whole life, and LDS is what the pipelined slots run out of first.
-    const uint32_t co_off = small ? WdLayout<false>::CO_OFF : W1dLayoutA::CO_OFF;
     const uint32_t cbits = small ? WdLayout<false>::CBITS : W1dLayoutA::CBITS;
     uint8_t *gt = dtab + ((uint64_t)j * M2_SLOTS + slot) * WD_TAB_MAX;
-    if (small) {
-        uint32_t *gfc = reinterpret_cast<uint32_t *>(gt);
-        for (uint32_t i = lane; i <= WdLayout<false>::FCN; i += 64) gfc[i] = i < Nnom ? fc[i] : 0xFFFFu;
-    } else {
-        uint16_t *gcu = reinterpret_cast<uint16_t *>(gt);
-        for (uint32_t i = lane; i <= W1dLayoutA::FCN + 1; i += 64) gcu[i] = (uint16_t)(i < Nnom ? fc[i] >> 16 : (i == Nnom ? 1u << pb : 0x8000u));
-    }
-    {   // coarse slot -> symbol
-        const uint32_t sh = pb > cbits ? pb - cbits : 0, entries = 1u << (pb - sh);
-        for (uint32_t g0 = lane * 4; g0 < entries; g0 += 256) {
-            uint32_t pk = 0;
-            for (uint32_t q = 0; q < 4; q++) {
-                const uint32_t s = (g0 + q) << sh;
-                uint32_t lo = 0, hi = Nnom - 1;  // largest index with cum <= s
-                while (lo < hi) {
-                    const uint32_t mid = (lo + hi + 1) >> 1;
-                    if ((fc[mid] >> 16) <= s) lo = mid; else hi = mid - 1;
-                }
-                while (lo > 0 && (fc[lo] & 0xFFFF) == 0) lo--;  // zero-frequency symbols share their successor's cum
-                pk |= lo << (8 * q);
-            }
-            *reinterpret_cast<uint32_t *>(gt + co_off + g0) = pk;
-        }
-    }
+    wd_store_tables<W1dLayoutA>(gt, small, fc, Nnom, pb, pb > cbits ? pb - cbits : 0, [](uint32_t s) { return s; });
     if (lane == 0) {
         WDec w;
         w.kind = small ? 1u : 2u; w.pb = pb; w.N = Nnom; w.n = n;
         w.nw = (size - 24) >> 2;
         w.words_off = mb.cnt + 24;
         w.out_off = out_off;
-        w.hot0 = hot0 & 255u; w.hot1 = hot1 & 255u;
+        w.hot0 = hot.x & 255u; w.hot1 = hot.y & 255u;
         *wd = w;
     }
 }
 
-template <bool BIG> struct Dec1ChainLds {  // dynamic LDS layout of one launch (common.hpp: why dynamic)
-    typedef typename std::conditional<BIG, W1dLayoutA, WdLayout<false>>::type L;
-    static constexpr uint32_t STREAMS = 32, TSTRIDE = L::TAB + 4, RSTRIDE = 4 * L::RING + 4;
-    static constexpr uint32_t OFF_RING = (STREAMS * TSTRIDE + 15u) & ~15u, OFF_OBUF = (OFF_RING + STREAMS * RSTRIDE + 31u) & ~31u;
-    static constexpr size_t BYTES = OFF_OBUF + STREAMS * OB_STRIDE + 12;
-};
+template <bool BIG>  // dynamic LDS of one launch: the whole table of every stream, no spare symbol slot (a wave has 32 streams)
+using Dec1ChainLds = WdChainLds<typename std::conditional<BIG, W1dLayoutA, WdLayout<false>>::type, BIG ? W1dLayoutA::TAB : WdLayout<false>::TAB, 32, 0>;
+static_assert(Dec1ChainLds<false>::BYTES == 15884 && (XPNG_W1D_CBITS != 9 || Dec1ChainLds<true>::BYTES == 42508), "LDS per wave of the v1 chains");
 template <bool BIG>
 __global__ __launch_bounds__(64) void k_rans1_dec_chain(const M2DecTile *__restrict__ info, uint32_t total, const WDec *__restrict__ wdec,
                                                         const uint8_t *__restrict__ dtab, uint8_t *__restrict__ scratch2) {
     typedef typename std::conditional<BIG, W1dLayoutA, WdLayout<false>>::type L;
-    constexpr uint32_t CBITS = L::CBITS, TAB = L::TAB, RING = L::RING, KIND = BIG ? 2 : 1, STREAMS = 32, NSLOT = BIG ? 7 : 11;
-    constexpr uint32_t TSTRIDE = TAB + 4;
-    constexpr uint32_t PER = RING / 8;            // words one lane requests per boundary
-    constexpr uint32_t RSTRIDE = 4 * RING + 4;    // per stream: [RING words][mirror of word 0]
     typedef Dec1ChainLds<BIG> LD;
-    static_assert(LD::TSTRIDE == TSTRIDE && LD::RSTRIDE == RSTRIDE && LD::STREAMS == STREAMS, "LDS layout");
+    constexpr uint32_t CBITS = L::CBITS, TAB = L::TAB, RING = L::RING, KIND = L::KIND, STREAMS = 32, NSLOT = BIG ? 7 : 11;
+    constexpr uint32_t TSTRIDE = LD::TSTRIDE;
+    constexpr uint32_t PER = RING / 8;            // words one lane requests per boundary
+    constexpr uint32_t RSTRIDE = LD::RSTRIDE;     // per stream: [RING words][mirror of word 0]
     extern __shared__ __align__(32) uint8_t dec1_chain_lds[];
     uint8_t *const ltab = dec1_chain_lds;                 // [STREAMS * TSTRIDE]
     uint8_t *const ring = dec1_chain_lds + LD::OFF_RING;  // [STREAMS * RSTRIDE]
@@ -158,18 +98,7 @@ __global__ __launch_bounds__(64) void k_rans1_dec_chain(const M2DecTile *__restr
     const uint32_t slot = BIG ? W1D_BIG_SLOT[blockIdx.x % NSLOT] : W1D_SMALL_SLOT[blockIdx.x % NSLOT], grp = blockIdx.x / NSLOT;
     const uint32_t j = grp * STREAMS + k;
     bool live = j < total;
-    for (uint32_t ts = 0; ts < STREAMS; ts++) {
-        const uint32_t jj = grp * STREAMS + ts;
-        uint32_t *dst = reinterpret_cast<uint32_t *>(ltab + ts * TSTRIDE);
-        if (jj >= total || sgpr(wdec[(uint64_t)jj * M2_SLOTS + slot].kind) != KIND) {
-            // no chain in this slot: its lanes idle through the loop, but their table lookups must still terminate
-            for (uint32_t i = lane; i < TAB / 4; i += 64) dst[i] = i < L::CO_OFF / 4 ? (BIG ? (i ? 0x80008000u : 0x80000000u) : 0xFFFFu) : 0u;
-            continue;
-        }
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(dtab + ((uint64_t)jj * M2_SLOTS + slot) * WD_TAB_MAX);
-#pragma unroll 4
-        for (uint32_t i = lane; i < TAB / 4; i += 64) dst[i] = src[i];
-    }
+    wd_load_tables<L, TAB, STREAMS>(ltab, grp * STREAMS, total, wdec, dtab, M2_SLOTS, slot);
     __syncthreads();
     const WDec *wd = wdec + (uint64_t)(live ? j : 0) * M2_SLOTS + slot;
     live = live && wd->kind == KIND;
@@ -204,6 +133,9 @@ __global__ __launch_bounds__(64) void k_rans1_dec_chain(const M2DecTile *__restr
         w1 = p[0]; w2 = p[1];
     };
     fetch_w();
+    // small layout: the cumulative counts c1..c9 and, in the step, the register search over them.  Both are the text of wd_cm_load and
+    // wd_reg9 (rans_dec.hpp; the v2 chain calls them): as calls they compile to the same instructions in another order and this
+    // kernel's small instance then holds 54 VGPRs instead of 50 (51 with either one called)
     uint32_t cm[10];
 #pragma unroll
     for (int i = 1; i <= 9; i++) {
@@ -214,7 +146,6 @@ __global__ __launch_bounds__(64) void k_rans1_dec_chain(const M2DecTile *__restr
         const uint32_t slot_ = slo & mask;
         uint32_t sym, F, off;
         if (!BIG) {
-            // (selects by value through pick32: see k_rans2_dec_chain)
             const uint32_t c1 = cm[1], c2 = cm[2], c3 = cm[3], c4 = cm[4], c5 = cm[5], c6 = cm[6], c7 = cm[7], c8 = cm[8], c9 = cm[9];
             const bool b2 = slot_ >= c4;
             const bool b1 = slot_ >= pick32(b2, c6, c2);
@@ -240,10 +171,8 @@ __global__ __launch_bounds__(64) void k_rans1_dec_chain(const M2DecTile *__restr
             F = (e >> 16) - (e & 0xFFFFu); off = slot_ - (e & 0xFFFFu);
         }
         if (!act) { F = ident; off = slot_; }
-        const uint32_t qlo = __builtin_amdgcn_alignbit(shi, slo, pb), qhi = shi >> pb;  // s >> pb
-        const uint64_t r0 = (uint64_t)qlo * F + off;
-        const uint32_t nlo = (uint32_t)r0, nhi = __umul24(qhi, F) + (uint32_t)(r0 >> 32);
-        const bool need = refill && (nhi | (nlo >> 31)) == 0;  // s < 2^31
+        uint32_t nlo, nhi;
+        const bool need = wd_advance(slo, shi, pb, F, off, nlo, nhi) && refill;
         const uint32_t needi = need ? 1u : 0u, other = swap_pair(needi);
         const uint32_t take = pick32(par && other, w2, w1);    // state0 refills first (libxpng.c:295-296)
         shi = need ? nlo : nhi;
@@ -255,10 +184,7 @@ __global__ __launch_bounds__(64) void k_rans1_dec_chain(const M2DecTile *__restr
         return sym;
     };
     // wave trip count: pairs, plus one step for an odd tail
-    uint32_t T = pairs + (n & 1u);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const uint32_t v = __shfl_xor(T, o); T = v > T ? v : T; }
-    T = sgpr((T + 7) & ~7u);
+    const uint32_t T = sgpr((wave_max(pairs + (n & 1u)) + 7) & ~7u);
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): nothing pending when the loop is entered (see k_rans2_dec_chain)
     for (uint32_t tb = 0; tb < T; tb += 8) {
         const uint32_t wi0 = wi;
@@ -269,14 +195,7 @@ __global__ __launch_bounds__(64) void k_rans1_dec_chain(const M2DecTile *__restr
 #pragma unroll
         for (int u = 0; u < 8; u++) step(true, true, 2 * (uint32_t)u + par);
         rw += (wi - wi0) & (RING - 1);
-        {   // in-flight words land (unconditional, like the request below: fhi == 0 when nothing was requested)
-            const uint32_t dw[9] = {q0.x, q0.y, q0.z, q0.w, PER > 4 ? q1.x : qx, q1.y, q1.z, q1.w, qx};
-#pragma unroll
-            for (int i = 0; i < (int)PER; i++) {
-                const uint32_t a = fa0 + (uint32_t)i;
-                if (a < fhi) *ring_w(a) = __builtin_amdgcn_alignbyte(dw[i + 1], dw[i], fsh);
-            }
-        }
+        wd_land<RING>(a_ring, q0, q1, qx, fa0, fhi, fsh);  // in-flight words land (unconditional, like the request below: fhi == 0 when nothing was requested)
         *(lds32 *)(uintptr_t)(a_ring + 4 * RING) = *ring_w(0);
         if (tb < pairs + (n & 1u) && par == 0) *reinterpret_cast<u32x4_t *>(out + 2ull * tb) = *(const lds128_al4 *)(uintptr_t)a_ob;
         hi = hif;

@@ -8,9 +8,10 @@
 //                     and progress counters, tiles up to 1024 rows whose rows fit the LDS) or recon_wavefront (barrier per step)
 //   k_dec_recon_band  one wavefront per tile sweeping 64-row bands (recon_band_core): what a batch uses
 //
-// recon_geometry chooses among them and recon_launch launches.  Included by m1_decode.hpp behind DecTile, ld32u and TILE_BAD.
+// recon_geometry chooses among them and recon_launch launches.
 #pragma once
 #include "common.hpp"
+#include "rans_dec.hpp"  // DecTile, TILE_BAD, ld32u
 
 namespace xpng {
 
