@@ -352,7 +352,8 @@ int xpnghip_decode_varsize_device_batch_as_float(xpnghip_ctx *ctx, int mode, con
 /* ---- crop, resize and flip in the same pass -------------------------------------------------
  * The float call above up to the copy-out - the same checks, blobs, size walk, staging raster and xpnghip_ctx_decode_status; every
  * tile is reconstructed as always - but the copy-out writes, for every image, a source rectangle resampled to ONE output size
- * out_h x out_w (each 1 .. 16384) with plain 2 x 2-tap bilinear interpolation (half-pixel centres, no antialiasing), optionally
+ * out_h x out_w (each 1 .. 16384) with plain 2 x 2-tap bilinear interpolation (half-pixel centres, no antialiasing: for that see
+ * xpnghip_decode_varsize_device_batch_resampled below), optionally
  * mirrored left to right.  Image i has the rectangle {x, y, w, h} = rects[4i .. 4i+3] (valid as for the region decode: not empty,
  * inside the image; rects == NULL: every whole image) and the flip flips[i] (0 or 1; flips == NULL: none).  With
  *     kx = (float)rw / (float)out_w,  ky = (float)rh / (float)out_h           one IEEE fp32 division each, on the host
@@ -384,6 +385,47 @@ int xpnghip_decode_varsize_device_batch_resized(xpnghip_ctx *ctx, int mode, cons
  * a bad pxsz, layout, dtype, size, rectangle or flip, a non-finite constant, a NULL raster, or a NULL or misaligned out. */
 int xpnghip_resize_host(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip, uint32_t out_w,
                         uint32_t out_h, uint32_t layout, uint32_t dtype, const float *scale, const float *bias, void *out);
+
+/* ---- the same pass with an antialiased downscale ----------------------------------------------
+ * The resized call above with one more word, `filter`: */
+#define XPNGHIP_FILTER_BILINEAR 0u    /* today's rule: exactly the resized call, the same kernel, the same bytes */
+#define XPNGHIP_FILTER_TRIANGLE_AA 1u /* a triangle filter wherever an axis shrinks (what F.interpolate(antialias=True) computes) */
+/* The rule of XPNGHIP_FILTER_TRIANGLE_AA.  Everything the host computes per image for the resized call stays:
+ * kx = (float)rw / (float)OW and ky are computed on the host, one fp32 division each.  The record gains ikx = 1.0f / kx and
+ * iky = 1.0f / ky, also one host fp32 division each.  The inverses travel in the per-image record.
+ * An axis operation maps a sequence q(0 .. n-1) of fp32 values to one fp32 value.  Here n is the extent of the RECTANGLE on that
+ * axis, O is the output extent and k is the ratio.  For output index u, the existing line f = fmaf((float)u + 0.5f, k, -0.5f) is
+ * kept.
+ *   k <= 1.0f, or filter 0.  Today's two taps, unchanged:
+ *     s = max(f, 0)   i0 = min((uint32_t)s, n-1)   i1 = min(i0+1, n-1)   l = s - (float)i0
+ *     result fmaf(l, q(i1) - q(i0), q(i0))
+ *   k > 1.0f with filter 1.  A triangle of half-width k, clamped to the rectangle and renormalised:
+ *     lo = f - k   j0 = lo > 0 ? (uint32_t)lo : 0   j1 = min((uint32_t)(f + k), n - 1)
+ *     W = 0, A = 0, then for j = j0 .. j1 ascending:
+ *         d = fabsf((float)j - f)   w = max(fmaf(-d, ik, 1.0f), 0.0f)   W = W + w   A = fmaf(w, q(j), A)
+ *     result A / W, one IEEE fp32 division.
+ * H(s) is the x-axis operation over the channel's bytes of source row s as floats, u = flip ? OW-1-ox : ox, as now.  v is the
+ * y-axis operation over H(.).  Then, as now, y = fmaf(v, scale[c], bias[c]) and out = (T)y, round to nearest even.  Each axis
+ * chooses its branch on its own k: a crop that shrinks in one direction and grows in the other mixes the branches.  Channel
+ * choice, the BGR exchange, alpha last, the alpha an RGB context lacks (v = 255 exactly, no read), the constants, the layouts and
+ * the dtypes are all as in the float and resized calls.
+ * Consequences: (a) with filter 1, an image whose kx <= 1 and ky <= 1 gives bit for bit what filter 0 gives (the identity crop is
+ * a special case); (b) a flip is a mirror on the bits; (c) no tap leaves the rectangle: the window is clamped to it, not to the
+ * image.  W > 0 always.  Every multiplication is inside an explicit fmaf, sums and the division are single
+ * operations, and the order of accumulation - ascending j within a row, ascending s over rows - is part of the rule.
+ * The call takes the resized call's arguments plus `filter` and refuses what that call refuses; any filter other than 0 or 1 is
+ * refused before anything reaches the device, with the value in xpnghip_last_error().  With filter 1 the per-image table is 48
+ * bytes per image, uploaded on every call by the resized call's protocol. */
+int xpnghip_decode_varsize_device_batch_resampled(xpnghip_ctx *ctx, int mode, const void *const *d_blobs, const uint64_t *blobs_len,
+                                                  uint32_t nimg, const uint64_t *tile_off, void *const *d_outs, uint32_t layout,
+                                                  uint32_t dtype, const float *scale, const float *bias, const uint64_t *rects,
+                                                  const uint8_t *flips, uint32_t out_w, uint32_t out_h, uint32_t filter, void *stream);
+/* host-only, needs no device: the twin of the call above, bit for bit what it writes, as xpnghip_resize_host is of the resized
+ * call (filter 0 IS xpnghip_resize_host).  Refuses a filter other than 0 or 1 and everything xpnghip_resize_host refuses, with
+ * nothing written. */
+int xpnghip_resample_host(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip, uint32_t out_w,
+                          uint32_t out_h, uint32_t layout, uint32_t dtype, const float *scale, const float *bias, uint32_t filter,
+                          void *out);
 
 /* ---- staged batch from device tensors: the inverse of the float call --------------------------
  * A model writes floats, not the file's bytes.  The call below is xpnghip_images_begin with the upload replaced by one staging

@@ -35,6 +35,7 @@ HIP_SYMBOLS = [
     "xpnghip_layout_channels", "xpnghip_decode_varsize_device_batch_as", "xpnghip_encode_varsize_device_batch_from",
     "xpnghip_dtype_bytes", "xpnghip_float_table", "xpnghip_decode_varsize_device_batch_as_float",
     "xpnghip_decode_varsize_device_batch_resized", "xpnghip_resize_host",
+    "xpnghip_decode_varsize_device_batch_resampled", "xpnghip_resample_host",
     "xpnghip_images_begin_device", "xpnghip_quantize_host",
 ]
 HOST_SYMBOLS = ["xpng_store", "xpng_load", "xpng_from_jpg", "xpng_store_T", "xpng_load_T", "xpng_from_jpg_T",
@@ -183,6 +184,13 @@ def _bind_hip(path):
         L.xpnghip_resize_host.restype = C.c_int
         L.xpnghip_resize_host.argtypes = [C.c_int, vp, u64, u64, C.POINTER(u64), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                           f32p, f32p, vp]
+        L.xpnghip_decode_varsize_device_batch_resampled.restype = C.c_int
+        L.xpnghip_decode_varsize_device_batch_resampled.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64), C.c_uint32, C.POINTER(u64),
+                                                                    C.POINTER(vp), C.c_uint32, C.c_uint32, f32p, f32p, C.POINTER(u64), u8p,
+                                                                    C.c_uint32, C.c_uint32, C.c_uint32, vp]
+        L.xpnghip_resample_host.restype = C.c_int
+        L.xpnghip_resample_host.argtypes = [C.c_int, vp, u64, u64, C.POINTER(u64), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                            f32p, f32p, C.c_uint32, vp]
         L.xpnghip_images_begin.restype = C.c_int
         L.xpnghip_images_begin.argtypes = [C.POINTER(vp), C.c_uint32, C.POINTER(vp), C.POINTER(u64), u8p, u8p]
         L.xpnghip_images_begin_device.restype = C.c_int
@@ -566,6 +574,32 @@ def resize_host(raster, size, layout: int, dtype: int, scale=None, bias=None, re
     return buf.tobytes()[:ch * oh * ow * dtype_bytes(dtype)]
 
 
+FILTER_BILINEAR, FILTER_TRIANGLE_AA = 0, 1  # include/xpng_hip.h XPNGHIP_FILTER_*: the filter word of a resampled call
+
+
+def resample_host(raster, size, layout: int, dtype: int, scale=None, bias=None, rect=None, flip=False, filter: int = FILTER_TRIANGLE_AA) -> bytes:
+    """The rule of MixedContext.decode_batch_resampled on the host (xpnghip_resample_host; needs no device): resize_host's
+    arguments and `filter`, FILTER_BILINEAR (resize_host itself) or FILTER_TRIANGLE_AA (a triangle filter wherever an axis
+    shrinks: an antialiased downscale).  Returns the C * OH * OW elements of `dtype` in `layout` as raw bytes, bit for bit what
+    the device call writes for these pixels."""
+    r = np.ascontiguousarray(raster, dtype=np.uint8)
+    if r.ndim != 3 or r.shape[2] not in (3, 4):
+        raise XpngError("resample_host: the raster must be (h, w, 3) or (h, w, 4) uint8")
+    try:
+        oh, ow = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise XpngError(f"resample_host: size must be (OH, OW), not {size!r}") from None
+    px = r.shape[2]
+    sc, bi, ch = _scale_bias(layout, px, scale, bias)
+    ra = _rect_array("resample_host", None if rect is None else [rect], 1)
+    ok = ch > 0 and 1 <= oh <= 16384 and 1 <= ow <= 16384          # (anything else the library refuses, naming the value)
+    buf = np.empty(ch * oh * ow if ok else 1, dtype=np.uint32)     # 4-byte aligned, room for the widest element
+    if hip_lib().xpnghip_resample_host(px, r.ctypes.data, r.shape[1], r.shape[0], ra, int(flip), ow & 0xFFFFFFFF, oh & 0xFFFFFFFF, layout, dtype, sc, bi,
+                                       int(filter) & 0xFFFFFFFF, buf.ctypes.data):
+        raise XpngError("xpnghip_resample_host: " + _err())
+    return buf.tobytes()[:ch * oh * ow * dtype_bytes(dtype)]
+
+
 def quantize_host(src, npx: int, channels: int, layout: int, dtype: int, scale=None, bias=None) -> np.ndarray:
     """The quantisation rule of StagedImages.from_device on the host (xpnghip_quantize_host; needs no device): `src` is a tight
     buffer of channels * npx elements of `dtype` (0 = uint8, DTYPE_F16, DTYPE_BF16, DTYPE_F32) in `layout` (LAYOUT_PLANAR and
@@ -932,6 +966,28 @@ class MixedContext(_Handle):
                 raise XpngError(f"decode_batch_resized: flips has {len(flips)} entries for {k} images")
             fl = (C.c_uint8 * max(k, 1))(*[int(f) & 0xFF for f in flips])
         self._decode("xpnghip_decode_varsize_device_batch_resized", mode, d_blobs, lens, d_outs, tile_offs, stream, layout, dtype, sc, bi, ra, fl, ow, oh)
+
+    def decode_batch_resampled(self, mode, d_blobs, lens, d_outs, layout, dtype, size, scale=None, bias=None, rects=None, flips=None,
+                               filter: int = FILTER_TRIANGLE_AA, tile_offs=None, stream=0):
+        """decode_batch_resized with a filter word: FILTER_BILINEAR is that call itself, the same kernel and the same bytes;
+        FILTER_TRIANGLE_AA resamples every axis that shrinks with a triangle filter of the ratio's half-width, clamped to the
+        rectangle and renormalised - an antialiased downscale, F.interpolate(mode="bilinear", antialias=True) of the cropped
+        rectangle up to the order of summation: xpnghip_decode_varsize_device_batch_resampled (the rule is in include/xpng_hip.h)."""
+        k = len(d_blobs)
+        try:
+            oh, ow = (int(v) & 0xFFFFFFFF for v in size)
+        except (TypeError, ValueError):
+            raise XpngError(f"decode_batch_resampled: size must be (OH, OW), not {size!r}") from None
+        sc, bi, _ = _scale_bias(layout, self.pxsz, scale, bias)
+        ra = _rect_array("decode_batch_resampled", rects, k)
+        fl = None
+        if flips is not None:
+            flips = list(flips)
+            if len(flips) != k:
+                raise XpngError(f"decode_batch_resampled: flips has {len(flips)} entries for {k} images")
+            fl = (C.c_uint8 * max(k, 1))(*[int(f) & 0xFF for f in flips])
+        self._decode("xpnghip_decode_varsize_device_batch_resampled", mode, d_blobs, lens, d_outs, tile_offs, stream, layout, dtype, sc, bi, ra, fl, ow, oh,
+                     int(filter) & 0xFFFFFFFF)
 
     def encode_batch_from(self, mode, d_rasters, layout, d_blobs, stream=0, sync=True):
         """encode_batch in its tight form, with every d_rasters[i] read in `layout` (api.layout(); its channels must be the

@@ -32,6 +32,7 @@
 #include "mixed.hpp"
 #include "mixed_float.hpp"
 #include "mixed_resize.hpp"
+#include "mixed_resample.hpp"
 #include "stage_from.hpp"
 
 using namespace xpng;
@@ -206,6 +207,7 @@ struct xpnghip_ctx {
     MixedLayout *d_m_out = nullptr, *d_m_in = nullptr;
     std::vector<const void *> h_m_out, h_m_in;  // the buffers the two tables hold (skip the upload when unchanged)
     ResizeRec *d_m_rect = nullptr;     // the rectangle table of a resized decode (mixed_resize.hpp): B records, uploaded by every call
+    ResampleRec *d_m_rsmp = nullptr;   // ... and that of a resampled decode with filter 1 (mixed_resample.hpp), alike
 };
 
 // the context's own stream, created when a call first needs it (the `stream == NULL` form of the device-resident entry points,
@@ -985,6 +987,7 @@ struct ResizeCall {
     const uint64_t *rects;
     const uint8_t *flips;
     uint32_t out_w, out_h;
+    uint32_t filter = XPNGHIP_FILTER_BILINEAR;  // (xpnghip_decode_varsize_device_batch_resampled: DESIGN.md 19)
 };
 static bool resize_size_ok(uint32_t out_w, uint32_t out_h, std::string &why) {
     if (out_w >= 1 && out_w <= 16384 && out_h >= 1 && out_h <= 16384) return true;
@@ -1022,18 +1025,18 @@ static ResizeTap resize_tap_host(uint32_t u, float k, uint32_t n) {
     r.l = s - (float)r.i0;
     return r;
 }
-static int resize_host_impl(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip, uint32_t out_w, uint32_t out_h,
-                            uint32_t layout, uint32_t dtype, const float *scale, const float *bias, void *out) {
-#pragma clang fp contract(off)
-    const int C = xpnghip_layout_channels(layout, pxsz);
-    if (pxsz != 3 && pxsz != 4) return fail("xpnghip_resize_host: pxsz is " + std::to_string(pxsz) + ", not 3 or 4");
+// the checks of the two host twins (`fn` names the entry point in the texts): the channels, the constants and the record of the call
+static int resize_host_args(const char *fn, int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip, uint32_t out_w,
+                            uint32_t out_h, uint32_t layout, uint32_t dtype, const float *scale, const float *bias, const void *out, int &C, FloatConsts &k,
+                            ResizeRec &z) {
+    C = xpnghip_layout_channels(layout, pxsz);
+    if (pxsz != 3 && pxsz != 4) return fail(std::string(fn) + ": pxsz is " + std::to_string(pxsz) + ", not 3 or 4");
     if (C < 0) return fail("bad layout word " + layout_hex(layout) + " (XPNGHIP_LAYOUT_PLANAR | XPNGHIP_LAYOUT_BGR | channels 0, 3 or 4 in bits 8..11)");
     const int es = xpnghip_dtype_bytes(dtype);
     if (es < 0) return fail("bad dtype " + std::to_string(dtype) + " (XPNGHIP_DTYPE_F16 = 1, _BF16 = 2, _F32 = 3)");
-    FloatConsts k;
     std::string why;
     if (!float_consts(C, scale, bias, k, why)) return fail(why);
-    if (!raster || !out) return fail("xpnghip_resize_host: null raster or output buffer");
+    if (!raster || !out) return fail(std::string(fn) + ": null raster or output buffer");
     if ((uintptr_t)out & (uintptr_t)(es - 1)) {
         char b[32];
         snprintf(b, sizeof b, "%p", out);
@@ -1041,8 +1044,16 @@ static int resize_host_impl(int pxsz, const uint8_t *raster, uint64_t w, uint64_
     }
     if (!w || !h || w > (1u << 24) || h > (1u << 24)) return fail("bad image size " + std::to_string(w) + " x " + std::to_string(h) + " (each side must be 1 .. 16777216)");
     if (!resize_size_ok(out_w, out_h, why)) return fail(why);
-    ResizeRec z;
     if (!resize_record(w, h, rect, (uint32_t)flip, out_w, out_h, z, why)) return fail(why);
+    return 0;
+}
+static int resize_host_impl(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip, uint32_t out_w, uint32_t out_h,
+                            uint32_t layout, uint32_t dtype, const float *scale, const float *bias, void *out) {
+#pragma clang fp contract(off)
+    int C;
+    FloatConsts k;
+    ResizeRec z;
+    if (resize_host_args("xpnghip_resize_host", pxsz, raster, w, h, rect, flip, out_w, out_h, layout, dtype, scale, bias, out, C, k, z)) return 1;
     const bool planar = layout & XPNGHIP_LAYOUT_PLANAR, bgr = layout & XPNGHIP_LAYOUT_BGR;
     std::vector<ResizeTap> tx(out_w);
     for (uint32_t ox = 0; ox < out_w; ox++) tx[ox] = resize_tap_host(z.flip ? out_w - 1 - ox : ox, z.kx, z.rw);
@@ -1071,6 +1082,103 @@ static int resize_host_impl(int pxsz, const uint8_t *raster, uint64_t w, uint64_
 extern "C" int xpnghip_resize_host(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip, uint32_t out_w, uint32_t out_h,
                                    uint32_t layout, uint32_t dtype, const float *scale, const float *bias, void *out) {
     XPNG_GUARDED(resize_host_impl(pxsz, raster, w, h, rect, flip, out_w, out_h, layout, dtype, scale, bias, out))
+}
+// ---- the antialiased downscale (mixed_resample.hpp) -------------------------------------------------------------
+static bool resample_filter_ok(uint32_t filter, std::string &why) {
+    if (filter <= XPNGHIP_FILTER_TRIANGLE_AA) return true;
+    why = "bad filter " + std::to_string(filter) + " (XPNGHIP_FILTER_BILINEAR = 0, XPNGHIP_FILTER_TRIANGLE_AA = 1)";
+    return false;
+}
+// the record of filter 1 from the resized call's: the inverses are one IEEE fp32 division each
+static ResampleRec resample_record(const ResizeRec &z) {
+    return ResampleRec{z.rx, z.ry, z.rw, z.rh, z.kx, z.ky, 1.0f / z.kx, 1.0f / z.ky, z.flip, {0, 0, 0}};
+}
+// The twin of k_mixed_resample_as_float on the host: the same operations in the same order, every multiplication inside an
+// explicit fmaf(), contraction off on top of that.  One axis of the rule for output index u: the two taps (aa false) or the window.
+struct ResampleAxis {
+    bool aa;
+    ResizeTap t;
+    uint32_t j0, j1;
+    float f;
+};
+static ResampleAxis resample_axis_host(uint32_t u, float k, uint32_t n) {
+#pragma clang fp contract(off)
+    ResampleAxis a{};
+    a.aa = k > 1.0f;
+    if (!a.aa) {
+        a.t = resize_tap_host(u, k, n);
+        return a;
+    }
+    const float c = (float)u + 0.5f;
+    a.f = fmaf(c, k, -0.5f);
+    const float lo = a.f - k, hi = a.f + k;
+    a.j0 = lo > 0.0f ? (uint32_t)lo : 0u;
+    const uint32_t t = (uint32_t)hi;
+    a.j1 = t < n - 1 ? t : n - 1;
+    return a;
+}
+// the axis operation over q(0 .. n-1); *bad is set where W is not positive (the rule's argument says never)
+template <class Q> static float resample_axis_apply(const ResampleAxis &a, float ik, Q q, bool *bad) {
+#pragma clang fp contract(off)
+    if (!a.aa) {
+        const float q0 = q(a.t.i0), q1 = q(a.t.i1);
+        const float d = q1 - q0;
+        return fmaf(a.t.l, d, q0);
+    }
+    float W = 0.0f, A = 0.0f;
+    for (uint32_t j = a.j0; j <= a.j1; j++) {
+        const float d = fabsf((float)j - a.f);
+        float w = fmaf(-d, ik, 1.0f);
+        if (!(w > 0.0f)) w = 0.0f;
+        W = W + w;
+        A = fmaf(w, q(j), A);
+    }
+    if (!(W > 0.0f)) *bad = true;
+    return A / W;
+}
+static int resample_host_impl(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip, uint32_t out_w, uint32_t out_h,
+                              uint32_t layout, uint32_t dtype, const float *scale, const float *bias, uint32_t filter, void *out) {
+#pragma clang fp contract(off)
+    std::string why;
+    if (!resample_filter_ok(filter, why)) return fail(why);
+    // filter 0 is the resized twin itself, whole
+    if (filter == XPNGHIP_FILTER_BILINEAR) return resize_host_impl(pxsz, raster, w, h, rect, flip, out_w, out_h, layout, dtype, scale, bias, out);
+    int C;
+    FloatConsts k;
+    ResizeRec z0;
+    if (resize_host_args("xpnghip_resample_host", pxsz, raster, w, h, rect, flip, out_w, out_h, layout, dtype, scale, bias, out, C, k, z0)) return 1;
+    const ResampleRec z = resample_record(z0);
+    const bool planar = layout & XPNGHIP_LAYOUT_PLANAR, bgr = layout & XPNGHIP_LAYOUT_BGR;
+    std::vector<ResampleAxis> ax(out_w), ay(out_h);
+    for (uint32_t ox = 0; ox < out_w; ox++) ax[ox] = resample_axis_host(z.flip ? out_w - 1 - ox : ox, z.kx, z.rw);
+    for (uint32_t oy = 0; oy < out_h; oy++) ay[oy] = resample_axis_host(oy, z.ky, z.rh);
+    // the values first, the elements after them: a call that fails writes nothing
+    std::vector<float> ys((uint64_t)C * out_h * out_w);
+    bool bad = false;
+    for (uint32_t oy = 0; oy < out_h; oy++)
+        for (uint32_t ox = 0; ox < out_w; ox++)
+            for (int c = 0; c < C; c++) {
+                float v = 255.0f;  // the alpha an RGB raster does not store
+                if (!(pxsz == 3 && c == 3)) {
+                    const uint32_t sc = bgr && c < 3 ? 2 - c : c;
+                    auto H = [&](uint32_t s) {
+                        const uint8_t *p = raster + ((uint64_t)(z.ry + s) * w + z.rx) * pxsz + sc;
+                        return resample_axis_apply(ax[ox], z.ikx, [&](uint32_t j) { return (float)p[(uint64_t)j * pxsz]; }, &bad);
+                    };
+                    v = resample_axis_apply(ay[oy], z.iky, H, &bad);
+                }
+                ys[planar ? ((uint64_t)c * out_h + oy) * out_w + ox : ((uint64_t)oy * out_w + ox) * C + c] = fmaf(v, k.scale[c], k.bias[c]);
+            }
+    if (bad) return fail("internal error: a window of the triangle filter has no weight");  // (W > 0 always: DESIGN.md 19)
+    for (uint64_t e = 0; e < ys.size(); e++) {
+        if (dtype == XPNGHIP_DTYPE_F32) reinterpret_cast<float *>(out)[e] = ys[e];
+        else reinterpret_cast<uint16_t *>(out)[e] = dtype == XPNGHIP_DTYPE_F16 ? f16_bits_rne(ys[e]) : bf16_bits_rne(ys[e]);
+    }
+    return 0;
+}
+extern "C" int xpnghip_resample_host(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip, uint32_t out_w, uint32_t out_h,
+                                     uint32_t layout, uint32_t dtype, const float *scale, const float *bias, uint32_t filter, void *out) {
+    XPNG_GUARDED(resample_host_impl(pxsz, raster, w, h, rect, flip, out_w, out_h, layout, dtype, scale, bias, filter, out))
 }
 // ---- staging from tensors (stage_from.hpp) ---------------------------------------------------------------------
 // the layout word of a call whose channel count is per image: the PLANAR and BGR bits and nothing else
@@ -1162,6 +1270,16 @@ static int resize_records(xpnghip_ctx *c, const std::vector<ResizeRec> &recs, hi
     HIPCHK(hipStreamSynchronize(s));
     return 0;
 }
+// ... and the table of a resampled call with filter 1, in its place and by the same protocol
+static int resample_records(xpnghip_ctx *c, const std::vector<ResizeRec> &recs, hipStream_t s) {
+    std::vector<ResampleRec> rr(recs.size());
+    for (size_t i = 0; i < recs.size(); i++) rr[i] = resample_record(recs[i]);
+    const uint64_t bytes = (uint64_t)c->B * sizeof(ResampleRec);
+    WS_GET(c->d_m_rsmp, bytes);
+    HIPCHK(hipMemcpyAsync(c->d_m_rsmp, rr.data(), bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
 
 // The staging raster of the tight forms (decode: reconstruct into it, k_mixed_copy out of it; encode: k_mixed_pack into it, the
 // kernels read it): image i's h_i rows at the pitch bpr in slot[i], every slot 256-byte aligned, 256 spare bytes behind the last.
@@ -1180,7 +1298,8 @@ static int mixed_stage_slots(xpnghip_ctx *c, uint64_t bpr, std::vector<uint64_t>
 
 // `layout` != NULL: the call of xpnghip_decode_varsize_device_batch_as (out_bpr == 0: its buffers are tight); `fc` != NULL beside
 // it: the call of xpnghip_decode_varsize_device_batch_as_float (its buffers hold elements of fc->dtype); `rz` != NULL beside both:
-// the call of xpnghip_decode_varsize_device_batch_resized (every buffer holds C * rz->out_h * rz->out_w such elements)
+// the call of xpnghip_decode_varsize_device_batch_resized (every buffer holds C * rz->out_h * rz->out_w such elements), or with
+// rz->filter that of xpnghip_decode_varsize_device_batch_resampled
 static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
                                    const uint64_t *tile_off, void *const *d_outs, uint64_t out_bpr, void *stream, const uint32_t *layout = nullptr,
                                    const FloatCall *fc = nullptr, const ResizeCall *rz = nullptr) {
@@ -1209,6 +1328,7 @@ static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *
     std::vector<ResizeRec> recs;
     if (rz) {
         std::string why;
+        if (!resample_filter_ok(rz->filter, why)) return fail(why);
         if (!resize_size_ok(rz->out_w, rz->out_h, why)) return fail(why);
         recs.resize(nimg);
         for (uint32_t i = 0; i < nimg; i++)
@@ -1235,7 +1355,7 @@ static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *
         std::vector<uint64_t> slot;
         if (mixed_stage_slots(c, bpr, slot)) return 1;
         if (mixed_records(c, c->d_m_out, c->h_m_out, slot, d_outs, s)) return 1;
-        if (rz && resize_records(c, recs, s)) return 1;
+        if (rz && (rz->filter == XPNGHIP_FILTER_TRIANGLE_AA ? resample_records(c, recs, s) : resize_records(c, recs, s))) return 1;
         for (uint32_t i = 0; i < nimg; i++) base[i] = c->d_m_stage + slot[i];
     }
     if (dec_prepare(c, mode, d_blobs, blobs_len, nimg, base.data(), s)) return 1;
@@ -1244,12 +1364,17 @@ static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *
     if (rc) return rc;
     if (rz || fc || as) {
         XPNG_REQUIRE(c->d_m_stage, c->d_m_out);
-        if (rz) XPNG_REQUIRE(c->d_m_rect);
+        const bool aa = rz && rz->filter == XPNGHIP_FILTER_TRIANGLE_AA;
+        if (rz) XPNG_REQUIRE(aa ? (const void *)c->d_m_rsmp : (const void *)c->d_m_rect);
         const uint32_t bgr = *layout & XPNGHIP_LAYOUT_BGR;
         with_3or4(c->pxsz, [&](auto PXc) { with_3or4(C, [&](auto Cc) { with_planar(*layout, [&](auto PL) {
             constexpr int PX = decltype(PXc)::value, CH = decltype(Cc)::value;
             constexpr bool P = decltype(PL)::value;
-            if (rz) {
+            if (aa) {
+                with_float(fc->dtype, [&](auto t) {
+                    k_mixed_resample_as_float<PX, CH, P, decltype(t)><<<mixed_grid(c, rz->out_h), 256, 0, s>>>(c->d_m_out, c->d_m_rsmp, c->d_m_stage, bpr, bgr, rz->out_w, rz->out_h, fk);
+                });
+            } else if (rz) {
                 with_float(fc->dtype, [&](auto t) {
                     k_mixed_resize_as_float<PX, CH, P, decltype(t)><<<mixed_grid(c, rz->out_h), 256, 0, s>>>(c->d_m_out, c->d_m_rect, c->d_m_stage, bpr, bgr, rz->out_w, rz->out_h, fk);
                 });
@@ -1287,6 +1412,14 @@ extern "C" int xpnghip_decode_varsize_device_batch_resized(xpnghip_ctx *c, int m
                                                            uint32_t out_w, uint32_t out_h, void *stream) {
     const FloatCall fc{dtype, scale, bias};
     const ResizeCall rz{rects, flips, out_w, out_h};
+    XPNG_GUARDED(decode_mixed_batch_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, d_outs, 0, stream, &layout, &fc, &rz))
+}
+extern "C" int xpnghip_decode_varsize_device_batch_resampled(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
+                                                             const uint64_t *tile_off, void *const *d_outs, uint32_t layout, uint32_t dtype,
+                                                             const float *scale, const float *bias, const uint64_t *rects, const uint8_t *flips,
+                                                             uint32_t out_w, uint32_t out_h, uint32_t filter, void *stream) {
+    const FloatCall fc{dtype, scale, bias};
+    const ResizeCall rz{rects, flips, out_w, out_h, filter};
     XPNG_GUARDED(decode_mixed_batch_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, d_outs, 0, stream, &layout, &fc, &rz))
 }
 

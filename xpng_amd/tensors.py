@@ -5,7 +5,8 @@
 pixel) and every group is decoded by mixed-size device calls straight into tensors of the final layout
 (MixedContext.decode_batch_as: the layout is written by the copy-out pass of the decode, include/xpng_hip.h XPNGHIP_LAYOUT_*;
 MixedContext.decode_batch_as_float when a float dtype is asked for: the same pass converts and normalises, XPNGHIP_DTYPE_*;
-MixedContext.decode_batch_resized when an output size is asked for: the same pass also crops, resizes and flips).
+MixedContext.decode_batch_resized when an output size is asked for: the same pass also crops, resizes and flips;
+MixedContext.decode_batch_resampled when that resize is to antialias).
 api.py stays free of torch; this module is the only one of the package that imports it at load time."""
 from __future__ import annotations
 
@@ -107,7 +108,7 @@ def centre_crop(width, height, ratio=(3.0 / 4.0, 4.0 / 3.0)):
 
 
 def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, device=None, dtype=torch.uint8, mean=None, std=None,
-               stack: bool = False, size=None, crops=None, flips=None):
+               stack: bool = False, size=None, crops=None, flips=None, antialias: bool = False):
     """The images of a list of .xpng files of any sizes as tensors on `device` (default: the current cuda device), each of
     shape (C, h, w) for layout "chw" or (h, w, C) for "hwc".  channels None keeps each file's own count (3 or 4); 3 drops the
     alpha of an RGBA file, 4 gives an RGB file alpha 255; bgr=True orders the colours B, G, R (alpha stays last).
@@ -129,11 +130,20 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
 
     size=(OH, OW) makes every returned tensor (C, OH, OW) or (OH, OW, C): the same pass of the decode crops, resizes with plain
     2 x 2-tap bilinear interpolation (half-pixel centres as F.interpolate(mode="bilinear", align_corners=False, antialias=False);
-    NOT an antialiased resize) and flips (MixedContext.decode_batch_resized; the rule is in include/xpng_hip.h).  It needs a float
+    NOT an antialiased resize: see antialias below) and flips (MixedContext.decode_batch_resized; the rule is in include/xpng_hip.h).  It needs a float
     dtype.  crops is one rectangle (x, y, w, h) per path (random_resized_crops makes them) or None for the whole images; flips one
     bool per path (True mirrors left to right) or None.  stack=True then works for files of ANY sizes - only C must agree.
     Host-answered files go through api.resize_host and are bit-identical.  Without size the function runs exactly the path above;
-    crops or flips without size is an error."""
+    crops or flips without size is an error.
+
+    antialias=True with size resamples every axis that SHRINKS with a triangle filter as wide as the ratio, clamped to the crop
+    rectangle and renormalised, and leaves an axis that grows to the two taps above (MixedContext.decode_batch_resampled with
+    FILTER_TRIANGLE_AA; the rule is in include/xpng_hip.h).  Before the normalisation this is
+    F.interpolate(mode="bilinear", align_corners=False, antialias=True) of the cropped rectangle as fp32, torchvision's default for
+    resize and RandomResizedCrop, up to the order of summation: the largest difference measured against torch's CPU kernel was
+    1.22e-4 of one byte step (tests/test_resample.py asserts 2^-10).  Host-answered files go through api.resample_host and are
+    bit-identical, so such files still load with device="cpu".  antialias=False (the default) runs today's path, call for call;
+    antialias=True without size is an error."""
     if layout not in ("chw", "hwc"):
         raise XpngError(f"load_files: layout must be 'chw' or 'hwc', not {layout!r}")
     if channels not in (None, 3, 4):
@@ -144,6 +154,8 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
         raise XpngError("load_files: mean and std need a float dtype (dtype=torch.uint8 returns the file's bytes)")
     if size is None and (crops is not None or flips is not None):
         raise XpngError("load_files: crops and flips need size=(OH, OW)")
+    if antialias and size is None:
+        raise XpngError("load_files: antialias=True needs size=(OH, OW): without a resize there is nothing to filter")
     if size is not None:
         if dtype == torch.uint8:
             raise XpngError("load_files: size needs a float dtype (torch.float16, bfloat16 or float32): the resize interpolates")
@@ -230,8 +242,11 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
             continue
         if size is not None:
             C = channels or px
-            raw = api.resize_host(t.numpy(), (OH, OW), api.layout(planar=layout == "chw", bgr=bgr, channels=C), dt, *consts(C),
-                                  rect=crops[i], flip=flips[i])
+            word = api.layout(planar=layout == "chw", bgr=bgr, channels=C)
+            if antialias:
+                raw = api.resample_host(t.numpy(), (OH, OW), word, dt, *consts(C), rect=crops[i], flip=flips[i], filter=api.FILTER_TRIANGLE_AA)
+            else:
+                raw = api.resize_host(t.numpy(), (OH, OW), word, dt, *consts(C), rect=crops[i], flip=flips[i])
             t = torch.frombuffer(bytearray(raw), dtype=dtype).view(shape(C, h, w))
         else:
             t = _arrange(t, layout, channels, bgr)
@@ -268,7 +283,11 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
                 ctx = api.MixedContext([(w, h) for (_, w, h, _) in part], px, device=index)
                 try:
                     ins, lens = [d_in.data_ptr() + o for o in offs], [len(buf) - 8 for (_, _, _, buf) in part]
-                    if size is not None:
+                    if size is not None and antialias:
+                        ctx.decode_batch_resampled(mode, ins, lens, [t.data_ptr() for t in outs], word, dt, (OH, OW), *consts(C),
+                                                   rects=[crops[i] or (0, 0, w, h) for (i, w, h, _) in part], flips=[flips[i] for (i, _, _, _) in part],
+                                                   filter=api.FILTER_TRIANGLE_AA)
+                    elif size is not None:
                         ctx.decode_batch_resized(mode, ins, lens, [t.data_ptr() for t in outs], word, dt, (OH, OW), *consts(C),
                                                  rects=[crops[i] or (0, 0, w, h) for (i, w, h, _) in part], flips=[flips[i] for (i, _, _, _) in part])
                     elif dt:
