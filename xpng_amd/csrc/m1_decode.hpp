@@ -135,7 +135,7 @@ __global__ void k_dec_parse(const uint8_t *const *__restrict__ blobs, const uint
 template <int MAXPB, bool COARSE = true>
 __device__ __forceinline__ void rans2_decode_stream(const DecTile *__restrict__ info, const TileDesc *__restrict__ tiles, TileSel sel,
                                                     const uint32_t j, const uint32_t c, int only_over, uint8_t *__restrict__ ctxsym,
-                                                    uint8_t *__restrict__ asym, uint64_t *__restrict__ dbg) {
+                                                    uint8_t *__restrict__ asym, uint64_t *__restrict__ dbg, const bool packed = false) {
     // per group of 8 slots: (F | cum << 16, symbol) of the symbol owning slot (g << 3): ONE LDS read resolves a slot whose group
     // lies inside one symbol's range (wide symbols: the probable ones), else a short forward scan over fc[] follows
     __shared__ uint2 coarse[COARSE ? 1 << (MAXPB - 3) : 1];
@@ -156,7 +156,7 @@ __device__ __forceinline__ void rans2_decode_stream(const DecTile *__restrict__ 
     const uint8_t *end = in + csz;
     const uint32_t h1 = sgpr(ld32u(in + 4)), n = h1 & 0xFFFFFF, v2 = h1 >> 24;
     if (type <= 2 && only_over) return;
-    if (rans2_dec_plain(type, in, end, n, v2, out)) return;
+    if (rans2_dec_plain(type, in, end, n, v2, out, packed)) return;
     const uint32_t N = v2 + 2;
     const uint32_t h2 = sgpr(ld32u(in + 8));
     const int pb = (int)(h2 >> 24);
@@ -204,12 +204,17 @@ __device__ __forceinline__ void rans2_decode_stream(const DecTile *__restrict__ 
             __syncthreads();                                                                                      \
         }                                                                                                         \
     } while (0)
-    // uniform: symbols [base, min(base+512, n)) leave the LDS ring
+    // uniform: symbols [base, min(base+512, n)) leave the LDS ring (packed: two to a byte, rans_dec.hpp; base is even)
 #define XPNG_DEC_FLUSH(base)                                                                                      \
     do {                                                                                                          \
         __syncthreads();                                                                                          \
         const uint32_t hi_ = (base) + 512 < n ? (base) + 512 : n;                                                 \
-        for (uint32_t i_ = (base) + lane; i_ < hi_; i_ += 64) out[i_] = oring[i_ & 511u];                          \
+        if (packed) {                                                                                             \
+            for (uint32_t i_ = (base) + 2 * lane; i_ < hi_; i_ += 128)                                            \
+                out[i_ >> 1] = (uint8_t)ctxn_byte(oring[i_ & 511u], i_ + 1 < hi_ ? oring[(i_ + 1) & 511u] : 0u);  \
+        } else {                                                                                                  \
+            for (uint32_t i_ = (base) + lane; i_ < hi_; i_ += 64) out[i_] = oring[i_ & 511u];                     \
+        }                                                                                                         \
         __syncthreads();                                                                                          \
     } while (0)
     // one symbol out of this lane's state -> sym; need = the state must refill
@@ -320,7 +325,8 @@ __global__ __launch_bounds__(64) void k_rans2_decode(const DecTile *__restrict__
 template <int MAXPB>
 __global__ __launch_bounds__(64) void k_rans2_decode_rest(const DecTile *__restrict__ info, const TileDesc *__restrict__ tiles, TileSel sel,
                                                           uint32_t total, uint32_t c_first, uint32_t c_count, uint8_t *__restrict__ ctxsym,
-                                                          uint8_t *__restrict__ asym, uint64_t *__restrict__ dbg, const WDec *__restrict__ wdec) {
+                                                          uint8_t *__restrict__ asym, uint64_t *__restrict__ dbg, const WDec *__restrict__ wdec,
+                                                          uint32_t pk0) {
     const uint32_t lane = threadIdx.x & 63, n = total * c_count;
     for (uint32_t base = blockIdx.x * 64; base < n; base += gridDim.x * 64) {
         const uint32_t idx = base + lane;
@@ -329,7 +335,8 @@ __global__ __launch_bounds__(64) void k_rans2_decode_rest(const DecTile *__restr
         while (m) {
             const uint32_t id2 = sgpr(base + (uint32_t)__builtin_ctzll(m));
             m &= m - 1;
-            rans2_decode_stream<MAXPB, false>(info, tiles, sel, id2 / c_count, c_first + id2 % c_count, 2, ctxsym, asym, dbg);
+            const uint32_t cs = c_first + id2 % c_count;
+            rans2_decode_stream<MAXPB, false>(info, tiles, sel, id2 / c_count, cs, 2, ctxsym, asym, dbg, cs < 9 && id2 / c_count >= pk0);
             __syncthreads();
         }
     }
@@ -660,14 +667,18 @@ __global__ __launch_bounds__(64) void k_dec_walk(const DecTile *__restrict__ inf
 // --------------------------------------------------------------------------------------------------
 // The same walk for large batches: one LANE per tile, 64 tiles per wave (k_dec_walk keeps a whole wave, and 9 KB of
 // LDS, busy per tile; with thousands of tiles in flight that footprint, not the chain latency, is what hurts).
-//   head[c][lane]  = { bytes left in the current dword of queue c (next symbol lowest), position, the following dword }
-//   ringw[c][w][lane] = 64-byte window of queue c as 16 dwords, lane-minor so that 64 lanes never share a bank
+// Its queues are PACKED, two symbols to a byte (rans_dec.hpp has the layout and the ctxn_* arithmetic; the producers pack every work
+// item from this kernel's j0 on): a dword holds 8 symbols, a 16-byte chunk 32.
+//   head[c][lane]  = { symbols left in the current dword of queue c (next symbol in the lowest nibble), position, the following dword }
+//   ringw[c][w][lane] = 64-byte window of queue c (128 symbols) as 16 dwords, lane-minor so that 64 lanes never share a bank
 // The dependent chain of a step is ONE LDS round trip: ds_read_b128 head[cur] -> symbol -> cur.  The bookkeeping of the
 // previous step (advance the position, pull the next window dword, write the head back) is issued behind that read and
 // completes while it is in flight; when the same queue is popped twice in a row the read is stale and the registers of
 // the previous step are forwarded instead.  Queue 9 is a parking queue that returns 9 forever: a lane whose tile is
-// finished walks it.  Global memory is touched only at 16-step block boundaries: aligned 16-byte chunks are requested for a
-// queue at one service and land in its window at the next (the chunk starts are 16-byte aligned, k_dec_parse).
+// finished walks it.  Global memory is touched only at 16-step block boundaries: ONE aligned 16-byte chunk is requested for a
+// queue at one service (every 32 steps) and lands in its window at the next (the chunk starts are 16-byte aligned, k_dec_parse) -
+// 9 loads per lane and 32 steps.  (With a symbol to a byte a chunk held 16 symbols, a queue could lose two chunks between two
+// services and each service had to request two: 18 loads, of which roughly eight in nine were requested again later.)
 // LPW = tiles per wavefront (lanes 0 .. LPW - 1 carry one each, the others idle through the loop): the LDS of a wavefront is 800 LPW
 // bytes - 51 KB at 64.  [r4] A workgroup that asks for 51 KB is placed only when a compute unit has that much free at once, and the
 // chip-filling kernels of the other pipeline slots re-occupy every smaller hole at once: profiles/r03_wave_probe_p4.txt has the
@@ -675,14 +686,16 @@ __global__ __launch_bounds__(64) void k_dec_walk(const DecTile *__restrict__ inf
 // of work spans ~30.  With 32 tiles per wavefront a workgroup asks for 25.6 KB (and waits for 288 scattered lines per service
 // instead of 576); the price is twice the wavefronts, i.e. twice the walk's vector instructions.
 constexpr uint32_t WALK_WIDE_COLS(uint32_t lpw) { return lpw + (lpw < 64 ? 1u : 0u); }  // LDS columns: one per tile + one that the idle lanes share
-constexpr size_t WALK_WIDE_LDS_BYTES(uint32_t lpw) { return 10 * (size_t)WALK_WIDE_COLS(lpw) * 16 + 10 * 16 * (size_t)WALK_WIDE_COLS(lpw) * 4; }  // heads + windows (k_dec_walk_wide)
+constexpr uint32_t WALK_WIDE_WCH = 4;  // 16-byte chunks (32 symbols each) in a queue's window: 4, or 2 (which does NOT hold the walk's invariant: see k_dec_walk_wide)
+constexpr size_t WALK_WIDE_LDS_BYTES(uint32_t lpw) { return 10 * (size_t)WALK_WIDE_COLS(lpw) * 16 + 10 * 4 * WALK_WIDE_WCH * (size_t)WALK_WIDE_COLS(lpw) * 4; }  // heads + windows (k_dec_walk_wide)
 template <uint32_t LPW>
 __global__ __launch_bounds__(64) void k_dec_walk_wide(const DecTile *__restrict__ info, const TileDesc *__restrict__ tiles,
                                                       TileSel sel, uint32_t total_tiles, const uint8_t *__restrict__ ctxsym,
                                                       uint8_t *__restrict__ nlseq, uint32_t j0) {
     // window: WCH chunks of 16 B per queue; a queue is serviced every SVC-th block.  (8 chunks / every 4th block is ~8 % faster
     // alone, but 90 KB of LDS per wave instead of 50 costs the kernels beside it more than that.)
-    constexpr uint32_t WCH = 4, SVC = 2, WDW = WCH * 4, lpw = LPW, COLS = WALK_WIDE_COLS(LPW);
+    constexpr uint32_t WCH = WALK_WIDE_WCH, SVC = 2, INIT = 2, WDW = WCH * 4, lpw = LPW, COLS = WALK_WIDE_COLS(LPW);
+    static_assert(16 * SVC == CTXN_CHUNK && INIT <= WCH, "one chunk is what a queue can lose between two of its services");
     static_assert(WALK_WIDE_LDS_BYTES(LPW) == 10 * COLS * 16 + 10 * WDW * COLS * 4 && LPW >= 8 && LPW <= 64, "LDS layout");
     extern __shared__ __align__(16) uint8_t walk_wide_lds[];  // dynamic (common.hpp: why)
     u32x4_t *const head = reinterpret_cast<u32x4_t *>(walk_wide_lds);                         // [10 * COLS]
@@ -704,7 +717,7 @@ __global__ __launch_bounds__(64) void k_dec_walk_wide(const DecTile *__restrict_
     const uint32_t seq_here = (dh->type != 0 && dh->type != TILE_BAD) ? dh->ctx_start[9] : 0u;
     const uint32_t dump = (seq_here + 15u) & ~15u;
     uint32_t qoff[9], have[9];
-    u32x4_t fl[9][SVC];  // in flight per queue: chunks have .. have + SVC - 1
+    u32x4_t fl[9];  // in flight per queue: chunk `have`
     typedef const __attribute__((address_space(1))) u32x4_t *gp128;
     const u32x4_t zero4 = {0, 0, 0, 0};
 #pragma unroll
@@ -712,27 +725,27 @@ __global__ __launch_bounds__(64) void k_dec_walk_wide(const DecTile *__restrict_
         qoff[c] = live ? d->ctx_start[c] : 0;
         const gp128 src = (gp128)(base + qoff[c]);
 #pragma unroll
-        for (int q = 0; q < (int)SVC; q++) {
+        for (int q = 0; q < (int)INIT; q++) {
             u32x4_t v = zero4;
             if (live) v = src[q];
             ringw[(c * WDW + q * 4 + 0) * COLS + lane] = v.x; ringw[(c * WDW + q * 4 + 1) * COLS + lane] = v.y;
             ringw[(c * WDW + q * 4 + 2) * COLS + lane] = v.z; ringw[(c * WDW + q * 4 + 3) * COLS + lane] = v.w;
             if (q == 0) { const u32x4_t h = {v.x, 0u, v.y, 0u}; head[c * COLS + lane] = h; }
         }
-        have[c] = SVC;
-#pragma unroll
-        for (int q = 0; q < (int)SVC; q++) { fl[c][q] = zero4; if (live) fl[c][q] = src[SVC + q]; }
+        have[c] = INIT;
+        fl[c] = zero4;
+        if (live) fl[c] = src[INIT];
     }
 #pragma unroll
-    for (int w = 0; w < (int)WDW; w++) ringw[(9 * WDW + w) * COLS + lane] = 0x09090909u;
-    { const u32x4_t h = {0x09090909u, 0u, 0x09090909u, 0u}; head[9 * COLS + lane] = h; }
+    for (int w = 0; w < (int)WDW; w++) ringw[(9 * WDW + w) * COLS + lane] = 0x99999999u;
+    { const u32x4_t h = {0x99999999u, 0u, 0x99999999u, 0u}; head[9 * COLS + lane] = h; }
     uint32_t T = total;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { const uint32_t v = __shfl_xor(T, o); T = v > T ? v : T; }
     T = sgpr(T);
     uint32_t cur = total > 0 ? 0u : 9u;
     // registers of the previous step: its queue and the head it popped from (lo, pos, nxt); queue 9 at start (harmless)
-    uint32_t pcur = 9, plo = 0x09090909u, ppos = 0, pnxt = 0x09090909u;
+    uint32_t pcur = 9, plo = 0x99999999u, ppos = 0, pnxt = 0x99999999u;
     auto block = [&](uint32_t kb) __attribute__((always_inline)) {
         uint32_t o[4] = {0, 0, 0, 0};
 #pragma unroll
@@ -740,15 +753,15 @@ __global__ __launch_bounds__(64) void k_dec_walk_wide(const DecTile *__restrict_
             // bookkeeping of the previous step: its window read goes out first, then this step's head read; both are in
             // flight together
             const uint32_t npos = ppos + 1;
-            const bool cross = (npos & 3u) == 0;
-            const uint32_t rr = ringw[(pcur * WDW + (((npos >> 2) + 1) & (WDW - 1))) * COLS + lane];
+            const bool cross = ctxn_cross(npos);
+            const uint32_t rr = ringw[(pcur * WDW + ((ctxn_dword(npos) + 1) & (WDW - 1))) * COLS + lane];
             const u32x4_t r = head[cur * COLS + lane];               // (stale if cur == pcur: forwarded below)
-            const uint32_t nlo = cross ? pnxt : plo >> 8, nnxt = cross ? rr : pnxt;
+            const uint32_t nlo = cross ? pnxt : ctxn_pop(plo), nnxt = cross ? rr : pnxt;
             { const u32x4_t h = {nlo, npos, nnxt, 0u}; head[pcur * COLS + lane] = h; }
             const bool same = cur == pcur;
             plo = same ? nlo : r.x; ppos = same ? npos : r.y; pnxt = same ? nnxt : (r.z | r.w);  // (r.w == 0; keeps the 4th register of the read alive so nothing else is loaded into it early)
             pcur = cur;
-            const uint32_t sym = plo & 255u;
+            const uint32_t sym = ctxn_sym(plo);
             o[u >> 2] |= sym << (8 * (u & 3));
             cur = kb + (uint32_t)u + 1 >= total ? 9u : (sym < 9u ? sym : 9u);  // (symbols > 8 only in corrupt streams)
         }
@@ -758,29 +771,31 @@ __global__ __launch_bounds__(64) void k_dec_walk_wide(const DecTile *__restrict_
         *reinterpret_cast<uint4 *>(out + (kb < total ? kb : dump)) = make_uint4(o[0], o[1], o[2], o[3]);
     };
     // Service of the queues of one phase, every SVC-th block boundary (so a request has 16 * SVC steps, not 16, to come back:
-    // 64 lanes x 9 queues are 576 different cache lines per round).  Up to SVC
-    // chunks land while their window slots have been read out; after a service the window holds >= 16 * SVC unread bytes
-    // (SVC blocks' worth) or everything up to its capacity; the next SVC missing chunks are requested again either way.
+    // 64 lanes x 9 queues are 576 different cache lines per round).  ONE chunk is in flight per queue: it lands when the slot it
+    // goes to has been read out, and the next missing chunk is requested again either way.  Between two services a queue loses at
+    // most 16 * SVC = 32 symbols, one chunk, so a landing per service keeps up with it.  What the window must hold behind a service
+    // at position p is the 32 symbols that may go and the dword behind them that the head looks ahead to: dwords up to
+    // (p >> 3) + 5, i.e. chunk (p >> 5) + 2 when p sits in its chunk's last dword.  With WCH = 4 the service keeps
+    // have >= (p >> 5) + 3 (it starts at INIT = 2 chunks at p = 0, where chunk 1 is enough, and every service that sees the
+    // position in a new chunk has room to land one).  With WCH = 2 the window cannot hold chunk (p >> 5) + 2 at all: a queue
+    // popped on every step (a flat raster's queue 0) reads a dword that has not landed.  tests/ctx_nibbles_host.cpp runs this
+    // rule for both sizes; only the four-chunk form passes, so that is the one built.
     // (The head of queue pcur in LDS is one pop behind the registers; a chunk index can only be underestimated by that.)
     auto service = [&](int phase) __attribute__((always_inline)) {
 #pragma unroll
         for (int c = 0; c < 9; c++) {
             if ((c & (int)(SVC - 1)) != phase) continue;
-            const uint32_t cq = head[c * COLS + lane].y >> 4;  // chunk the queue is reading from
-#pragma unroll
-            for (int q = 0; q < (int)SVC; q++) {
-                if (have[c] - cq < WCH) {  // (once one chunk does not fit, neither do the later ones: have stops growing)
-                    const uint32_t w0 = (c * WDW + (have[c] & (WCH - 1)) * 4) * COLS + lane;
-                    ringw[w0] = fl[c][q].x; ringw[w0 + COLS] = fl[c][q].y; ringw[w0 + 2 * COLS] = fl[c][q].z; ringw[w0 + 3 * COLS] = fl[c][q].w;
-                    have[c]++;
-                }
+            const uint32_t cq = ctxn_chunk(head[c * COLS + lane].y);  // chunk the queue is reading from
+            if (have[c] - cq < WCH) {
+                const uint32_t w0 = (c * WDW + (have[c] & (WCH - 1)) * 4) * COLS + lane;
+                ringw[w0] = fl[c].x; ringw[w0 + COLS] = fl[c].y; ringw[w0 + 2 * COLS] = fl[c].z; ringw[w0 + 3 * COLS] = fl[c].w;
+                have[c]++;
             }
-            {   // (unconditional: a branch around these loads makes the compiler copy the loaded registers into the loop-carried
-                //  ones, and a copy is a use - it waits for the loads it has just issued; lanes without a tile read their
+            {   // (unconditional: a branch around this load makes the compiler copy the loaded registers into the loop-carried
+                //  ones, and a copy is a use - it waits for the load it has just issued; lanes without a tile read their
                 //  placeholder tile's bytes, which nobody looks at)
                 const gp128 src = (gp128)(base + qoff[c]) + have[c];
-#pragma unroll
-                for (int q = 0; q < (int)SVC; q++) fl[c][q] = src[q];
+                fl[c] = src[0];
             }
         }
     };
@@ -1113,6 +1128,8 @@ inline int decode_ws_prepare(DecodeWs &ws, WsTable &tab, const DecodeJob &j, std
     return 0;
 }
 
+constexpr uint32_t WD_CTX_STREAMS = 32, WD_ALPHA_STREAMS = 32;  // streams per chain wavefront (16 alpha streams per wave - half the LDS per workgroup, twice the waves - measures the same)
+
 // What decode_m1_launch decides before its first kernel.
 struct DecodePlan {
     // Many tiles in flight: instruction issue is the bound, so the rANS chains run 32 streams to a wave (rans2_wide_dec.hpp);
@@ -1123,6 +1140,7 @@ struct DecodePlan {
     bool fold;
     bool split;   // two size classes on two streams (see decode_m1_launch)
     uint32_t jb;  // split: work items [0, jb) are the big-tile class
+    uint32_t pk0;  // work items from pk0 on go to the lane-per-tile walk: their context queues are packed (rans_dec.hpp); `total` = none
     ReconPlan recon;  // the form of the reconstruction (recon.hpp)
     // probe builds: bytes of unused dynamic LDS per workgroup (occupancy throttles); all 0 in the release library
     size_t pad_chain, pad_alpha, pad_walk, pad_resid;
@@ -1134,7 +1152,12 @@ inline DecodePlan decode_m1_plan(const DecodeJob &j) {
     p.fold = j.pxsz == 4 && j.min_w >= 4 && !probe_env("XPNG_NO_ALPHA_FOLD");
     p.recon = recon_geometry(j.max_w, j.max_h, p.wide);
     p.split = p.recon.band && !j.list && j.order && j.n_big > 0 && j.n_big < cnt && !probe_env("XPNG_NARROW_WALK") && !getenv("XPNG_NO_SPLIT");
-    p.jb = p.split ? j.n_big * j.B : 0;
+    // (the big-tile class keeps a symbol to a byte for the scalar walk, the rest is packed for the lane-per-tile walk: the class
+    //  boundary is rounded down to a whole wavefront of context chains, which then produces one form or the other)
+    p.jb = p.split ? j.n_big * j.B / WD_CTX_STREAMS * WD_CTX_STREAMS : 0;
+    p.split = p.jb > 0;
+    const bool lane_walk = p.split || (p.wide && !probe_env("XPNG_NARROW_WALK"));
+    p.pk0 = lane_walk ? p.jb : total;
     p.pad_chain = probe_pad("XPNG_PAD_CHAIN"); p.pad_alpha = probe_pad("XPNG_PAD_AL"); p.pad_walk = probe_pad("XPNG_PAD_WALK");
     p.pad_resid = probe_pad("XPNG_PAD_RS");
     return p;
@@ -1177,15 +1200,14 @@ inline int decode_m1_launch(DecodeWs &ws, WsTable &tab, const DecodeJob &j, std:
 
     // ---- parse + prep
     k_dec_parse<<<(total + 63) / 64, 64, 0, s>>>(j.blobs, ws.d_off, j.blob_len, cnt, total, spt, j.pxsz, j.tiles, sel, ws.d_info, j.status);
-    constexpr uint32_t WD_CTX_STREAMS = 32, WD_ALPHA_STREAMS = 32;  // (16 alpha streams per wave - half the LDS per workgroup, twice the waves - measures the same)
     const uint32_t groups = (total + WD_CTX_STREAMS - 1) / WD_CTX_STREAMS, agroups = (total + WD_ALPHA_STREAMS - 1) / WD_ALPHA_STREAMS;
-    if (p.wide && !dbg_skip("dec_prep")) k_rans2_dec_prep<<<total * spt, 64, 0, s>>>(ws.d_info, j.tiles, sel, spt, ws.d_ctxsym, ws.d_asym, ws.d_wdec, ws.d_dtab);
+    if (p.wide && !dbg_skip("dec_prep")) k_rans2_dec_prep<<<total * spt, 64, 0, s>>>(ws.d_info, j.tiles, sel, spt, ws.d_ctxsym, ws.d_asym, ws.d_wdec, ws.d_dtab, p.pk0);
 
     // ---- alpha branch, on the side stream: its rANS block is the longest serial chain of a tile, and it is independent of the
     // nl-context branch (nine short rANS blocks, then the serial context walk) until k_dec_resid
     if (rgba) {
         if (hipEventRecord(ws.ev_fork, s) != hipSuccess || hipStreamWaitEvent(side, ws.ev_fork, 0) != hipSuccess) return bad("fork failed");
-        if (p.wide && !probe_env("XPNG_NARROW_ALPHA")) { if (!dbg_skip("dec_chain_a")) k_rans2_dec_chain<true, WD_ALPHA_STREAMS, true><<<agroups, 64, DecChainLds<true, WD_ALPHA_STREAMS>::BYTES + p.pad_chain, side>>>(ws.d_info, total, 9, 1, ws.d_wdec, ws.d_dtab, ws.d_ctxsym, ws.d_asym); }
+        if (p.wide && !probe_env("XPNG_NARROW_ALPHA")) { if (!dbg_skip("dec_chain_a")) k_rans2_dec_chain<true, WD_ALPHA_STREAMS, true><<<agroups, 64, DecChainLds<true, WD_ALPHA_STREAMS>::BYTES + p.pad_chain, side>>>(ws.d_info, total, 9, 1, ws.d_wdec, ws.d_dtab, ws.d_ctxsym, ws.d_asym, total); }
         else k_rans2_decode<15><<<total, 64, 0, side>>>(ws.d_info, j.tiles, sel, 9, 1, 0, ws.d_ctxsym, ws.d_asym, j.stamps);
         if (p.fold || dbg_skip("dec_alpha")) {} else if (p.wide) k_dec_alpha<256><<<total, 256, p.pad_alpha, side>>>(ws.d_info, j.tiles, sel, ws.d_asym, ws.d_alpha);
         else k_dec_alpha<1024><<<total, 1024, 0, side>>>(ws.d_info, j.tiles, sel, ws.d_asym, ws.d_alpha);
@@ -1194,9 +1216,9 @@ inline int decode_m1_launch(DecodeWs &ws, WsTable &tab, const DecodeJob &j, std:
 
     // ---- context chains
     if (p.wide) {
-        if (!dbg_skip("dec_chain_c")) k_rans2_dec_chain<false, WD_CTX_STREAMS, false><<<groups * 9, 64, DecChainLds<false, WD_CTX_STREAMS>::BYTES + p.pad_chain, s>>>(ws.d_info, total, 0, 9, ws.d_wdec, ws.d_dtab, ws.d_ctxsym, ws.d_asym);
+        if (!dbg_skip("dec_chain_c")) k_rans2_dec_chain<false, WD_CTX_STREAMS, false><<<groups * 9, 64, DecChainLds<false, WD_CTX_STREAMS>::BYTES + p.pad_chain, s>>>(ws.d_info, total, 0, 9, ws.d_wdec, ws.d_dtab, ws.d_ctxsym, ws.d_asym, p.pk0);
         // context streams the small layout cannot hold (PROB_BITS > 12 or more than 16 symbols: never written by the reference)
-        if (!dbg_skip("dec_odd")) k_rans2_decode_rest<15><<<128, 64, 0, s>>>(ws.d_info, j.tiles, sel, total, 0, 9, ws.d_ctxsym, ws.d_asym, j.stamps, ws.d_wdec);
+        if (!dbg_skip("dec_odd")) k_rans2_decode_rest<15><<<128, 64, 0, s>>>(ws.d_info, j.tiles, sel, total, 0, 9, ws.d_ctxsym, ws.d_asym, j.stamps, ws.d_wdec, p.pk0);
         // (k_rans2_decode_rest resolves slots by binary search: 4.6 KB of LDS, so its 128 workgroups are placed at once - with the
         //  37 KB slot table of k_rans2_decode<15> they waited up to 5 ms, between the chains and the walk, to find nothing to do)
     } else {

@@ -13,7 +13,10 @@
 // The chain loop touches global memory only at block boundaries (every 8 steps): renormalisation words are staged
 // through a 64-word LDS ring per stream, refilled by loads that are issued at one boundary and landed at the next
 // (so no s_waitcnt for global memory sits inside the 8 steps), and decoded symbols leave as one aligned 16-byte
-// store per stream and block.
+// store per stream and block - or, for the context streams of a work item that the lane-per-tile walk will read (from the launch
+// argument pk0 on), two symbols to a byte (rans_dec.hpp: ctxn_*) as one aligned 8-byte store: a lane gathers its eight symbols of a
+// block in two registers, one shift-or per step instead of an LDS byte store, and the pair merges them at the boundary with one
+// cross-lane move per dword.  k_rans2_dec_prep packs the blocks it finishes itself (types 1 and 2) the same way.
 #pragma once
 #include "common.hpp"
 #include "rans_dec.hpp"
@@ -24,7 +27,7 @@ namespace xpng {
 __global__ __launch_bounds__(64) void k_rans2_dec_prep(const DecTile *__restrict__ info, const TileDesc *__restrict__ tiles,
                                                        TileSel sel, uint32_t spt, uint8_t *__restrict__ ctxsym,
                                                        uint8_t *__restrict__ asym, WDec *__restrict__ wdec,
-                                                       uint8_t *__restrict__ dtab) {
+                                                       uint8_t *__restrict__ dtab, uint32_t pk0) {
     bw_prio();
     __shared__ uint32_t fc[256];
     __shared__ uint32_t Fs[260];
@@ -42,7 +45,7 @@ __global__ __launch_bounds__(64) void k_rans2_dec_prep(const DecTile *__restrict
     const uint32_t csz = h0 & 0xFFFFFF;
     const uint8_t *end = in + csz;
     const uint32_t h1 = sgpr(ld32u(in + 4)), n = h1 & 0xFFFFFF, v2 = h1 >> 24;
-    if (rans2_dec_plain(type, in, end, n, v2, out)) return;
+    if (rans2_dec_plain(type, in, end, n, v2, out, c < 9 && j >= pk0)) return;  // (work items from pk0 on: packed context queues, rans_dec.hpp)
     const uint32_t N = v2 + 2;
     const uint32_t h2 = sgpr(ld32u(in + 8));
     const uint32_t pb = h2 >> 24;  // 10..15, checked by k_dec_parse
@@ -105,7 +108,7 @@ template <bool BIG, int STREAMS, bool HOT>
 __global__ __launch_bounds__(64) void k_rans2_dec_chain(const DecTile *__restrict__ info, uint32_t total, uint32_t c_first,
                                                         uint32_t c_count, const WDec *__restrict__ wdec,
                                                         const uint8_t *__restrict__ dtab, uint8_t *__restrict__ ctxsym,
-                                                        uint8_t *__restrict__ asym) {
+                                                        uint8_t *__restrict__ asym, uint32_t pk0) {
     __builtin_amdgcn_s_setprio(XPNG_CHAIN_PRIO);  // a serial chain: its latency is the critical path, the throughput kernels beside it are not
     XPNG_PROBE_BEGIN()
     typedef typename std::conditional<BIG, WdLayoutA, WdLayout<false>>::type L;
@@ -122,6 +125,9 @@ __global__ __launch_bounds__(64) void k_rans2_dec_chain(const DecTile *__restric
     const uint32_t c = c_first + blockIdx.x % c_count, grp = blockIdx.x / c_count;
     const uint32_t j = grp * WD_STREAMS + kraw;
     bool live = kraw < WD_STREAMS && j < total;
+    // context streams of packed work items (from pk0 on, a multiple of STREAMS: the whole wavefront or none of it) leave two symbols
+    // to a byte (rans_dec.hpp: the layout): 8 bytes per block and stream, gathered in registers instead of the LDS staging bytes
+    const bool packed = !BIG && sgpr(grp * WD_STREAMS) >= pk0;
     wd_load_tables<L, LTAB, WD_STREAMS>(ltab, grp * WD_STREAMS, total, wdec, dtab, 10, c);
     __syncthreads();
     const WDec *wd = wdec + (uint64_t)(live ? j : 0) * 10 + c;
@@ -177,7 +183,8 @@ __global__ __launch_bounds__(64) void k_rans2_dec_chain(const DecTile *__restric
     uint32_t cm[10];  // small layout (nl-context streams, at most 9 symbols): the cumulative counts c1..c9 of wd_reg9
     wd_cm_load<!BIG>(cm, live, wd, a_fc, pb);
     // one symbol out of this lane's state, the pair's renormalisation (state1 refills first, libxpng.c:486-487)
-    auto step = [&](bool act, uint32_t obpos) __attribute__((always_inline)) -> uint32_t {
+    uint32_t acc0 = 0, acc1 = 0;  // packed: this lane's symbols of pair steps 0..3 and 4..7 of the block, one to a byte
+    auto step = [&](auto pk, bool act, uint32_t obpos, uint32_t u) __attribute__((always_inline)) -> uint32_t {
         const uint32_t slot = slo & mask;
         uint32_t sym, F, off;
         const uint32_t d0 = slot - hC0, d1 = slot - hC1;
@@ -245,12 +252,23 @@ __global__ __launch_bounds__(64) void k_rans2_dec_chain(const DecTile *__restric
         const uint32_t cons = needi + other;
         wi = (wi - cons) & (WD_RING - 1);
         fetch_w();
-        *(lds8 *)(uintptr_t)(a_ob + (act ? obpos : 16u)) = (uint8_t)sym;
+        if constexpr (decltype(pk)::value) {  // (u is a constant of the unrolled block: one shift-or; an inactive step leaves its place alone)
+            if (u < 4) acc0 = ctxn_gather(acc0, act ? sym : 0u, u); else acc1 = ctxn_gather(acc1, act ? sym : 0u, u);
+        } else {
+            *(lds8 *)(uintptr_t)(a_ob + (act ? obpos : 16u)) = (uint8_t)sym;
+        }
         return sym;
     };
     if (n & 1) {  // odd tail comes from state0 only (libxpng.c:471-476)
-        const uint32_t sym = step(par == 0, (n - 1) & 15u);
-        if (par == 0) out[n - 1] = (uint8_t)sym;
+        const uint32_t sym = step(std::false_type{}, par == 0, (n - 1) & 15u, 0);
+        if (par == 0 && !packed) out[n - 1] = (uint8_t)sym;
+        if (par == 0 && packed) {
+            // a byte of its own (the nibble above it lies behind the stream's end), and its place in the stream's top block, whose
+            // 8-byte store covers that byte - unless the pairs fill their blocks exactly: then the tail's block is never stored
+            out[(n - 1) >> 1] = (uint8_t)sym;
+            const uint32_t ut = npairs & 7u;
+            if (ut) { if (ut < 4) acc0 = ctxn_gather(0u, sym, ut); else acc1 = ctxn_gather(0u, sym, ut); }
+        }
     }
     // the wave's trip count, and the pairs every lane is inside its stream for (a lane without a chain steps on the identity entry
     // whatever the variant: it counts as 0xFFFFFFFF pairs, and the minimum is the complement's maximum)
@@ -259,49 +277,64 @@ __global__ __launch_bounds__(64) void k_rans2_dec_chain(const DecTile *__restric
     //  that of the back edge conservatively, and a load still in flight from before the loop turns into a wait at the top of
     //  EVERY iteration - right behind the block loads the previous iteration has just issued)
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-    for (uint32_t jb = T; jb > 0;) {
-        jb -= 8;
-        const uint32_t wi0 = wi;
-        if (jb + 8 <= Tmin) {  // every lane of the wave is inside its stream
+    // the loop, once per output form (pk: packed); a wavefront runs one of them
+    auto run = [&](auto pk) __attribute__((always_inline)) {
+        for (uint32_t jb = T; jb > 0;) {
+            jb -= 8;
+            const uint32_t wi0 = wi;
+            if (jb + 8 <= Tmin) {  // every lane of the wave is inside its stream
 #pragma unroll
-            for (int u = 7; u >= 0; u--) step(true, 2 * (uint32_t)u + par);
-        } else {
+                for (int u = 7; u >= 0; u--) step(pk, true, 2 * (uint32_t)u + par, (uint32_t)u);
+            } else {
 #pragma unroll
-            for (int u = 7; u >= 0; u--) step(jb + (uint32_t)u < npairs, 2 * (uint32_t)u + par);
-        }
-        rw -= (wi0 - wi) & (WD_RING - 1);  // words the pair consumed in this block (at most two per step)
-        // ---- block boundary: in-flight words land, symbols out, next words requested
-        // (landing first: its wait then covers only what the previous boundary issued, 8 steps ago, not this block's store)
-        XPNG_PROBE_WAIT()
-        XPNG_PROBE_ISSUE_BEGIN()
-        wd_land<WD_RING>(a_ring, q0, q1, qx, fa0, fhi, fsh);  // (unconditional, like the request below: fhi == 0 when nothing was requested)
-        *(lds32 *)(uintptr_t)(a_ring - 4) = *ring_w(WD_RING - 1);
-        if (jb < npairs && par == 0) *reinterpret_cast<u32x4_t *>(out + 2ull * jb) = *(const lds128_al4 *)(uintptr_t)a_ob;
-        lo = lof;
-        {
-            int32_t want = (int32_t)lo - (int32_t)(2 * PER);
-            const int32_t room = (int32_t)rw - (int32_t)WD_RING;
-            want = want > room ? want : room;
-            want = want > 0 ? want : 0;
-            {   // The loads are issued on every boundary, from a clamped address when there is nothing to fetch (fhi = 0 then keeps
-                // the landing from writing): a branch around them makes the compiler load into temporaries and copy those into
-                // the loop-carried registers at once - a wait for loads it has just issued, once per block.
-                const bool any = (uint32_t)want < lo;
-                const uint32_t a0r = (uint32_t)want + PER * par;
-                const bool req = any && a0r < lo;
-                const uint32_t a0 = req ? a0r : 0u;
-                const uintptr_t A = words_safe + 4ull * a0;
-                const gptr32 p = (gptr32)(A & ~(uintptr_t)3);
-                const u32x4_a4 v0 = *(gptr128)p;
-                q0 = make_uint4(v0.x, v0.y, v0.z, v0.w);
-                if (PER > 4) { const u32x4_a4 v1 = *(gptr128)(p + 4); q1 = make_uint4(v1.x, v1.y, v1.z, v1.w); }
-                qx = p[PER];
-                fa0 = a0; fhi = req ? lo : 0u; fsh = (uint32_t)(A & 3);
-                lof = any ? (uint32_t)want : lof;
+                for (int u = 7; u >= 0; u--) step(pk, jb + (uint32_t)u < npairs, 2 * (uint32_t)u + par, (uint32_t)u);
             }
+            rw -= (wi0 - wi) & (WD_RING - 1);  // words the pair consumed in this block (at most two per step)
+            // ---- block boundary: in-flight words land, symbols out, next words requested
+            // (landing first: its wait then covers only what the previous boundary issued, 8 steps ago, not this block's store)
+            XPNG_PROBE_WAIT()
+            XPNG_PROBE_ISSUE_BEGIN()
+            wd_land<WD_RING>(a_ring, q0, q1, qx, fa0, fhi, fsh);  // (unconditional, like the request below: fhi == 0 when nothing was requested)
+            *(lds32 *)(uintptr_t)(a_ring - 4) = *ring_w(WD_RING - 1);
+            if constexpr (decltype(pk)::value) {
+                // the pair's 16 symbols: one cross-lane move per dword, the odd lane's (state 1) symbols into the high nibbles.  A block
+                // that is not stored (the stream has not begun: every step inactive) keeps its registers - they may hold the odd tail
+                const bool st = jb < npairs;
+                const uint32_t m0 = ctxn_merge(acc0, swap_pair(acc0)), m1 = ctxn_merge(acc1, swap_pair(acc1));
+                if (st && par == 0) *reinterpret_cast<uint2 *>(out + jb) = make_uint2(m0, m1);
+                acc0 = st ? 0u : acc0; acc1 = st ? 0u : acc1;
+            } else {
+                if (jb < npairs && par == 0) *reinterpret_cast<u32x4_t *>(out + 2ull * jb) = *(const lds128_al4 *)(uintptr_t)a_ob;
+            }
+            lo = lof;
+            {
+                int32_t want = (int32_t)lo - (int32_t)(2 * PER);
+                const int32_t room = (int32_t)rw - (int32_t)WD_RING;
+                want = want > room ? want : room;
+                want = want > 0 ? want : 0;
+                {   // The loads are issued on every boundary, from a clamped address when there is nothing to fetch (fhi = 0 then keeps
+                    // the landing from writing): a branch around them makes the compiler load into temporaries and copy those into
+                    // the loop-carried registers at once - a wait for loads it has just issued, once per block.
+                    const bool any = (uint32_t)want < lo;
+                    const uint32_t a0r = (uint32_t)want + PER * par;
+                    const bool req = any && a0r < lo;
+                    const uint32_t a0 = req ? a0r : 0u;
+                    const uintptr_t A = words_safe + 4ull * a0;
+                    const gptr32 p = (gptr32)(A & ~(uintptr_t)3);
+                    const u32x4_a4 v0 = *(gptr128)p;
+                    q0 = make_uint4(v0.x, v0.y, v0.z, v0.w);
+                    if (PER > 4) { const u32x4_a4 v1 = *(gptr128)(p + 4); q1 = make_uint4(v1.x, v1.y, v1.z, v1.w); }
+                    qx = p[PER];
+                    fa0 = a0; fhi = req ? lo : 0u; fsh = (uint32_t)(A & 3);
+                    lof = any ? (uint32_t)want : lof;
+                }
+            }
+            XPNG_PROBE_ISSUE_END()
         }
-        XPNG_PROBE_ISSUE_END()
-    }
+    };
+    if constexpr (BIG) run(std::false_type{});
+    else if (packed) run(std::true_type{});
+    else run(std::false_type{});
     XPNG_PROBE_END(BIG ? 4 : 3)
 }
 

@@ -6,6 +6,7 @@
 // chain kernels share every piece of their step that does not depend on the direction they decode in.  Here:
 //   types      DecTile, WDec, the table layouts, the address-space typedefs, the unaligned loads, the bit readers
 //   look-up    rans_dec_owner (slot -> symbol over fc[]), wd_reg9 (the same over nine counts in registers), wd_advance (the state update)
+//   nibbles    ctxn_* (the packed context queues between the wide v2 decoders and the lane-per-tile walk: the layout and its arithmetic)
 //   set-up     rans_dec_cum, rans2_dec_freqs, rans2_dec_plain / rans1_dec_plain (the blocks that need no chain)
 //   wide prep  wd_store_tables
 //   wide chain WdChainLds, wd_load_tables, wd_cm_load, wd_land, wave_max
@@ -165,6 +166,29 @@ __device__ __forceinline__ bool wd_advance(uint32_t slo, uint32_t shi, uint32_t 
 }
 // (end of the host-run pieces)
 
+// ---- context symbols at four bits (tests/test_ctx_nibbles_host.py runs the text from here to the end mark on the host) -----------
+// The wide level-1 decode hands the nine context queues of a PACKED work item (every work item of the lane-per-tile walk
+// k_dec_walk_wide; the first one is a launch argument of the producers) from the rANS kernels to the walk two symbols to a byte:
+//     symbol i of queue c = nibble (i & 1), low nibble first, of byte ctx_start[c] + (i >> 1)
+// so a dword holds 8 symbols and an aligned 16-byte chunk CTXN_CHUNK = 32 - as many as one queue can lose between two services of
+// the walk.  The symbols are nl = 0..8; anything above (only a stream the reference cannot write) is stored as 9, which the walk
+// turns into "park".  Queue starts stay where k_dec_parse puts them: a packed queue uses the first half of its room.
+constexpr uint32_t CTXN_CHUNK = 32;
+__host__ __device__ __forceinline__ uint32_t ctxn_clamp(uint32_t sym) { return sym < 9u ? sym : 9u; }
+// producers without a pair of lanes: the byte of symbols 2 k (s0) and 2 k + 1 (s1; 0 behind an odd queue's end)
+__host__ __device__ __forceinline__ uint32_t ctxn_byte(uint32_t s0, uint32_t s1) { return ctxn_clamp(s0) | (ctxn_clamp(s1) << 4); }
+// chain: a lane gathers its symbol (< 16) of pair step u = 0..7 of a block into the dword u >> 2 at BYTE u & 3 (low nibble) ...
+__host__ __device__ __forceinline__ uint32_t ctxn_gather(uint32_t acc, uint32_t sym, uint32_t u) { return acc | (sym << (8 * (u & 3u))); }
+// ... and at the block boundary the even lane (state 0: symbols 2 u) takes the odd lane's dword (state 1: symbols 2 u + 1) on top
+__host__ __device__ __forceinline__ uint32_t ctxn_merge(uint32_t even, uint32_t odd) { return even | (odd << 4); }
+// walk: the head dword holds the next symbol lowest; position p lies in dword p >> 3 and chunk p >> 5 of its queue
+__host__ __device__ __forceinline__ uint32_t ctxn_sym(uint32_t lo) { return lo & 15u; }
+__host__ __device__ __forceinline__ uint32_t ctxn_pop(uint32_t lo) { return lo >> 4; }
+__host__ __device__ __forceinline__ bool ctxn_cross(uint32_t npos) { return (npos & 7u) == 0; }
+__host__ __device__ __forceinline__ uint32_t ctxn_dword(uint32_t pos) { return pos >> 3; }
+__host__ __device__ __forceinline__ uint32_t ctxn_chunk(uint32_t pos) { return pos >> 5; }
+// (end of the nibble pieces)
+
 __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) { const uint32_t o = __shfl_xor(v, off); v = o > v ? o : v; }
@@ -208,18 +232,27 @@ __device__ __forceinline__ void rans2_dec_freqs(uint32_t type, uint32_t pb, uint
 }
 
 // The blocks that need no chain: one distinct symbol (type 1) and raw symbols (type 2).  Each returns whether it finished the block.
-__device__ __forceinline__ bool rans2_dec_plain(uint32_t type, const uint8_t *in, const uint8_t *end, uint32_t n, uint32_t v2, uint8_t *out) {
+// packed: a context queue of a packed work item, two symbols to a byte (ctxn_byte above)
+__device__ __forceinline__ bool rans2_dec_plain(uint32_t type, const uint8_t *in, const uint8_t *end, uint32_t n, uint32_t v2, uint8_t *out,
+                                                bool packed = false) {
     const uint32_t lane = threadIdx.x & 63;
-    if (type == 1) {
-        for (uint32_t i = lane; i < n; i += 64) out[i] = (uint8_t)v2;
-    } else if (type == 2) {  // v2 bits per symbol behind the two header words, MSB first
-        for (uint32_t i = lane; i < n; i += 64) {
-            const uint64_t b0 = (uint64_t)i * v2;
-            const uint8_t *wp = in + 8 + (b0 >> 5) * 4;
-            const uint32_t rel = (uint32_t)(b0 & 31);
-            const uint64_t two = ((uint64_t)ld32u(wp) << 32) | (wp + 4 < end ? ld32u(wp + 4) : 0u);
-            out[i] = (uint8_t)((two >> (64 - rel - v2)) & ((1u << v2) - 1));
+    auto raw = [&](uint32_t i) -> uint32_t {  // v2 bits per symbol behind the two header words, MSB first
+        const uint64_t b0 = (uint64_t)i * v2;
+        const uint8_t *wp = in + 8 + (b0 >> 5) * 4;
+        const uint32_t rel = (uint32_t)(b0 & 31);
+        const uint64_t two = ((uint64_t)ld32u(wp) << 32) | (wp + 4 < end ? ld32u(wp + 4) : 0u);
+        return (uint32_t)((two >> (64 - rel - v2)) & ((1u << v2) - 1));
+    };
+    if (packed) {
+        if (type == 1) {
+            for (uint32_t i = 2 * lane; i < n; i += 128) out[i >> 1] = (uint8_t)ctxn_byte(v2, i + 1 < n ? v2 : 0u);
+        } else if (type == 2) {
+            for (uint32_t i = 2 * lane; i < n; i += 128) out[i >> 1] = (uint8_t)ctxn_byte(raw(i), i + 1 < n ? raw(i + 1) : 0u);
         }
+    } else if (type == 1) {
+        for (uint32_t i = lane; i < n; i += 64) out[i] = (uint8_t)v2;
+    } else if (type == 2) {
+        for (uint32_t i = lane; i < n; i += 64) out[i] = (uint8_t)raw(i);
     }
     return type == 1 || type == 2;
 }
