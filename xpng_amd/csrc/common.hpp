@@ -11,9 +11,9 @@
 namespace xpng {
 
 // ---- build flavours ---------------------------------------------------------------------------------------------------
-// The release library (libxpng_hip.so) reads exactly these five environment variables, each of which selects between forms that
-// produce the SAME bytes (INTEGRATION.md lists them): XPNG_DEVICE, XPNG_GPUS, XPNG_WIDE_RANS, XPNG_NARROW_RANS,
-// XPNG_NO_SPLIT (it also WRITES the runtime's GPU_MAX_HW_QUEUES when it is loaded, unless the caller has set it).  Everything that exists for timing
+// The release library (libxpng_hip.so) reads exactly these four environment variables, each of which selects between forms that
+// produce the SAME bytes (INTEGRATION.md lists them): XPNG_DEVICE, XPNG_GPUS, XPNG_WIDE_RANS, XPNG_NARROW_RANS
+// (it also WRITES the runtime's GPU_MAX_HW_QUEUES when it is loaded, unless the caller has set it).  Everything that exists for timing
 // studies - kernel knock-outs, unused-LDS pads, no-store switches, phase stamps, the wave probe, stream priorities, fake
 // devices - is compiled only into libxpng_hip_probes.so (-DXPNG_PROBES, `make probes`; tools/ load that one): a product
 // library whose output can be falsified through the environment is not shippable.
@@ -39,8 +39,8 @@ inline bool small_blocks(uint64_t items) { return items > NARROW_MAX_ITEMS && !p
 // outside probe builds.
 inline hipError_t chain_stream_create(hipStream_t *s) {
     int lo = 0, hi = 0;
-    // (probe builds) XPNG_SIDE_CUMASK=K: the side streams of a context - alpha encode chains, alpha decode chains, the small-tile decode
-    // tail - may use only the first K compute units of the runtime's numbering (the driver deals a queue's mask bits round-robin over
+    // (probe builds) XPNG_SIDE_CUMASK=K: the side stream of a context - the alpha branch of a narrow decode, the big-alphabet chains of a
+    // level-2 decode - may use only the first K compute units of the runtime's numbering (the driver deals a queue's mask bits round-robin over
     // the shader engines and XCDs: K / 8 per XCD); the caller's stream keeps all of them.  VERDICT r3 item 1a: a CU partition.
     if (const char *m = probe_env("XPNG_SIDE_CUMASK")) {
         const int k = atoi(m);

@@ -38,8 +38,8 @@ struct DecodeWs {
     uint64_t cap2 = 0;
     std::vector<uint64_t> last_off;      // tile offsets already resident in d_off (skip the upload when unchanged)
     uint32_t last_t0 = 0;
-    hipStream_t side = nullptr;          // the context's one side stream: alpha branch beside the nl-context branch, big-tile class of a split decode
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_ctx = nullptr, ev_small = nullptr;
+    hipStream_t side = nullptr;          // the context's one side stream (narrow level-1 RGBA decode: the alpha branch beside the nl-context branch; level 2: rans1_wide_dec.hpp); the wide level-1 form has none
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     DecTile *d_info = nullptr;
     uint64_t *d_off = nullptr;
     uint8_t *d_ctxsym = nullptr, *d_asym = nullptr, *d_alpha = nullptr, *d_nlseq = nullptr;  // (inside the arena)
@@ -48,7 +48,7 @@ struct DecodeWs {
     uint64_t arena_bytes = 0;
 };
 inline void decode_ws_free(DecodeWs &w) {
-    for (hipEvent_t e : {w.ev_fork, w.ev_join, w.ev_ctx, w.ev_small}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {w.ev_fork, w.ev_join}) if (e) (void)hipEventDestroy(e);
     w = DecodeWs();
 }
 // an event of the workspace, created when a launch sequence first needs it
@@ -688,10 +688,11 @@ __global__ __launch_bounds__(64) void k_dec_walk(const DecTile *__restrict__ inf
 constexpr uint32_t WALK_WIDE_COLS(uint32_t lpw) { return lpw + (lpw < 64 ? 1u : 0u); }  // LDS columns: one per tile + one that the idle lanes share
 constexpr uint32_t WALK_WIDE_WCH = 4;  // 16-byte chunks (32 symbols each) in a queue's window: 4, or 2 (which does NOT hold the walk's invariant: see k_dec_walk_wide)
 constexpr size_t WALK_WIDE_LDS_BYTES(uint32_t lpw) { return 10 * (size_t)WALK_WIDE_COLS(lpw) * 16 + 10 * 4 * WALK_WIDE_WCH * (size_t)WALK_WIDE_COLS(lpw) * 4; }  // heads + windows (k_dec_walk_wide)
+// (A device function of the role-local workgroup index `bid`: k_dec_walk_wide launches it alone, k_dec_serial beside the alpha chains.)
 template <uint32_t LPW>
-__global__ __launch_bounds__(64) void k_dec_walk_wide(const DecTile *__restrict__ info, const TileDesc *__restrict__ tiles,
+__device__ __attribute__((always_inline)) inline void dec_walk_wide_body(const DecTile *__restrict__ info, const TileDesc *__restrict__ tiles,
                                                       TileSel sel, uint32_t total_tiles, const uint8_t *__restrict__ ctxsym,
-                                                      uint8_t *__restrict__ nlseq, uint32_t j0) {
+                                                      uint8_t *__restrict__ nlseq, uint32_t j0, const uint32_t bid) {
     // window: WCH chunks of 16 B per queue; a queue is serviced every SVC-th block.  (8 chunks / every 4th block is ~8 % faster
     // alone, but 90 KB of LDS per wave instead of 50 costs the kernels beside it more than that.)
     constexpr uint32_t WCH = WALK_WIDE_WCH, SVC = 2, INIT = 2, WDW = WCH * 4, lpw = LPW, COLS = WALK_WIDE_COLS(LPW);
@@ -702,7 +703,7 @@ __global__ __launch_bounds__(64) void k_dec_walk_wide(const DecTile *__restrict_
     uint32_t *const ringw = reinterpret_cast<uint32_t *>(walk_wide_lds + 10 * COLS * 16);    // [10 * WDW * COLS]
     __builtin_amdgcn_s_setprio(XPNG_CHAIN_PRIO);  // a serial chain: its latency is the critical path, the throughput kernels beside it are not
     XPNG_PROBE_BEGIN()
-    const uint32_t lane_ = threadIdx.x & 63, j = j0 + blockIdx.x * lpw + lane_;  // work items [j0, total_tiles)
+    const uint32_t lane_ = threadIdx.x & 63, j = j0 + bid * lpw + lane_;  // work items [j0, total_tiles)
     bool live = lane_ < lpw && j < total_tiles;
     const uint32_t lane = lane_ < lpw ? lane_ : lpw;  // LDS column of this lane (the idle lanes of a narrower form share the last one: they only ever walk the parking queue, whose heads are self-consistent whoever wrote them)
     const DecTile *d = info + (live ? j : 0);
@@ -811,6 +812,29 @@ __global__ __launch_bounds__(64) void k_dec_walk_wide(const DecTile *__restrict_
         service(1);
     }
     XPNG_PROBE_END(5)
+}
+template <uint32_t LPW>
+__global__ __launch_bounds__(64) void k_dec_walk_wide(const DecTile *__restrict__ info, const TileDesc *__restrict__ tiles,
+                                                      TileSel sel, uint32_t total_tiles, const uint8_t *__restrict__ ctxsym,
+                                                      uint8_t *__restrict__ nlseq, uint32_t j0) {
+    dec_walk_wide_body<LPW>(info, tiles, sel, total_tiles, ctxsym, nlseq, j0, blockIdx.x);
+}
+
+// The two serial stages of a batched decode that need nothing of each other, in ONE launch: workgroups [0, agroups) are the alpha
+// chains (the longest: dispatched first; none for RGB), the rest the lane-per-tile walk over all work items.  Through round 4 they
+// ran beside each other on two streams, each holding a hardware queue for its whole duration; as two ranges of one grid they run
+// beside each other on the chip just the same and hold ONE queue for the longer of the two.  The role branch is
+// uniform over the (single-wavefront) workgroup.  Dynamic LDS: the larger of the roles present (dec_serial_lds_bytes).
+inline size_t dec_serial_lds_bytes(uint32_t agroups, uint32_t wgroups) {
+    const size_t a = agroups ? DecChainLds<true, 32>::BYTES : 0, w = wgroups ? WALK_WIDE_LDS_BYTES(64) : 0;
+    return a > w ? a : w;
+}
+__global__ __launch_bounds__(64) void k_dec_serial(const DecTile *__restrict__ info, const TileDesc *__restrict__ tiles, TileSel sel,
+                                                   uint32_t total, const WDec *__restrict__ wdec, const uint8_t *__restrict__ dtab,
+                                                   uint8_t *__restrict__ ctxsym, uint8_t *__restrict__ asym,
+                                                   uint8_t *__restrict__ nlseq, uint32_t agroups) {
+    if (blockIdx.x < agroups) rans2_dec_chain_body<true, 32, true>(info, total, 9, 1, wdec, dtab, ctxsym, asym, total, blockIdx.x);
+    else dec_walk_wide_body<64>(info, tiles, sel, total, ctxsym, nlseq, 0, blockIdx.x - agroups);
 }
 
 // --------------------------------------------------------------------------------------------------
@@ -1067,10 +1091,9 @@ struct DecodeJob {
     // geometry: B images of n_tiles tiles, `plane` bytes per symbol plane of the batch, rasters W pixels wide; the widest, tallest
     // and narrowest tile of the selection
     uint32_t B; uint64_t n_tiles, plane, W; uint32_t max_w, max_h, min_w; int pxsz;
-    // selection: tiles [t0, t1) of every image, enumerated by `order` (n_big of its tiles form the big-tile size class) or image-major
-    // (order == nullptr); or, for a region decode, the list_n work items of `list` (TileSel::list; t0, t1 = 0, n_tiles; no order:
-    // list launches run unsplit)
-    uint32_t t0, t1; const uint32_t *order; uint32_t n_big; const uint32_t *list; uint32_t list_n;
+    // selection: tiles [t0, t1) of every image, enumerated by `order` or image-major (order == nullptr); or, for a region decode,
+    // the list_n work items of `list` (TileSel::list; t0, t1 = 0, n_tiles; no order)
+    uint32_t t0, t1; const uint32_t *order; const uint32_t *list; uint32_t list_n;
     // device tables: tile table, B blob pointers and lengths, B raster pointers, status word; tile_off is a HOST array of blob
     // offsets (image-major: B * (t1 - t0), or B * n_tiles for a list) or nullptr (walk the sizes on the device)
     const TileDesc *tiles; const uint8_t *const *blobs; const uint64_t *blob_len; uint8_t *const *rasters; uint32_t *status;
@@ -1129,6 +1152,7 @@ inline int decode_ws_prepare(DecodeWs &ws, WsTable &tab, const DecodeJob &j, std
 }
 
 constexpr uint32_t WD_CTX_STREAMS = 32, WD_ALPHA_STREAMS = 32;  // streams per chain wavefront (16 alpha streams per wave - half the LDS per workgroup, twice the waves - measures the same)
+static_assert(WD_ALPHA_STREAMS == 32, "k_dec_serial's alpha role is written for 32 streams per wavefront");
 
 // What decode_m1_launch decides before its first kernel.
 struct DecodePlan {
@@ -1138,47 +1162,38 @@ struct DecodePlan {
     // RGBA: the residual kernel rebuilds alpha from its symbols itself (k_dec_resid FOLD) when every tile is at least 4 pixels wide -
     // every tile of a file the reference can write (RGBA narrower than 4 px is stored at level 7); otherwise k_dec_alpha makes the plane
     bool fold;
-    bool split;   // two size classes on two streams (see decode_m1_launch)
-    uint32_t jb;  // split: work items [0, jb) are the big-tile class
-    uint32_t pk0;  // work items from pk0 on go to the lane-per-tile walk: their context queues are packed (rans_dec.hpp); `total` = none
+    uint32_t pk0;  // work items from pk0 on go to the lane-per-tile walk: their context queues are packed (rans_dec.hpp); 0 = all of them (the wide form), `total` = none
     ReconPlan recon;  // the form of the reconstruction (recon.hpp)
     // probe builds: bytes of unused dynamic LDS per workgroup (occupancy throttles); all 0 in the release library
     size_t pad_chain, pad_alpha, pad_walk, pad_resid;
 };
 inline DecodePlan decode_m1_plan(const DecodeJob &j) {
     DecodePlan p{};
-    const uint32_t cnt = j.cnt(), total = j.total(), spt = j.pxsz == 4 ? 10 : 9;
+    const uint32_t total = j.total(), spt = j.pxsz == 4 ? 10 : 9;
     p.wide = wide_form((uint64_t)total * spt);
     p.fold = j.pxsz == 4 && j.min_w >= 4 && !probe_env("XPNG_NO_ALPHA_FOLD");
     p.recon = recon_geometry(j.max_w, j.max_h, p.wide);
-    p.split = p.recon.band && !j.list && j.order && j.n_big > 0 && j.n_big < cnt && !probe_env("XPNG_NARROW_WALK") && !getenv("XPNG_NO_SPLIT");
-    // (the big-tile class keeps a symbol to a byte for the scalar walk, the rest is packed for the lane-per-tile walk: the class
-    //  boundary is rounded down to a whole wavefront of context chains, which then produces one form or the other)
-    p.jb = p.split ? j.n_big * j.B / WD_CTX_STREAMS * WD_CTX_STREAMS : 0;
-    p.split = p.jb > 0;
-    const bool lane_walk = p.split || (p.wide && !probe_env("XPNG_NARROW_WALK"));
-    p.pk0 = lane_walk ? p.jb : total;
+    p.pk0 = p.wide && !probe_env("XPNG_NARROW_WALK") ? 0 : total;
     p.pad_chain = probe_pad("XPNG_PAD_CHAIN"); p.pad_alpha = probe_pad("XPNG_PAD_AL"); p.pad_walk = probe_pad("XPNG_PAD_WALK");
     p.pad_resid = probe_pad("XPNG_PAD_RS");
     return p;
 }
 
-// The tail of a size class: residual extraction, then reconstruction, of work items [first, first + n) on stream st.
-// skip_resid / skip_recon: the knock-out names of the two kernels (probe builds).
+// The tail of a decode: residual extraction, then reconstruction, of all `n` work items on stream st (knock-out names of probe
+// builds: resid_big, recon_big).
 template <int PXSZ>
-inline void dec_tail(const DecodeWs &ws, const DecodeJob &j, const DecodePlan &p, const TileSel &sel, uint32_t first, uint32_t n,
-                     hipStream_t st, const char *skip_resid, const char *skip_recon) {
-    if (dbg_skip(skip_resid)) {}
+inline void dec_tail(const DecodeWs &ws, const DecodeJob &j, const DecodePlan &p, const TileSel &sel, uint32_t n, hipStream_t st) {
+    if (dbg_skip("resid_big")) {}
     else if constexpr (PXSZ == 4) {
-        if (p.wide && p.fold) k_dec_resid<4, 256, true><<<n, 256, p.pad_resid, st>>>(ws.d_info, j.tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, first);
-        else if (p.wide) k_dec_resid<4, 256><<<n, 256, p.pad_resid, st>>>(ws.d_info, j.tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, first);
-        else if (p.fold) k_dec_resid<4, 1024, true><<<n, 1024, 0, st>>>(ws.d_info, j.tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, first);
-        else k_dec_resid<4, 1024><<<n, 1024, 0, st>>>(ws.d_info, j.tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, first);
+        if (p.wide && p.fold) k_dec_resid<4, 256, true><<<n, 256, p.pad_resid, st>>>(ws.d_info, j.tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, 0);
+        else if (p.wide) k_dec_resid<4, 256><<<n, 256, p.pad_resid, st>>>(ws.d_info, j.tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, 0);
+        else if (p.fold) k_dec_resid<4, 1024, true><<<n, 1024, 0, st>>>(ws.d_info, j.tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, 0);
+        else k_dec_resid<4, 1024><<<n, 1024, 0, st>>>(ws.d_info, j.tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, 0);
     } else {  // (RGB has no alpha to fold)
-        if (p.wide) k_dec_resid<3, 256><<<n, 256, p.pad_resid, st>>>(ws.d_info, j.tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, first);
-        else k_dec_resid<3, 1024><<<n, 1024, 0, st>>>(ws.d_info, j.tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, first);
+        if (p.wide) k_dec_resid<3, 256><<<n, 256, p.pad_resid, st>>>(ws.d_info, j.tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, 0);
+        else k_dec_resid<3, 1024><<<n, 1024, 0, st>>>(ws.d_info, j.tiles, sel, ws.d_alpha, ws.d_asym, ws.d_nlseq, ws.d_resid, 0);
     }
-    if (!dbg_skip(skip_recon)) recon_launch<PXSZ>(p.recon, ws.d_info, j.tiles, sel, ws.d_resid, j.rasters, j.pitch(), first, n, st);
+    if (!dbg_skip("recon_big")) recon_launch<PXSZ>(p.recon, ws.d_info, j.tiles, sel, ws.d_resid, j.rasters, j.pitch(), 0, n, st);
 }
 
 // Launch the whole level-1 decode of a job.
@@ -1186,8 +1201,8 @@ inline int decode_m1_launch(DecodeWs &ws, WsTable &tab, const DecodeJob &j, std:
     auto bad = [&](const char *m) { err = m; return 1; };
     const DecodePlan p = decode_m1_plan(j);
     const TileSel sel = j.sel();
-    const uint32_t cnt = j.cnt(), total = j.total(), spt = j.pxsz == 4 ? 10 : 9, jb = p.jb;
-    const hipStream_t s = j.s, side = ws.side;
+    const uint32_t cnt = j.cnt(), total = j.total(), spt = j.pxsz == 4 ? 10 : 9;
+    const hipStream_t s = j.s;
     const bool rgba = j.pxsz == 4;
     const auto tail = rgba ? &dec_tail<4> : &dec_tail<3>;
     dbg_count_sequence();
@@ -1195,66 +1210,51 @@ inline int decode_m1_launch(DecodeWs &ws, WsTable &tab, const DecodeJob &j, std:
     // (a null workspace pointer handed to a kernel is a GPU fault, i.e. abort(): refuse to launch instead)
     if (!ws.d_info || !ws.d_off || !ws.d_wdec || !ws.d_dtab || !ws.d_ctxsym || !ws.d_asym || !ws.d_alpha || !ws.d_nlseq || !ws.d_resid || !j.tiles || !j.blobs || !j.rasters)
         return bad("internal error: a decode workspace buffer was never allocated");
-    if (!side) return bad("internal error: the decode has no side stream");
-    if (!decode_ws_event(ws.ev_fork) || !decode_ws_event(ws.ev_join) || (p.split && (!decode_ws_event(ws.ev_ctx) || !decode_ws_event(ws.ev_small)))) return bad("event creation failed");
 
-    // ---- parse + prep
     k_dec_parse<<<(total + 63) / 64, 64, 0, s>>>(j.blobs, ws.d_off, j.blob_len, cnt, total, spt, j.pxsz, j.tiles, sel, ws.d_info, j.status);
-    const uint32_t groups = (total + WD_CTX_STREAMS - 1) / WD_CTX_STREAMS, agroups = (total + WD_ALPHA_STREAMS - 1) / WD_ALPHA_STREAMS;
-    if (p.wide && !dbg_skip("dec_prep")) k_rans2_dec_prep<<<total * spt, 64, 0, s>>>(ws.d_info, j.tiles, sel, spt, ws.d_ctxsym, ws.d_asym, ws.d_wdec, ws.d_dtab, p.pk0);
 
-    // ---- alpha branch, on the side stream: its rANS block is the longest serial chain of a tile, and it is independent of the
-    // nl-context branch (nine short rANS blocks, then the serial context walk) until k_dec_resid
-    if (rgba) {
-        if (hipEventRecord(ws.ev_fork, s) != hipSuccess || hipStreamWaitEvent(side, ws.ev_fork, 0) != hipSuccess) return bad("fork failed");
-        if (p.wide && !probe_env("XPNG_NARROW_ALPHA")) { if (!dbg_skip("dec_chain_a")) k_rans2_dec_chain<true, WD_ALPHA_STREAMS, true><<<agroups, 64, DecChainLds<true, WD_ALPHA_STREAMS>::BYTES + p.pad_chain, side>>>(ws.d_info, total, 9, 1, ws.d_wdec, ws.d_dtab, ws.d_ctxsym, ws.d_asym, total); }
-        else k_rans2_decode<15><<<total, 64, 0, side>>>(ws.d_info, j.tiles, sel, 9, 1, 0, ws.d_ctxsym, ws.d_asym, j.stamps);
-        if (p.fold || dbg_skip("dec_alpha")) {} else if (p.wide) k_dec_alpha<256><<<total, 256, p.pad_alpha, side>>>(ws.d_info, j.tiles, sel, ws.d_asym, ws.d_alpha);
-        else k_dec_alpha<1024><<<total, 1024, 0, side>>>(ws.d_info, j.tiles, sel, ws.d_asym, ws.d_alpha);
-        if (hipEventRecord(ws.ev_join, side) != hipSuccess) return bad("join record failed");
-    }
-
-    // ---- context chains
     if (p.wide) {
+        // ---- the wide form: every kernel on the caller's stream, no fork, no event.  The serial stages that need nothing of each other
+        // - the alpha chains and the context walk - are two ranges of ONE grid (k_dec_serial) behind the context chains: a hardware queue
+        // is held for the longer of the two, not two queues for their sum, and no barrier packet stands in a queue that other contexts'
+        // streams share (the runtime gives a process 4 queues unless it asked for more before HIP started: DESIGN.md 6.2).  (Through round
+        // 4: the alpha chains on a side stream beside the context chains, and two tile size classes walked, extracted and reconstructed
+        // side by side on the two streams.)
+        const uint32_t groups = (total + WD_CTX_STREAMS - 1) / WD_CTX_STREAMS;
+        if (!dbg_skip("dec_prep")) k_rans2_dec_prep<<<total * spt, 64, 0, s>>>(ws.d_info, j.tiles, sel, spt, ws.d_ctxsym, ws.d_asym, ws.d_wdec, ws.d_dtab, p.pk0);
         if (!dbg_skip("dec_chain_c")) k_rans2_dec_chain<false, WD_CTX_STREAMS, false><<<groups * 9, 64, DecChainLds<false, WD_CTX_STREAMS>::BYTES + p.pad_chain, s>>>(ws.d_info, total, 0, 9, ws.d_wdec, ws.d_dtab, ws.d_ctxsym, ws.d_asym, p.pk0);
         // context streams the small layout cannot hold (PROB_BITS > 12 or more than 16 symbols: never written by the reference)
         if (!dbg_skip("dec_odd")) k_rans2_decode_rest<15><<<128, 64, 0, s>>>(ws.d_info, j.tiles, sel, total, 0, 9, ws.d_ctxsym, ws.d_asym, j.stamps, ws.d_wdec, p.pk0);
         // (k_rans2_decode_rest resolves slots by binary search: 4.6 KB of LDS, so its 128 workgroups are placed at once - with the
         //  37 KB slot table of k_rans2_decode<15> they waited up to 5 ms, between the chains and the walk, to find nothing to do)
+        // (probe builds: XPNG_NARROW_ALPHA / XPNG_NARROW_WALK run that stage in its one-wavefront-per-stream / per-tile form, a launch of
+        //  its own; a knocked-out role gets no workgroups, and a launch without workgroups is not made)
+        uint32_t agroups = rgba && !dbg_skip("dec_chain_a") ? (total + WD_ALPHA_STREAMS - 1) / WD_ALPHA_STREAMS : 0;
+        uint32_t wgroups = dbg_skip("walk_small") ? 0 : (total + 63) / 64;  // (the lane-per-tile walk keeps its name; walk_big, resid_small and recon_small name nothing any more)
+        if (rgba && probe_env("XPNG_NARROW_ALPHA")) { agroups = 0; k_rans2_decode<15><<<total, 64, 0, s>>>(ws.d_info, j.tiles, sel, 9, 1, 0, ws.d_ctxsym, ws.d_asym, j.stamps); }
+        if (probe_env("XPNG_NARROW_WALK")) { wgroups = 0; k_dec_walk<<<total, 64, 0, s>>>(ws.d_info, j.tiles, sel, ws.d_ctxsym, ws.d_nlseq); }
+        if (agroups + wgroups)
+            k_dec_serial<<<agroups + wgroups, 64, dec_serial_lds_bytes(agroups, wgroups) + p.pad_chain + p.pad_walk, s>>>(ws.d_info, j.tiles, sel, total, ws.d_wdec, ws.d_dtab, ws.d_ctxsym, ws.d_asym, ws.d_nlseq, agroups);
+        if (rgba && !p.fold && !dbg_skip("dec_alpha")) k_dec_alpha<256><<<total, 256, p.pad_alpha, s>>>(ws.d_info, j.tiles, sel, ws.d_asym, ws.d_alpha);
+        tail(ws, j, p, sel, total, s);
     } else {
+        // ---- the narrow form: a wavefront per stream.  The alpha branch runs on the side stream: its rANS block is the longest serial
+        // chain of a tile, and it is independent of the nl-context branch (nine short rANS blocks, then the serial context walk) until
+        // k_dec_resid
+        const hipStream_t side = ws.side;
+        if (rgba) {
+            if (!side) return bad("internal error: the decode has no side stream");
+            if (!decode_ws_event(ws.ev_fork) || !decode_ws_event(ws.ev_join)) return bad("event creation failed");
+            if (hipEventRecord(ws.ev_fork, s) != hipSuccess || hipStreamWaitEvent(side, ws.ev_fork, 0) != hipSuccess) return bad("fork failed");
+            k_rans2_decode<15><<<total, 64, 0, side>>>(ws.d_info, j.tiles, sel, 9, 1, 0, ws.d_ctxsym, ws.d_asym, j.stamps);
+            if (!p.fold && !dbg_skip("dec_alpha")) k_dec_alpha<1024><<<total, 1024, 0, side>>>(ws.d_info, j.tiles, sel, ws.d_asym, ws.d_alpha);
+            if (hipEventRecord(ws.ev_join, side) != hipSuccess) return bad("join record failed");
+        }
         k_rans2_decode<12><<<total * 9, 64, 0, s>>>(ws.d_info, j.tiles, sel, 0, 9, 0, ws.d_ctxsym, ws.d_asym, j.stamps);
         k_rans2_decode<15><<<total * 9, 64, 0, s>>>(ws.d_info, j.tiles, sel, 0, 9, 1, ws.d_ctxsym, ws.d_asym, j.stamps);  // blocks with PROB_BITS > 12 only
-    }
-
-    // ---- walk(s) and tail(s)
-    // Two size classes: the walk's duration is the chain of the biggest tile, and the work enumeration is sorted by size, so the
-    // first n_big tiles of the order (x B images) are walked beside the rest - shorter chains, the lane-per-tile form - and each
-    // class goes on to its own residual extraction and reconstruction: what is left behind the longer walk is the tail of ITS tiles only.
-    // On TWO streams: the small-tile class stays on the caller's stream behind the context chains; the big-tile class runs on the
-    // side stream BEHIND the alpha chains (its walk, ~14 ms, starts ~13 ms later than it could and still ends before the small tiles'
-    // walk, ~28 ms, does).  A third stream for the small-tile class LOST: every stream alive is a hardware queue, and with 4 streams per
-    // context the fifth and sixth pipeline slot cost throughput (36 / 33 against 38.5 Gpx/s; DESIGN.md 6, profiles/r04_experiments.txt).
-    if (p.split) {
-        if (hipEventRecord(ws.ev_ctx, s) != hipSuccess || hipStreamWaitEvent(side, ws.ev_ctx, 0) != hipSuccess) return bad("fork failed");
-        // (64 tiles per wavefront; 32 gave the same bytes no faster: profiles/r04_experiments.txt)
-        if (!dbg_skip("walk_small")) k_dec_walk_wide<64><<<(total - jb + 63) / 64, 64, WALK_WIDE_LDS_BYTES(64) + p.pad_chain + p.pad_walk, s>>>(ws.d_info, j.tiles, sel, total, ws.d_ctxsym, ws.d_nlseq, jb);
-        // the biggest tiles' chains are the longest of the decode: they get the scalar-unit walk, one wave per tile (~40 ns per
-        // step against ~95 for the lane-per-tile form; a few waves per CU, so the CU's one scalar ALU is not contended), while
-        // the many smaller tiles keep the lane-per-tile form beside them (the lane-per-tile form for both lost: DESIGN.md 6,
-        // profiles/r03_experiments.txt)
-        if (!dbg_skip("walk_big")) k_dec_walk<<<jb, 64, p.pad_chain, side>>>(ws.d_info, j.tiles, sel, ws.d_ctxsym, ws.d_nlseq);
-        // (RGBA: the alpha symbols are complete at ev_join, recorded on the side stream right behind the alpha chains - in front of the
-        //  big-tile walk, so only the caller's stream has to wait for it)
+        k_dec_walk<<<total, 64, 0, s>>>(ws.d_info, j.tiles, sel, ws.d_ctxsym, ws.d_nlseq);
         if (rgba && s != side && hipStreamWaitEvent(s, ws.ev_join, 0) != hipSuccess) return bad("join failed");
-        tail(ws, j, p, sel, jb, total - jb, s, "resid_small", "recon_small");
-        tail(ws, j, p, sel, 0, jb, side, "resid_big", "recon_big");
-        // the side stream hands in its tail's end
-        if (hipEventRecord(ws.ev_small, side) != hipSuccess || hipStreamWaitEvent(s, ws.ev_small, 0) != hipSuccess) return bad("join failed");
-    } else {
-        if (p.wide && !probe_env("XPNG_NARROW_WALK")) k_dec_walk_wide<64><<<(total + 63) / 64, 64, WALK_WIDE_LDS_BYTES(64), s>>>(ws.d_info, j.tiles, sel, total, ws.d_ctxsym, ws.d_nlseq, 0);
-        else k_dec_walk<<<total, 64, 0, s>>>(ws.d_info, j.tiles, sel, ws.d_ctxsym, ws.d_nlseq);
-        if (rgba && s != side && hipStreamWaitEvent(s, ws.ev_join, 0) != hipSuccess) return bad("join failed");
-        tail(ws, j, p, sel, 0, total, s, "resid_big", "recon_big");
+        tail(ws, j, p, sel, total, s);
     }
     if (hipGetLastError() != hipSuccess) return bad("decode kernel launch failed");
     return 0;

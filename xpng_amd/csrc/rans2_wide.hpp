@@ -104,12 +104,14 @@ template <bool BIG> constexpr uint32_t chain2_ltab_bytes() { return BIG ? 0u : 3
 //  global_load_lds_dwordx4, the mechanism of tools/ubench/ldsdma.hip - bit-exact, 60 GPU tests green: 6.5 -> 7.5 ms alone, 11.2 ms
 //  median in the pipeline before and after.  This chain does not wait for its symbols there; removed.  DESIGN.md 6.2b.)
 template <bool BIG> constexpr size_t chain2_lds_bytes() { return chain2_ltab_bytes<BIG>() + 32u * WB_STRIDE * 4u; }  // dynamic LDS of one launch (common.hpp: why dynamic)
+// (The chain is a device function of the role-local workgroup index `bid`: k_rans2_chain2 launches one class, k_rans2_chain_all
+//  both classes of a batched RGBA encode as ranges of one grid.)
 template <bool BIG>
-__global__ __launch_bounds__(64) void k_rans2_chain2(const TileDesc *__restrict__ tiles, TileSel sel, uint32_t total,
+__device__ __attribute__((always_inline)) inline void rans2_chain2_body(const TileDesc *__restrict__ tiles, TileSel sel, uint32_t total,
                                                      const uint8_t *__restrict__ planes, uint64_t plane_stride,
                                                      uint8_t *__restrict__ scratch, const uint32_t *__restrict__ ctx_n,
                                                      WPrep *__restrict__ prep, const uint8_t *__restrict__ wtab, uint32_t j0,
-                                                     const uint8_t *__restrict__ watab) {
+                                                     const uint8_t *__restrict__ watab, const uint32_t bid) {
     constexpr uint32_t TPW = 32;                  // tiles (streams) per wave: every lane carries a state (alpha ran 16 per wave while its tables took 4 KB of LDS each)
     // bytes of one encoder table in LDS: a context stream has the nine symbols nl = 0..8 (the alpha class keeps none there)
     constexpr uint32_t TAB = 144;
@@ -123,7 +125,7 @@ __global__ __launch_bounds__(64) void k_rans2_chain2(const TileDesc *__restrict_
     __builtin_amdgcn_s_setprio(XPNG_CHAIN_PRIO);
     XPNG_PROBE_BEGIN()
     const uint32_t lane = threadIdx.x & 63, k = lane >> 1, par = lane & 1;
-    const uint32_t c = BIG ? 9 : blockIdx.x % 9, grp = BIG ? blockIdx.x : blockIdx.x / 9;
+    const uint32_t c = BIG ? 9 : bid % 9, grp = BIG ? bid : bid / 9;
     const uint32_t j = j0 + grp * TPW + k;
     bool live = k < TPW && j < total;
     if (!BIG) {
@@ -290,6 +292,27 @@ __global__ __launch_bounds__(64) void k_rans2_chain2(const TileDesc *__restrict_
     }
     if (live) { p->st[par] = s; if (par == 0) p->cnt = cnt; }
     XPNG_PROBE_END(BIG ? 2 : 1)
+}
+template <bool BIG>
+__global__ __launch_bounds__(64) void k_rans2_chain2(const TileDesc *__restrict__ tiles, TileSel sel, uint32_t total,
+                                                     const uint8_t *__restrict__ planes, uint64_t plane_stride,
+                                                     uint8_t *__restrict__ scratch, const uint32_t *__restrict__ ctx_n,
+                                                     WPrep *__restrict__ prep, const uint8_t *__restrict__ wtab, uint32_t j0,
+                                                     const uint8_t *__restrict__ watab) {
+    rans2_chain2_body<BIG>(tiles, sel, total, planes, plane_stride, scratch, ctx_n, prep, wtab, j0, watab, blockIdx.x);
+}
+// Both classes of a batched RGBA encode in ONE launch: workgroups [0, agroups) are the alpha chains - the longest, so they are
+// dispatched first - and the context chains follow.  The two classes ran beside each other on two streams through round 4; as
+// two ranges of one grid they still run beside each other on the chip and hold one hardware queue for the longer of the two,
+// not two queues for the sum.  The role branch is uniform over the (single-wavefront) workgroup.
+constexpr size_t chain_all_lds_bytes() { return chain2_lds_bytes<true>() > chain2_lds_bytes<false>() ? chain2_lds_bytes<true>() : chain2_lds_bytes<false>(); }
+__global__ __launch_bounds__(64) void k_rans2_chain_all(const TileDesc *__restrict__ tiles, TileSel sel, uint32_t total,
+                                                        const uint8_t *__restrict__ planes, uint64_t plane_stride,
+                                                        uint8_t *__restrict__ scratch, const uint32_t *__restrict__ ctx_n,
+                                                        WPrep *__restrict__ prep, const uint8_t *__restrict__ wtab,
+                                                        const uint8_t *__restrict__ watab, uint32_t agroups) {
+    if (blockIdx.x < agroups) rans2_chain2_body<true>(tiles, sel, total, planes, plane_stride, scratch, ctx_n, prep, wtab, 0, watab, blockIdx.x);
+    else rans2_chain2_body<false>(tiles, sel, total, planes, plane_stride, scratch, ctx_n, prep, wtab, 0, watab, blockIdx.x - agroups);
 }
 
 __global__ __launch_bounds__(64) void k_rans2_finish(const TileDesc *__restrict__ tiles, TileSel sel, uint32_t spt,

@@ -104,11 +104,13 @@ static_assert(DecChainLds<false, 32>::BYTES == 7728 && DecChainLds<true, 32>::BY
 // and a step in which EVERY lane of the wave lands in one of them skips both table reads (which is most steps when the
 // streams are skewed and the wave carries few of them: alpha runs 8 streams per wave for that reason, trading lanes for
 // latency on the longest chain of the decode).
+// (A device function of the role-local workgroup index `bid`: k_rans2_dec_chain launches one class; the alpha class of a batched
+//  decode is a range of k_dec_serial's grid, m1_decode.hpp.)
 template <bool BIG, int STREAMS, bool HOT>
-__global__ __launch_bounds__(64) void k_rans2_dec_chain(const DecTile *__restrict__ info, uint32_t total, uint32_t c_first,
+__device__ __attribute__((always_inline)) inline void rans2_dec_chain_body(const DecTile *__restrict__ info, uint32_t total, uint32_t c_first,
                                                         uint32_t c_count, const WDec *__restrict__ wdec,
                                                         const uint8_t *__restrict__ dtab, uint8_t *__restrict__ ctxsym,
-                                                        uint8_t *__restrict__ asym, uint32_t pk0) {
+                                                        uint8_t *__restrict__ asym, uint32_t pk0, const uint32_t bid) {
     __builtin_amdgcn_s_setprio(XPNG_CHAIN_PRIO);  // a serial chain: its latency is the critical path, the throughput kernels beside it are not
     XPNG_PROBE_BEGIN()
     typedef typename std::conditional<BIG, WdLayoutA, WdLayout<false>>::type L;
@@ -122,7 +124,7 @@ __global__ __launch_bounds__(64) void k_rans2_dec_chain(const DecTile *__restric
     uint8_t *const ring = dec_chain_lds + LD::OFF_RING;  // [WD_STREAMS * RSTRIDE]
     uint8_t *const obuf = dec_chain_lds + LD::OFF_OBUF;  // [(WD_STREAMS + 1) * OB_STRIDE] per stream: 16 symbol bytes of the block + a dump byte nobody reads; the last slot belongs to the lanes without a stream (STREAMS < 32)
     const uint32_t lane = threadIdx.x & 63, kraw = lane >> 1, k = kraw < WD_STREAMS ? kraw : 0, par = lane & 1;  // (idle lanes alias stream 0's LDS harmlessly)
-    const uint32_t c = c_first + blockIdx.x % c_count, grp = blockIdx.x / c_count;
+    const uint32_t c = c_first + bid % c_count, grp = bid / c_count;
     const uint32_t j = grp * WD_STREAMS + kraw;
     bool live = kraw < WD_STREAMS && j < total;
     // context streams of packed work items (from pk0 on, a multiple of STREAMS: the whole wavefront or none of it) leave two symbols
@@ -336,6 +338,13 @@ __global__ __launch_bounds__(64) void k_rans2_dec_chain(const DecTile *__restric
     else if (packed) run(std::true_type{});
     else run(std::false_type{});
     XPNG_PROBE_END(BIG ? 4 : 3)
+}
+template <bool BIG, int STREAMS, bool HOT>
+__global__ __launch_bounds__(64) void k_rans2_dec_chain(const DecTile *__restrict__ info, uint32_t total, uint32_t c_first,
+                                                        uint32_t c_count, const WDec *__restrict__ wdec,
+                                                        const uint8_t *__restrict__ dtab, uint8_t *__restrict__ ctxsym,
+                                                        uint8_t *__restrict__ asym, uint32_t pk0) {
+    rans2_dec_chain_body<BIG, STREAMS, HOT>(info, total, c_first, c_count, wdec, dtab, ctxsym, asym, pk0, blockIdx.x);
 }
 
 }  // namespace xpng

@@ -479,7 +479,7 @@ template <int PXSZ, class Info>
 inline void recon_launch(const ReconPlan &p, const Info *info, const TileDesc *tiles, const TileSel &sel, const uint32_t *resid,
                          uint8_t *const *rasters, uint64_t bpr, uint32_t first, uint32_t n, hipStream_t st) {
     if (p.band) k_dec_recon_band<PXSZ, Info><<<recon_grid(n), p.threads, p.lds, st>>>(info, tiles, sel, resid, rasters, bpr, p.nostore, first, first + n);
-    else k_dec_recon<PXSZ, Info><<<n, p.threads, p.lds, st>>>(info, tiles, sel, resid, rasters, bpr, p.free_ew);  // (only a band decode is split: first == 0)
+    else k_dec_recon<PXSZ, Info><<<n, p.threads, p.lds, st>>>(info, tiles, sel, resid, rasters, bpr, p.free_ew);  // (only the band form takes a sub-range: first == 0)
 }
 
 }  // namespace xpng

@@ -118,7 +118,7 @@ static void ctx_quiesce(xpnghip_ctx *c) {
     int prev = -1;
     (void)hipGetDevice(&prev);
     if (hipSetDevice(c->device) == hipSuccess) {
-        hipStream_t qs[3] = {c->stream, c->enc_side, c->dec.side};
+        hipStream_t qs[3] = {c->stream, c->side, c->dec.side};
         for (hipStream_t q : qs) if (q) (void)hipStreamSynchronize(q);
     }
     if (prev >= 0 && prev != c->device) (void)hipSetDevice(prev);

@@ -70,12 +70,15 @@ static int fail(const std::string &m) { g_err = m; return 1; }
             if (!q_) return fail("internal error: a workspace buffer of this launch sequence was never allocated (one of: " #__VA_ARGS__ ")"); \
     } while (0)
 
-// A context forks a side stream and a pipelined caller keeps several contexts in flight: with the runtime's default of 4 hardware
-// queues those streams share queues and serialise (measured: 31 -> 21 Gpx/s).  The runtime reads GPU_MAX_HW_QUEUES when it
+// A pipelined caller keeps several contexts in flight, each on a stream of its own: with the runtime's default of 4 hardware queues
+// those streams share queues, and kernels that share a queue run one after the other.  The runtime reads GPU_MAX_HW_QUEUES when it
 // initialises - the first HIP call of the process - so the library asks for 32 when it is LOADED, unless the caller has chosen a
-// value.  A process that has already initialised HIP before loading this library keeps what it had (export the variable yourself in
-// that case: INTEGRATION.md).  Nothing in the library reads the variable back: no code path depends on the queues being there
-// (round 3's decode took a third stream per context when it saw >= 24 here - ADVICE r3; the split needs no third stream any more).
+// value.  A process that has already initialised HIP before loading this library (any PyTorch process), or whose environment already
+// sets the variable, keeps what it had: four queues are the common case, so the batched level-1 forms put every kernel of a call on
+// the caller's ONE stream and launch the serial stages that may run beside each other as ranges of one grid (k_dec_serial,
+// k_rans2_chain_all) - queue time is the step's bound there.  Only the narrow (single-image) RGBA decode and the
+// level-2 decode still fork the context's side stream.  Nothing in the library reads the variable back: no code path depends on the
+// queues being there.
 __attribute__((constructor)) static void xpnghip_on_load(void) { (void)setenv("GPU_MAX_HW_QUEUES", "32", 0); }
 
 extern "C" int xpnghip_abi_version(void) { return XPNGHIP_ABI_VERSION; }
@@ -146,11 +149,10 @@ struct xpnghip_ctx {
     // decode keeps its own pair of tables: a caller that alternates encode and decode on one context (a pipeline) would
     // otherwise re-upload, and synchronise its stream, on every call
     uint32_t *d_order = nullptr;          // tile indices of [r0, r1) by decreasing pixel count (TileSel::order)
-    // ONE side stream per context [r4]: the alpha chains of a batched encode run on it beside the context chains, and the alpha branch
-    // of a decode (DecodeWs::side borrows it) - never at the same time, the calls on a context are ordered.  Every stream alive takes
-    // a hardware queue, and the chip runs ~16-20 of them side by side before the pipeline slots start to cost each other (r04_experiments)
-    hipStream_t enc_side = nullptr;
-    hipEvent_t ev_enc_fork = nullptr, ev_enc_join = nullptr;
+    // ONE side stream per context, created by the first call that forks (dec_launch): the alpha branch of a narrow level-1 RGBA decode
+    // and the big-alphabet chains of a level-2 decode run on it (DecodeWs::side borrows it).  The batched level-1 forms and every
+    // encode stay on the caller's stream: every stream alive takes a share of the runtime's hardware queues
+    hipStream_t side = nullptr;
     const uint8_t **d_dec_in_ptrs = nullptr;
     uint8_t **d_dec_out_ptrs = nullptr;
     std::vector<const void *> h_dec_in_ptrs;
@@ -158,7 +160,6 @@ struct xpnghip_ctx {
     WPrep *d_wprep = nullptr;   // wide entropy stage: per (tile, stream) record, encoder tables, normalised frequencies
     uint8_t *d_wtab = nullptr;
     uint32_t nlh_slots = 0, nlh_generic = 0;  // records per tile in d_nlh (m1_encode.hpp); which transform form wrote them last
-    uint32_t n_big = 0;  // tiles of the biggest size class (>= 3/4 of the largest pixel count)
     uint16_t *d_wF = nullptr;
     // mode 2 (RGB slow level): allocated on first use
     bool m2_ready = false;                // ensure_m2 has allocated all of them and uploaded d_sbase2
@@ -227,8 +228,7 @@ extern "C" void xpnghip_ctx_destroy(xpnghip_ctx *c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     c->ws.free_all();
-    if (c->enc_side) (void)hipStreamDestroy(c->enc_side);
-    for (hipEvent_t e : {c->ev_enc_fork, c->ev_enc_join}) if (e) (void)hipEventDestroy(e);
+    if (c->side) (void)hipStreamDestroy(c->side);
     decode_ws_free(c->dec);
     if (c->h_total) (void)hipHostFree(c->h_total);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
@@ -304,9 +304,6 @@ static int ctx_create_range_impl(xpnghip_ctx **out, int device, uint64_t w, uint
         for (uint64_t i = c->r0; i < c->r1; i++) ord.push_back((uint32_t)i);
         std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return c->tiles[a].n > c->tiles[b].n; });
         if (hipMemcpy(c->d_order, ord.data(), ord.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { xpnghip_ctx_destroy(c); return fail("context setup failed"); }
-        // size class of the biggest tiles (>= 3/4 of the largest pixel count): the decode walks them beside the rest (m1_decode.hpp)
-        c->n_big = 0;
-        for (uint32_t i : ord) if ((uint64_t)c->tiles[i].n * 4 >= (uint64_t)c->tiles[ord[0]].n * 3) c->n_big++;
     }
     c->stamps = c->d_dbg && probe_env("XPNG_STAMPS") != nullptr;  // (probe builds only)
 #ifdef XPNG_PROBES
@@ -393,7 +390,7 @@ static int ensure_scratch(xpnghip_ctx *c, hipStream_t s = nullptr) {
         // tiny images: a tile's stream scratch has ~6 KB of fixed room): once per context.  The decode places its planes again.
         // The context is a single-queue object: its earlier work is on the call's stream, its own stream or its side stream.
         // (hipFree itself may still wait for the device: xpng_hip.h says so.)
-        for (hipStream_t q : {s, c->stream, c->enc_side}) if (q) HIPCHK(hipStreamSynchronize(q));
+        for (hipStream_t q : {s, c->stream, c->side}) if (q) HIPCHK(hipStreamSynchronize(q));
         c->ws.drop((void **)&c->d_scratch); c->cap_scratch = 0;
         c->dec.arena = nullptr; c->dec.arena_bytes = 0; c->dec.cap_plane = 0;
     }
@@ -511,28 +508,10 @@ static int launch_encode_m1(xpnghip_ctx *c, const EncSpan &e, hipStream_t s) {
                  c->d_blk_sz, c->d_tile_sz, c->d_tile_hdr, c->d_off, c->d_totals, c->d_wprep, c->d_wtab, c->d_wF, c->h_total);
     const uint8_t *planesA = c->d_planes;
     uint8_t *const watab = c->d_wtab + ((e.VN * WTAB_TILE_BYTES + 4096 + 511) & ~511ull);
-    const bool alpha_side = !narrow && PXSZ == 4;
-    if (alpha_side && !c->enc_side) HIPCHK(chain_stream_create(&c->enc_side));
-    if (alpha_side && !c->ev_enc_fork) {
-        HIPCHK(hipEventCreateWithFlags(&c->ev_enc_fork, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&c->ev_enc_join, hipEventDisableTiming));
-    }
     // (A fused transform + routing kernel - no nl / r / g / b planes, 3.7 B/px less HBM traffic - existed through round 3 behind
     //  XPNG_FUSED: one long-lived 28 KB workgroup per tile, 12 % slower in the pipeline every time it was measured, and it cannot
     //  know the stream lengths before it routes.  Removed with the worst-case stream layout; git history has it.)
     if (launch_transform<PXSZ>(c, e, s, pad_tr, true)) return 1;
-    // Wide form, RGBA: the alpha chains are the longest serial stage of the encode and need only the alpha plane, so their
-    // preparation and the chains themselves run on their own stream behind the transform
-    // (Size classes of the alpha chains - the biggest tiles' alpha streams a wavefront each on a third stream - LOST: DESIGN.md 6,
-    //  profiles/r04_experiments.txt.)
-    if (alpha_side) {
-        HIPCHK(hipEventRecord(c->ev_enc_fork, s));
-        hipStream_t as = probe_env("XPNG_ONE_STREAM") ? s : c->enc_side;  // (probe builds: every kernel of the context on the caller's stream)
-        HIPCHK(hipStreamWaitEvent(as, c->ev_enc_fork, 0));
-        if (!dbg_skip("prep_a")) k_rans2_prep<<<total, 64, 0, as>>>(c->d_tiles, sel, 9, 1, planesA, c->plane_stride, c->d_scratch, c->d_ctx_n, c->d_blk_sz, c->d_wprep, c->d_wtab, c->d_wF, 0, watab);
-        if (!dbg_skip("chain_a")) k_rans2_chain2<true><<<(total + 31) / 32, 64, chain2_lds_bytes<true>() + probe_pad("XPNG_PAD_CHAIN"), as>>>(c->d_tiles, sel, total, planesA, c->plane_stride, c->d_scratch, c->d_ctx_n, c->d_wprep, c->d_wtab, 0, watab);
-        HIPCHK(hipEventRecord(c->ev_enc_join, as));
-    }
     // stream lengths (from the histogram of the nl plane the transform took as it wrote it) -> places of the nine context streams -> routing
     k_m1_lens<<<total, 64, 0, s>>>(c->d_nlh, c->nlh_slots, c->nlh_generic, c->d_tiles, sel, c->d_ctx_n);
     if (dbg_skip("streams")) {} else if (small_wg) k_m1_streams<PXSZ, 256><<<total, 256, pad_st, s>>>(c->d_in_ptrs, bpr, c->d_tiles, sel, c->d_planes, c->plane_stride, c->d_scratch, c->d_ctx_n, c->d_k_n);
@@ -540,10 +519,18 @@ static int launch_encode_m1(xpnghip_ctx *c, const EncSpan &e, hipStream_t s) {
     if (narrow) {
         // one wave per (tile, stream): fewer instructions per step (scalar cursors), best latency while every pair gets its own wave slot
         k_rans2_encode<<<total * c->spt, 64, 0, s>>>(c->d_tiles, sel, 0, c->spt, planesA, c->plane_stride, c->d_scratch, c->d_ctx_n, c->d_blk_sz, nullptr, c->stamps ? c->d_dbg : nullptr);
-    } else {                           // every lane a chain: prep -> chain -> finish
-        if (!dbg_skip("prep_c")) k_rans2_prep<<<total * 9, 64, 0, s>>>(c->d_tiles, sel, 0, 9, planesA, c->plane_stride, c->d_scratch, c->d_ctx_n, c->d_blk_sz, c->d_wprep, c->d_wtab, c->d_wF, 0, watab);
-        if (!dbg_skip("chain_c")) k_rans2_chain2<false><<<((total + 31) / 32) * 9, 64, chain2_lds_bytes<false>() + probe_pad("XPNG_PAD_CHAIN"), s>>>(c->d_tiles, sel, total, planesA, c->plane_stride, c->d_scratch, c->d_ctx_n, c->d_wprep, c->d_wtab, 0, watab);
-        if (alpha_side) HIPCHK(hipStreamWaitEvent(s, c->ev_enc_join, 0));
+    } else {
+        // every lane a chain: prep -> chains -> finish, all on the caller's stream.  ONE preparation launch over every stream of
+        // every tile, and ONE chain launch whose grid holds the alpha class (RGBA) in front of the context classes
+        // (k_rans2_chain_all, rans2_wide.hpp: why).  (Through round 4 the alpha streams were prepared and chained on a side stream
+        // behind the transform, beside the routing kernel and the context chains.)
+        // (Size classes of the alpha chains - the biggest tiles' alpha streams a wavefront each on a third stream - LOST: DESIGN.md 6,
+        //  profiles/r04_experiments.txt.)
+        // (probe builds: a knocked-out preparation narrows the launch to the other class; a knocked-out chain class gets no workgroups)
+        const uint32_t pa = PXSZ == 4 && !dbg_skip("prep_a") ? 1u : 0u, pc = dbg_skip("prep_c") ? 0u : 9u;
+        if (pa + pc) k_rans2_prep<<<total * (pa + pc), 64, 0, s>>>(c->d_tiles, sel, pc ? 0 : 9, pa + pc, planesA, c->plane_stride, c->d_scratch, c->d_ctx_n, c->d_blk_sz, c->d_wprep, c->d_wtab, c->d_wF, 0, watab);
+        const uint32_t agroups = PXSZ == 4 && !dbg_skip("chain_a") ? (total + 31) / 32 : 0u, cgroups = dbg_skip("chain_c") ? 0u : ((total + 31) / 32) * 9;
+        if (agroups + cgroups) k_rans2_chain_all<<<agroups + cgroups, 64, chain_all_lds_bytes() + probe_pad("XPNG_PAD_CHAIN"), s>>>(c->d_tiles, sel, total, planesA, c->plane_stride, c->d_scratch, c->d_ctx_n, c->d_wprep, c->d_wtab, watab, agroups);
         if (!dbg_skip("finish")) k_rans2_finish<<<total * c->spt, 64, 0, s>>>(c->d_tiles, sel, c->spt, planesA, c->plane_stride, c->d_scratch, c->d_ctx_n, c->d_blk_sz, c->d_wprep, c->d_wF);
     }
     k_tile_sizes<<<(total + 255) / 256, 256, 0, s>>>(c->d_tiles, sel, total, PXSZ, c->spt, c->d_sums, c->d_k_n, c->d_blk_sz, c->d_tile_sz, c->d_tile_hdr);
@@ -662,9 +649,7 @@ static int dec_prepare(xpnghip_ctx *c, int mode, const void *const *d_blobs, con
     }
     HIPCHK(hipMemsetAsync(c->d_status, 0, 4, s));
     if (ensure_arena(c)) return 1;
-    if (!c->enc_side) HIPCHK(chain_stream_create(&c->enc_side));
-    c->dec.side = probe_env("XPNG_ONE_STREAM") ? s : c->enc_side;  // (probe builds: every kernel of the context on the caller's stream)
-    XPNG_REQUIRE(c->d_dec_in_ptrs, c->d_dec_out_ptrs, c->d_blob_len, c->d_status, c->d_tiles, c->dec.arena, c->dec.side);
+    XPNG_REQUIRE(c->d_dec_in_ptrs, c->d_dec_out_ptrs, c->d_blob_len, c->d_status, c->d_tiles, c->dec.arena);
     if (mode == 2) {
         if (ensure_m2(c)) return 1;
         XPNG_REQUIRE(c->d_info2, c->d_blk2, c->d_tabs2, c->d_scratch2, c->d_sbase2, c->d_stream_n2);
@@ -688,12 +673,16 @@ static int dec_launch(xpnghip_ctx *c, int mode, uint32_t nimg, uint64_t W, const
     else for (uint32_t i = t0; i < t1; i++) scan(c->tiles[i]);
     j.t0 = t0; j.t1 = t1;
     j.order = list ? nullptr : order_for(c, t0, t1);
-    j.n_big = j.order ? c->n_big : 0u;
     j.list = d_list; j.list_n = list ? (uint32_t)list->size() : 0u;
     j.tiles = c->d_tiles; j.blobs = c->d_dec_in_ptrs; j.blob_len = c->d_blob_len; j.rasters = c->d_dec_out_ptrs; j.status = c->d_status;
     j.tile_off = tile_off;
     j.s = s;
     j.stamps = c->stamps && !list ? c->d_dbg + N * c->B * 80 : nullptr;
+    // the side stream, for the forms that fork one: level 2, and the narrow level-1 RGBA form (the wide form has no second stream)
+    if (mode == 2 || (c->pxsz == 4 && !decode_m1_plan(j).wide)) {
+        if (!c->side) HIPCHK(chain_stream_create(&c->side));
+        c->dec.side = probe_env("XPNG_ONE_STREAM") ? s : c->side;  // (probe builds: every kernel of the context on the caller's stream)
+    }
     if (mode == 2) return decode_m2_launch(c->dec, c->ws, j, M2DecBufs{c->d_info2, c->d_blk2, c->d_tabs2, c->d_scratch2, c->d_sbase2, c->d_stream_n2}, g_err);
     return decode_m1_launch(c->dec, c->ws, j, g_err);
 }
