@@ -427,6 +427,50 @@ int xpnghip_resample_host(int pxsz, const uint8_t *raster, uint64_t w, uint64_t 
                           uint32_t out_h, uint32_t layout, uint32_t dtype, const float *scale, const float *bias, uint32_t filter,
                           void *out);
 
+/* ---- several views per image, only the tiles they touch --------------------------------------
+ * The resampled call above writes one output per image, all of one size, and reconstructs every tile whatever the rectangles.  The
+ * views call writes `nviews` outputs (1 .. 65535) from the `nimg` images of a mixed context - any number per image, none included -
+ * each with its own rectangle, flip and output size, and decodes ONLY the tiles that some view of their image touches.
+ *   view_image[v]   the image view v reads, 0 .. nimg-1.  NULL: the identity, and then nviews must equal nimg.
+ *   rects           nviews * 4 values {x, y, w, h}, each valid inside ITS image as for the region decode.  NULL: whole images.
+ *   flips           nviews bytes, 0 or 1.  NULL: none.
+ *   out_sizes       nviews pairs {out_w, out_h}, each value 1 .. 16384; the sizes of one call may differ.  Required.
+ *   d_outs[v]       exactly C * out_h_v * out_w_v elements of `dtype` in `layout`, aligned to the element size (slices of stacked
+ *                   tensors qualify); nothing else is written.  Outputs that overlap are the caller's business.
+ *   layout, dtype, scale, bias, filter   the resampled call's, one value per call.
+ * THE VALUES.  View v of image i receives, bit for bit, what
+ *     xpnghip_resample_host(pxsz, raster_i, w_i, h_i, rect_v, flip_v, out_w_v, out_h_v, layout, dtype, scale, bias, filter, out)
+ * writes: that function is the rule, and consequences (a), (b) and (c) of the resampled call hold per view.
+ * THE SELECTION.  A tile of the concatenated table is decoded if and only if it intersects the rectangle of at least one view of
+ * its image (the test of xpnghip_region_tiles).  The launch list is the context's size-sorted list with the unselected entries
+ * removed: decreasing pixel count, equal sizes in table order.  xpnghip_view_tiles below returns exactly that list, and the device
+ * call uses the same function.  The size walk still covers every tile of every image (offsets are a serial sum), and the staging
+ * raster, its slots and its size are those of every tight call (STAGING SIZE above).  Pixels of unselected tiles in the staging
+ * raster are whatever earlier calls left; no tap reads them, because every window is clamped to its rectangle (consequence (c)).
+ * xpnghip_ctx_decode_status reports on the tiles that were decoded: an unselected tile is not validated.
+ * RECORDS.  One 64-byte record per view (the image's staging slot, the buffer, the rectangle, the output size, kx, ky, 1/kx, 1/ky
+ * - one host fp32 division each, as in the resized and resampled calls - and the flip) and the selected list (4 bytes per tile)
+ * are uploaded on every call and never cached, by the resized call's protocol: one upload and one synchronisation of `stream`,
+ * queued before the call's own kernels.  Both buffers belong to the context's workspace and grow only when a call needs more than
+ * any call before it.  The cached per-image table of the other tight calls is not touched.
+ * Refused before anything reaches the device, with the offending value in xpnghip_last_error() and nothing written: nviews outside
+ * 1 .. 65535; NULL view_image with nviews != nimg; a view_image[v] >= nimg (the text names the view); an invalid rectangle (the
+ * view and the image); an output size outside 1 .. 16384 (the view); a flip byte above 1; a filter other than 0 or 1; NULL
+ * out_sizes; a NULL or misaligned d_outs[v]; and everything the float call refuses. */
+int xpnghip_decode_varsize_device_batch_views(xpnghip_ctx *ctx, int mode, const void *const *d_blobs, const uint64_t *blobs_len,
+                                              uint32_t nimg, const uint64_t *tile_off, uint32_t nviews, const uint32_t *view_image,
+                                              void *const *d_outs, const uint32_t *out_sizes, const uint64_t *rects,
+                                              const uint8_t *flips, uint32_t layout, uint32_t dtype, const float *scale,
+                                              const float *bias, uint32_t filter, void *stream);
+/* host-only, needs no device: the launch list of a views call over images of `dims` (nimg pairs {w, h}, as for
+ * xpnghip_ctx_create_mixed) - indices into the concatenated tile table, in launch order.  view_image and rects as above (NULL
+ * allowed as above).  Returns the count, or -1 on a bad argument or when `cap` entries are too few. */
+int64_t xpnghip_view_tiles(const uint64_t *dims, uint32_t nimg, uint32_t nviews, const uint32_t *view_image, const uint64_t *rects,
+                           uint32_t *tiles, uint64_t cap);
+/* The number of tile work items in the context's most recent decode launch: M after the other mixed calls, the length of the list
+ * after a views or a region call, nimg * (t1 - t0) after a range decode, 0 before any decode. */
+uint64_t xpnghip_ctx_last_decode_tiles(const xpnghip_ctx *ctx);
+
 /* ---- staged batch from device tensors: the inverse of the float call --------------------------
  * A model writes floats, not the file's bytes.  The call below is xpnghip_images_begin with the upload replaced by one staging
  * kernel that reads the caller's DEVICE buffers - planar or interleaved, RGB or BGR, uint8, f16, bf16 or f32 - and writes the

@@ -37,6 +37,7 @@ HIP_SYMBOLS = [
     "xpnghip_decode_varsize_device_batch_resized", "xpnghip_resize_host",
     "xpnghip_decode_varsize_device_batch_resampled", "xpnghip_resample_host",
     "xpnghip_images_begin_device", "xpnghip_quantize_host",
+    "xpnghip_decode_varsize_device_batch_views", "xpnghip_view_tiles", "xpnghip_ctx_last_decode_tiles",
 ]
 HOST_SYMBOLS = ["xpng_store", "xpng_load", "xpng_from_jpg", "xpng_store_T", "xpng_load_T", "xpng_from_jpg_T",
                 "store_7", "load_7"]
@@ -191,6 +192,15 @@ def _bind_hip(path):
         L.xpnghip_resample_host.restype = C.c_int
         L.xpnghip_resample_host.argtypes = [C.c_int, vp, u64, u64, C.POINTER(u64), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                             f32p, f32p, C.c_uint32, vp]
+        u32p = C.POINTER(C.c_uint32)
+        L.xpnghip_decode_varsize_device_batch_views.restype = C.c_int
+        L.xpnghip_decode_varsize_device_batch_views.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64), C.c_uint32, C.POINTER(u64), C.c_uint32, u32p,
+                                                                C.POINTER(vp), u32p, C.POINTER(u64), u8p, C.c_uint32, C.c_uint32, f32p, f32p,
+                                                                C.c_uint32, vp]
+        L.xpnghip_view_tiles.restype = C.c_int64
+        L.xpnghip_view_tiles.argtypes = [C.POINTER(u64), C.c_uint32, C.c_uint32, u32p, C.POINTER(u64), u32p, u64]
+        L.xpnghip_ctx_last_decode_tiles.restype = u64
+        L.xpnghip_ctx_last_decode_tiles.argtypes = [vp]
         L.xpnghip_images_begin.restype = C.c_int
         L.xpnghip_images_begin.argtypes = [C.POINTER(vp), C.c_uint32, C.POINTER(vp), C.POINTER(u64), u8p, u8p]
         L.xpnghip_images_begin_device.restype = C.c_int
@@ -552,6 +562,16 @@ def _rect_array(name, rects, n):
         raise XpngError(f"{name}: a rectangle is four non-negative integers (x, y, w, h)") from None
 
 
+def _flip_array(name, flips, n, what="images"):
+    """n flips as a C array of bytes (None stays None: no flips)"""
+    if flips is None:
+        return None
+    flips = list(flips)
+    if len(flips) != n:
+        raise XpngError(f"{name}: flips has {len(flips)} entries for {n} {what}")
+    return (C.c_uint8 * max(n, 1))(*[int(f) & 0xFF for f in flips])
+
+
 def resize_host(raster, size, layout: int, dtype: int, scale=None, bias=None, rect=None, flip=False) -> bytes:
     """The rule of MixedContext.decode_batch_resized on the host (xpnghip_resize_host; needs no device): `raster` is an
     (h, w, 3|4) uint8 array in the file's form, size = (OH, OW), rect = (x, y, w, h) or None for the whole raster.  Returns the
@@ -598,6 +618,35 @@ def resample_host(raster, size, layout: int, dtype: int, scale=None, bias=None, 
                                        int(filter) & 0xFFFFFFFF, buf.ctypes.data):
         raise XpngError("xpnghip_resample_host: " + _err())
     return buf.tobytes()[:ch * oh * ow * dtype_bytes(dtype)]
+
+
+def _view_images(name, view_image, nviews):
+    """the image of every view as a C array of uint32 (None stays None: the identity)"""
+    if view_image is None:
+        return None
+    try:
+        return (C.c_uint32 * max(nviews, 1))(*[int(i) & 0xFFFFFFFF for i in view_image])
+    except (TypeError, ValueError):
+        raise XpngError(f"{name}: view_image must be a sequence of image indices") from None
+
+
+def view_tiles(dims, view_image, rects) -> list:
+    """The launch list of MixedContext.decode_batch_views (xpnghip_view_tiles; host-only, needs no device): the tiles of the
+    concatenated table of images dims[i] = (w, h) that some view of their image touches, by decreasing pixel count, equal sizes in
+    table order.  view_image[v] is the image of view v (None: view v reads image v), rects[v] = (x, y, w, h) inside that image
+    (rects None: whole images).  Raises XpngError on a bad index, rectangle or size."""
+    dims = [(int(w), int(h)) for (w, h) in dims]
+    nviews = len(dims) if view_image is None else len(list(view_image))
+    vi = _view_images("view_tiles", None if view_image is None else list(view_image), nviews)
+    ra = _rect_array("view_tiles", rects, nviews)
+    ok = 0 < len(dims) <= 4096 and all(0 < v <= 1 << 24 for d in dims for v in d)
+    cap = sum(_tile_count(w, h) for (w, h) in dims) if ok else 1
+    flat, arr = (C.c_uint64 * max(2 * len(dims), 1))(*[v & 0xFFFFFFFFFFFFFFFF for d in dims for v in d]), (C.c_uint32 * max(cap, 1))()
+    n = hip_lib().xpnghip_view_tiles(flat, len(dims), nviews, vi, ra, arr, cap)
+    if n < 0:
+        raise XpngError(f"view_tiles: bad arguments ({len(dims)} images, {nviews} views: an image index outside the batch, a rectangle that is "
+                        "empty or leaves its image, or a side outside 1 .. 16777216)")
+    return list(arr[:n])
 
 
 def quantize_host(src, npx: int, channels: int, layout: int, dtype: int, scale=None, bias=None) -> np.ndarray:
@@ -923,8 +972,9 @@ class MixedContext(_Handle):
         offsets of its tiles."""
         self._decode("xpnghip_decode_mixed_device_batch", mode, d_blobs, lens, d_outs, tile_offs, stream, out_bpr)
 
-    def _decode(self, symbol, mode, d_blobs, lens, d_outs, tile_offs, stream, *between):
-        """the marshalling of every decode call; between = the arguments of this form, which sit between d_outs and stream"""
+    def _decode(self, symbol, mode, d_blobs, lens, d_outs, tile_offs, stream, *between, before=()):
+        """the marshalling of every decode call; between = the arguments of this form, which sit between d_outs and stream (before:
+        those of the views call in front of d_outs)"""
         k = len(d_blobs)
         off_arr = None
         if tile_offs is not None:
@@ -932,7 +982,7 @@ class MixedContext(_Handle):
             assert len(flat) == self.n_tiles
             off_arr = (C.c_uint64 * len(flat))(*flat)
         ins, outs, ln = (C.c_void_p * k)(*d_blobs), (C.c_void_p * len(d_outs))(*d_outs), (C.c_uint64 * len(lens))(*lens)
-        if getattr(hip_lib(), symbol)(self._h, mode, ins, ln, k, off_arr, outs, *between, stream):
+        if getattr(hip_lib(), symbol)(self._h, mode, ins, ln, k, off_arr, *before, outs, *between, stream):
             raise XpngError(symbol + ": " + _err())
 
     def decode_batch_as(self, mode, d_blobs, lens, d_outs, layout, tile_offs=None, stream=0):
@@ -959,12 +1009,7 @@ class MixedContext(_Handle):
             raise XpngError(f"decode_batch_resized: size must be (OH, OW), not {size!r}") from None
         sc, bi, _ = _scale_bias(layout, self.pxsz, scale, bias)
         ra = _rect_array("decode_batch_resized", rects, k)
-        fl = None
-        if flips is not None:
-            flips = list(flips)
-            if len(flips) != k:
-                raise XpngError(f"decode_batch_resized: flips has {len(flips)} entries for {k} images")
-            fl = (C.c_uint8 * max(k, 1))(*[int(f) & 0xFF for f in flips])
+        fl = _flip_array("decode_batch_resized", flips, k)
         self._decode("xpnghip_decode_varsize_device_batch_resized", mode, d_blobs, lens, d_outs, tile_offs, stream, layout, dtype, sc, bi, ra, fl, ow, oh)
 
     def decode_batch_resampled(self, mode, d_blobs, lens, d_outs, layout, dtype, size, scale=None, bias=None, rects=None, flips=None,
@@ -980,14 +1025,41 @@ class MixedContext(_Handle):
             raise XpngError(f"decode_batch_resampled: size must be (OH, OW), not {size!r}") from None
         sc, bi, _ = _scale_bias(layout, self.pxsz, scale, bias)
         ra = _rect_array("decode_batch_resampled", rects, k)
-        fl = None
-        if flips is not None:
-            flips = list(flips)
-            if len(flips) != k:
-                raise XpngError(f"decode_batch_resampled: flips has {len(flips)} entries for {k} images")
-            fl = (C.c_uint8 * max(k, 1))(*[int(f) & 0xFF for f in flips])
+        fl = _flip_array("decode_batch_resampled", flips, k)
         self._decode("xpnghip_decode_varsize_device_batch_resampled", mode, d_blobs, lens, d_outs, tile_offs, stream, layout, dtype, sc, bi, ra, fl, ow, oh,
                      int(filter) & 0xFFFFFFFF)
+
+    def decode_batch_views(self, mode, d_blobs, lens, view_image, d_outs, layout, dtype, sizes, scale=None, bias=None, rects=None, flips=None,
+                           filter: int = FILTER_TRIANGLE_AA, tile_offs=None, stream=0):
+        """decode_batch_resampled with any number of outputs per image, and only the tiles they touch decoded: view v reads image
+        view_image[v] (None: view v reads image v), its rectangle rects[v] = (x, y, w, h) (None: whole images), mirrored where
+        flips[v] is true, resampled to its own size: `sizes` is one (OH, OW) for every view or one pair per view.  d_outs[v] is
+        C * OH_v * OW_v elements of `dtype`: xpnghip_decode_varsize_device_batch_views (the rule is in include/xpng_hip.h)."""
+        n = len(d_outs)
+        vi = _view_images("decode_batch_views", None if view_image is None else list(view_image), n)
+        if view_image is not None and len(list(view_image)) != n:
+            raise XpngError(f"decode_batch_views: view_image has {len(list(view_image))} entries for {n} output buffers")
+        so = None
+        if sizes is not None:
+            try:
+                sizes = list(sizes)
+                if len(sizes) == 2 and not hasattr(sizes[0], "__len__"):
+                    sizes = [sizes] * n
+                if len(sizes) != n:
+                    raise XpngError(f"decode_batch_views: sizes has {len(sizes)} entries for {n} views")
+                so = (C.c_uint32 * max(2 * n, 1))(*[int(v) & 0xFFFFFFFF for (oh, ow) in sizes for v in (ow, oh)])
+            except (TypeError, ValueError):
+                raise XpngError(f"decode_batch_views: sizes must be (OH, OW) or one (OH, OW) per view, not {sizes!r}") from None
+        sc, bi, _ = _scale_bias(layout, self.pxsz, scale, bias)
+        ra = _rect_array("decode_batch_views", rects, n)
+        fl = _flip_array("decode_batch_views", flips, n, "views")
+        self._decode("xpnghip_decode_varsize_device_batch_views", mode, d_blobs, lens, d_outs, tile_offs, stream, so, ra, fl, layout, dtype, sc, bi,
+                     int(filter) & 0xFFFFFFFF, before=(n, vi))
+
+    def last_decode_tiles(self) -> int:
+        """tile work items of the context's most recent decode launch (xpnghip_ctx_last_decode_tiles): n_tiles after the other
+        decode calls, len(view_tiles(...)) after decode_batch_views, 0 before any decode"""
+        return hip_lib().xpnghip_ctx_last_decode_tiles(self._h)
 
     def encode_batch_from(self, mode, d_rasters, layout, d_blobs, stream=0, sync=True):
         """encode_batch in its tight form, with every d_rasters[i] read in `layout` (api.layout(); its channels must be the

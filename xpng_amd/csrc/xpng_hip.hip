@@ -33,6 +33,7 @@
 #include "mixed_float.hpp"
 #include "mixed_resize.hpp"
 #include "mixed_resample.hpp"
+#include "mixed_views.hpp"
 #include "stage_from.hpp"
 
 using namespace xpng;
@@ -209,6 +210,12 @@ struct xpnghip_ctx {
     std::vector<const void *> h_m_out, h_m_in;  // the buffers the two tables hold (skip the upload when unchanged)
     ResizeRec *d_m_rect = nullptr;     // the rectangle table of a resized decode (mixed_resize.hpp): B records, uploaded by every call
     ResampleRec *d_m_rsmp = nullptr;   // ... and that of a resampled decode with filter 1 (mixed_resample.hpp), alike
+    // a views decode (mixed_views.hpp): one record per view, grown when a call has more views than any before it, and the launch
+    // list of the call (room for all M entries, so it never grows); both uploaded by every call
+    ViewRec *d_m_views = nullptr;
+    uint64_t cap_m_views = 0;          // records d_m_views has room for
+    uint32_t *d_m_vlist = nullptr;
+    uint64_t last_tiles = 0;           // tile work items of the most recent decode launch (xpnghip_ctx_last_decode_tiles)
 };
 
 // the context's own stream, created when a call first needs it (the `stream == NULL` form of the device-resident entry points,
@@ -677,6 +684,7 @@ static int dec_launch(xpnghip_ctx *c, int mode, uint32_t nimg, uint64_t W, const
     j.tiles = c->d_tiles; j.blobs = c->d_dec_in_ptrs; j.blob_len = c->d_blob_len; j.rasters = c->d_dec_out_ptrs; j.status = c->d_status;
     j.tile_off = tile_off;
     j.s = s;
+    c->last_tiles = j.total();
     j.stamps = c->stamps && !list ? c->d_dbg + N * c->B * 80 : nullptr;
     // the side stream, for the forms that fork one: level 2, and the narrow level-1 RGBA form (the wide form has no second stream)
     if (mode == 2 || (c->pxsz == 4 && !decode_m1_plan(j).wide)) {
@@ -1285,24 +1293,18 @@ static int mixed_stage_slots(xpnghip_ctx *c, uint64_t bpr, std::vector<uint64_t>
     return 0;
 }
 
-// `layout` != NULL: the call of xpnghip_decode_varsize_device_batch_as (out_bpr == 0: its buffers are tight); `fc` != NULL beside
-// it: the call of xpnghip_decode_varsize_device_batch_as_float (its buffers hold elements of fc->dtype); `rz` != NULL beside both:
-// the call of xpnghip_decode_varsize_device_batch_resized (every buffer holds C * rz->out_h * rz->out_w such elements), or with
-// rz->filter that of xpnghip_decode_varsize_device_batch_resampled
-static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
-                                   const uint64_t *tile_off, void *const *d_outs, uint64_t out_bpr, void *stream, const uint32_t *layout = nullptr,
-                                   const FloatCall *fc = nullptr, const ResizeCall *rz = nullptr) {
-    // every argument is checked before anything reaches the device: a rejected call writes nothing
+// What every decode call of a mixed context checks first, in this order: the context, the layout word (`layout` == NULL: the file's
+// own form), the dtype and the constants of a float call (`fc` == NULL: bytes), the mode, the number of images, the arrays.  Gives
+// the channels and the element size of the caller's buffers and the constants.
+static int mixed_decode_args(const xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg, void *const *d_outs,
+                             const uint32_t *layout, const FloatCall *fc, int &C, int &es, FloatConsts &fk) {
     if (!c) return fail("null context");
     if (!c->mixed) return fail("not a mixed context (xpnghip_ctx_create_mixed)");
-    const int C = layout ? xpnghip_layout_channels(*layout, c->pxsz) : c->pxsz;
+    C = layout ? xpnghip_layout_channels(*layout, c->pxsz) : c->pxsz;
     if (C < 0) return fail("bad layout word " + layout_hex(*layout) + " (XPNGHIP_LAYOUT_PLANAR | XPNGHIP_LAYOUT_BGR | channels 0, 3 or 4 in bits 8..11)");
-    // (interleaved, the file's colour order and channel count: the tight form itself, k_mixed_copy and its records)
-    const bool as = !fc && layout && ((*layout & (XPNGHIP_LAYOUT_PLANAR | XPNGHIP_LAYOUT_BGR)) || C != c->pxsz);
-    const int es = fc ? xpnghip_dtype_bytes(fc->dtype) : 1;
+    es = fc ? xpnghip_dtype_bytes(fc->dtype) : 1;
     if (es < 0)
         return fail("bad dtype " + std::to_string(fc->dtype) + " (XPNGHIP_DTYPE_F16 = 1, _BF16 = 2, _F32 = 3; uint8 buffers are written by xpnghip_decode_varsize_device_batch_as)");
-    FloatConsts fk{};
     if (fc) {
         std::string why;
         if (!float_consts(C, fc->scale, fc->bias, fk, why)) return fail(why);
@@ -1311,6 +1313,22 @@ static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *
     if (mode == 2 && c->pxsz != 3) return fail("mode 2 codes RGB only");
     if (nimg != c->B) return fail("nimg is " + std::to_string(nimg) + ", the mixed context holds " + std::to_string(c->B) + " images");
     if (!d_blobs || !blobs_len || !d_outs) return fail("null argument");
+    return 0;
+}
+
+// `layout` != NULL: the call of xpnghip_decode_varsize_device_batch_as (out_bpr == 0: its buffers are tight); `fc` != NULL beside
+// it: the call of xpnghip_decode_varsize_device_batch_as_float (its buffers hold elements of fc->dtype); `rz` != NULL beside both:
+// the call of xpnghip_decode_varsize_device_batch_resized (every buffer holds C * rz->out_h * rz->out_w such elements), or with
+// rz->filter that of xpnghip_decode_varsize_device_batch_resampled
+static int decode_mixed_batch_impl(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
+                                   const uint64_t *tile_off, void *const *d_outs, uint64_t out_bpr, void *stream, const uint32_t *layout = nullptr,
+                                   const FloatCall *fc = nullptr, const ResizeCall *rz = nullptr) {
+    // every argument is checked before anything reaches the device: a rejected call writes nothing
+    int C, es;
+    FloatConsts fk{};
+    if (mixed_decode_args(c, mode, d_blobs, blobs_len, nimg, d_outs, layout, fc, C, es, fk)) return 1;
+    // (interleaved, the file's colour order and channel count: the tight form itself, k_mixed_copy and its records)
+    const bool as = !fc && layout && ((*layout & (XPNGHIP_LAYOUT_PLANAR | XPNGHIP_LAYOUT_BGR)) || C != c->pxsz);
     const uint64_t px = (uint64_t)c->pxsz, widest = c->m_max_w * px;
     if (out_bpr && out_bpr < widest)
         return fail("out_bpr " + std::to_string(out_bpr) + " is smaller than the widest row of the batch (" + std::to_string(widest) + " bytes)");
@@ -1410,6 +1428,150 @@ extern "C" int xpnghip_decode_varsize_device_batch_resampled(xpnghip_ctx *c, int
     const FloatCall fc{dtype, scale, bias};
     const ResizeCall rz{rects, flips, out_w, out_h, filter};
     XPNG_GUARDED(decode_mixed_batch_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, d_outs, 0, stream, &layout, &fc, &rz))
+}
+
+// ---- several views per image, only the tiles they touch (mixed_views.hpp) -----------------------------------------
+// what the two entry points below check alike: the number of views, the image of every view and its rectangle (NULL: whole images)
+static bool view_args_ok(const uint64_t *dims, uint32_t nimg, uint32_t nviews, const uint32_t *view_image, const uint64_t *rects, std::string &why) {
+    if (nviews < 1 || nviews > 65535) { why = "nviews is " + std::to_string(nviews) + ", not 1 .. 65535"; return false; }
+    if (!view_image && nviews != nimg) {
+        why = "view_image is NULL (the identity) but nviews is " + std::to_string(nviews) + " and nimg " + std::to_string(nimg);
+        return false;
+    }
+    for (uint32_t v = 0; v < nviews; v++) {
+        const uint32_t i = view_image ? view_image[v] : v;
+        if (i >= nimg) { why = "view_image[" + std::to_string(v) + "] is " + std::to_string(i) + ", the batch holds " + std::to_string(nimg) + " images"; return false; }
+        if (!rects) continue;
+        const uint64_t W = dims[2ull * i], H = dims[2ull * i + 1], *r = rects + 4ull * v;
+        if (!region_valid(W, H, r)) {
+            why = "bad rectangle {" + std::to_string(r[0]) + ", " + std::to_string(r[1]) + ", " + std::to_string(r[2]) + ", " + std::to_string(r[3]) +
+                  "}: it is empty or leaves the " + std::to_string(W) + " x " + std::to_string(H) + " image (view " + std::to_string(v) + ", image " + std::to_string(i) + ")";
+            return false;
+        }
+    }
+    return true;
+}
+// The launch list of a views call: `sorted` - every index of the concatenated table `tiles` by decreasing pixel count, equal sizes in
+// table order; image i owns [first[i], first[i + 1]) - without the tiles that no view of their image touches (region_select's
+// test).  The arguments have passed view_args_ok.
+static void view_select(const std::vector<TileDesc> &tiles, const std::vector<uint32_t> &first, const std::vector<uint32_t> &sorted, const uint64_t *dims,
+                        uint32_t nviews, const uint32_t *view_image, const uint64_t *rects, std::vector<uint32_t> &out) {
+    std::vector<uint8_t> keep(tiles.size(), 0);
+    std::vector<TileDesc> one;
+    std::vector<uint32_t> sel;
+    for (uint32_t v = 0; v < nviews; v++) {
+        const uint32_t i = view_image ? view_image[v] : v;
+        const uint64_t whole[4] = {0, 0, dims[2ull * i], dims[2ull * i + 1]};
+        one.assign(tiles.begin() + first[i], tiles.begin() + first[i + 1]);
+        region_select(one, rects ? rects + 4ull * v : whole, sel);
+        for (uint32_t t : sel) keep[first[i] + t] = 1;
+    }
+    out.clear();
+    for (uint32_t t : sorted) if (keep[t]) out.push_back(t);
+}
+extern "C" int64_t xpnghip_view_tiles(const uint64_t *dims, uint32_t nimg, uint32_t nviews, const uint32_t *view_image, const uint64_t *rects,
+                                      uint32_t *tiles, uint64_t cap) {
+    try {
+        if (!dims || nimg < 1 || nimg > 4096) return -1;
+        for (uint32_t i = 0; i < 2 * nimg; i++) if (!dims[i] || dims[i] > (1u << 24)) return -1;
+        std::string why;
+        if (!view_args_ok(dims, nimg, nviews, view_image, rects, why)) return -1;
+        // the concatenated table and its size-sorted list, as xpnghip_ctx_create_mixed builds them
+        std::vector<TileDesc> all, one;
+        std::vector<uint32_t> first((size_t)nimg + 1);
+        for (uint32_t i = 0; i < nimg; i++) {
+            build_tiles(dims[2ull * i], dims[2ull * i + 1], one);
+            first[i] = (uint32_t)all.size();
+            all.insert(all.end(), one.begin(), one.end());
+            if (all.size() > 0xFFFFFFFFull) return -1;
+        }
+        first[nimg] = (uint32_t)all.size();
+        std::vector<uint32_t> sorted(all.size()), list;
+        for (size_t i = 0; i < all.size(); i++) sorted[i] = (uint32_t)i;
+        std::stable_sort(sorted.begin(), sorted.end(), [&](uint32_t a, uint32_t b) { return all[a].n > all[b].n; });
+        view_select(all, first, sorted, dims, nviews, view_image, rects, list);
+        if (list.size() > cap || !tiles) return -1;
+        std::copy(list.begin(), list.end(), tiles);
+        return (int64_t)list.size();
+    } catch (...) { return -1; }
+}
+extern "C" uint64_t xpnghip_ctx_last_decode_tiles(const xpnghip_ctx *c) { return c ? c->last_tiles : 0; }
+
+static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg, const uint64_t *tile_off,
+                             uint32_t nviews, const uint32_t *view_image, void *const *d_outs, const uint32_t *out_sizes, const uint64_t *rects,
+                             const uint8_t *flips, uint32_t layout, uint32_t dtype, const float *scale, const float *bias, uint32_t filter, void *stream) {
+    // every argument is checked before anything reaches the device: a rejected call writes nothing
+    int C, es;
+    FloatConsts fk{};
+    const FloatCall fc{dtype, scale, bias};
+    if (mixed_decode_args(c, mode, d_blobs, blobs_len, nimg, d_outs, &layout, &fc, C, es, fk)) return 1;  // (everything the float call refuses)
+    std::string why;
+    if (!resample_filter_ok(filter, why)) return fail(why);
+    if (!out_sizes) return fail("out_sizes is NULL: a views call needs the pair {out_w, out_h} of every view");
+    if (!view_args_ok(c->m_dims.data(), nimg, nviews, view_image, rects, why)) return fail(why);
+    const uint64_t px = (uint64_t)c->pxsz, bpr = rup(c->m_max_w * px, 16);
+    std::vector<uint64_t> slot((size_t)nimg + 1, 0);  // (mixed_stage_slots' layout: the refusals below come before anything is allocated)
+    for (uint32_t i = 0; i < nimg; i++) slot[i + 1] = slot[i] + rup(c->m_dims[2ull * i + 1] * bpr, 256);
+    std::vector<ViewRec> recs(nviews);
+    uint32_t max_oh = 0;
+    for (uint32_t v = 0; v < nviews; v++) {
+        const uint32_t i = view_image ? view_image[v] : v, ow = out_sizes[2ull * v], oh = out_sizes[2ull * v + 1];
+        const std::string who = " (view " + std::to_string(v) + ", image " + std::to_string(i) + ")";
+        ResizeRec z;
+        if (!resize_size_ok(ow, oh, why)) return fail(why + who);
+        if (!resize_record(c->m_dims[2ull * i], c->m_dims[2ull * i + 1], rects ? rects + 4ull * v : nullptr, flips ? flips[v] : 0u, ow, oh, z, why)) return fail(why + who);
+        if (!d_outs[v]) return fail("null output buffer of view " + std::to_string(v));
+        if ((uintptr_t)d_outs[v] & (uintptr_t)(es - 1)) {
+            char b[32];
+            snprintf(b, sizeof b, "%p", d_outs[v]);
+            return fail("output buffer " + std::string(b) + " of view " + std::to_string(v) + " is not aligned to its " + std::to_string(es) + "-byte elements");
+        }
+        const ResampleRec q = resample_record(z);  // (the four ratios exactly as the resized and the resampled calls compute them)
+        recs[v] = ViewRec{slot[i], (uint8_t *)d_outs[v], q.rx, q.ry, q.rw, q.rh, ow, oh, q.kx, q.ky, q.ikx, q.iky, q.flip, 0};
+        max_oh = std::max(max_oh, oh);
+    }
+    for (uint32_t i = 0; i < nimg; i++) {
+        if (!d_blobs[i]) return fail("null blob of image " + std::to_string(i));
+        if ((uintptr_t)d_blobs[i] & 3) return fail("device buffers must be 16-byte aligned");
+    }
+    std::vector<uint32_t> list;
+    view_select(c->tiles, c->m_first, c->m_list, c->m_dims.data(), nviews, view_image, rects, list);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(c);
+    if (mixed_stage_slots(c, bpr, slot)) return 1;
+    if (c->cap_m_views < nviews) {
+        if (c->d_m_views) {  // (an earlier call's copy-out may still read the old table: the context's work is on these streams)
+            for (hipStream_t q : {s, c->stream, c->side}) if (q) HIPCHK(hipStreamSynchronize(q));
+            c->ws.drop((void **)&c->d_m_views); c->cap_m_views = 0;
+        }
+        WS_GET(c->d_m_views, (uint64_t)nviews * sizeof(ViewRec));
+        c->cap_m_views = nviews;
+    }
+    WS_GET(c->d_m_vlist, (uint64_t)c->tiles.size() * 4);
+    // the resized call's protocol: both tables are in pageable host memory that ends with this call, so the stream is synchronised
+    // once behind the two copies - queued before the decode's own kernels, so the wait never covers this call's work
+    HIPCHK(hipMemcpyAsync(c->d_m_views, recs.data(), (uint64_t)nviews * sizeof(ViewRec), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->d_m_vlist, list.data(), (uint64_t)list.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    std::vector<void *> base(nimg);
+    for (uint32_t i = 0; i < nimg; i++) base[i] = c->d_m_stage + slot[i];
+    if (dec_prepare(c, mode, d_blobs, blobs_len, nimg, base.data(), s)) return 1;
+    XPNG_REQUIRE(c->d_m_first, c->d_m_stage, c->d_m_views, c->d_m_vlist);
+    const int rc = dec_launch(c, mode, nimg, c->m_max_w, tile_off, s, 0, (uint32_t)c->tiles.size(), &list, c->d_m_vlist, bpr);
+    if (rc) return rc;
+    const uint32_t bgr = layout & XPNGHIP_LAYOUT_BGR;
+    const dim3 grid((max_oh + MC_ROWS - 1) / MC_ROWS, nviews);
+    with_3or4(c->pxsz, [&](auto PXc) { with_3or4(C, [&](auto Cc) { with_planar(layout, [&](auto PL) { with_float(dtype, [&](auto t) {
+        k_mixed_views_as_float<decltype(PXc)::value, decltype(Cc)::value, decltype(PL)::value, decltype(t)><<<grid, 256, 0, s>>>(c->d_m_views, c->d_m_stage, bpr, bgr, filter, fk);
+    }); }); }); });
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+extern "C" int xpnghip_decode_varsize_device_batch_views(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
+                                                         const uint64_t *tile_off, uint32_t nviews, const uint32_t *view_image, void *const *d_outs,
+                                                         const uint32_t *out_sizes, const uint64_t *rects, const uint8_t *flips, uint32_t layout,
+                                                         uint32_t dtype, const float *scale, const float *bias, uint32_t filter, void *stream) {
+    XPNG_GUARDED(decode_views_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, nviews, view_image, d_outs, out_sizes, rects, flips, layout, dtype, scale, bias, filter, stream))
 }
 
 // ---- mixed-size batch encode (mixed.hpp) ---------------------------------------------------------

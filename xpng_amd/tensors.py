@@ -7,6 +7,8 @@ pixel) and every group is decoded by mixed-size device calls straight into tenso
 MixedContext.decode_batch_as_float when a float dtype is asked for: the same pass converts and normalises, XPNGHIP_DTYPE_*;
 MixedContext.decode_batch_resized when an output size is asked for: the same pass also crops, resizes and flips;
 MixedContext.decode_batch_resampled when that resize is to antialias).
+`load_views` gives any number of crops per file from ONE decode of it, and decodes only the tiles they touch
+(MixedContext.decode_batch_views).
 api.py stays free of torch; this module is the only one of the package that imports it at load time."""
 from __future__ import annotations
 
@@ -107,6 +109,48 @@ def centre_crop(width, height, ratio=(3.0 / 4.0, 4.0 / 3.0)):
     return ((width - w) // 2, (height - h) // 2, w, h)
 
 
+def _read_xpng(fn, p):
+    """the bytes of a .xpng file and (level, w, h, bytes per pixel) from its 8-byte header; fn names the caller in the errors"""
+    try:
+        with open(p, "rb") as f:
+            buf = f.read()
+    except OSError as e:
+        raise XpngError(f"{fn}: cannot read {os.fspath(p)!r}: {e}") from None
+    if len(buf) < 8:
+        raise XpngError(f"{fn}: {os.fspath(p)!r} is shorter than a header")
+    h0, h1 = int.from_bytes(buf[0:4], "little"), int.from_bytes(buf[4:8], "little")
+    mode, w, h, alpha = h0 >> 24, (h0 & 0xFFFFFF) + 1, (h1 & 0xFFFFFF) + 1, (h1 >> 24) & 1
+    if mode not in (1, 2, 7):
+        raise XpngError(f"{fn}: {os.fspath(p)!r} has level {mode}")
+    return buf, (mode, w, h, 3 + alpha)
+
+
+def _host_raster(fn, p, buf, head):
+    """the (h, w, px) uint8 tensor of a file that is answered from its host bytes - level 7, or a whole-image single colour - or
+    None for a file that needs the tile codec"""
+    mode, w, h, px = head
+    if mode == 7:
+        if len(buf) < 8 + w * h * px:
+            raise XpngError(f"{fn}: {os.fspath(p)!r} is shorter than its raster")
+        return torch.frombuffer(bytearray(buf[8:8 + w * h * px]), dtype=torch.uint8).view(h, w, px)
+    if len(buf) == 8 + px and buf[7] & 2:                      # whole-image single colour: the file holds one pixel
+        return torch.frombuffer(bytearray(buf[8:8 + px]), dtype=torch.uint8).view(1, 1, px).expand(h, w, px)
+    return None
+
+
+def _pack_bodies(part):
+    """the tile bodies of the files of one device call, (index, w, h, bytes) each, in one host buffer: each 16-byte aligned, 64
+    readable bytes behind the last -> (buffer, offsets)"""
+    offs, total = [], 0
+    for (_, _, _, buf) in part:
+        offs.append(total)
+        total += -(-(len(buf) - 8) // 16) * 16
+    host = bytearray(total + 64)
+    for o, (_, _, _, buf) in zip(offs, part):
+        host[o:o + len(buf) - 8] = buf[8:]
+    return host, offs
+
+
 def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, device=None, dtype=torch.uint8, mean=None, std=None,
                stack: bool = False, size=None, crops=None, flips=None, antialias: bool = False):
     """The images of a list of .xpng files of any sizes as tensors on `device` (default: the current cuda device), each of
@@ -194,18 +238,8 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
         raise XpngError("load_files: no GPU is visible (device='cpu' answers level-7 and single-colour files without one)")
     heads, bufs = [], []
     for p in paths:
-        try:
-            with open(p, "rb") as f:
-                buf = f.read()
-        except OSError as e:
-            raise XpngError(f"load_files: cannot read {os.fspath(p)!r}: {e}") from None
-        if len(buf) < 8:
-            raise XpngError(f"load_files: {os.fspath(p)!r} is shorter than a header")
-        h0, h1 = int.from_bytes(buf[0:4], "little"), int.from_bytes(buf[4:8], "little")
-        mode, w, h, alpha = h0 >> 24, (h0 & 0xFFFFFF) + 1, (h1 & 0xFFFFFF) + 1, (h1 >> 24) & 1
-        if mode not in (1, 2, 7):
-            raise XpngError(f"load_files: {os.fspath(p)!r} has level {mode}")
-        heads.append((mode, w, h, 3 + alpha))
+        buf, head = _read_xpng("load_files", p)
+        heads.append(head)
         bufs.append(buf)
     if dt:
         for (_, _, _, px) in heads:
@@ -229,14 +263,7 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
         whole = torch.empty((len(paths),) + shape(*first), dtype=dtype, device=dev)
     out, groups = [None] * len(paths), {}
     for i, (p, buf, (mode, w, h, px)) in enumerate(zip(paths, bufs, heads)):
-        alpha = px - 3
-        t = None
-        if mode == 7:
-            if len(buf) < 8 + w * h * px:
-                raise XpngError(f"load_files: {os.fspath(p)!r} is shorter than its raster")
-            t = torch.frombuffer(bytearray(buf[8:8 + w * h * px]), dtype=torch.uint8).view(h, w, px)
-        elif len(buf) == 11 + alpha and buf[7] & 2:              # whole-image single colour: the file holds one pixel
-            t = torch.frombuffer(bytearray(buf[8:8 + px]), dtype=torch.uint8).view(1, 1, px).expand(h, w, px)
+        t = _host_raster("load_files", p, buf, (mode, w, h, px))
         if t is None:
             groups.setdefault((mode, px), []).append((i, w, h, buf))
             continue
@@ -265,14 +292,7 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
         starts = api.batch_cuts([(w, h) for (_, w, h, _) in members], [px] * len(members), BATCH_MAX, BATCH_BYTES) + [len(members)]
         for a, b in zip(starts, starts[1:]):
             part = members[a:b]
-            # the tile bodies of the call in one upload: each 16-byte aligned, 64 readable bytes behind the last
-            offs, total = [], 0
-            for (_, _, _, buf) in part:
-                offs.append(total)
-                total += -(-(len(buf) - 8) // 16) * 16
-            host = bytearray(total + 64)
-            for o, (_, _, _, buf) in zip(offs, part):
-                host[o:o + len(buf) - 8] = buf[8:]
+            host, offs = _pack_bodies(part)                       # the tile bodies of the call in one upload
             with torch.cuda.device(index):
                 d_in = torch.frombuffer(host, dtype=torch.uint8).to(dev)
                 if whole is not None:                             # (the kernels take any pointers: the slices are the buffers)
@@ -302,6 +322,156 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
             for (i, _, _, _), t in zip(part, outs):
                 out[i] = t
     return whole if whole is not None else out
+
+
+def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool = False, device=None, dtype=torch.float16, mean=None,
+               std=None, antialias: bool = True, stack: bool = False, out=None):
+    """Any number of views per file, each decoded once: views is a list of (path_index, rect_or_None, flip) - rect = (x, y, w, h)
+    inside file path_index, None for the whole image; flip True mirrors left to right - and view v comes back as a tensor
+    (C, OH_v, OW_v) for layout "chw" or (OH_v, OW_v, C) for "hwc", in view order.  size is one (OH, OW) for every view or one pair
+    per view.  layout, channels, bgr, device, mean and std are load_files'; dtype must be a float dtype (the resize interpolates).
+    antialias=True (the default, torchvision's) resamples a shrinking axis with the triangle filter of load_files(antialias=True);
+    False gives plain bilinear taps.  View v equals, bit for bit, api.resample_host of api.load(paths[path_index]).
+
+    The files that reach the tile codec are grouped and cut into device calls as load_files does, and every call is ONE
+    MixedContext.decode_batch_views: each file is entropy-decoded once however many views read it, and only the tiles that some
+    view of the file touches are decoded at all.  A path that no view names is not read.  Level-7 and single-colour files go
+    through api.resample_host per view, so a list of only those also works with device="cpu".
+
+    stack=True returns ONE tensor (V, C, OH, OW) or (V, OH, OW, C): it needs one size and one C.  out is a list of preallocated
+    tensors, one per view, written in place and returned: each must have the view's shape, `dtype`, the device and be contiguous
+    (slices along the first dimension of a stacked tensor are) - this is how a multi-crop caller fills its two stacked tensors of
+    different sizes from one call.  Any failure raises XpngError."""
+    if layout not in ("chw", "hwc"):
+        raise XpngError(f"load_views: layout must be 'chw' or 'hwc', not {layout!r}")
+    if channels not in (None, 3, 4):
+        raise XpngError(f"load_views: channels must be None, 3 or 4, not {channels!r}")
+    if dtype not in _DTYPES:
+        raise XpngError(f"load_views: dtype must be torch.float16, bfloat16 or float32, not {dtype!r}: the resize interpolates")
+    if stack and out is not None:
+        raise XpngError("load_views: stack=True allocates the result, out= is the caller's: give one of them")
+    dt = _DTYPES[dtype]
+    mean, std = (x.tolist() if isinstance(x, torch.Tensor) else x for x in (mean, std))
+    paths = list(paths)
+    try:
+        views = [(int(i), None if r is None else tuple(int(v) for v in r), bool(f)) for (i, r, f) in views]
+    except (TypeError, ValueError):
+        raise XpngError("load_views: a view is (path_index, (x, y, w, h) or None, flip)") from None
+    V = len(views)
+    if not V:
+        raise XpngError("load_views: empty list of views")
+    for v, (i, r, _) in enumerate(views):
+        if not 0 <= i < len(paths):
+            raise XpngError(f"load_views: view {v} names path {i}, the list has {len(paths)}")
+        if r is not None and len(r) != 4:
+            raise XpngError(f"load_views: the rectangle of view {v} is {r!r}, not (x, y, w, h)")
+    try:
+        sizes = list(size)
+        if len(sizes) == 2 and not hasattr(sizes[0], "__len__"):
+            sizes = [sizes] * V
+        sizes = [tuple(int(x) for x in s) for s in sizes]
+        if any(len(s) != 2 for s in sizes):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise XpngError(f"load_views: size must be (OH, OW) or one (OH, OW) per view, not {size!r}") from None
+    if len(sizes) != V:
+        raise XpngError(f"load_views: {len(sizes)} sizes for {V} views: one (OH, OW), or one per view")
+    for v, (oh, ow) in enumerate(sizes):
+        if not (1 <= oh <= 16384 and 1 <= ow <= 16384):
+            raise XpngError(f"load_views: size {(oh, ow)} of view {v} is outside 1 .. 16384")
+    dev = torch.device("cuda" if device is None else device)
+    if dev.type == "cuda" and not torch.cuda.is_available():
+        raise XpngError("load_views: no GPU is visible (device='cpu' answers level-7 and single-colour files without one)")
+    filt = api.FILTER_TRIANGLE_AA if antialias else api.FILTER_BILINEAR
+    # only the files that a view names are read
+    heads, bufs = {}, {}
+    for i in sorted({i for (i, _, _) in views}):
+        bufs[i], heads[i] = _read_xpng("load_views", paths[i])
+    for v, (i, r, _) in enumerate(views):
+        _, w, h, _ = heads[i]
+        if r is not None and not (r[2] > 0 and r[3] > 0 and 0 <= r[0] <= w - r[2] and 0 <= r[1] <= h - r[3]):
+            raise XpngError(f"load_views: the rectangle {r} of view {v} is empty or leaves the {w} x {h} image {os.fspath(paths[i])!r}")
+    chans = [channels or heads[i][3] for (i, _, _) in views]
+    cache = {}
+    for C in set(chans):
+        cache[C] = _scale_bias(mean, std, C)
+
+    def shape(v):
+        (oh, ow), C = sizes[v], chans[v]
+        return (C, oh, ow) if layout == "chw" else (oh, ow, C)
+
+    whole = None
+    if stack:
+        for v in range(V):
+            if shape(v) != shape(0):
+                raise XpngError(f"load_views: stack=True needs one size and one channel count, but view {v} is {shape(v)} and view 0 is {shape(0)}")
+        whole = torch.empty((V,) + shape(0), dtype=dtype, device=dev)
+        res = list(whole.unbind(0))
+    elif out is not None:
+        res = list(out)
+        if len(res) != V:
+            raise XpngError(f"load_views: out has {len(res)} tensors for {V} views")
+        for v, t in enumerate(res):
+            if not isinstance(t, torch.Tensor):
+                raise XpngError(f"load_views: out[{v}] is not a tensor")
+            if tuple(t.shape) != shape(v):
+                raise XpngError(f"load_views: out[{v}] has shape {tuple(t.shape)}, view {v} is {shape(v)}")
+            if t.dtype != dtype:
+                raise XpngError(f"load_views: out[{v}] has dtype {t.dtype}, not {dtype}")
+            if t.device.type != dev.type or (dev.index is not None and t.device.index != dev.index):
+                raise XpngError(f"load_views: out[{v}] is on {t.device}, not on {dev}")
+            if not t.is_contiguous():
+                raise XpngError(f"load_views: out[{v}] is not contiguous")
+    else:
+        res = [None] * V
+    groups = {}
+    for i, (mode, w, h, px) in heads.items():
+        t = _host_raster("load_views", paths[i], bufs[i], (mode, w, h, px))
+        if t is None:
+            groups.setdefault((mode, px), []).append((i, w, h, bufs[i]))
+            continue
+        ras = t.contiguous().numpy()
+        for v, (vi, r, f) in enumerate(views):
+            if vi != i:
+                continue
+            word = api.layout(planar=layout == "chw", bgr=bgr, channels=chans[v])
+            raw = api.resample_host(ras, sizes[v], word, dt, *cache[chans[v]], rect=r, flip=f, filter=filt)
+            tv = torch.frombuffer(bytearray(raw), dtype=dtype).view(shape(v))
+            if res[v] is None:
+                res[v] = tv.to(dev)
+            else:
+                res[v].copy_(tv)
+    if groups and dev.type != "cuda":
+        raise XpngError("load_views: these files need the tile codec, which runs on a GPU only (there is no CPU fallback)")
+    for (mode, px), members in sorted(groups.items()):
+        index = dev.index if dev.index is not None else torch.cuda.current_device()
+        C = channels or px
+        word = api.layout(planar=layout == "chw", bgr=bgr, channels=C)
+        starts = api.batch_cuts([(w, h) for (_, w, h, _) in members], [px] * len(members), BATCH_MAX, BATCH_BYTES) + [len(members)]
+        for a, b in zip(starts, starts[1:]):
+            part = members[a:b]
+            local = {i: k for k, (i, _, _, _) in enumerate(part)}
+            mine = [v for v, (i, _, _) in enumerate(views) if i in local]
+            host, offs = _pack_bodies(part)                       # the tile bodies of the call in one upload
+            with torch.cuda.device(index):
+                d_in = torch.frombuffer(host, dtype=torch.uint8).to(dev)
+                for v in mine:
+                    if res[v] is None:
+                        res[v] = torch.empty(shape(v), dtype=dtype, device=dev)
+                torch.cuda.current_stream().synchronize()          # the upload is there before the context's stream reads it
+                ctx = api.MixedContext([(w, h) for (_, w, h, _) in part], px, device=index)
+                try:
+                    ins, lens = [d_in.data_ptr() + o for o in offs], [len(buf) - 8 for (_, _, _, buf) in part]
+                    ctx.decode_batch_views(mode, ins, lens, [local[views[v][0]] for v in mine], [res[v].data_ptr() for v in mine], word, dt,
+                                           [sizes[v] for v in mine], *cache[C],
+                                           rects=[views[v][1] or (0, 0, heads[views[v][0]][1], heads[views[v][0]][2]) for v in mine],
+                                           flips=[views[v][2] for v in mine], filter=filt)
+                    status = ctx.decode_status()                  # (synchronises the context's stream: the tensors are complete)
+                finally:
+                    ctx.close()
+            if status != 0:
+                raise XpngError("load_views: a tile of a level-%d file was rejected or the device call failed (status %d)" % (mode, status))
+    return whole if whole is not None else res
 
 
 def _inverse_scale_bias(mean, std, present):
