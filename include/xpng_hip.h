@@ -471,6 +471,43 @@ int64_t xpnghip_view_tiles(const uint64_t *dims, uint32_t nimg, uint32_t nviews,
  * after a views or a region call, nimg * (t1 - t0) after a range decode, 0 before any decode. */
 uint64_t xpnghip_ctx_last_decode_tiles(const xpnghip_ctx *ctx);
 
+/* ---- a colour matrix per view in the copy-out of a views call -------------------------------
+ * Two-view and multi-crop pipelines give every view a colour jitter of its own, and some views a grayscale.  Brightness, contrast
+ * about a fixed centre, saturation, a hue rotation, grayscale, a channel permutation and every product of them are linear per
+ * pixel: one 3 x 4 matrix.  The copy-out pass holds every output value in a register just before the store, so the matrix is
+ * applied there and no further pass over the views is needed.
+ * THE RULE.  `colour` is 12 floats, row-major 3 x 4.  Row k is the OUTPUT colour k in the order R, G, B - whatever the layout's BGR
+ * bit says - and the columns are the inputs R, G, B and a constant, all in byte units (0 .. 255).  With vR, vG, vB the fp32 values
+ * the resample rule above produces for the three colour bytes of an output pixel (its v, before the constants):
+ *     t_k = fmaf(m[k][0], vR, fmaf(m[k][1], vG, fmaf(m[k][2], vB, m[k][3])))      three explicit fp32 fmas, this nesting
+ *     t_k = t_k < 0.0f ? 0.0f : t_k > 255.0f ? 255.0f : t_k                       the clamp a uint8 pipeline would apply
+ *     y   = fmaf(t_k, scale[c], bias[c])    out = (T)y                            as above; c = position in the CALLER's buffer
+ * With XPNGHIP_LAYOUT_BGR position c < 3 holds colour k = 2 - c.  Alpha does not pass through the matrix: position 3, whether it
+ * is stored or the 255 an RGB context lacks, takes fmaf(v, scale[3], bias[3]) as above, and C == 3 on an RGBA context drops alpha
+ * as above.  Every entry must be finite with |m| <= 65536, so that no intermediate overflows and no NaN can arise; anything else
+ * is refused before anything is written, and the message names the entry (and, in the device call, the view).
+ * Consequences: (d) with filter 0 an identity matrix gives bit for bit what colour == NULL gives, because every v lies within
+ * 0 .. 255 and fmaf(1, v, 0 + 0) is v; with filter 1 the quotient A / W may round a hair past 255 and the clamp may then differ,
+ * which is why NULL, not the identity, is the "off" value; (e) a flip is still a mirror on the bits; (f) no tap leaves the
+ * rectangle: nothing about the source side changes.
+ * host-only, needs no device: xpnghip_resample_host with one more argument.  colour == NULL is xpnghip_resample_host itself. */
+int xpnghip_resample_colour_host(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip,
+                                 uint32_t out_w, uint32_t out_h, uint32_t layout, uint32_t dtype, const float *scale,
+                                 const float *bias, uint32_t filter, const float *colour, void *out);
+/* The views call with `colours`: nviews * 12 floats on the host, the matrix of view v at colours + 12 * v.  View v receives, bit
+ * for bit, what xpnghip_resample_colour_host writes with its matrix.  colours == NULL is the views call: the same kernel, the same
+ * bytes, and nothing more allocated or uploaded.  The checks, their order and their texts are the views call's, followed by the
+ * matrices' (the text names the view and the entry).  The matrices travel in a table of their own, 48 bytes per view, which belongs
+ * to the context's workspace, grows only when a call has more views than any colour call before it, and is uploaded with the
+ * views call's two tables in front of the call's kernels, under the same single synchronisation of `stream`.  The 64-byte view
+ * record, the selection and the decode stages are the views call's. */
+int xpnghip_decode_varsize_device_batch_views_colour(xpnghip_ctx *ctx, int mode, const void *const *d_blobs, const uint64_t *blobs_len,
+                                                     uint32_t nimg, const uint64_t *tile_off, uint32_t nviews,
+                                                     const uint32_t *view_image, void *const *d_outs, const uint32_t *out_sizes,
+                                                     const uint64_t *rects, const uint8_t *flips, uint32_t layout, uint32_t dtype,
+                                                     const float *scale, const float *bias, uint32_t filter, const float *colours,
+                                                     void *stream);
+
 /* ---- staged batch from device tensors: the inverse of the float call --------------------------
  * A model writes floats, not the file's bytes.  The call below is xpnghip_images_begin with the upload replaced by one staging
  * kernel that reads the caller's DEVICE buffers - planar or interleaved, RGB or BGR, uint8, f16, bf16 or f32 - and writes the

@@ -38,6 +38,7 @@ HIP_SYMBOLS = [
     "xpnghip_decode_varsize_device_batch_resampled", "xpnghip_resample_host",
     "xpnghip_images_begin_device", "xpnghip_quantize_host",
     "xpnghip_decode_varsize_device_batch_views", "xpnghip_view_tiles", "xpnghip_ctx_last_decode_tiles",
+    "xpnghip_resample_colour_host", "xpnghip_decode_varsize_device_batch_views_colour",
 ]
 HOST_SYMBOLS = ["xpng_store", "xpng_load", "xpng_from_jpg", "xpng_store_T", "xpng_load_T", "xpng_from_jpg_T",
                 "store_7", "load_7"]
@@ -197,6 +198,13 @@ def _bind_hip(path):
         L.xpnghip_decode_varsize_device_batch_views.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64), C.c_uint32, C.POINTER(u64), C.c_uint32, u32p,
                                                                 C.POINTER(vp), u32p, C.POINTER(u64), u8p, C.c_uint32, C.c_uint32, f32p, f32p,
                                                                 C.c_uint32, vp]
+        L.xpnghip_resample_colour_host.restype = C.c_int
+        L.xpnghip_resample_colour_host.argtypes = [C.c_int, vp, u64, u64, C.POINTER(u64), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                   f32p, f32p, C.c_uint32, f32p, vp]
+        L.xpnghip_decode_varsize_device_batch_views_colour.restype = C.c_int
+        L.xpnghip_decode_varsize_device_batch_views_colour.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64), C.c_uint32, C.POINTER(u64), C.c_uint32,
+                                                                       u32p, C.POINTER(vp), u32p, C.POINTER(u64), u8p, C.c_uint32, C.c_uint32, f32p,
+                                                                       f32p, C.c_uint32, f32p, vp]
         L.xpnghip_view_tiles.restype = C.c_int64
         L.xpnghip_view_tiles.argtypes = [C.POINTER(u64), C.c_uint32, C.c_uint32, u32p, C.POINTER(u64), u32p, u64]
         L.xpnghip_ctx_last_decode_tiles.restype = u64
@@ -620,6 +628,49 @@ def resample_host(raster, size, layout: int, dtype: int, scale=None, bias=None, 
     return buf.tobytes()[:ch * oh * ow * dtype_bytes(dtype)]
 
 
+COLOUR_IDENTITY = (1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0)  # the matrix a None entry of a `colours` list stands for
+
+
+def _colour12(name, m):
+    """one colour matrix - 12 numbers or a (3, 4) array, row k the output colour k of R, G, B, columns R, G, B, 1 - as 12 floats"""
+    try:
+        a = np.asarray(m, dtype=np.float64)
+    except (TypeError, ValueError):
+        a = None
+    if a is None or a.shape not in ((12,), (3, 4)):
+        raise XpngError(f"{name}: a colour matrix is 12 numbers or a (3, 4) array, not {m!r}")
+    return [float(v) for v in a.reshape(12)]
+
+
+def resample_colour_host(raster, size, layout: int, dtype: int, scale=None, bias=None, rect=None, flip=False, filter: int = FILTER_TRIANGLE_AA,
+                         colour=None) -> bytes:
+    """The rule of MixedContext.decode_batch_views with a colour matrix on the host (xpnghip_resample_colour_host; needs no
+    device): resample_host's arguments and `colour`, 12 numbers or a (3, 4) array - row k the output colour k in the order R, G, B
+    whatever the layout's BGR bit says, columns the inputs R, G, B and a constant, in byte units.  Every output pixel's three
+    resampled colours go through the matrix (three nested fp32 fmaf) and a clamp to 0 .. 255 before the constants; alpha does not.
+    colour None is resample_host itself.  Returns the C * OH * OW elements of `dtype` in `layout` as raw bytes, bit for bit what
+    the device call writes for these pixels."""
+    if colour is None:
+        return resample_host(raster, size, layout, dtype, scale, bias, rect, flip, filter)
+    r = np.ascontiguousarray(raster, dtype=np.uint8)
+    if r.ndim != 3 or r.shape[2] not in (3, 4):
+        raise XpngError("resample_colour_host: the raster must be (h, w, 3) or (h, w, 4) uint8")
+    try:
+        oh, ow = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise XpngError(f"resample_colour_host: size must be (OH, OW), not {size!r}") from None
+    px = r.shape[2]
+    sc, bi, ch = _scale_bias(layout, px, scale, bias)
+    ra = _rect_array("resample_colour_host", None if rect is None else [rect], 1)
+    cm = (C.c_float * 12)(*_colour12("resample_colour_host", colour))
+    ok = ch > 0 and 1 <= oh <= 16384 and 1 <= ow <= 16384          # (anything else the library refuses, naming the value)
+    buf = np.empty(ch * oh * ow if ok else 1, dtype=np.uint32)     # 4-byte aligned, room for the widest element
+    if hip_lib().xpnghip_resample_colour_host(px, r.ctypes.data, r.shape[1], r.shape[0], ra, int(flip), ow & 0xFFFFFFFF, oh & 0xFFFFFFFF, layout, dtype,
+                                              sc, bi, int(filter) & 0xFFFFFFFF, cm, buf.ctypes.data):
+        raise XpngError("xpnghip_resample_colour_host: " + _err())
+    return buf.tobytes()[:ch * oh * ow * dtype_bytes(dtype)]
+
+
 def _view_images(name, view_image, nviews):
     """the image of every view as a C array of uint32 (None stays None: the identity)"""
     if view_image is None:
@@ -1030,12 +1081,24 @@ class MixedContext(_Handle):
                      int(filter) & 0xFFFFFFFF)
 
     def decode_batch_views(self, mode, d_blobs, lens, view_image, d_outs, layout, dtype, sizes, scale=None, bias=None, rects=None, flips=None,
-                           filter: int = FILTER_TRIANGLE_AA, tile_offs=None, stream=0):
+                           filter: int = FILTER_TRIANGLE_AA, tile_offs=None, stream=0, colours=None):
         """decode_batch_resampled with any number of outputs per image, and only the tiles they touch decoded: view v reads image
         view_image[v] (None: view v reads image v), its rectangle rects[v] = (x, y, w, h) (None: whole images), mirrored where
         flips[v] is true, resampled to its own size: `sizes` is one (OH, OW) for every view or one pair per view.  d_outs[v] is
-        C * OH_v * OW_v elements of `dtype`: xpnghip_decode_varsize_device_batch_views (the rule is in include/xpng_hip.h)."""
+        C * OH_v * OW_v elements of `dtype`: xpnghip_decode_varsize_device_batch_views (the rule is in include/xpng_hip.h).
+        colours is None or one entry per view, each None (the identity matrix) or a colour matrix of 12 numbers or a (3, 4) array as
+        resample_colour_host takes it: the copy-out then puts every pixel of view v through matrix v and a clamp to 0 .. 255
+        before the constants (xpnghip_decode_varsize_device_batch_views_colour).  colours None, or every entry None, is the
+        plain call."""
         n = len(d_outs)
+        cm = None
+        if colours is not None:
+            colours = list(colours)
+            if len(colours) != n:
+                raise XpngError(f"decode_batch_views: colours has {len(colours)} entries for {n} views")
+            if any(m is not None for m in colours):
+                flat = [x for v, m in enumerate(colours) for x in (COLOUR_IDENTITY if m is None else _colour12(f"decode_batch_views: colours[{v}]", m))]
+                cm = (C.c_float * (12 * n))(*flat)
         vi = _view_images("decode_batch_views", None if view_image is None else list(view_image), n)
         if view_image is not None and len(list(view_image)) != n:
             raise XpngError(f"decode_batch_views: view_image has {len(list(view_image))} entries for {n} output buffers")
@@ -1053,6 +1116,10 @@ class MixedContext(_Handle):
         sc, bi, _ = _scale_bias(layout, self.pxsz, scale, bias)
         ra = _rect_array("decode_batch_views", rects, n)
         fl = _flip_array("decode_batch_views", flips, n, "views")
+        if cm is not None:
+            self._decode("xpnghip_decode_varsize_device_batch_views_colour", mode, d_blobs, lens, d_outs, tile_offs, stream, so, ra, fl, layout, dtype,
+                         sc, bi, int(filter) & 0xFFFFFFFF, cm, before=(n, vi))
+            return
         self._decode("xpnghip_decode_varsize_device_batch_views", mode, d_blobs, lens, d_outs, tile_offs, stream, so, ra, fl, layout, dtype, sc, bi,
                      int(filter) & 0xFFFFFFFF, before=(n, vi))
 

@@ -34,6 +34,7 @@
 #include "mixed_resize.hpp"
 #include "mixed_resample.hpp"
 #include "mixed_views.hpp"
+#include "mixed_views_colour.hpp"
 #include "stage_from.hpp"
 
 using namespace xpng;
@@ -215,6 +216,10 @@ struct xpnghip_ctx {
     ViewRec *d_m_views = nullptr;
     uint64_t cap_m_views = 0;          // records d_m_views has room for
     uint32_t *d_m_vlist = nullptr;
+    // ... and, for a views call with colour matrices only (mixed_views_colour.hpp), one 48-byte matrix per view: grown, dropped
+    // and uploaded as d_m_views is; a plain views call never allocates it
+    ViewColour *d_m_vcolour = nullptr;
+    uint64_t cap_m_vcolour = 0;        // matrices d_m_vcolour has room for
     uint64_t last_tiles = 0;           // tile work items of the most recent decode launch (xpnghip_ctx_last_decode_tiles)
 };
 
@@ -1177,6 +1182,81 @@ extern "C" int xpnghip_resample_host(int pxsz, const uint8_t *raster, uint64_t w
                                      uint32_t layout, uint32_t dtype, const float *scale, const float *bias, uint32_t filter, void *out) {
     XPNG_GUARDED(resample_host_impl(pxsz, raster, w, h, rect, flip, out_w, out_h, layout, dtype, scale, bias, filter, out))
 }
+// ---- a colour matrix behind the resampling (mixed_views_colour.hpp) ---------------------------------------------
+// every entry finite and |m| <= 65536: no intermediate of the rule overflows and no NaN arises.  `who` names the view in a device call
+static bool colour_matrix_ok(const float *m, const std::string &who, std::string &why) {
+    for (int e = 0; e < 12; e++) {
+        if (std::isfinite(m[e]) && fabsf(m[e]) <= 65536.0f) continue;
+        char b[48];
+        snprintf(b, sizeof b, "%g", (double)m[e]);
+        why = "bad colour matrix" + who + ": entry [" + std::to_string(e / 4) + "][" + std::to_string(e % 4) + "] is " + b + " (every entry must be finite and at most 65536 in magnitude)";
+        return false;
+    }
+    return true;
+}
+// The twin of k_mixed_views_colour on the host: the resampled twin's operations for the bytes of a pixel, then the matrix, the clamp
+// and the constants, every multiplication inside an explicit fmaf(), contraction off on top of that.
+static int resample_colour_host_impl(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip, uint32_t out_w, uint32_t out_h,
+                                     uint32_t layout, uint32_t dtype, const float *scale, const float *bias, uint32_t filter, const float *colour, void *out) {
+#pragma clang fp contract(off)
+    if (!colour) return resample_host_impl(pxsz, raster, w, h, rect, flip, out_w, out_h, layout, dtype, scale, bias, filter, out);
+    std::string why;
+    if (!resample_filter_ok(filter, why)) return fail(why);
+    int C;
+    FloatConsts k;
+    ResizeRec z0;
+    if (resize_host_args("xpnghip_resample_colour_host", pxsz, raster, w, h, rect, flip, out_w, out_h, layout, dtype, scale, bias, out, C, k, z0)) return 1;
+    if (!colour_matrix_ok(colour, "", why)) return fail(why);
+    const ResampleRec z = resample_record(z0);
+    const bool planar = layout & XPNGHIP_LAYOUT_PLANAR, bgr = layout & XPNGHIP_LAYOUT_BGR;
+    // filter 0: the two taps on both axes whatever the ratio
+    auto axis = [&](uint32_t u, float kk, uint32_t n) {
+        if (filter) return resample_axis_host(u, kk, n);
+        ResampleAxis a{};
+        a.t = resize_tap_host(u, kk, n);
+        return a;
+    };
+    std::vector<ResampleAxis> ax(out_w), ay(out_h);
+    for (uint32_t ox = 0; ox < out_w; ox++) ax[ox] = axis(z.flip ? out_w - 1 - ox : ox, z.kx, z.rw);
+    for (uint32_t oy = 0; oy < out_h; oy++) ay[oy] = axis(oy, z.ky, z.rh);
+    // the values first, the elements after them: a call that fails writes nothing
+    std::vector<float> ys((uint64_t)C * out_h * out_w);
+    bool bad = false;
+    for (uint32_t oy = 0; oy < out_h; oy++)
+        for (uint32_t ox = 0; ox < out_w; ox++) {
+            float v[4] = {0.0f, 0.0f, 0.0f, 255.0f};  // R, G, B of the file and its alpha (255: the alpha an RGB raster does not store)
+            for (int sc = 0; sc < (pxsz == 4 && C == 4 ? 4 : 3); sc++) {
+                auto H = [&](uint32_t s) {
+                    const uint8_t *p = raster + ((uint64_t)(z.ry + s) * w + z.rx) * pxsz + sc;
+                    return resample_axis_apply(ax[ox], z.ikx, [&](uint32_t j) { return (float)p[(uint64_t)j * pxsz]; }, &bad);
+                };
+                v[sc] = resample_axis_apply(ay[oy], z.iky, H, &bad);
+            }
+            float t[3];
+            for (int q = 0; q < 3; q++) {
+                const float *m = colour + 4 * q;
+                const float a = fmaf(m[2], v[2], m[3]);
+                const float b = fmaf(m[1], v[1], a);
+                const float x = fmaf(m[0], v[0], b);
+                t[q] = x < 0.0f ? 0.0f : x > 255.0f ? 255.0f : x;
+            }
+            for (int c = 0; c < C; c++) {
+                const float u = c == 3 ? v[3] : t[bgr ? 2 - c : c];
+                ys[planar ? ((uint64_t)c * out_h + oy) * out_w + ox : ((uint64_t)oy * out_w + ox) * C + c] = fmaf(u, k.scale[c], k.bias[c]);
+            }
+        }
+    if (bad) return fail("internal error: a window of the triangle filter has no weight");  // (W > 0 always: DESIGN.md 19)
+    for (uint64_t e = 0; e < ys.size(); e++) {
+        if (dtype == XPNGHIP_DTYPE_F32) reinterpret_cast<float *>(out)[e] = ys[e];
+        else reinterpret_cast<uint16_t *>(out)[e] = dtype == XPNGHIP_DTYPE_F16 ? f16_bits_rne(ys[e]) : bf16_bits_rne(ys[e]);
+    }
+    return 0;
+}
+extern "C" int xpnghip_resample_colour_host(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip, uint32_t out_w,
+                                            uint32_t out_h, uint32_t layout, uint32_t dtype, const float *scale, const float *bias, uint32_t filter,
+                                            const float *colour, void *out) {
+    XPNG_GUARDED(resample_colour_host_impl(pxsz, raster, w, h, rect, flip, out_w, out_h, layout, dtype, scale, bias, filter, colour, out))
+}
 // ---- staging from tensors (stage_from.hpp) ---------------------------------------------------------------------
 // the layout word of a call whose channel count is per image: the PLANAR and BGR bits and nothing else
 static bool stage_layout_ok(uint32_t layout, std::string &why) {
@@ -1499,7 +1579,8 @@ extern "C" uint64_t xpnghip_ctx_last_decode_tiles(const xpnghip_ctx *c) { return
 
 static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg, const uint64_t *tile_off,
                              uint32_t nviews, const uint32_t *view_image, void *const *d_outs, const uint32_t *out_sizes, const uint64_t *rects,
-                             const uint8_t *flips, uint32_t layout, uint32_t dtype, const float *scale, const float *bias, uint32_t filter, void *stream) {
+                             const uint8_t *flips, uint32_t layout, uint32_t dtype, const float *scale, const float *bias, uint32_t filter,
+                             const float *colours, void *stream) {
     // every argument is checked before anything reaches the device: a rejected call writes nothing
     int C, es;
     FloatConsts fk{};
@@ -1534,6 +1615,8 @@ static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
         if (!d_blobs[i]) return fail("null blob of image " + std::to_string(i));
         if ((uintptr_t)d_blobs[i] & 3) return fail("device buffers must be 16-byte aligned");
     }
+    for (uint32_t v = 0; colours && v < nviews; v++)
+        if (!colour_matrix_ok(colours + 12ull * v, " of view " + std::to_string(v), why)) return fail(why);
     std::vector<uint32_t> list;
     view_select(c->tiles, c->m_first, c->m_list, c->m_dims.data(), nviews, view_image, rects, list);
     HIPCHK(hipSetDevice(c->device));
@@ -1548,10 +1631,19 @@ static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
         c->cap_m_views = nviews;
     }
     WS_GET(c->d_m_vlist, (uint64_t)c->tiles.size() * 4);
+    if (colours && c->cap_m_vcolour < nviews) {
+        if (c->d_m_vcolour) {
+            for (hipStream_t q : {s, c->stream, c->side}) if (q) HIPCHK(hipStreamSynchronize(q));
+            c->ws.drop((void **)&c->d_m_vcolour); c->cap_m_vcolour = 0;
+        }
+        WS_GET(c->d_m_vcolour, (uint64_t)nviews * sizeof(ViewColour));
+        c->cap_m_vcolour = nviews;
+    }
     // the resized call's protocol: both tables are in pageable host memory that ends with this call, so the stream is synchronised
     // once behind the two copies - queued before the decode's own kernels, so the wait never covers this call's work
     HIPCHK(hipMemcpyAsync(c->d_m_views, recs.data(), (uint64_t)nviews * sizeof(ViewRec), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(c->d_m_vlist, list.data(), (uint64_t)list.size() * 4, hipMemcpyHostToDevice, s));
+    if (colours) HIPCHK(hipMemcpyAsync(c->d_m_vcolour, colours, (uint64_t)nviews * sizeof(ViewColour), hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
     std::vector<void *> base(nimg);
     for (uint32_t i = 0; i < nimg; i++) base[i] = c->d_m_stage + slot[i];
@@ -1561,8 +1653,12 @@ static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
     if (rc) return rc;
     const uint32_t bgr = layout & XPNGHIP_LAYOUT_BGR;
     const dim3 grid((max_oh + MC_ROWS - 1) / MC_ROWS, nviews);
+    if (colours) XPNG_REQUIRE(c->d_m_vcolour);
     with_3or4(c->pxsz, [&](auto PXc) { with_3or4(C, [&](auto Cc) { with_planar(layout, [&](auto PL) { with_float(dtype, [&](auto t) {
-        k_mixed_views_as_float<decltype(PXc)::value, decltype(Cc)::value, decltype(PL)::value, decltype(t)><<<grid, 256, 0, s>>>(c->d_m_views, c->d_m_stage, bpr, bgr, filter, fk);
+        constexpr int PXv = decltype(PXc)::value, Cv = decltype(Cc)::value;
+        constexpr bool PLv = decltype(PL)::value;
+        if (colours) k_mixed_views_colour<PXv, Cv, PLv, decltype(t)><<<grid, 256, 0, s>>>(c->d_m_views, c->d_m_vcolour, c->d_m_stage, bpr, bgr, filter, fk);
+        else k_mixed_views_as_float<PXv, Cv, PLv, decltype(t)><<<grid, 256, 0, s>>>(c->d_m_views, c->d_m_stage, bpr, bgr, filter, fk);
     }); }); }); });
     HIPCHK(hipGetLastError());
     return 0;
@@ -1571,7 +1667,14 @@ extern "C" int xpnghip_decode_varsize_device_batch_views(xpnghip_ctx *c, int mod
                                                          const uint64_t *tile_off, uint32_t nviews, const uint32_t *view_image, void *const *d_outs,
                                                          const uint32_t *out_sizes, const uint64_t *rects, const uint8_t *flips, uint32_t layout,
                                                          uint32_t dtype, const float *scale, const float *bias, uint32_t filter, void *stream) {
-    XPNG_GUARDED(decode_views_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, nviews, view_image, d_outs, out_sizes, rects, flips, layout, dtype, scale, bias, filter, stream))
+    XPNG_GUARDED(decode_views_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, nviews, view_image, d_outs, out_sizes, rects, flips, layout, dtype, scale, bias, filter, nullptr, stream))
+}
+extern "C" int xpnghip_decode_varsize_device_batch_views_colour(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
+                                                                const uint64_t *tile_off, uint32_t nviews, const uint32_t *view_image, void *const *d_outs,
+                                                                const uint32_t *out_sizes, const uint64_t *rects, const uint8_t *flips, uint32_t layout,
+                                                                uint32_t dtype, const float *scale, const float *bias, uint32_t filter, const float *colours,
+                                                                void *stream) {
+    XPNG_GUARDED(decode_views_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, nviews, view_image, d_outs, out_sizes, rects, flips, layout, dtype, scale, bias, filter, colours, stream))
 }
 
 // ---- mixed-size batch encode (mixed.hpp) ---------------------------------------------------------

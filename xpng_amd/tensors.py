@@ -8,13 +8,15 @@ MixedContext.decode_batch_as_float when a float dtype is asked for: the same pas
 MixedContext.decode_batch_resized when an output size is asked for: the same pass also crops, resizes and flips;
 MixedContext.decode_batch_resampled when that resize is to antialias).
 `load_views` gives any number of crops per file from ONE decode of it, and decodes only the tiles they touch
-(MixedContext.decode_batch_views).
+(MixedContext.decode_batch_views); with colour= every view also gets a colour matrix of its own in the same pass (colour_matrix,
+random_colour_jitter).
 api.py stays free of torch; this module is the only one of the package that imports it at load time."""
 from __future__ import annotations
 
 import math
 import os
 
+import numpy as np
 import torch
 
 from . import api
@@ -325,7 +327,7 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
 
 
 def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool = False, device=None, dtype=torch.float16, mean=None,
-               std=None, antialias: bool = True, stack: bool = False, out=None):
+               std=None, antialias: bool = True, stack: bool = False, out=None, colour=None):
     """Any number of views per file, each decoded once: views is a list of (path_index, rect_or_None, flip) - rect = (x, y, w, h)
     inside file path_index, None for the whole image; flip True mirrors left to right - and view v comes back as a tensor
     (C, OH_v, OW_v) for layout "chw" or (OH_v, OW_v, C) for "hwc", in view order.  size is one (OH, OW) for every view or one pair
@@ -341,7 +343,16 @@ def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool
     stack=True returns ONE tensor (V, C, OH, OW) or (V, OH, OW, C): it needs one size and one C.  out is a list of preallocated
     tensors, one per view, written in place and returned: each must have the view's shape, `dtype`, the device and be contiguous
     (slices along the first dimension of a stacked tensor are) - this is how a multi-crop caller fills its two stacked tensors of
-    different sizes from one call.  Any failure raises XpngError."""
+    different sizes from one call.  Any failure raises XpngError.
+
+    colour is None or one entry per view, each None (the identity matrix) or a colour matrix - 12 numbers or a (3, 4) array as
+    colour_matrix, compose_colour and random_colour_jitter return them: row k the output colour k of R, G, B whatever bgr says,
+    columns the inputs R, G, B and a constant in byte units.  The copy-out pass of the decode puts every pixel of the view through
+    its matrix and a clamp to 0 .. 255 before the normalisation, so a colour jitter and a grayscale per view cost no further pass
+    (the rule is in include/xpng_hip.h; alpha does not pass through the matrix).  View v then equals, bit for bit,
+    api.resample_colour_host with its matrix, which is also what answers level-7 and single-colour files.  Without colour, or
+    with every entry None, the function runs exactly the calls it runs without the argument; beside a matrix a None entry is the
+    identity matrix, whose clamp can differ from no matrix in the last bits where the antialiased quotient rounds past 255."""
     if layout not in ("chw", "hwc"):
         raise XpngError(f"load_views: layout must be 'chw' or 'hwc', not {layout!r}")
     if channels not in (None, 3, 4):
@@ -379,6 +390,14 @@ def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool
     for v, (oh, ow) in enumerate(sizes):
         if not (1 <= oh <= 16384 and 1 <= ow <= 16384):
             raise XpngError(f"load_views: size {(oh, ow)} of view {v} is outside 1 .. 16384")
+    cols = [None] * V
+    if colour is not None:
+        cols = list(colour)
+        if len(cols) != V:
+            raise XpngError(f"load_views: colour has {len(cols)} entries for {V} views: one matrix (or None) per view")
+        cols = [None if m is None else api._colour12(f"load_views: colour[{v}]", m) for v, m in enumerate(cols)]
+        if any(m is not None for m in cols):                           # beside a matrix, None is the identity MATRIX: every view is clamped
+            cols = [list(api.COLOUR_IDENTITY) if m is None else m for m in cols]
     dev = torch.device("cuda" if device is None else device)
     if dev.type == "cuda" and not torch.cuda.is_available():
         raise XpngError("load_views: no GPU is visible (device='cpu' answers level-7 and single-colour files without one)")
@@ -435,7 +454,7 @@ def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool
             if vi != i:
                 continue
             word = api.layout(planar=layout == "chw", bgr=bgr, channels=chans[v])
-            raw = api.resample_host(ras, sizes[v], word, dt, *cache[chans[v]], rect=r, flip=f, filter=filt)
+            raw = api.resample_colour_host(ras, sizes[v], word, dt, *cache[chans[v]], rect=r, flip=f, filter=filt, colour=cols[v])
             tv = torch.frombuffer(bytearray(raw), dtype=dtype).view(shape(v))
             if res[v] is None:
                 res[v] = tv.to(dev)
@@ -465,13 +484,93 @@ def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool
                     ctx.decode_batch_views(mode, ins, lens, [local[views[v][0]] for v in mine], [res[v].data_ptr() for v in mine], word, dt,
                                            [sizes[v] for v in mine], *cache[C],
                                            rects=[views[v][1] or (0, 0, heads[views[v][0]][1], heads[views[v][0]][2]) for v in mine],
-                                           flips=[views[v][2] for v in mine], filter=filt)
+                                           flips=[views[v][2] for v in mine], filter=filt,
+                                           colours=[cols[v] for v in mine] if cols[mine[0]] is not None else None)
                     status = ctx.decode_status()                  # (synchronises the context's stream: the tensors are complete)
                 finally:
                     ctx.close()
             if status != 0:
                 raise XpngError("load_views: a tile of a level-%d file was rejected or the device call failed (status %d)" % (mode, status))
     return whole if whole is not None else res
+
+
+_LUMA = (0.299, 0.587, 0.114)
+
+
+def _colour64(brightness, contrast, saturation, hue):
+    """colour_matrix in float64, before the one rounding"""
+    b, c, s, h = float(brightness), float(contrast), float(saturation), float(hue)
+    M = np.concatenate([np.eye(3), np.zeros((3, 1))], axis=1)
+    M = b * M
+    M = c * M
+    M[:, 3] += (1.0 - c) * 127.5
+    S = s * np.eye(3) + (1.0 - s) * np.ones((3, 1)) * np.array([_LUMA])
+    M = S @ M
+    co, si = (1.0, 0.0) if h == 0.0 else (math.cos(2.0 * math.pi * h), math.sin(2.0 * math.pi * h))
+    K = np.array([[0.0, -1.0, 1.0], [1.0, 0.0, -1.0], [-1.0, 1.0, 0.0]])
+    R = co * np.eye(3) + (1.0 - co) / 3.0 * np.ones((3, 3)) + si / math.sqrt(3.0) * K
+    return R @ M
+
+
+def _compose64(a, b):
+    a, b = (np.asarray(api._colour12("compose_colour", m), dtype=np.float64).reshape(3, 4) for m in (a, b))
+    out = b[:, :3] @ a
+    out[:, 3] += b[:, 3]
+    return out
+
+
+def colour_matrix(brightness=1.0, contrast=1.0, saturation=1.0, hue=0.0):
+    """The (3, 4) float32 colour matrix of a brightness, a contrast, a saturation and a hue step, as load_views(colour=...) and
+    MixedContext.decode_batch_views(colours=...) take it: row k the output colour k of R, G, B, columns the inputs R, G, B and a
+    constant, in byte units (0 .. 255).  Composed in float64 in this fixed order, each step left-multiplied onto the 3 x 4 with
+    its constant column, then rounded once to fp32:
+      brightness b   b * M
+      contrast c     about the fixed centre 127.5: c * M, constant += (1 - c) * 127.5
+      saturation s   S = s * I + (1 - s) * 1 * [0.299, 0.587, 0.114]: 0 is the luma in every colour, 1 the identity
+      hue h          a fraction of a turn: the rotation by 2 pi h about the gray axis,
+                     cos * I + (1 - cos) / 3 * J + sin / sqrt(3) * K with J all ones and K = [[0, -1, 1], [1, 0, -1], [-1, 1, 0]]
+    All ones and hue 0 give exactly the identity.  This is NOT torchvision's ColorJitter value for value: there the contrast
+    blends with the image's own mean gray level and not with a fixed centre, the hue shift goes through HSV and not through a
+    rotation in RGB, every step clamps to the value range before the next one, and the order of the four steps is drawn at random.
+    Here the steps are linear and fixed, so that a whole jitter is ONE matrix and one clamp at its end.  The call itself takes any
+    matrix: a caller who wants another order or another step composes it with compose_colour."""
+    return _colour64(brightness, contrast, saturation, hue).astype(np.float32)
+
+
+def compose_colour(a, b):
+    """The (3, 4) float32 matrix that applies colour matrix b AFTER colour matrix a (without a's clamp in between): b's 3 x 3 times
+    a, plus b's constant column; computed in float64, rounded once."""
+    return _compose64(a, b).astype(np.float32)
+
+
+def random_colour_jitter(n, brightness=0.4, contrast=0.4, saturation=0.4, hue=0.1, p=0.8, gray_p=0.2, generator=None):
+    """n colour matrices, one per view, drawn as SimCLR's and BYOL's colour augmentation draws its parameters: with probability p a
+    jitter colour_matrix(b, c, s, h) with b uniform in [max(0, 1 - brightness), 1 + brightness], c and s alike and h uniform in
+    [-hue, hue]; with probability gray_p a grayscale (saturation 0) on top of it; otherwise the identity.  A pure host function;
+    with a seeded torch.Generator the list is reproducible.  What load_views(..., colour=...) takes."""
+    n = int(n)
+    if n < 0:
+        raise XpngError(f"random_colour_jitter: n is {n}")
+    for name, x in (("brightness", brightness), ("contrast", contrast), ("saturation", saturation)):
+        if not 0.0 <= float(x) <= 16.0:
+            raise XpngError(f"random_colour_jitter: {name} must be within 0 .. 16, not {x!r}")
+    if not 0.0 <= float(hue) <= 0.5:
+        raise XpngError(f"random_colour_jitter: hue must be within 0 .. 0.5, not {hue!r}")
+    u = torch.rand((n, 6), dtype=torch.float64, generator=generator).tolist()   # one draw whatever the outcomes: entry k depends on row k alone
+
+    def span(x, r):
+        lo, hi = max(0.0, 1.0 - float(r)), 1.0 + float(r)
+        return lo + (hi - lo) * x
+
+    out = []
+    for (jit, ub, uc, us, uh, gray) in u:
+        M = _colour64(1.0, 1.0, 1.0, 0.0)
+        if jit < p:
+            M = _colour64(span(ub, brightness), span(uc, contrast), span(us, saturation), (2.0 * uh - 1.0) * float(hue))
+        if gray < gray_p:
+            M = _compose64(M, _colour64(1.0, 1.0, 0.0, 0.0))
+        out.append(M.astype(np.float32))
+    return out
 
 
 def _inverse_scale_bias(mean, std, present):
