@@ -24,8 +24,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import pyoracle as po  # noqa: E402
-from tools.to7 import png_to_raster, raster_to_seven  # noqa: E402
-from xpng_amd.synth import special_cases, synth_raster  # noqa: E402
+from oracle.validate_vs_ref import png_to_raster  # noqa: E402
+from xpng_amd.synth import special_cases, synth_raster, to_seven_bytes as raster_to_seven  # noqa: E402
 
 GOLD = os.path.join(ROOT, "tests", "golden")
 KEEP_XPNG_BELOW = 120_000

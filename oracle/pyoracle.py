@@ -57,6 +57,12 @@ def lib():
         L.xo_rans2_encode_table.restype = u64
         L.xo_rans2_encode_table.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, u64, C.c_void_p, C.c_int, C.c_int]
         L.xo_rans2_decode.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(u64)]
+        L.xo_rans1_encode.restype = u64
+        L.xo_rans1_encode.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, u64, C.c_void_p, C.c_void_p, C.POINTER(u64), C.c_int]
+        L.xo_rans1_encode_table.restype = u64
+        L.xo_rans1_encode_table.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, u64, C.c_void_p, C.c_void_p, C.POINTER(u64), C.c_int, C.c_int]
+        L.xo_rans1_decode.restype = u64
+        L.xo_rans1_decode.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, u64, C.POINTER(u64), C.POINTER(u64), C.c_int]
         L.xo_tile_blob_bound.restype = u64
         L.xo_tile_blob_bound.argtypes = [C.POINTER(XoTile), C.c_int]
         L.xo_encode_tile.restype = u64
@@ -158,6 +164,48 @@ def rans2_decode(block: bytes, max_n: int):
     n = C.c_uint64()
     csz = lib().xo_rans2_decode(_ptr(buf), _ptr(out), C.byref(n))
     return out[: n.value].copy(), csz
+
+
+def _bits_int(buf: np.ndarray, nbits: int) -> int:
+    """the first nbits bits of a bit stream (little-endian words, fields from the top) as one integer, first bit highest"""
+    words = buf[: 4 * ((nbits + 31) // 32)].view("<u4").astype(">u4").tobytes()
+    return int.from_bytes(words, "big") >> (8 * len(words) - nbits) if nbits else 0
+
+
+def rans1_encode(hist, nominal_n: int, syms: np.ndarray, pb: int):
+    """The v1 block of a stream (level 2) -> (block bytes, the bits it puts into the tile's shared bit stream as an integer, how many)."""
+    F = np.ascontiguousarray(hist, dtype=np.uint32).copy()
+    assert len(F) >= nominal_n
+    syms = np.ascontiguousarray(syms, dtype=np.uint8)
+    blk, bits = np.zeros(2 * len(syms) + 4096, dtype=np.uint8), np.zeros(len(syms) + 1024 + 8, dtype=np.uint8)
+    nb = C.c_uint64()
+    sz = lib().xo_rans1_encode(_ptr(F), nominal_n, _ptr(syms), len(syms), _ptr(blk), _ptr(bits), C.byref(nb), pb)
+    if not sz:
+        raise ValueError("rans1_encode: arguments out of range")
+    return blk[:sz].tobytes(), _bits_int(bits, nb.value), nb.value
+
+
+def rans1_encode_table(F, syms: np.ndarray, pb: int, sparse: bool):
+    """A type 3 (dense) or type 4 (sparse) v1 block with the table F written as given (len(F) = the slot's nominal alphabet):
+    never raw, never one-symbol, no normalisation.  -> (block bytes, table bits as an integer, how many)."""
+    F = np.ascontiguousarray(F, dtype=np.uint32)
+    syms = np.ascontiguousarray(syms, dtype=np.uint8)
+    blk, bits = np.zeros(2 * len(syms) + 4096, dtype=np.uint8), np.zeros(len(syms) + 1024 + 8, dtype=np.uint8)
+    nb = C.c_uint64()
+    sz = lib().xo_rans1_encode_table(_ptr(F), len(F), _ptr(syms), len(syms), _ptr(blk), _ptr(bits), C.byref(nb), pb, int(bool(sparse)))
+    if not sz:
+        raise ValueError("rans1_encode_table: table or symbols out of range")
+    return blk[:sz].tobytes(), _bits_int(bits, nb.value), nb.value
+
+
+def rans1_decode(block: bytes, nominal_n: int, bits: bytes, bitpos: int, pb: int, max_n: int):
+    """One v1 block whose piece of the shared bit stream `bits` starts at bit `bitpos` -> (symbols, block bytes, the bit position behind the piece)."""
+    buf = np.frombuffer(block + b"\0" * 16, dtype=np.uint8).copy()
+    bw = np.frombuffer(bits + b"\0" * 16, dtype=np.uint8).copy()
+    out = np.zeros(max_n + 16, dtype=np.uint8)
+    pos, n = C.c_uint64(bitpos), C.c_uint64()
+    sz = lib().xo_rans1_decode(_ptr(buf), nominal_n, _ptr(out), _ptr(bw), len(bits), C.byref(pos), C.byref(n), pb)
+    return out[: n.value].copy(), sz, pos.value
 
 
 def encode_tile(mode: int, raster: np.ndarray, tile) -> bytes:

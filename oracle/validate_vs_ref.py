@@ -14,8 +14,23 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import pyoracle as po  # noqa: E402
-from tools.to7 import png_to_raster, raster_to_seven  # noqa: E402
-from xpng_amd.synth import synth_raster  # noqa: E402
+from xpng_amd.synth import synth_raster, to_seven_bytes as raster_to_seven  # noqa: E402
+
+
+def png_to_raster(path):
+    """RGBA if the PNG has alpha / tRNS else RGB, then the reference's normalisation: RGB zeroed under alpha 0, a fully opaque
+    alpha channel dropped (oracle/make_golden.py reads the corpus with it too)."""
+    from PIL import Image
+    im = Image.open(path)
+    has_alpha = im.mode in ("RGBA", "LA", "PA") or "transparency" in im.info
+    a = np.asarray(im.convert("RGBA" if has_alpha else "RGB")).copy()
+    if a.shape[2] == 4:
+        al = a[..., 3]
+        if ((al == 0) & (a[..., :3].any(axis=2))).any():
+            a[al == 0] = 0
+        elif (al == 255).all():
+            a = np.ascontiguousarray(a[..., :3])
+    return a
 
 
 def edge_rasters(quick):

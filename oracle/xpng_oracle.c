@@ -456,19 +456,8 @@ uint64_t xo_rans2_decode(const uint8_t *in, uint8_t *out, uint64_t *n_out) {
 /* ------------------------------------------------------------------ rANS v1 (mode 2) libxpng.c:160-301
  * The block is built downward from *top (bytes); symbols are st[0..n).  The frequency table or the
  * raw symbols go to the tile-wide shared bit stream `tb`.  Returns the new (lower) top. */
-static uint8_t *rans1_encode(uint32_t *F, unsigned N, const uint8_t *st, uint64_t n, uint8_t *top, bitw *tb, int pb) {
-    const unsigned rawBits = (unsigned)bit_width(N - 1);
-    uint8_t *w = top;
-    if (n == 0) { w -= 4; wr32(w, 4); return w; }
-    uint32_t cum[257], distinct = 0;
-    cum[0] = 0;
-    for (unsigned i = 0; i < N; i++) { cum[i + 1] = cum[i] + F[i]; distinct += F[i] != 0; }
-    if (distinct == 1) {
-        w -= 4; wr32(w, (uint32_t)n + ((uint32_t)st[n - 1] << 24));
-        w -= 4; wr32(w, 8u + (1u << 24));
-        return w;
-    }
-    normalise_freqs(F, cum, N, n, pb);
+/* States and words of a v1 block with the final table F[0..N) and its cum[], downward from w; returns the new (lower) w. */
+static uint8_t *rans1_emit(const uint32_t *F, const uint32_t *cum, unsigned N, const uint8_t *st, uint64_t n, uint8_t *w, int pb) {
     rans_enc_sym e[256];
     make_enc_syms(e, F, cum, N, pb);
     uint64_t s0 = RANS_L, s1 = RANS_L;
@@ -483,6 +472,36 @@ static uint8_t *rans1_encode(uint32_t *F, unsigned N, const uint8_t *st, uint64_
     }
     w -= 8; wr64(w, s1);
     w -= 8; wr64(w, s0);
+    return w;
+}
+
+/* The table into the shared bit stream (dense: pb bits per entry; sparse: a flag bit, then pb bits where it is set), then the
+ * two header words below w. */
+static uint8_t *rans1_finish(const uint32_t *F, unsigned N, uint64_t n, uint8_t *top, uint8_t *w, bitw *tb, int pb, int sparse) {
+    for (unsigned k = 0; k < N; k++) {
+        if (!sparse) bitw_put(tb, (unsigned)pb, F[k]);
+        else if (F[k]) bitw_put(tb, (unsigned)pb + 1, F[k] + (1u << pb));
+        else bitw_put(tb, 1, 0);
+    }
+    w -= 4; wr32(w, (uint32_t)n);
+    w -= 4; wr32(w, (uint32_t)(top - w) + ((3u + (uint32_t)sparse) << 24));
+    return w;
+}
+
+static uint8_t *rans1_encode(uint32_t *F, unsigned N, const uint8_t *st, uint64_t n, uint8_t *top, bitw *tb, int pb) {
+    const unsigned rawBits = (unsigned)bit_width(N - 1);
+    uint8_t *w = top;
+    if (n == 0) { w -= 4; wr32(w, 4); return w; }
+    uint32_t cum[257], distinct = 0;
+    cum[0] = 0;
+    for (unsigned i = 0; i < N; i++) { cum[i + 1] = cum[i] + F[i]; distinct += F[i] != 0; }
+    if (distinct == 1) {
+        w -= 4; wr32(w, (uint32_t)n + ((uint32_t)st[n - 1] << 24));
+        w -= 4; wr32(w, 8u + (1u << 24));
+        return w;
+    }
+    normalise_freqs(F, cum, N, n, pb);
+    w = rans1_emit(F, cum, N, st, n, w, pb);
     uint32_t tabBits = (N - distinct) + distinct * ((uint32_t)pb + 1);
     const int sparse = tabBits < N * (uint32_t)pb;
     if (!sparse) tabBits = N * (uint32_t)pb;
@@ -493,14 +512,7 @@ static uint8_t *rans1_encode(uint32_t *F, unsigned N, const uint8_t *st, uint64_
         w -= 4; wr32(w, 8u + (2u << 24));
         return w;
     }
-    for (unsigned k = 0; k < N; k++) {
-        if (!sparse) bitw_put(tb, (unsigned)pb, F[k]);
-        else if (F[k]) bitw_put(tb, (unsigned)pb + 1, F[k] + (1u << pb));
-        else bitw_put(tb, 1, 0);
-    }
-    w -= 4; wr32(w, (uint32_t)n);
-    w -= 4; wr32(w, (uint32_t)(top - w) + ((3u + (uint32_t)sparse) << 24));
-    return w;
+    return rans1_finish(F, N, n, top, w, tb, pb, sparse);
 }
 
 /* libxpng.c:262-301.  Returns block size in bytes (low 24 bits of the header). */
@@ -535,6 +547,66 @@ static uint32_t rans1_decode(const uint8_t *blk, unsigned N, uint8_t *x, bitr *t
         if (s1 < RANS_L) { s1 = (s1 << 32) | (rp + 4 <= end ? rd32(rp) : rd32(end - 4)); if (rp < end) rp += 4; }
     }
     if (n & 1) x[i] = slot2sym[s0 & mask];
+    return size;
+}
+
+/* Test infrastructure: the v1 coder on a stream of its own.  The block goes to blk, what it puts into the shared bit stream
+ * (table or raw symbols) to bits from bit 0, *nbits of them (the last word is padded with zeros).  bits holds n + 1024 bytes,
+ * blk 2 n + 4096.  F[0..N) holds the symbol counts and is clobbered (normalised).  Returns the block's bytes. */
+uint64_t xo_rans1_encode(uint32_t *F, unsigned N, const uint8_t *in, uint64_t n, uint8_t *blk, uint8_t *bits, uint64_t *nbits, int pb) {
+    if (pb < 10 || pb > 15 || N < 2 || N > 256 || n > 0xFFFFFF) return 0;
+    const uint64_t cap = 2 * n + 4096;
+    uint8_t *mem = malloc(cap);
+    if (!mem) return 0;
+    bitw tb = { 0, 0, bits };
+    uint8_t *lo = rans1_encode(F, N, in, n, mem + cap, &tb, pb);
+    *nbits = (uint64_t)(tb.p - bits) * 8 + tb.pend;
+    bitw_finish(&tb);
+    const uint64_t sz = (uint64_t)(mem + cap - lo);
+    memcpy(blk, lo, sz);
+    free(mem);
+    return sz;
+}
+
+/* The same with the caller's table and form, bypassing normalise_freqs and the raw / one-symbol forms: a type 3 (dense) or
+ * type 4 (sparse) block.  F[0..N) is written as given, each entry below 2^pb, the sum at most 2^pb, every symbol of in[]
+ * with F >= 1; N is the slot's nominal alphabet (a v1 table always has that many entries).  Returns 0 when the table or the symbols break
+ * these rules. */
+uint64_t xo_rans1_encode_table(const uint32_t *F, unsigned N, const uint8_t *in, uint64_t n, uint8_t *blk, uint8_t *bits, uint64_t *nbits,
+                               int pb, int sparse) {
+    if (pb < 10 || pb > 15 || N < 2 || N > 256 || n == 0 || n > 0xFFFFFF) return 0;
+    uint32_t cum[257];
+    cum[0] = 0;
+    for (unsigned i = 0; i < N; i++) {
+        if (F[i] >= (1u << pb)) return 0;
+        cum[i + 1] = cum[i] + F[i];
+    }
+    if (cum[N] > (1u << pb)) return 0;
+    for (uint64_t k = 0; k < n; k++) if (in[k] >= N || !F[in[k]]) return 0;
+    const uint64_t cap = 2 * n + 4096;
+    uint8_t *mem = malloc(cap);
+    if (!mem) return 0;
+    bitw tb = { 0, 0, bits };
+    uint8_t *lo = rans1_finish(F, N, n, mem + cap, rans1_emit(F, cum, N, in, n, mem + cap, pb), &tb, pb, sparse != 0);
+    *nbits = (uint64_t)(tb.p - bits) * 8 + tb.pend;
+    bitw_finish(&tb);
+    const uint64_t sz = (uint64_t)(mem + cap - lo);
+    memcpy(blk, lo, sz);
+    free(mem);
+    return sz;
+}
+
+/* One v1 block -> symbols.  The shared bit stream is bits[0 .. bits_len), followed by 8 readable zero bytes (the reader fills a
+ * word ahead; with them its cursor counts every bit it handed out), and the block's piece starts at bit *bitpos, which moves
+ * behind it.  Returns the block's bytes, *n_out symbols in out. */
+uint64_t xo_rans1_decode(const uint8_t *blk, unsigned N, uint8_t *out, const uint8_t *bits, uint64_t bits_len, uint64_t *bitpos,
+                         uint64_t *n_out, int pb) {
+    bitr tb = { 0, 0, bits + (*bitpos / 32) * 4, bits + bits_len + 8 };
+    for (uint64_t k = *bitpos % 32; k; ) { unsigned c = k > 16 ? 16 : (unsigned)k; bitr_get(&tb, c); k -= c; }
+    const uint32_t h0 = rd32(blk), type = h0 >> 24;
+    *n_out = type == 0 ? 0 : type == 1 ? (rd32(blk + 4) & 0xFFFFFF) : rd32(blk + 4);
+    const uint32_t size = type == 0 ? 4 : rans1_decode(blk, N, out, &tb, pb);
+    *bitpos = (uint64_t)(tb.p - bits) * 8 - tb.have;
     return size;
 }
 

@@ -68,6 +68,14 @@ uint64_t xo_rans2_encode(uint32_t *F, unsigned nominalN, const uint8_t *in, uint
 uint64_t xo_rans2_decode(const uint8_t *in, uint8_t *out, uint64_t *n_out);
 uint64_t xo_rans2_encode_table(const uint32_t *F, unsigned N, const uint8_t *in, uint64_t n, uint8_t *out, int pb, int sparse);
 
+/* rANS v1 block (libxpng.c:160-301) on a stream of its own: the block and what it puts into the tile's shared bit stream
+ * (frequency table or raw symbols, *nbits bits from bit 0 of bits).  F holds the counts over the nominal alphabet N. */
+uint64_t xo_rans1_encode(uint32_t *F, unsigned N, const uint8_t *in, uint64_t n, uint8_t *blk, uint8_t *bits, uint64_t *nbits, int pb);
+uint64_t xo_rans1_encode_table(const uint32_t *F, unsigned N, const uint8_t *in, uint64_t n, uint8_t *blk, uint8_t *bits, uint64_t *nbits,
+                               int pb, int sparse);
+uint64_t xo_rans1_decode(const uint8_t *blk, unsigned N, uint8_t *out, const uint8_t *bits, uint64_t bits_len, uint64_t *bitpos,
+                         uint64_t *n_out, int pb);
+
 /* Whole tile.  `out` must hold w*h*pxsz + 4 + slack (xo_tile_blob_bound). Returns blob bytes, 0 on error. */
 uint64_t xo_tile_blob_bound(const xo_tile *t, int pxsz);
 uint64_t xo_encode_tile(int mode, const uint8_t *raster, uint64_t W, int pxsz, const xo_tile *t, uint8_t *out);

@@ -10,7 +10,7 @@ CPU part: the checker is pinned to the oracle - table, type and length of every 
 branch it is named after (the census; run with -s to read it).  GPU part (-m gpu): bytes against the oracle, per block
 (Context.fetch serves the blocks of the narrow and of the wide form: both write them to the same place), per file, in one batch
 that selects the wide kernels by itself, in one mixed-size call, and at level 2.  The level-2 colour streams (pb 14) are compared
-as bytes only: the repository has no parser for the level-2 colour blocks, so there is no census of their steals."""
+as bytes only here; tests/test_m2_colour_streams.py parses the level-2 colour blocks and holds the census of their steals."""
 import numpy as np
 import pytest
 
