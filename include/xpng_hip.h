@@ -508,6 +508,53 @@ int xpnghip_decode_varsize_device_batch_views_colour(xpnghip_ctx *ctx, int mode,
                                                      const float *scale, const float *bias, uint32_t filter, const float *colours,
                                                      void *stream);
 
+/* ---- antialiased bicubic resampling in the copy-out of a views call -------------------------
+ * DINO, BYOL, MAE and the ViT recipes resize with BICUBIC: PIL's BICUBIC, F.interpolate(mode="bicubic", antialias=True) on tensors.
+ * Every entry point above that takes a `filter` word keeps its domain, 0 or 1.  The cubic rule has entry points of its own, which
+ * take no filter word at all: they are always this rule.
+ * THE RULE.  Everything outside the axis operation is the views-colour call's: the 64-byte view record (nothing added), the
+ * selection of tiles, channel choice, the BGR exchange, alpha last, the layouts, the dtypes and the constants; v = 255 exactly, with
+ * no read, still stands in for the alpha an RGB context lacks.  One axis operation maps q(0 .. n-1), fp32, to one fp32 value; n is
+ * the extent of the RECTANGLE on the axis, k the ratio from the record and ik its inverse, also from the record.  For output
+ * index u:
+ *     f  = fmaf((float)u + 0.5f, k, -0.5f)                  (as above)
+ *     s  = k > 1.0f ? k : 1.0f       is = k > 1.0f ? ik : 1.0f       r = s + s
+ *     lo = f - r    j0 = lo > 0 ? (uint32_t)lo : 0          j1 = min((uint32_t)(f + r), n - 1)
+ *     W = 0, A = 0, then for j = j0 .. j1 ascending:
+ *         d = fabsf((float)j - f)        t = fmaf(d, is, 0.0f)
+ *         w = t < 1 ? fmaf(fmaf(fmaf( 1.5f, t, -2.5f), t,  0.0f), t, 1.0f)
+ *           : t < 2 ? fmaf(fmaf(fmaf(-0.5f, t,  2.5f), t, -4.0f), t, 2.0f)
+ *           : 0.0f
+ *         W = W + w        A = fmaf(w, q(j), A)
+ *     result A / W        one IEEE fp32 division
+ * This is Keys' cubic with a = -0.5, stretched by the ratio where the axis shrinks, clamped to the rectangle and renormalised: the
+ * kernel and the window of PIL's BICUBIC and of ATen's _upsample_bicubic2d_aa.  Unlike the triangle rule there is no two-tap
+ * branch: an axis with k <= 1 takes the same window with s = 1, four to five taps.  H(s) is the x-axis operation over row s of the
+ * rectangle with u = flip ? OW-1-ox : ox, and the y-axis operation runs over H(.).  Then
+ *     v = result < 0.0f ? 0.0f : result > 255.0f ? 255.0f : result
+ * because a cubic overshoots (random bytes range about -47 .. 272) and a uint8 pipeline clamps exactly there.  After that the colour
+ * matrix applies where one is given, by the rule of the views-colour call on these clamped v; last y = fmaf(v_or_t, scale[c],
+ * bias[c]) and out = (T)y, round to nearest even.  Every multiplication is inside an explicit fmaf, sums and the division are
+ * single operations, and the order of accumulation - ascending j within a row, ascending s over rows - is part of the rule.
+ * Consequences: (a) a rectangle of the output's size is a pure crop, bit for bit the slice of the float call: at k = 1, f is an
+ * integer and the weights are exactly 1, 0, 0; (b) a flip is a mirror on the bits; (c) no tap leaves the rectangle, which is what
+ * keeps skipping untouched tiles safe; (d) an identity matrix gives the bits of colour == NULL, because v already lies in
+ * 0 .. 255 (under the triangle filter this does not hold).  W > 0 always.
+ * host-only, needs no device, and it is the rule: the arguments of xpnghip_resample_colour_host without `filter`; colour may be
+ * NULL.  Refuses everything xpnghip_resample_colour_host refuses, with the same texts and with nothing written. */
+int xpnghip_resample_cubic_host(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip,
+                                uint32_t out_w, uint32_t out_h, uint32_t layout, uint32_t dtype, const float *scale,
+                                const float *bias, const float *colour, void *out);
+/* The views-colour call without `filter`: view v receives, bit for bit, what xpnghip_resample_cubic_host writes with its matrix
+ * (colours == NULL: with colour == NULL, and then no matrix table is allocated or uploaded).  The checks, their order and their
+ * texts - without the filter's -, the selection (xpnghip_view_tiles), the records, the upload protocol, the workspace growth and
+ * xpnghip_ctx_last_decode_tiles are the views-colour call's. */
+int xpnghip_decode_varsize_device_batch_views_cubic(xpnghip_ctx *ctx, int mode, const void *const *d_blobs, const uint64_t *blobs_len,
+                                                    uint32_t nimg, const uint64_t *tile_off, uint32_t nviews,
+                                                    const uint32_t *view_image, void *const *d_outs, const uint32_t *out_sizes,
+                                                    const uint64_t *rects, const uint8_t *flips, uint32_t layout, uint32_t dtype,
+                                                    const float *scale, const float *bias, const float *colours, void *stream);
+
 /* ---- staged batch from device tensors: the inverse of the float call --------------------------
  * A model writes floats, not the file's bytes.  The call below is xpnghip_images_begin with the upload replaced by one staging
  * kernel that reads the caller's DEVICE buffers - planar or interleaved, RGB or BGR, uint8, f16, bf16 or f32 - and writes the

@@ -39,6 +39,7 @@ HIP_SYMBOLS = [
     "xpnghip_images_begin_device", "xpnghip_quantize_host",
     "xpnghip_decode_varsize_device_batch_views", "xpnghip_view_tiles", "xpnghip_ctx_last_decode_tiles",
     "xpnghip_resample_colour_host", "xpnghip_decode_varsize_device_batch_views_colour",
+    "xpnghip_resample_cubic_host", "xpnghip_decode_varsize_device_batch_views_cubic",
 ]
 HOST_SYMBOLS = ["xpng_store", "xpng_load", "xpng_from_jpg", "xpng_store_T", "xpng_load_T", "xpng_from_jpg_T",
                 "store_7", "load_7"]
@@ -205,6 +206,13 @@ def _bind_hip(path):
         L.xpnghip_decode_varsize_device_batch_views_colour.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64), C.c_uint32, C.POINTER(u64), C.c_uint32,
                                                                        u32p, C.POINTER(vp), u32p, C.POINTER(u64), u8p, C.c_uint32, C.c_uint32, f32p,
                                                                        f32p, C.c_uint32, f32p, vp]
+        L.xpnghip_resample_cubic_host.restype = C.c_int
+        L.xpnghip_resample_cubic_host.argtypes = [C.c_int, vp, u64, u64, C.POINTER(u64), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                  f32p, f32p, f32p, vp]
+        L.xpnghip_decode_varsize_device_batch_views_cubic.restype = C.c_int
+        L.xpnghip_decode_varsize_device_batch_views_cubic.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64), C.c_uint32, C.POINTER(u64), C.c_uint32,
+                                                                      u32p, C.POINTER(vp), u32p, C.POINTER(u64), u8p, C.c_uint32, C.c_uint32, f32p,
+                                                                      f32p, f32p, vp]
         L.xpnghip_view_tiles.restype = C.c_int64
         L.xpnghip_view_tiles.argtypes = [C.POINTER(u64), C.c_uint32, C.c_uint32, u32p, C.POINTER(u64), u32p, u64]
         L.xpnghip_ctx_last_decode_tiles.restype = u64
@@ -671,6 +679,34 @@ def resample_colour_host(raster, size, layout: int, dtype: int, scale=None, bias
     return buf.tobytes()[:ch * oh * ow * dtype_bytes(dtype)]
 
 
+def resample_cubic_host(raster, size, layout: int, dtype: int, scale=None, bias=None, rect=None, flip=False, colour=None) -> bytes:
+    """The rule of MixedContext.decode_batch_views_cubic on the host (xpnghip_resample_cubic_host; needs no device):
+    resample_colour_host's arguments without `filter` - the call is always the antialiased bicubic: Keys' cubic with a = -0.5 on
+    both axes, stretched by the ratio where an axis shrinks, clamped to the rectangle and renormalised, every resampled value
+    clamped to 0 .. 255, then the colour matrix where one is given (None: none), then the constants.  Returns the C * OH * OW
+    elements of `dtype` in `layout` as raw bytes, bit for bit what the device call writes for these pixels."""
+    r = np.ascontiguousarray(raster, dtype=np.uint8)
+    if r.ndim != 3 or r.shape[2] not in (3, 4):
+        raise XpngError("resample_cubic_host: the raster must be (h, w, 3) or (h, w, 4) uint8")
+    try:
+        oh, ow = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise XpngError(f"resample_cubic_host: size must be (OH, OW), not {size!r}") from None
+    px = r.shape[2]
+    sc, bi, ch = _scale_bias(layout, px, scale, bias)
+    ra = _rect_array("resample_cubic_host", None if rect is None else [rect], 1)
+    cm = None if colour is None else (C.c_float * 12)(*_colour12("resample_cubic_host", colour))
+    ok = ch > 0 and 1 <= oh <= 16384 and 1 <= ow <= 16384          # (anything else the library refuses, naming the value)
+    buf = np.empty(ch * oh * ow if ok else 1, dtype=np.uint32)     # 4-byte aligned, room for the widest element
+    if hip_lib().xpnghip_resample_cubic_host(px, r.ctypes.data, r.shape[1], r.shape[0], ra, int(flip), ow & 0xFFFFFFFF, oh & 0xFFFFFFFF, layout, dtype,
+                                             sc, bi, cm, buf.ctypes.data):
+        raise XpngError("xpnghip_resample_cubic_host: " + _err())
+    return buf.tobytes()[:ch * oh * ow * dtype_bytes(dtype)]
+
+
+_CUBIC = object()  # in place of a filter word: the views call that has none
+
+
 def _view_images(name, view_image, nviews):
     """the image of every view as a C array of uint32 (None stays None: the identity)"""
     if view_image is None:
@@ -1080,6 +1116,45 @@ class MixedContext(_Handle):
         self._decode("xpnghip_decode_varsize_device_batch_resampled", mode, d_blobs, lens, d_outs, tile_offs, stream, layout, dtype, sc, bi, ra, fl, ow, oh,
                      int(filter) & 0xFFFFFFFF)
 
+    def _views(self, name, mode, d_blobs, lens, view_image, d_outs, layout, dtype, sizes, scale, bias, rects, flips, tile_offs, stream, colours, filter):
+        """the marshalling of both views calls; filter _CUBIC: the cubic call, which has no filter word and always takes `colours`"""
+        n = len(d_outs)
+        cm = None
+        if colours is not None:
+            colours = list(colours)
+            if len(colours) != n:
+                raise XpngError(f"{name}: colours has {len(colours)} entries for {n} views")
+            if any(m is not None for m in colours):
+                flat = [x for v, m in enumerate(colours) for x in (COLOUR_IDENTITY if m is None else _colour12(f"{name}: colours[{v}]", m))]
+                cm = (C.c_float * (12 * n))(*flat)
+        vi = _view_images(name, None if view_image is None else list(view_image), n)
+        if view_image is not None and len(list(view_image)) != n:
+            raise XpngError(f"{name}: view_image has {len(list(view_image))} entries for {n} output buffers")
+        so = None
+        if sizes is not None:
+            try:
+                sizes = list(sizes)
+                if len(sizes) == 2 and not hasattr(sizes[0], "__len__"):
+                    sizes = [sizes] * n
+                if len(sizes) != n:
+                    raise XpngError(f"{name}: sizes has {len(sizes)} entries for {n} views")
+                so = (C.c_uint32 * max(2 * n, 1))(*[int(v) & 0xFFFFFFFF for (oh, ow) in sizes for v in (ow, oh)])
+            except (TypeError, ValueError):
+                raise XpngError(f"{name}: sizes must be (OH, OW) or one (OH, OW) per view, not {sizes!r}") from None
+        sc, bi, _ = _scale_bias(layout, self.pxsz, scale, bias)
+        ra = _rect_array(name, rects, n)
+        fl = _flip_array(name, flips, n, "views")
+        if filter is _CUBIC:
+            self._decode("xpnghip_decode_varsize_device_batch_views_cubic", mode, d_blobs, lens, d_outs, tile_offs, stream, so, ra, fl, layout, dtype,
+                         sc, bi, cm, before=(n, vi))
+            return
+        if cm is not None:
+            self._decode("xpnghip_decode_varsize_device_batch_views_colour", mode, d_blobs, lens, d_outs, tile_offs, stream, so, ra, fl, layout, dtype,
+                         sc, bi, int(filter) & 0xFFFFFFFF, cm, before=(n, vi))
+            return
+        self._decode("xpnghip_decode_varsize_device_batch_views", mode, d_blobs, lens, d_outs, tile_offs, stream, so, ra, fl, layout, dtype, sc, bi,
+                     int(filter) & 0xFFFFFFFF, before=(n, vi))
+
     def decode_batch_views(self, mode, d_blobs, lens, view_image, d_outs, layout, dtype, sizes, scale=None, bias=None, rects=None, flips=None,
                            filter: int = FILTER_TRIANGLE_AA, tile_offs=None, stream=0, colours=None):
         """decode_batch_resampled with any number of outputs per image, and only the tiles they touch decoded: view v reads image
@@ -1090,38 +1165,18 @@ class MixedContext(_Handle):
         resample_colour_host takes it: the copy-out then puts every pixel of view v through matrix v and a clamp to 0 .. 255
         before the constants (xpnghip_decode_varsize_device_batch_views_colour).  colours None, or every entry None, is the
         plain call."""
-        n = len(d_outs)
-        cm = None
-        if colours is not None:
-            colours = list(colours)
-            if len(colours) != n:
-                raise XpngError(f"decode_batch_views: colours has {len(colours)} entries for {n} views")
-            if any(m is not None for m in colours):
-                flat = [x for v, m in enumerate(colours) for x in (COLOUR_IDENTITY if m is None else _colour12(f"decode_batch_views: colours[{v}]", m))]
-                cm = (C.c_float * (12 * n))(*flat)
-        vi = _view_images("decode_batch_views", None if view_image is None else list(view_image), n)
-        if view_image is not None and len(list(view_image)) != n:
-            raise XpngError(f"decode_batch_views: view_image has {len(list(view_image))} entries for {n} output buffers")
-        so = None
-        if sizes is not None:
-            try:
-                sizes = list(sizes)
-                if len(sizes) == 2 and not hasattr(sizes[0], "__len__"):
-                    sizes = [sizes] * n
-                if len(sizes) != n:
-                    raise XpngError(f"decode_batch_views: sizes has {len(sizes)} entries for {n} views")
-                so = (C.c_uint32 * max(2 * n, 1))(*[int(v) & 0xFFFFFFFF for (oh, ow) in sizes for v in (ow, oh)])
-            except (TypeError, ValueError):
-                raise XpngError(f"decode_batch_views: sizes must be (OH, OW) or one (OH, OW) per view, not {sizes!r}") from None
-        sc, bi, _ = _scale_bias(layout, self.pxsz, scale, bias)
-        ra = _rect_array("decode_batch_views", rects, n)
-        fl = _flip_array("decode_batch_views", flips, n, "views")
-        if cm is not None:
-            self._decode("xpnghip_decode_varsize_device_batch_views_colour", mode, d_blobs, lens, d_outs, tile_offs, stream, so, ra, fl, layout, dtype,
-                         sc, bi, int(filter) & 0xFFFFFFFF, cm, before=(n, vi))
-            return
-        self._decode("xpnghip_decode_varsize_device_batch_views", mode, d_blobs, lens, d_outs, tile_offs, stream, so, ra, fl, layout, dtype, sc, bi,
-                     int(filter) & 0xFFFFFFFF, before=(n, vi))
+        self._views("decode_batch_views", mode, d_blobs, lens, view_image, d_outs, layout, dtype, sizes, scale, bias, rects, flips, tile_offs, stream,
+                    colours, filter)
+
+    def decode_batch_views_cubic(self, mode, d_blobs, lens, view_image, d_outs, layout, dtype, sizes, scale=None, bias=None, rects=None, flips=None,
+                                 tile_offs=None, stream=0, colours=None):
+        """decode_batch_views without `filter`: every view is resampled with the antialiased bicubic of resample_cubic_host - Keys'
+        cubic, a = -0.5, stretched where an axis shrinks, clamped to the rectangle, the values clamped to 0 .. 255 - and view v
+        equals that function's bytes.  The selection of tiles, sizes, rects, flips and colours (a None entry beside a matrix is the
+        identity matrix, which here gives the bits of no matrix) are decode_batch_views':
+        xpnghip_decode_varsize_device_batch_views_cubic (the rule is in include/xpng_hip.h)."""
+        self._views("decode_batch_views_cubic", mode, d_blobs, lens, view_image, d_outs, layout, dtype, sizes, scale, bias, rects, flips, tile_offs,
+                    stream, colours, _CUBIC)
 
     def last_decode_tiles(self) -> int:
         """tile work items of the context's most recent decode launch (xpnghip_ctx_last_decode_tiles): n_tiles after the other

@@ -35,6 +35,7 @@
 #include "mixed_resample.hpp"
 #include "mixed_views.hpp"
 #include "mixed_views_colour.hpp"
+#include "mixed_views_cubic.hpp"
 #include "stage_from.hpp"
 
 using namespace xpng;
@@ -1257,6 +1258,97 @@ extern "C" int xpnghip_resample_colour_host(int pxsz, const uint8_t *raster, uin
                                             const float *colour, void *out) {
     XPNG_GUARDED(resample_colour_host_impl(pxsz, raster, w, h, rect, flip, out_w, out_h, layout, dtype, scale, bias, filter, colour, out))
 }
+// ---- the antialiased bicubic of a views call (mixed_views_cubic.hpp) --------------------------------------------
+// One axis of the cubic rule for output index u: the window and the centre; `is` is the inverse of the stretch
+struct CubicAxis {
+    uint32_t j0, j1;
+    float f;
+};
+static CubicAxis cubic_axis_host(uint32_t u, float k, uint32_t n) {
+#pragma clang fp contract(off)
+    CubicAxis a{};
+    const float c = (float)u + 0.5f;
+    a.f = fmaf(c, k, -0.5f);
+    const float s = k > 1.0f ? k : 1.0f;
+    const float r = s + s;
+    const float lo = a.f - r, hi = a.f + r;
+    a.j0 = lo > 0.0f ? (uint32_t)lo : 0u;
+    const uint32_t t = (uint32_t)hi;
+    a.j1 = t < n - 1 ? t : n - 1;
+    return a;
+}
+// the axis operation over q(0 .. n-1); *bad is set where W is not positive (the rule's argument says never)
+template <class Q> static float cubic_axis_apply(const CubicAxis &a, float is, Q q, bool *bad) {
+#pragma clang fp contract(off)
+    float W = 0.0f, A = 0.0f;
+    for (uint32_t j = a.j0; j <= a.j1; j++) {
+        const float d = fabsf((float)j - a.f);
+        const float t = fmaf(d, is, 0.0f);
+        float w = 0.0f;
+        if (t < 1.0f) w = fmaf(fmaf(fmaf(1.5f, t, -2.5f), t, 0.0f), t, 1.0f);
+        else if (t < 2.0f) w = fmaf(fmaf(fmaf(-0.5f, t, 2.5f), t, -4.0f), t, 2.0f);
+        W = W + w;
+        A = fmaf(w, q(j), A);
+    }
+    if (!(W > 0.0f)) *bad = true;
+    return A / W;
+}
+// The twin of k_mixed_views_cubic on the host: the same operations in the same order, every multiplication inside an explicit
+// fmaf(), contraction off on top of that.  It IS the rule of the cubic views call.
+static int resample_cubic_host_impl(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip, uint32_t out_w, uint32_t out_h,
+                                    uint32_t layout, uint32_t dtype, const float *scale, const float *bias, const float *colour, void *out) {
+#pragma clang fp contract(off)
+    std::string why;
+    int C;
+    FloatConsts k;
+    ResizeRec z0;
+    if (resize_host_args("xpnghip_resample_cubic_host", pxsz, raster, w, h, rect, flip, out_w, out_h, layout, dtype, scale, bias, out, C, k, z0)) return 1;
+    if (colour && !colour_matrix_ok(colour, "", why)) return fail(why);
+    const ResampleRec z = resample_record(z0);
+    const bool planar = layout & XPNGHIP_LAYOUT_PLANAR, bgr = layout & XPNGHIP_LAYOUT_BGR;
+    const float isx = z.kx > 1.0f ? z.ikx : 1.0f, isy = z.ky > 1.0f ? z.iky : 1.0f;
+    std::vector<CubicAxis> ax(out_w), ay(out_h);
+    for (uint32_t ox = 0; ox < out_w; ox++) ax[ox] = cubic_axis_host(z.flip ? out_w - 1 - ox : ox, z.kx, z.rw);
+    for (uint32_t oy = 0; oy < out_h; oy++) ay[oy] = cubic_axis_host(oy, z.ky, z.rh);
+    // the values first, the elements after them: a call that fails writes nothing
+    std::vector<float> ys((uint64_t)C * out_h * out_w);
+    bool bad = false;
+    for (uint32_t oy = 0; oy < out_h; oy++)
+        for (uint32_t ox = 0; ox < out_w; ox++) {
+            float v[4] = {0.0f, 0.0f, 0.0f, 255.0f};  // R, G, B of the file and its alpha (255: the alpha an RGB raster does not store)
+            for (int sc = 0; sc < (pxsz == 4 && C == 4 ? 4 : 3); sc++) {
+                auto H = [&](uint32_t s) {
+                    const uint8_t *p = raster + ((uint64_t)(z.ry + s) * w + z.rx) * pxsz + sc;
+                    return cubic_axis_apply(ax[ox], isx, [&](uint32_t j) { return (float)p[(uint64_t)j * pxsz]; }, &bad);
+                };
+                const float x = cubic_axis_apply(ay[oy], isy, H, &bad);
+                v[sc] = x < 0.0f ? 0.0f : x > 255.0f ? 255.0f : x;  // a cubic overshoots: the clamp a uint8 pipeline applies
+            }
+            float t[3] = {v[0], v[1], v[2]};
+            for (int q = 0; colour && q < 3; q++) {
+                const float *m = colour + 4 * q;
+                const float a = fmaf(m[2], v[2], m[3]);
+                const float b = fmaf(m[1], v[1], a);
+                const float x = fmaf(m[0], v[0], b);
+                t[q] = x < 0.0f ? 0.0f : x > 255.0f ? 255.0f : x;
+            }
+            for (int c = 0; c < C; c++) {
+                const float u = c == 3 ? v[3] : t[bgr ? 2 - c : c];
+                ys[planar ? ((uint64_t)c * out_h + oy) * out_w + ox : ((uint64_t)oy * out_w + ox) * C + c] = fmaf(u, k.scale[c], k.bias[c]);
+            }
+        }
+    if (bad) return fail("internal error: a window of the cubic filter has no weight");  // (W > 0 always: DESIGN.md 22)
+    for (uint64_t e = 0; e < ys.size(); e++) {
+        if (dtype == XPNGHIP_DTYPE_F32) reinterpret_cast<float *>(out)[e] = ys[e];
+        else reinterpret_cast<uint16_t *>(out)[e] = dtype == XPNGHIP_DTYPE_F16 ? f16_bits_rne(ys[e]) : bf16_bits_rne(ys[e]);
+    }
+    return 0;
+}
+extern "C" int xpnghip_resample_cubic_host(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip, uint32_t out_w,
+                                           uint32_t out_h, uint32_t layout, uint32_t dtype, const float *scale, const float *bias, const float *colour,
+                                           void *out) {
+    XPNG_GUARDED(resample_cubic_host_impl(pxsz, raster, w, h, rect, flip, out_w, out_h, layout, dtype, scale, bias, colour, out))
+}
 // ---- staging from tensors (stage_from.hpp) ---------------------------------------------------------------------
 // the layout word of a call whose channel count is per image: the PLANAR and BGR bits and nothing else
 static bool stage_layout_ok(uint32_t layout, std::string &why) {
@@ -1580,14 +1672,14 @@ extern "C" uint64_t xpnghip_ctx_last_decode_tiles(const xpnghip_ctx *c) { return
 static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg, const uint64_t *tile_off,
                              uint32_t nviews, const uint32_t *view_image, void *const *d_outs, const uint32_t *out_sizes, const uint64_t *rects,
                              const uint8_t *flips, uint32_t layout, uint32_t dtype, const float *scale, const float *bias, uint32_t filter,
-                             const float *colours, void *stream) {
+                             const float *colours, void *stream, bool cubic = false) {
     // every argument is checked before anything reaches the device: a rejected call writes nothing
     int C, es;
     FloatConsts fk{};
     const FloatCall fc{dtype, scale, bias};
     if (mixed_decode_args(c, mode, d_blobs, blobs_len, nimg, d_outs, &layout, &fc, C, es, fk)) return 1;  // (everything the float call refuses)
     std::string why;
-    if (!resample_filter_ok(filter, why)) return fail(why);
+    if (!cubic && !resample_filter_ok(filter, why)) return fail(why);  // (the cubic call has no filter word)
     if (!out_sizes) return fail("out_sizes is NULL: a views call needs the pair {out_w, out_h} of every view");
     if (!view_args_ok(c->m_dims.data(), nimg, nviews, view_image, rects, why)) return fail(why);
     const uint64_t px = (uint64_t)c->pxsz, bpr = rup(c->m_max_w * px, 16);
@@ -1657,7 +1749,8 @@ static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
     with_3or4(c->pxsz, [&](auto PXc) { with_3or4(C, [&](auto Cc) { with_planar(layout, [&](auto PL) { with_float(dtype, [&](auto t) {
         constexpr int PXv = decltype(PXc)::value, Cv = decltype(Cc)::value;
         constexpr bool PLv = decltype(PL)::value;
-        if (colours) k_mixed_views_colour<PXv, Cv, PLv, decltype(t)><<<grid, 256, 0, s>>>(c->d_m_views, c->d_m_vcolour, c->d_m_stage, bpr, bgr, filter, fk);
+        if (cubic) k_mixed_views_cubic<PXv, Cv, PLv, decltype(t)><<<grid, 256, 0, s>>>(c->d_m_views, colours ? c->d_m_vcolour : nullptr, c->d_m_stage, bpr, bgr, fk);
+        else if (colours) k_mixed_views_colour<PXv, Cv, PLv, decltype(t)><<<grid, 256, 0, s>>>(c->d_m_views, c->d_m_vcolour, c->d_m_stage, bpr, bgr, filter, fk);
         else k_mixed_views_as_float<PXv, Cv, PLv, decltype(t)><<<grid, 256, 0, s>>>(c->d_m_views, c->d_m_stage, bpr, bgr, filter, fk);
     }); }); }); });
     HIPCHK(hipGetLastError());
@@ -1675,6 +1768,13 @@ extern "C" int xpnghip_decode_varsize_device_batch_views_colour(xpnghip_ctx *c, 
                                                                 uint32_t dtype, const float *scale, const float *bias, uint32_t filter, const float *colours,
                                                                 void *stream) {
     XPNG_GUARDED(decode_views_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, nviews, view_image, d_outs, out_sizes, rects, flips, layout, dtype, scale, bias, filter, colours, stream))
+}
+// the views-colour call without a filter word: always the cubic rule (mixed_views_cubic.hpp)
+extern "C" int xpnghip_decode_varsize_device_batch_views_cubic(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
+                                                               const uint64_t *tile_off, uint32_t nviews, const uint32_t *view_image, void *const *d_outs,
+                                                               const uint32_t *out_sizes, const uint64_t *rects, const uint8_t *flips, uint32_t layout,
+                                                               uint32_t dtype, const float *scale, const float *bias, const float *colours, void *stream) {
+    XPNG_GUARDED(decode_views_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, nviews, view_image, d_outs, out_sizes, rects, flips, layout, dtype, scale, bias, 0, colours, stream, true))
 }
 
 // ---- mixed-size batch encode (mixed.hpp) ---------------------------------------------------------

@@ -153,8 +153,18 @@ def _pack_bodies(part):
     return host, offs
 
 
+def _cubic(name, interpolation, antialias):
+    """True for interpolation "bicubic" (which needs antialias=True), False for "bilinear"; anything else is an error"""
+    if interpolation not in ("bilinear", "bicubic"):
+        raise XpngError(f"{name}: interpolation must be 'bilinear' or 'bicubic', not {interpolation!r}")
+    if interpolation == "bicubic" and not antialias:
+        raise XpngError(f"{name}: interpolation='bicubic' needs antialias=True: the rule is the antialiased bicubic (a = -0.5, PIL's BICUBIC); "
+                        "torch's bicubic without antialias is another kernel (a = -0.75) and is not offered")
+    return interpolation == "bicubic"
+
+
 def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, device=None, dtype=torch.uint8, mean=None, std=None,
-               stack: bool = False, size=None, crops=None, flips=None, antialias: bool = False):
+               stack: bool = False, size=None, crops=None, flips=None, antialias: bool = False, interpolation: str = "bilinear"):
     """The images of a list of .xpng files of any sizes as tensors on `device` (default: the current cuda device), each of
     shape (C, h, w) for layout "chw" or (h, w, C) for "hwc".  channels None keeps each file's own count (3 or 4); 3 drops the
     alpha of an RGBA file, 4 gives an RGB file alpha 255; bgr=True orders the colours B, G, R (alpha stays last).
@@ -189,7 +199,12 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
     resize and RandomResizedCrop, up to the order of summation: the largest difference measured against torch's CPU kernel was
     1.22e-4 of one byte step (tests/test_resample.py asserts 2^-10).  Host-answered files go through api.resample_host and are
     bit-identical, so such files still load with device="cpu".  antialias=False (the default) runs today's path, call for call;
-    antialias=True without size is an error."""
+    antialias=True without size is an error.
+
+    interpolation="bicubic" with size and antialias=True resamples with the antialiased bicubic of load_views - PIL's BICUBIC,
+    F.interpolate(mode="bicubic", antialias=True) with its result clamped to 0 .. 255 - through the same device call
+    (MixedContext.decode_batch_views_cubic, one view per file); host-answered files go through api.resample_cubic_host.
+    "bilinear" (the default) runs the paths above, call for call."""
     if layout not in ("chw", "hwc"):
         raise XpngError(f"load_files: layout must be 'chw' or 'hwc', not {layout!r}")
     if channels not in (None, 3, 4):
@@ -202,6 +217,9 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
         raise XpngError("load_files: crops and flips need size=(OH, OW)")
     if antialias and size is None:
         raise XpngError("load_files: antialias=True needs size=(OH, OW): without a resize there is nothing to filter")
+    cubic = _cubic("load_files", interpolation, antialias)
+    if cubic and size is None:
+        raise XpngError("load_files: interpolation='bicubic' needs size=(OH, OW): without a resize there is nothing to interpolate")
     if size is not None:
         if dtype == torch.uint8:
             raise XpngError("load_files: size needs a float dtype (torch.float16, bfloat16 or float32): the resize interpolates")
@@ -272,7 +290,9 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
         if size is not None:
             C = channels or px
             word = api.layout(planar=layout == "chw", bgr=bgr, channels=C)
-            if antialias:
+            if cubic:
+                raw = api.resample_cubic_host(t.numpy(), (OH, OW), word, dt, *consts(C), rect=crops[i], flip=flips[i])
+            elif antialias:
                 raw = api.resample_host(t.numpy(), (OH, OW), word, dt, *consts(C), rect=crops[i], flip=flips[i], filter=api.FILTER_TRIANGLE_AA)
             else:
                 raw = api.resize_host(t.numpy(), (OH, OW), word, dt, *consts(C), rect=crops[i], flip=flips[i])
@@ -305,7 +325,10 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
                 ctx = api.MixedContext([(w, h) for (_, w, h, _) in part], px, device=index)
                 try:
                     ins, lens = [d_in.data_ptr() + o for o in offs], [len(buf) - 8 for (_, _, _, buf) in part]
-                    if size is not None and antialias:
+                    if cubic:                                    # (the views call with the identity view_image: one view per file)
+                        ctx.decode_batch_views_cubic(mode, ins, lens, None, [t.data_ptr() for t in outs], word, dt, (OH, OW), *consts(C),
+                                                     rects=[crops[i] or (0, 0, w, h) for (i, w, h, _) in part], flips=[flips[i] for (i, _, _, _) in part])
+                    elif size is not None and antialias:
                         ctx.decode_batch_resampled(mode, ins, lens, [t.data_ptr() for t in outs], word, dt, (OH, OW), *consts(C),
                                                    rects=[crops[i] or (0, 0, w, h) for (i, w, h, _) in part], flips=[flips[i] for (i, _, _, _) in part],
                                                    filter=api.FILTER_TRIANGLE_AA)
@@ -327,7 +350,7 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
 
 
 def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool = False, device=None, dtype=torch.float16, mean=None,
-               std=None, antialias: bool = True, stack: bool = False, out=None, colour=None):
+               std=None, antialias: bool = True, stack: bool = False, out=None, colour=None, interpolation: str = "bilinear"):
     """Any number of views per file, each decoded once: views is a list of (path_index, rect_or_None, flip) - rect = (x, y, w, h)
     inside file path_index, None for the whole image; flip True mirrors left to right - and view v comes back as a tensor
     (C, OH_v, OW_v) for layout "chw" or (OH_v, OW_v, C) for "hwc", in view order.  size is one (OH, OW) for every view or one pair
@@ -352,7 +375,17 @@ def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool
     (the rule is in include/xpng_hip.h; alpha does not pass through the matrix).  View v then equals, bit for bit,
     api.resample_colour_host with its matrix, which is also what answers level-7 and single-colour files.  Without colour, or
     with every entry None, the function runs exactly the calls it runs without the argument; beside a matrix a None entry is the
-    identity matrix, whose clamp can differ from no matrix in the last bits where the antialiased quotient rounds past 255."""
+    identity matrix, whose clamp can differ from no matrix in the last bits where the antialiased quotient rounds past 255.
+
+    interpolation="bicubic" resamples every view with the ANTIALIASED BICUBIC that DINO, BYOL, MAE and timm's ViT recipes use:
+    Keys' cubic with a = -0.5 on both axes, stretched by the ratio where an axis shrinks, clamped to the view's rectangle and
+    renormalised, and every resampled value clamped to 0 .. 255 before the matrix and the normalisation - PIL's BICUBIC, and
+    F.interpolate(mode="bicubic", align_corners=False, antialias=True) of the cropped rectangle followed by that clamp, up to the
+    order of summation (tests/test_cubic.py states the measured difference).  It needs antialias=True: torch's bicubic without
+    antialias is another kernel (a = -0.75) with another border rule, and is not offered.  Every device call is then ONE
+    MixedContext.decode_batch_views_cubic and view v equals, bit for bit, api.resample_cubic_host with its matrix, which also
+    answers level-7 and single-colour files; here an identity matrix and no matrix give the same bits.  "bilinear" (the
+    default) runs exactly the calls the function ran without the argument."""
     if layout not in ("chw", "hwc"):
         raise XpngError(f"load_views: layout must be 'chw' or 'hwc', not {layout!r}")
     if channels not in (None, 3, 4):
@@ -401,6 +434,7 @@ def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool
     dev = torch.device("cuda" if device is None else device)
     if dev.type == "cuda" and not torch.cuda.is_available():
         raise XpngError("load_views: no GPU is visible (device='cpu' answers level-7 and single-colour files without one)")
+    cubic = _cubic("load_views", interpolation, antialias)
     filt = api.FILTER_TRIANGLE_AA if antialias else api.FILTER_BILINEAR
     # only the files that a view names are read
     heads, bufs = {}, {}
@@ -454,7 +488,10 @@ def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool
             if vi != i:
                 continue
             word = api.layout(planar=layout == "chw", bgr=bgr, channels=chans[v])
-            raw = api.resample_colour_host(ras, sizes[v], word, dt, *cache[chans[v]], rect=r, flip=f, filter=filt, colour=cols[v])
+            if cubic:
+                raw = api.resample_cubic_host(ras, sizes[v], word, dt, *cache[chans[v]], rect=r, flip=f, colour=cols[v])
+            else:
+                raw = api.resample_colour_host(ras, sizes[v], word, dt, *cache[chans[v]], rect=r, flip=f, filter=filt, colour=cols[v])
             tv = torch.frombuffer(bytearray(raw), dtype=dtype).view(shape(v))
             if res[v] is None:
                 res[v] = tv.to(dev)
@@ -481,11 +518,15 @@ def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool
                 ctx = api.MixedContext([(w, h) for (_, w, h, _) in part], px, device=index)
                 try:
                     ins, lens = [d_in.data_ptr() + o for o in offs], [len(buf) - 8 for (_, _, _, buf) in part]
-                    ctx.decode_batch_views(mode, ins, lens, [local[views[v][0]] for v in mine], [res[v].data_ptr() for v in mine], word, dt,
-                                           [sizes[v] for v in mine], *cache[C],
-                                           rects=[views[v][1] or (0, 0, heads[views[v][0]][1], heads[views[v][0]][2]) for v in mine],
-                                           flips=[views[v][2] for v in mine], filter=filt,
-                                           colours=[cols[v] for v in mine] if cols[mine[0]] is not None else None)
+                    args = (mode, ins, lens, [local[views[v][0]] for v in mine], [res[v].data_ptr() for v in mine], word, dt,
+                            [sizes[v] for v in mine], *cache[C])
+                    kw = dict(rects=[views[v][1] or (0, 0, heads[views[v][0]][1], heads[views[v][0]][2]) for v in mine],
+                              flips=[views[v][2] for v in mine],
+                              colours=[cols[v] for v in mine] if cols[mine[0]] is not None else None)
+                    if cubic:
+                        ctx.decode_batch_views_cubic(*args, **kw)
+                    else:
+                        ctx.decode_batch_views(*args, filter=filt, **kw)
                     status = ctx.decode_status()                  # (synchronises the context's stream: the tensors are complete)
                 finally:
                     ctx.close()
