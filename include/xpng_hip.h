@@ -555,6 +555,63 @@ int xpnghip_decode_varsize_device_batch_views_cubic(xpnghip_ctx *ctx, int mode, 
                                                     const uint64_t *rects, const uint8_t *flips, uint32_t layout, uint32_t dtype,
                                                     const float *scale, const float *bias, const float *colours, void *stream);
 
+/* ---- Gaussian blur and solarise per view in a views call ------------------------------------
+ * SimCLR, BYOL and DINO put a Gaussian blur with a sigma per view, and a solarise on the second view, between the colour jitter
+ * and the normalisation.  Neither is linear per pixel and a blur reads its neighbours' finished values, so views that ask for
+ * either take a second pass.  One 16-byte record per view: */
+typedef struct { float sigma; uint32_t radius; float solarise; uint32_t reserved; } xpnghip_view_blur;
+/* radius is 0 .. 31: the blur has 2 * radius + 1 taps per axis.  0 means no blur, and then sigma must be 0.0f; with radius > 0,
+ * sigma must be finite and lie in 2^-10 .. 1024.  solarise is a threshold in byte units: 0 .. 255 turns it on, exactly 256.0f turns
+ * it off, anything else (NaN included) is refused.  reserved must be 0.  {0.0f, 0, 256.0f, 0} is the record that is all off.
+ * The third filter word.  It is accepted ONLY by the two functions of this section, where it selects the rule of
+ * xpnghip_resample_cubic_host; every other entry point with a filter word keeps its domain of 0 and 1. */
+#define XPNGHIP_FILTER_CUBIC_AA 2u
+/* THE WEIGHTS, host-only: w[0 .. radius] (radius + 1 floats) of the blur, one statement for the device call, the host rule, Python
+ * and the tests.  In double: g[d] = exp(-(double)(d * d) / (2.0 * s * s)) with s = (double)sigma; S = g[0] + 2 * (g[1] + .. + g[R]),
+ * the inner sum in ascending d; w[d] = (float)(g[d] / S).  Returns 1, with the text, for radius > 31, for a sigma that is not
+ * finite or outside 2^-10 .. 1024 with radius > 0, for a sigma other than 0.0f with radius 0, and for w == NULL; radius 0 gives
+ * w[0] = 1.0f.
+ * THE RULE.  The intermediate T - C planes of out_h x out_w fp32 in byte units - is, bit for bit, what the existing host functions
+ * write for the view: xpnghip_resample_colour_host for filter 0 or 1, xpnghip_resample_cubic_host for filter 2, with layout
+ * XPNGHIP_LAYOUT_PLANAR | (C << 8) without the BGR bit, dtype F32, every scale 1.0f, every bias 0.0f and the view's matrix where
+ * it has one.  Nothing about resampling or colour is restated here.  The blur applies to the three colour planes only: alpha, or
+ * the 255 an RGB context lacks, passes through untouched, as with the colour matrix.  With
+ *     refl(i, n) = i < 0 ? -i : i >= n ? 2 * (n - 1) - i : i              (torch's "reflect")
+ * the horizontal operation on plane q is, in fp32 with explicit fmaf,
+ *     A = 0.0f
+ *     for d = R down to 1:  A = fmaf(w[d], q(y, refl(x - d, out_w)) + q(y, refl(x + d, out_w)), A)
+ *     A = fmaf(w[0], q(y, x), A)
+ * and the vertical operation is the same over the horizontal results, with out_h.  Then b = A < 0 ? 0 : A > 255 ? 255 : A.  With
+ * R == 0 the blur step is skipped and b = q.  The order of accumulation is part of the rule.  Solarise, where it is on:
+ * b = b >= thr ? 255.0f - b : b, on the colour channels only.  Last y = fmaf(b, scale[c], bias[c]) and out = (T)y; the BGR exchange
+ * and c, the position in the caller's buffer, are exactly the existing calls'.
+ * Refused, before anything is written or reaches the device, with a text that names the view (in the device call) and the field:
+ * radius > 31; radius >= out_w or radius >= out_h of that view (reflect needs it, and torch refuses the same); the sigma, solarise
+ * and reserved conditions above; a filter above 2; everything the underlying call refuses.
+ * Consequences: (a) a record that is all off gives the bits of the plain call for that view, and blurs == NULL IS the underlying
+ * call: same kernels, same bytes, nothing more allocated or uploaded; (b) a flip is still a mirror on the bits, because the pair
+ * sum commutes; (c) no tap leaves the view's own plane.
+ * Not offered: PIL's ImageFilter.GaussianBlur (a box-blur approximation), blurred alpha, uint8 outputs.
+ * host-only, needs no device, and it is the rule: xpnghip_resample_colour_host's arguments, with filter 0, 1 or 2, plus one record
+ * (NULL: all off).  colour may be NULL. */
+int xpnghip_blur_weights(float sigma, uint32_t radius, float *w);
+int xpnghip_resample_blur_host(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip,
+                               uint32_t out_w, uint32_t out_h, uint32_t layout, uint32_t dtype, const float *scale,
+                               const float *bias, uint32_t filter, const float *colour, const xpnghip_view_blur *blur, void *out);
+/* The views-colour call plus `blurs`: nviews records on the host, or NULL.  View v receives, bit for bit, what
+ * xpnghip_resample_blur_host writes with its matrix and its record.  filter may be 0, 1 or 2; colours may be NULL.  Views whose
+ * record is all off are written by the copy-out kernel of the underlying call, straight into the caller's buffer.  The others are
+ * written by that kernel as fp32 planes into a scratch of the context's workspace - C * out_h * out_w floats per view, each slice
+ * rounded up to 256 bytes; counted by xpnghip_ctx_workspace_bytes; it grows only when a call needs more than any call before it -
+ * and a second kernel (xpng_amd/csrc/mixed_views_blur.hpp) blurs, solarises, applies the constants and stores.  The tables of the
+ * second pass are uploaded with the call's other tables under the same single synchronisation. */
+int xpnghip_decode_varsize_device_batch_views_blur(xpnghip_ctx *ctx, int mode, const void *const *d_blobs, const uint64_t *blobs_len,
+                                                   uint32_t nimg, const uint64_t *tile_off, uint32_t nviews,
+                                                   const uint32_t *view_image, void *const *d_outs, const uint32_t *out_sizes,
+                                                   const uint64_t *rects, const uint8_t *flips, uint32_t layout, uint32_t dtype,
+                                                   const float *scale, const float *bias, uint32_t filter, const float *colours,
+                                                   const xpnghip_view_blur *blurs, void *stream);
+
 /* ---- staged batch from device tensors: the inverse of the float call --------------------------
  * A model writes floats, not the file's bytes.  The call below is xpnghip_images_begin with the upload replaced by one staging
  * kernel that reads the caller's DEVICE buffers - planar or interleaved, RGB or BGR, uint8, f16, bf16 or f32 - and writes the

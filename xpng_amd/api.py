@@ -40,6 +40,7 @@ HIP_SYMBOLS = [
     "xpnghip_decode_varsize_device_batch_views", "xpnghip_view_tiles", "xpnghip_ctx_last_decode_tiles",
     "xpnghip_resample_colour_host", "xpnghip_decode_varsize_device_batch_views_colour",
     "xpnghip_resample_cubic_host", "xpnghip_decode_varsize_device_batch_views_cubic",
+    "xpnghip_blur_weights", "xpnghip_resample_blur_host", "xpnghip_decode_varsize_device_batch_views_blur",
 ]
 HOST_SYMBOLS = ["xpng_store", "xpng_load", "xpng_from_jpg", "xpng_store_T", "xpng_load_T", "xpng_from_jpg_T",
                 "store_7", "load_7"]
@@ -73,6 +74,10 @@ class XpngT(C.Structure):  # include/xpng.h xpng_t
 _hip = None
 _host = None
 _probes = None
+
+
+class ViewBlur(C.Structure):  # include/xpng_hip.h xpnghip_view_blur
+    _fields_ = [("sigma", C.c_float), ("radius", C.c_uint32), ("solarise", C.c_float), ("reserved", C.c_uint32)]
 
 
 def _bind_hip(path):
@@ -213,6 +218,15 @@ def _bind_hip(path):
         L.xpnghip_decode_varsize_device_batch_views_cubic.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64), C.c_uint32, C.POINTER(u64), C.c_uint32,
                                                                       u32p, C.POINTER(vp), u32p, C.POINTER(u64), u8p, C.c_uint32, C.c_uint32, f32p,
                                                                       f32p, f32p, vp]
+        L.xpnghip_blur_weights.restype = C.c_int
+        L.xpnghip_blur_weights.argtypes = [C.c_float, C.c_uint32, f32p]
+        L.xpnghip_resample_blur_host.restype = C.c_int
+        L.xpnghip_resample_blur_host.argtypes = [C.c_int, vp, u64, u64, C.POINTER(u64), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                 f32p, f32p, C.c_uint32, f32p, C.POINTER(ViewBlur), vp]
+        L.xpnghip_decode_varsize_device_batch_views_blur.restype = C.c_int
+        L.xpnghip_decode_varsize_device_batch_views_blur.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64), C.c_uint32, C.POINTER(u64), C.c_uint32,
+                                                                     u32p, C.POINTER(vp), u32p, C.POINTER(u64), u8p, C.c_uint32, C.c_uint32, f32p,
+                                                                     f32p, C.c_uint32, f32p, C.POINTER(ViewBlur), vp]
         L.xpnghip_view_tiles.restype = C.c_int64
         L.xpnghip_view_tiles.argtypes = [C.POINTER(u64), C.c_uint32, C.c_uint32, u32p, C.POINTER(u64), u32p, u64]
         L.xpnghip_ctx_last_decode_tiles.restype = u64
@@ -706,6 +720,65 @@ def resample_cubic_host(raster, size, layout: int, dtype: int, scale=None, bias=
 
 _CUBIC = object()  # in place of a filter word: the views call that has none
 
+FILTER_CUBIC_AA = 2  # XPNGHIP_FILTER_CUBIC_AA: the third filter word, which resample_blur_host and decode_batch_views_blur alone take
+SOLARISE_OFF = 256.0  # the threshold of a record that does not solarise
+
+
+def blur_weights(sigma: float, radius: int) -> np.ndarray:
+    """The radius + 1 fp32 weights w[0 .. radius] of a Gaussian blur (xpnghip_blur_weights; needs no device), the one statement the
+    device call, the host rule and the tests share: in double g[d] = exp(-d^2 / (2 sigma^2)), S = g[0] + 2 (g[1] + .. + g[R]),
+    w[d] = float32(g[d] / S).  radius is 0 .. 31; radius 0 needs sigma 0 and gives [1.0]."""
+    try:
+        sigma, radius = float(sigma), int(radius)
+    except (TypeError, ValueError):
+        raise XpngError(f"blur_weights: sigma and radius must be numbers, not {sigma!r}, {radius!r}") from None
+    w = np.zeros(max(min(radius, 31), 0) + 1, dtype=np.float32)
+    if hip_lib().xpnghip_blur_weights(sigma, radius & 0xFFFFFFFF, w.ctypes.data_as(C.POINTER(C.c_float))):
+        raise XpngError("xpnghip_blur_weights: " + _err())
+    return w
+
+
+def _blur_record(name, b):
+    """None or (sigma, radius, solarise_or_None) as a ViewBlur; the library checks the values"""
+    if b is None:
+        return ViewBlur(0.0, 0, SOLARISE_OFF, 0)
+    if isinstance(b, ViewBlur):
+        return b
+    try:
+        sigma, radius, sol = b
+        return ViewBlur(float(sigma), int(radius) & 0xFFFFFFFF, SOLARISE_OFF if sol is None else float(sol), 0)
+    except (TypeError, ValueError):
+        raise XpngError(f"{name}: a blur is None or (sigma, radius, solarise_or_None), not {b!r}") from None
+
+
+def resample_blur_host(raster, size, layout: int, dtype: int, scale=None, bias=None, rect=None, flip=False, filter: int = FILTER_TRIANGLE_AA,
+                       colour=None, blur=None) -> bytes:
+    """The rule of MixedContext.decode_batch_views_blur on the host (xpnghip_resample_blur_host; needs no device):
+    resample_colour_host's arguments with filter 0, 1 or FILTER_CUBIC_AA (the rule of resample_cubic_host), plus blur = None or
+    (sigma, radius, solarise_or_None).  The resampled and colour-transformed values of the view are blurred with the 2 * radius + 1
+    taps of blur_weights(sigma, radius) on each axis over a reflected border (torch's "reflect") and clamped to 0 .. 255 - radius 0:
+    no blur, and then sigma must be 0 -, then solarised where a threshold is given (b >= threshold: 255 - b), then the constants;
+    alpha passes through untouched.  Returns the C * OH * OW elements of `dtype` in `layout` as raw bytes, bit for bit what the
+    device call writes for these pixels."""
+    r = np.ascontiguousarray(raster, dtype=np.uint8)
+    if r.ndim != 3 or r.shape[2] not in (3, 4):
+        raise XpngError("resample_blur_host: the raster must be (h, w, 3) or (h, w, 4) uint8")
+    try:
+        oh, ow = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise XpngError(f"resample_blur_host: size must be (OH, OW), not {size!r}") from None
+    px = r.shape[2]
+    sc, bi, ch = _scale_bias(layout, px, scale, bias)
+    ra = _rect_array("resample_blur_host", None if rect is None else [rect], 1)
+    cm = None if colour is None else (C.c_float * 12)(*_colour12("resample_blur_host", colour))
+    rec = _blur_record("resample_blur_host", blur)
+    ok = ch > 0 and 1 <= oh <= 16384 and 1 <= ow <= 16384          # (anything else the library refuses, naming the value)
+    buf = np.empty(ch * oh * ow if ok else 1, dtype=np.uint32)     # 4-byte aligned, room for the widest element
+    if hip_lib().xpnghip_resample_blur_host(px, r.ctypes.data, r.shape[1], r.shape[0], ra, int(flip), ow & 0xFFFFFFFF, oh & 0xFFFFFFFF, layout, dtype,
+                                            sc, bi, int(filter) & 0xFFFFFFFF, cm, C.byref(rec), buf.ctypes.data):
+        raise XpngError("xpnghip_resample_blur_host: " + _err())
+    return buf.tobytes()[:ch * oh * ow * dtype_bytes(dtype)]
+
 
 def _view_images(name, view_image, nviews):
     """the image of every view as a C array of uint32 (None stays None: the identity)"""
@@ -1116,9 +1189,17 @@ class MixedContext(_Handle):
         self._decode("xpnghip_decode_varsize_device_batch_resampled", mode, d_blobs, lens, d_outs, tile_offs, stream, layout, dtype, sc, bi, ra, fl, ow, oh,
                      int(filter) & 0xFFFFFFFF)
 
-    def _views(self, name, mode, d_blobs, lens, view_image, d_outs, layout, dtype, sizes, scale, bias, rects, flips, tile_offs, stream, colours, filter):
-        """the marshalling of both views calls; filter _CUBIC: the cubic call, which has no filter word and always takes `colours`"""
+    def _views(self, name, mode, d_blobs, lens, view_image, d_outs, layout, dtype, sizes, scale, bias, rects, flips, tile_offs, stream, colours, filter,
+               blurs=None):
+        """the marshalling of the views calls; filter _CUBIC: the cubic call, which has no filter word and always takes `colours`;
+        blurs not None: the blur call, which takes a filter word, `colours` and the records"""
         n = len(d_outs)
+        br = None
+        if blurs is not None:
+            blurs = list(blurs)
+            if len(blurs) != n:
+                raise XpngError(f"{name}: blurs has {len(blurs)} entries for {n} views")
+            br = (ViewBlur * max(n, 1))(*[_blur_record(f"{name}: blurs[{v}]", b) for v, b in enumerate(blurs)])
         cm = None
         if colours is not None:
             colours = list(colours)
@@ -1144,6 +1225,10 @@ class MixedContext(_Handle):
         sc, bi, _ = _scale_bias(layout, self.pxsz, scale, bias)
         ra = _rect_array(name, rects, n)
         fl = _flip_array(name, flips, n, "views")
+        if name == "decode_batch_views_blur":
+            self._decode("xpnghip_decode_varsize_device_batch_views_blur", mode, d_blobs, lens, d_outs, tile_offs, stream, so, ra, fl, layout, dtype,
+                         sc, bi, int(filter) & 0xFFFFFFFF, cm, br, before=(n, vi))
+            return
         if filter is _CUBIC:
             self._decode("xpnghip_decode_varsize_device_batch_views_cubic", mode, d_blobs, lens, d_outs, tile_offs, stream, so, ra, fl, layout, dtype,
                          sc, bi, cm, before=(n, vi))
@@ -1177,6 +1262,17 @@ class MixedContext(_Handle):
         xpnghip_decode_varsize_device_batch_views_cubic (the rule is in include/xpng_hip.h)."""
         self._views("decode_batch_views_cubic", mode, d_blobs, lens, view_image, d_outs, layout, dtype, sizes, scale, bias, rects, flips, tile_offs,
                     stream, colours, _CUBIC)
+
+    def decode_batch_views_blur(self, mode, d_blobs, lens, view_image, d_outs, layout, dtype, sizes, scale=None, bias=None, rects=None, flips=None,
+                                filter: int = FILTER_TRIANGLE_AA, tile_offs=None, stream=0, colours=None, blurs=None):
+        """decode_batch_views plus a Gaussian blur and a solarise per view: blurs is None or one entry per view, each None (neither)
+        or (sigma, radius, solarise_or_None) as resample_blur_host takes it, and view v equals that function's bytes.  filter is
+        0, 1 or FILTER_CUBIC_AA (the rule of decode_batch_views_cubic).  Views with a None entry are written by the copy-out
+        kernel of the underlying call; the others take a second kernel over fp32 planes in the context's workspace
+        (C * OH * OW floats per such view).  blurs None is the underlying call itself:
+        xpnghip_decode_varsize_device_batch_views_blur (the rule is in include/xpng_hip.h)."""
+        self._views("decode_batch_views_blur", mode, d_blobs, lens, view_image, d_outs, layout, dtype, sizes, scale, bias, rects, flips, tile_offs,
+                    stream, colours, filter, blurs)
 
     def last_decode_tiles(self) -> int:
         """tile work items of the context's most recent decode launch (xpnghip_ctx_last_decode_tiles): n_tiles after the other

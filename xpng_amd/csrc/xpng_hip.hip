@@ -36,6 +36,7 @@
 #include "mixed_views.hpp"
 #include "mixed_views_colour.hpp"
 #include "mixed_views_cubic.hpp"
+#include "mixed_views_blur.hpp"
 #include "stage_from.hpp"
 
 using namespace xpng;
@@ -221,6 +222,13 @@ struct xpnghip_ctx {
     // and uploaded as d_m_views is; a plain views call never allocates it
     ViewColour *d_m_vcolour = nullptr;
     uint64_t cap_m_vcolour = 0;        // matrices d_m_vcolour has room for
+    // ... and, for a views call with views that blur or solarise only (mixed_views_blur.hpp), the fp32 planes of those views between
+    // the two passes and one 160-byte record per such view: grown when a call needs more than any before it, dropped and uploaded as
+    // d_m_views is; no other call allocates them
+    float *d_m_bscratch = nullptr;
+    uint64_t cap_m_bscratch = 0;       // bytes d_m_bscratch holds
+    BlurRec *d_m_blur = nullptr;
+    uint64_t cap_m_blur = 0;           // records d_m_blur has room for
     uint64_t last_tiles = 0;           // tile work items of the most recent decode launch (xpnghip_ctx_last_decode_tiles)
 };
 
@@ -1349,6 +1357,132 @@ extern "C" int xpnghip_resample_cubic_host(int pxsz, const uint8_t *raster, uint
                                            void *out) {
     XPNG_GUARDED(resample_cubic_host_impl(pxsz, raster, w, h, rect, flip, out_w, out_h, layout, dtype, scale, bias, colour, out))
 }
+// ---- Gaussian blur and solarise behind the resampling (mixed_views_blur.hpp) ------------------------------------
+// the third filter word: the two entry points of the blur alone take it
+static bool blur_filter_ok(uint32_t filter, std::string &why) {
+    if (filter <= XPNGHIP_FILTER_CUBIC_AA) return true;
+    why = "bad filter " + std::to_string(filter) + " (XPNGHIP_FILTER_BILINEAR = 0, XPNGHIP_FILTER_TRIANGLE_AA = 1, XPNGHIP_FILTER_CUBIC_AA = 2)";
+    return false;
+}
+static std::string blur_num(float v) {
+    char b[48];
+    snprintf(b, sizeof b, "%g", (double)v);
+    return b;
+}
+// sigma and radius of a record or of xpnghip_blur_weights.  `who` names the view in a device call
+static bool blur_sigma_ok(float sigma, uint32_t radius, const std::string &who, std::string &why) {
+    if (radius > BLUR_RMAX) { why = "bad blur" + who + ": radius is " + std::to_string(radius) + ", not 0 .. 31"; return false; }
+    if (radius == 0 && !(sigma == 0.0f)) { why = "bad blur" + who + ": sigma is " + blur_num(sigma) + " with radius 0 (no blur: sigma must be 0)"; return false; }
+    if (radius > 0 && !(std::isfinite(sigma) && sigma >= 0.0009765625f && sigma <= 1024.0f)) {
+        why = "bad blur" + who + ": sigma is " + blur_num(sigma) + " (with radius > 0 it must be finite and lie in 2^-10 .. 1024)";
+        return false;
+    }
+    return true;
+}
+// a whole record against the output size of its view
+static bool blur_record_ok(const xpnghip_view_blur &b, uint32_t out_w, uint32_t out_h, const std::string &who, std::string &why) {
+    if (!blur_sigma_ok(b.sigma, b.radius, who, why)) return false;
+    if (b.radius >= out_w || b.radius >= out_h) {
+        why = "bad blur" + who + ": radius " + std::to_string(b.radius) + " does not lie below both sides of the " + std::to_string(out_w) + " x " + std::to_string(out_h) +
+              " output (the border is a reflection)";
+        return false;
+    }
+    if (!(b.solarise == 256.0f || (b.solarise >= 0.0f && b.solarise <= 255.0f))) {
+        why = "bad blur" + who + ": solarise is " + blur_num(b.solarise) + " (a threshold of 0 .. 255, or exactly 256 for none)";
+        return false;
+    }
+    if (b.reserved) { why = "bad blur" + who + ": reserved is " + std::to_string(b.reserved) + ", not 0"; return false; }
+    return true;
+}
+static bool blur_off(const xpnghip_view_blur &b) { return b.radius == 0 && b.solarise == 256.0f; }
+// the weights of a checked (sigma, radius): the one statement (include/xpng_hip.h)
+static void blur_weights(float sigma, uint32_t radius, float *w) {
+    if (!radius) { w[0] = 1.0f; return; }
+    const double s = (double)sigma;
+    double g[BLUR_RMAX + 1], t = 0.0;
+    for (uint32_t d = 0; d <= radius; d++) g[d] = exp(-(double)(d * d) / (2.0 * s * s));
+    for (uint32_t d = 1; d <= radius; d++) t += g[d];
+    const double S = g[0] + 2.0 * t;
+    for (uint32_t d = 0; d <= radius; d++) w[d] = (float)(g[d] / S);
+}
+extern "C" int xpnghip_blur_weights(float sigma, uint32_t radius, float *w) {
+    std::string why;
+    if (!blur_sigma_ok(sigma, radius, "", why)) return fail(why);
+    if (!w) return fail("xpnghip_blur_weights: w is NULL");
+    blur_weights(sigma, radius, w);
+    return 0;
+}
+// The twin of the two passes on the host: the intermediate from the host rule of the filter, then k_mixed_views_blur's operations
+// in its order, every multiplication inside an explicit fmaf(), contraction off on top of that.  It IS the rule of the blur call.
+static int resample_blur_host_impl(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip, uint32_t out_w, uint32_t out_h,
+                                   uint32_t layout, uint32_t dtype, const float *scale, const float *bias, uint32_t filter, const float *colour,
+                                   const xpnghip_view_blur *blur, void *out) {
+#pragma clang fp contract(off)
+    std::string why;
+    if (!blur_filter_ok(filter, why)) return fail(why);
+    int C;
+    FloatConsts k;
+    ResizeRec z0;
+    if (resize_host_args("xpnghip_resample_blur_host", pxsz, raster, w, h, rect, flip, out_w, out_h, layout, dtype, scale, bias, out, C, k, z0)) return 1;
+    if (colour && !colour_matrix_ok(colour, "", why)) return fail(why);
+    const xpnghip_view_blur b = blur ? *blur : xpnghip_view_blur{0.0f, 0u, 256.0f, 0u};
+    if (!blur_record_ok(b, out_w, out_h, "", why)) return fail(why);
+    // T: C planes of fp32 in byte units, from the host rule of the filter
+    const uint64_t plane = (uint64_t)out_h * out_w;
+    std::vector<float> T((uint64_t)C * plane);
+    const float one[4] = {1.0f, 1.0f, 1.0f, 1.0f}, zero[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    const uint32_t tl = XPNGHIP_LAYOUT_PLANAR | ((uint32_t)C << 8);
+    if (filter == XPNGHIP_FILTER_CUBIC_AA ? resample_cubic_host_impl(pxsz, raster, w, h, rect, flip, out_w, out_h, tl, XPNGHIP_DTYPE_F32, one, zero, colour, T.data())
+                                          : resample_colour_host_impl(pxsz, raster, w, h, rect, flip, out_w, out_h, tl, XPNGHIP_DTYPE_F32, one, zero, filter, colour, T.data()))
+        return 1;
+    const uint32_t R = b.radius;
+    if (R) {
+        float wt[BLUR_RMAX + 1];
+        blur_weights(b.sigma, R, wt);
+        auto refl = [](int64_t i, int64_t n) { return (uint64_t)(i < 0 ? -i : i >= n ? 2 * (n - 1) - i : i); };
+        std::vector<float> Hh(plane);
+        for (int q = 0; q < 3; q++) {
+            float *p = T.data() + q * plane;
+            for (uint32_t y = 0; y < out_h; y++)
+                for (uint32_t x = 0; x < out_w; x++) {
+                    const float *row = p + (uint64_t)y * out_w;
+                    float A = 0.0f;
+                    for (uint32_t d = R; d >= 1; d--) {
+                        const float s = row[refl((int64_t)x - d, out_w)] + row[refl((int64_t)x + d, out_w)];
+                        A = fmaf(wt[d], s, A);
+                    }
+                    Hh[(uint64_t)y * out_w + x] = fmaf(wt[0], row[x], A);
+                }
+            for (uint32_t y = 0; y < out_h; y++)
+                for (uint32_t x = 0; x < out_w; x++) {
+                    float A = 0.0f;
+                    for (uint32_t d = R; d >= 1; d--) {
+                        const float s = Hh[refl((int64_t)y - d, out_h) * out_w + x] + Hh[refl((int64_t)y + d, out_h) * out_w + x];
+                        A = fmaf(wt[d], s, A);
+                    }
+                    A = fmaf(wt[0], Hh[(uint64_t)y * out_w + x], A);
+                    p[(uint64_t)y * out_w + x] = A < 0.0f ? 0.0f : A > 255.0f ? 255.0f : A;
+                }
+        }
+    }
+    const bool planar = layout & XPNGHIP_LAYOUT_PLANAR, bgr = layout & XPNGHIP_LAYOUT_BGR, sol = b.solarise < 256.0f;
+    for (uint32_t oy = 0; oy < out_h; oy++)
+        for (uint32_t ox = 0; ox < out_w; ox++)
+            for (int c = 0; c < C; c++) {
+                float v = T[(uint64_t)(c == 3 ? 3 : bgr ? 2 - c : c) * plane + (uint64_t)oy * out_w + ox];
+                if (c < 3 && sol && v >= b.solarise) v = 255.0f - v;
+                const float y = fmaf(v, k.scale[c], k.bias[c]);
+                const uint64_t e = planar ? ((uint64_t)c * out_h + oy) * out_w + ox : ((uint64_t)oy * out_w + ox) * C + c;
+                if (dtype == XPNGHIP_DTYPE_F32) reinterpret_cast<float *>(out)[e] = y;
+                else reinterpret_cast<uint16_t *>(out)[e] = dtype == XPNGHIP_DTYPE_F16 ? f16_bits_rne(y) : bf16_bits_rne(y);
+            }
+    return 0;
+}
+extern "C" int xpnghip_resample_blur_host(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip, uint32_t out_w,
+                                          uint32_t out_h, uint32_t layout, uint32_t dtype, const float *scale, const float *bias, uint32_t filter,
+                                          const float *colour, const xpnghip_view_blur *blur, void *out) {
+    XPNG_GUARDED(resample_blur_host_impl(pxsz, raster, w, h, rect, flip, out_w, out_h, layout, dtype, scale, bias, filter, colour, blur, out))
+}
 // ---- staging from tensors (stage_from.hpp) ---------------------------------------------------------------------
 // the layout word of a call whose channel count is per image: the PLANAR and BGR bits and nothing else
 static bool stage_layout_ok(uint32_t layout, std::string &why) {
@@ -1672,7 +1806,7 @@ extern "C" uint64_t xpnghip_ctx_last_decode_tiles(const xpnghip_ctx *c) { return
 static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg, const uint64_t *tile_off,
                              uint32_t nviews, const uint32_t *view_image, void *const *d_outs, const uint32_t *out_sizes, const uint64_t *rects,
                              const uint8_t *flips, uint32_t layout, uint32_t dtype, const float *scale, const float *bias, uint32_t filter,
-                             const float *colours, void *stream, bool cubic = false) {
+                             const float *colours, void *stream, bool cubic = false, const xpnghip_view_blur *blurs = nullptr) {
     // every argument is checked before anything reaches the device: a rejected call writes nothing
     int C, es;
     FloatConsts fk{};
@@ -1709,6 +1843,44 @@ static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
     }
     for (uint32_t v = 0; colours && v < nviews; v++)
         if (!colour_matrix_ok(colours + 12ull * v, " of view " + std::to_string(v), why)) return fail(why);
+    // the views that blur or solarise take two passes (mixed_views_blur.hpp): the tables are partitioned, plain views first, and each
+    // copy-out launch gets its part by pointer offset.  Without such a view nothing below differs from the underlying call
+    std::vector<uint32_t> order(nviews);
+    for (uint32_t v = 0; v < nviews; v++) order[v] = v;
+    uint32_t nplain = nviews, max_oh2 = 0, max_tiles2 = 0;
+    std::vector<BlurRec> brecs;
+    std::vector<ViewColour> pcol;
+    uint64_t scratch_floats = 0;
+    if (blurs) {
+        for (uint32_t v = 0; v < nviews; v++)
+            if (!blur_record_ok(blurs[v], recs[v].ow, recs[v].oh, " of view " + std::to_string(v), why)) return fail(why);
+        std::stable_partition(order.begin(), order.end(), [&](uint32_t v) { return blur_off(blurs[v]); });
+        nplain = 0;
+        while (nplain < nviews && blur_off(blurs[order[nplain]])) nplain++;
+    }
+    if (nplain < nviews) {
+        std::vector<ViewRec> part(nviews);
+        for (uint32_t i = 0; i < nviews; i++) part[i] = recs[order[i]];
+        recs.swap(part);
+        if (colours) {
+            pcol.resize(nviews);
+            for (uint32_t i = 0; i < nviews; i++) memcpy(pcol[i].m, colours + 12ull * order[i], sizeof(ViewColour));
+            colours = pcol[0].m;
+        }
+        max_oh = 0;
+        for (uint32_t i = 0; i < nplain; i++) max_oh = std::max(max_oh, recs[i].oh);
+        brecs.resize(nviews - nplain);
+        for (uint32_t i = nplain; i < nviews; i++) {
+            ViewRec &r = recs[i];
+            BlurRec &b = brecs[i - nplain];
+            const xpnghip_view_blur &q = blurs[order[i]];
+            b = BlurRec{scratch_floats, r.buf, r.ow, r.oh, q.radius, q.solarise, {}};
+            blur_weights(q.sigma, q.radius, b.w);
+            scratch_floats += rup((uint64_t)C * r.oh * r.ow * 4, 256) / 4;  // (the slice's own planes, rounded up to 256 bytes)
+            max_oh2 = std::max(max_oh2, r.oh);
+            max_tiles2 = std::max(max_tiles2, ((r.ow + BLUR_TW - 1) / BLUR_TW) * ((r.oh + BLUR_TH - 1) / BLUR_TH));
+        }
+    }
     std::vector<uint32_t> list;
     view_select(c->tiles, c->m_first, c->m_list, c->m_dims.data(), nviews, view_image, rects, list);
     HIPCHK(hipSetDevice(c->device));
@@ -1731,6 +1903,25 @@ static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
         WS_GET(c->d_m_vcolour, (uint64_t)nviews * sizeof(ViewColour));
         c->cap_m_vcolour = nviews;
     }
+    if (!brecs.empty()) {
+        if (c->cap_m_bscratch < scratch_floats * 4 || c->cap_m_blur < brecs.size()) {
+            if (c->d_m_bscratch || c->d_m_blur)
+                for (hipStream_t q : {s, c->stream, c->side}) if (q) HIPCHK(hipStreamSynchronize(q));
+            if (c->cap_m_bscratch < scratch_floats * 4) {
+                c->ws.drop((void **)&c->d_m_bscratch); c->cap_m_bscratch = 0;
+                WS_GET(c->d_m_bscratch, scratch_floats * 4);
+                c->cap_m_bscratch = scratch_floats * 4;
+            }
+            if (c->cap_m_blur < brecs.size()) {
+                c->ws.drop((void **)&c->d_m_blur); c->cap_m_blur = 0;
+                WS_GET(c->d_m_blur, (uint64_t)brecs.size() * sizeof(BlurRec));
+                c->cap_m_blur = brecs.size();
+            }
+        }
+        // the first pass of these views writes their slices of the scratch
+        for (uint32_t i = nplain; i < nviews; i++) recs[i].buf = (uint8_t *)(c->d_m_bscratch + brecs[i - nplain].src);
+        HIPCHK(hipMemcpyAsync(c->d_m_blur, brecs.data(), (uint64_t)brecs.size() * sizeof(BlurRec), hipMemcpyHostToDevice, s));
+    }
     // the resized call's protocol: both tables are in pageable host memory that ends with this call, so the stream is synchronised
     // once behind the two copies - queued before the decode's own kernels, so the wait never covers this call's work
     HIPCHK(hipMemcpyAsync(c->d_m_views, recs.data(), (uint64_t)nviews * sizeof(ViewRec), hipMemcpyHostToDevice, s));
@@ -1744,8 +1935,9 @@ static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
     const int rc = dec_launch(c, mode, nimg, c->m_max_w, tile_off, s, 0, (uint32_t)c->tiles.size(), &list, c->d_m_vlist, bpr);
     if (rc) return rc;
     const uint32_t bgr = layout & XPNGHIP_LAYOUT_BGR;
-    const dim3 grid((max_oh + MC_ROWS - 1) / MC_ROWS, nviews);
+    const dim3 grid((max_oh + MC_ROWS - 1) / MC_ROWS, nplain);
     if (colours) XPNG_REQUIRE(c->d_m_vcolour);
+    if (nplain)
     with_3or4(c->pxsz, [&](auto PXc) { with_3or4(C, [&](auto Cc) { with_planar(layout, [&](auto PL) { with_float(dtype, [&](auto t) {
         constexpr int PXv = decltype(PXc)::value, Cv = decltype(Cc)::value;
         constexpr bool PLv = decltype(PL)::value;
@@ -1753,6 +1945,26 @@ static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
         else if (colours) k_mixed_views_colour<PXv, Cv, PLv, decltype(t)><<<grid, 256, 0, s>>>(c->d_m_views, c->d_m_vcolour, c->d_m_stage, bpr, bgr, filter, fk);
         else k_mixed_views_as_float<PXv, Cv, PLv, decltype(t)><<<grid, 256, 0, s>>>(c->d_m_views, c->d_m_stage, bpr, bgr, filter, fk);
     }); }); }); });
+    HIPCHK(hipGetLastError());
+    if (brecs.empty()) return 0;
+    // the two passes of the views that blur or solarise: the copy-out kernel of the filter as <PX, C, planar, float> with no BGR
+    // exchange and identity constants into the scratch, then k_mixed_views_blur into the caller's layout and dtype
+    XPNG_REQUIRE(c->d_m_bscratch, c->d_m_blur);
+    const uint32_t n2 = nviews - nplain;
+    const dim3 grid1((max_oh2 + MC_ROWS - 1) / MC_ROWS, n2), grid2(max_tiles2, n2);
+    const FloatConsts ident{{1.0f, 1.0f, 1.0f, 1.0f}, {0.0f, 0.0f, 0.0f, 0.0f}};
+    const ViewRec *vr2 = c->d_m_views + nplain;
+    const ViewColour *vm2 = colours ? c->d_m_vcolour + nplain : nullptr;
+    with_3or4(c->pxsz, [&](auto PXc) { with_3or4(C, [&](auto Cc) {
+        constexpr int PXv = decltype(PXc)::value, Cv = decltype(Cc)::value;
+        if (cubic) k_mixed_views_cubic<PXv, Cv, true, float><<<grid1, 256, 0, s>>>(vr2, vm2, c->d_m_stage, bpr, 0u, ident);
+        else if (colours) k_mixed_views_colour<PXv, Cv, true, float><<<grid1, 256, 0, s>>>(vr2, vm2, c->d_m_stage, bpr, 0u, filter, ident);
+        else k_mixed_views_as_float<PXv, Cv, true, float><<<grid1, 256, 0, s>>>(vr2, c->d_m_stage, bpr, 0u, filter, ident);
+    }); });
+    HIPCHK(hipGetLastError());
+    with_3or4(C, [&](auto Cc) { with_planar(layout, [&](auto PL) { with_float(dtype, [&](auto t) {
+        k_mixed_views_blur<decltype(Cc)::value, decltype(PL)::value, decltype(t)><<<grid2, 256, 0, s>>>(c->d_m_blur, c->d_m_bscratch, bgr, fk);
+    }); }); });
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1775,6 +1987,18 @@ extern "C" int xpnghip_decode_varsize_device_batch_views_cubic(xpnghip_ctx *c, i
                                                                const uint32_t *out_sizes, const uint64_t *rects, const uint8_t *flips, uint32_t layout,
                                                                uint32_t dtype, const float *scale, const float *bias, const float *colours, void *stream) {
     XPNG_GUARDED(decode_views_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, nviews, view_image, d_outs, out_sizes, rects, flips, layout, dtype, scale, bias, 0, colours, stream, true))
+}
+// the views-colour call plus one blur record per view (mixed_views_blur.hpp); filter 2 is the cubic rule, blurs == NULL the
+// underlying call itself
+extern "C" int xpnghip_decode_varsize_device_batch_views_blur(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
+                                                              const uint64_t *tile_off, uint32_t nviews, const uint32_t *view_image, void *const *d_outs,
+                                                              const uint32_t *out_sizes, const uint64_t *rects, const uint8_t *flips, uint32_t layout,
+                                                              uint32_t dtype, const float *scale, const float *bias, uint32_t filter, const float *colours,
+                                                              const xpnghip_view_blur *blurs, void *stream) {
+    std::string why;
+    if (!blur_filter_ok(filter, why)) return fail(why);
+    const bool cubic = filter == XPNGHIP_FILTER_CUBIC_AA;
+    XPNG_GUARDED(decode_views_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, nviews, view_image, d_outs, out_sizes, rects, flips, layout, dtype, scale, bias, cubic ? 0 : filter, colours, stream, cubic, blurs))
 }
 
 // ---- mixed-size batch encode (mixed.hpp) ---------------------------------------------------------

@@ -9,7 +9,8 @@ MixedContext.decode_batch_resized when an output size is asked for: the same pas
 MixedContext.decode_batch_resampled when that resize is to antialias).
 `load_views` gives any number of crops per file from ONE decode of it, and decodes only the tiles they touch
 (MixedContext.decode_batch_views); with colour= every view also gets a colour matrix of its own in the same pass (colour_matrix,
-random_colour_jitter).
+random_colour_jitter), and with blur= and solarise= a Gaussian blur and a solarise of its own in a second kernel of that call
+(MixedContext.decode_batch_views_blur; random_gaussian_blur, random_solarise).
 api.py stays free of torch; this module is the only one of the package that imports it at load time."""
 from __future__ import annotations
 
@@ -350,7 +351,8 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
 
 
 def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool = False, device=None, dtype=torch.float16, mean=None,
-               std=None, antialias: bool = True, stack: bool = False, out=None, colour=None, interpolation: str = "bilinear"):
+               std=None, antialias: bool = True, stack: bool = False, out=None, colour=None, interpolation: str = "bilinear", blur=None,
+               solarise=None):
     """Any number of views per file, each decoded once: views is a list of (path_index, rect_or_None, flip) - rect = (x, y, w, h)
     inside file path_index, None for the whole image; flip True mirrors left to right - and view v comes back as a tensor
     (C, OH_v, OW_v) for layout "chw" or (OH_v, OW_v, C) for "hwc", in view order.  size is one (OH, OW) for every view or one pair
@@ -385,7 +387,19 @@ def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool
     antialias is another kernel (a = -0.75) with another border rule, and is not offered.  Every device call is then ONE
     MixedContext.decode_batch_views_cubic and view v equals, bit for bit, api.resample_cubic_host with its matrix, which also
     answers level-7 and single-colour files; here an identity matrix and no matrix give the same bits.  "bilinear" (the
-    default) runs exactly the calls the function ran without the argument."""
+    default) runs exactly the calls the function ran without the argument.
+
+    blur and solarise are the two augmentations of SimCLR, BYOL and DINO that are not linear per pixel; both sit between the colour
+    matrix and the normalisation.  blur is None or one entry per view, each None or (sigma, kernel_size) with kernel_size odd, 3 ..
+    63 and below twice the view's smaller side: a Gaussian blur of kernel_size taps per axis over a reflected border, on the colour
+    channels (alpha is not blurred), clamped to 0 .. 255 - torchvision's GaussianBlur on tensors up to the order of summation
+    (tests/test_views_blur.py states the measured difference), not PIL's ImageFilter.GaussianBlur, which is a box-blur
+    approximation.  solarise is None or one entry per view, each None or a threshold in 0 .. 255: a colour value b at or above it
+    becomes 255 - b (torchvision's solarize in byte units).  random_gaussian_blur and random_solarise draw such lists.  With either
+    list given - with both interpolations - every device call is ONE MixedContext.decode_batch_views_blur: views that ask for
+    neither are written as before, the others take a second kernel over fp32 planes in the context's workspace; view v equals,
+    bit for bit, api.resample_blur_host, which also answers level-7 and single-colour files.  With both None the function runs
+    exactly the calls it ran without the arguments."""
     if layout not in ("chw", "hwc"):
         raise XpngError(f"load_views: layout must be 'chw' or 'hwc', not {layout!r}")
     if channels not in (None, 3, 4):
@@ -431,6 +445,33 @@ def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool
         cols = [None if m is None else api._colour12(f"load_views: colour[{v}]", m) for v, m in enumerate(cols)]
         if any(m is not None for m in cols):                           # beside a matrix, None is the identity MATRIX: every view is clamped
             cols = [list(api.COLOUR_IDENTITY) if m is None else m for m in cols]
+    blurs = None
+    if blur is not None or solarise is not None:
+        bl, so = ([None] * V if x is None else list(x) for x in (blur, solarise))
+        for name, x in (("blur", bl), ("solarise", so)):
+            if len(x) != V:
+                raise XpngError(f"load_views: {name} has {len(x)} entries for {V} views: one entry (or None) per view")
+        blurs = []
+        for v, (b, t) in enumerate(zip(bl, so)):
+            sigma, radius = 0.0, 0
+            if b is not None:
+                try:
+                    sigma, ks = float(b[0]), int(b[1])
+                    if len(b) != 2 or ks != b[1]:
+                        raise ValueError
+                except (TypeError, ValueError, IndexError):
+                    raise XpngError(f"load_views: blur[{v}] is {b!r}, not None or (sigma, kernel_size)") from None
+                if ks < 3 or ks > 63 or ks % 2 == 0:
+                    raise XpngError(f"load_views: the kernel_size of blur[{v}] is {ks}: it must be odd and 3 .. 63")
+                radius = ks // 2
+            if t is not None:
+                try:
+                    t = float(t)
+                except (TypeError, ValueError):
+                    raise XpngError(f"load_views: solarise[{v}] is {t!r}, not None or a threshold in 0 .. 255") from None
+                if not 0.0 <= t <= 255.0:
+                    raise XpngError(f"load_views: solarise[{v}] is {t!r}, not None or a threshold in 0 .. 255")
+            blurs.append(None if b is None and t is None else (sigma, radius, t))
     dev = torch.device("cuda" if device is None else device)
     if dev.type == "cuda" and not torch.cuda.is_available():
         raise XpngError("load_views: no GPU is visible (device='cpu' answers level-7 and single-colour files without one)")
@@ -488,7 +529,10 @@ def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool
             if vi != i:
                 continue
             word = api.layout(planar=layout == "chw", bgr=bgr, channels=chans[v])
-            if cubic:
+            if blurs is not None:
+                raw = api.resample_blur_host(ras, sizes[v], word, dt, *cache[chans[v]], rect=r, flip=f, filter=api.FILTER_CUBIC_AA if cubic else filt,
+                                             colour=cols[v], blur=blurs[v])
+            elif cubic:
                 raw = api.resample_cubic_host(ras, sizes[v], word, dt, *cache[chans[v]], rect=r, flip=f, colour=cols[v])
             else:
                 raw = api.resample_colour_host(ras, sizes[v], word, dt, *cache[chans[v]], rect=r, flip=f, filter=filt, colour=cols[v])
@@ -523,7 +567,9 @@ def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool
                     kw = dict(rects=[views[v][1] or (0, 0, heads[views[v][0]][1], heads[views[v][0]][2]) for v in mine],
                               flips=[views[v][2] for v in mine],
                               colours=[cols[v] for v in mine] if cols[mine[0]] is not None else None)
-                    if cubic:
+                    if blurs is not None:
+                        ctx.decode_batch_views_blur(*args, filter=api.FILTER_CUBIC_AA if cubic else filt, blurs=[blurs[v] for v in mine], **kw)
+                    elif cubic:
                         ctx.decode_batch_views_cubic(*args, **kw)
                     else:
                         ctx.decode_batch_views(*args, filter=filt, **kw)
@@ -612,6 +658,43 @@ def random_colour_jitter(n, brightness=0.4, contrast=0.4, saturation=0.4, hue=0.
             M = _compose64(M, _colour64(1.0, 1.0, 0.0, 0.0))
         out.append(M.astype(np.float32))
     return out
+
+
+def random_gaussian_blur(n, kernel_size=23, sigma=(0.1, 2.0), p=0.5, generator=None):
+    """n entries for load_views(blur=...), one per view, drawn as SimCLR's, BYOL's and DINO's GaussianBlur draws its parameter: with
+    probability p the pair (sigma, kernel_size) with sigma uniform in [sigma[0], sigma[1]], otherwise None.  kernel_size is odd and
+    3 .. 63 (23 is BYOL's and DINO's for 224 x 224; SimCLR takes a tenth of the side, made odd); a multi-crop caller draws one
+    list per view size with its own kernel_size and p (DINO: p = 1.0 and 0.1 for the two global views, 0.5 for the local ones).
+    A pure host function; with a seeded torch.Generator the list is reproducible."""
+    n, ks = int(n), int(kernel_size)
+    if n < 0:
+        raise XpngError(f"random_gaussian_blur: n is {n}")
+    if ks != kernel_size or ks < 3 or ks > 63 or ks % 2 == 0:
+        raise XpngError(f"random_gaussian_blur: kernel_size must be odd and 3 .. 63, not {kernel_size!r}")
+    try:
+        lo, hi = (float(x) for x in sigma)
+    except (TypeError, ValueError):
+        raise XpngError(f"random_gaussian_blur: sigma must be (low, high), not {sigma!r}") from None
+    if not 2.0 ** -10 <= lo <= hi <= 1024.0:
+        raise XpngError(f"random_gaussian_blur: sigma must satisfy 2^-10 <= low <= high <= 1024, not {sigma!r}")
+    if not 0.0 <= float(p) <= 1.0:
+        raise XpngError(f"random_gaussian_blur: p must be within 0 .. 1, not {p!r}")
+    u = torch.rand((n, 2), dtype=torch.float64, generator=generator).tolist()   # one draw whatever the outcomes: entry k depends on row k alone
+    return [(lo + (hi - lo) * us, ks) if coin < p else None for (coin, us) in u]
+
+
+def random_solarise(n, threshold=128, p=0.2, generator=None):
+    """n entries for load_views(solarise=...), one per view: with probability p the threshold (0 .. 255, in byte units; 128 is
+    BYOL's and DINO's), otherwise None.  A pure host function; with a seeded torch.Generator the list is reproducible."""
+    n = int(n)
+    if n < 0:
+        raise XpngError(f"random_solarise: n is {n}")
+    if not 0.0 <= float(threshold) <= 255.0:
+        raise XpngError(f"random_solarise: threshold must be within 0 .. 255, not {threshold!r}")
+    if not 0.0 <= float(p) <= 1.0:
+        raise XpngError(f"random_solarise: p must be within 0 .. 1, not {p!r}")
+    u = torch.rand((n,), dtype=torch.float64, generator=generator).tolist()
+    return [float(threshold) if coin < p else None for coin in u]
 
 
 def _inverse_scale_bias(mean, std, present):
