@@ -169,42 +169,27 @@ __device__ inline void rans_tables(uint32_t *hist, uint32_t *cum, EncSym *tab, u
 
 }
 
-// Encode one block.  `in` = symbol bytes (global), n = count, nominalN = 9 or 256, pb = 12 or 15,
-// out = 4-byte aligned global buffer with the capacity of common.hpp.  Returns the block size in bytes
-// (uniform across the wave).  Must be called by all 64 lanes of a single-wave workgroup.
-// LDS: hist[256], cum[257], tab[256].
-__device__ inline uint32_t rans2_encode_block(const uint8_t *__restrict__ in, uint32_t n, uint32_t nominalN, int pb,
-                                              uint8_t *__restrict__ out8, uint32_t *hist, uint32_t *cum, EncSym *tab,
-                                              uint64_t *stamp = nullptr) {
+// LDS of the recurrence beside the encoder table: the ring of spilled words and the symbol ring (2 KB + its 16-byte mirror)
+constexpr uint32_t ENC_RING_WORDS = 512, ENC_SRING_BYTES = 2048 + 16;
+
+// ---- the recurrence (libxpng.c:362-392) of one block whose encoder table `tab` is in LDS: the symbols in[0..n) through both
+// states, the spilled words to w[0..cnt); on return s is this lane's final state (lane 0: state0, lane 1: state1) and cnt the
+// word count (uniform).  Even lanes run state0 (even symbols), odd lanes state1 (odd
+// symbols); lanes 2..63 replicate lanes 0/1 so the loop has no per-lane validity masks (they never write).
+//  * symbols: each lane walks its own stride-2 byte sequence through a 64-bit register window (4 symbols)
+//    backed by two prefetched 8-byte chunks, so no global-load latency sits in the loop;
+//  * table entries: fetched three steps ahead of the state update (rotating registers), so the LDS latency is
+//    off the dependent chain, which is only: spill test -> 64x64 mulhi -> shift -> mad;
+//  * spilled words: positions come from a 2-bit ballot (state0's word before state1's, as the reference emits
+//    them), so the cursor is a scalar; words are staged in an LDS ring and flushed 256 at a time, coalesced.
+// Two callers - rans2_encode_block (k_rans2_encode: the whole block) and the narrow alpha role of k_rans2_chain_all (rans2_wide.hpp:
+// the recurrence alone, between k_rans2_prep and k_rans2_finish) - so it is always_inline: left to the compiler, a second caller
+// turned the hand-scheduled loop into a function call (tile_container.hpp, k_rans2_encode).  The two rings come from the caller:
+// static arrays in rans2_encode_block, a piece of the launch's dynamic LDS in the role.
+__device__ __attribute__((always_inline)) inline void rans2_encode_chain(const uint8_t *__restrict__ in, const uint32_t n, const int pb,
+                                                                         const EncSym *tab, uint32_t *w, uint32_t *const ring,
+                                                                         uint8_t *const sring, uint64_t &s_out, uint32_t &cnt_out) {
     const uint32_t lane = threadIdx.x & 63;
-    uint32_t *out = reinterpret_cast<uint32_t *>(out8);
-    if (n == 0) {  // libxpng.c:313
-        if (lane == 0) out[0] = 4;
-        return 4;
-    }
-#define XPNG_STAMP(k) do { if (stamp && lane == 0) stamp[k] = __builtin_readcyclecounter(); } while (0)
-    XPNG_STAMP(0);
-    rans_histogram(in, n, hist);
-    XPNG_STAMP(1);
-    uint32_t top, distinct;
-    rans_alphabet(hist, nominalN, top, distinct);
-    const uint32_t N = top + 1, rawBits = (uint32_t)bit_width(top);
-    if (distinct == 1) {  // libxpng.c:318
-        if (lane == 0) { out[0] = 8u | (1u << 24); out[1] = n | ((uint32_t)in[0] << 24); }
-        return 8;
-    }
-    rans_tables(hist, cum, tab, N, n, pb);
-    XPNG_STAMP(2);
-    // ---- the recurrence (libxpng.c:362-392).  Even lanes run state0 (even symbols), odd lanes state1 (odd
-    // symbols); lanes 2..63 replicate lanes 0/1 so the loop has no per-lane validity masks (they never write).
-    //  * symbols: each lane walks its own stride-2 byte sequence through a 64-bit register window (4 symbols)
-    //    backed by two prefetched 8-byte chunks, so no global-load latency sits in the loop;
-    //  * table entries: fetched three steps ahead of the state update (rotating registers), so the LDS latency is
-    //    off the dependent chain, which is only: spill test -> 64x64 mulhi -> shift -> mad;
-    //  * spilled words: positions come from a 2-bit ballot (state0's word before state1's, as the reference emits
-    //    them), so the cursor is a scalar; words are staged in an LDS ring and flushed 256 at a time, coalesced.
-    uint32_t *w = out + 3;
-    __shared__ uint32_t ring[512];
     const uint32_t par = lane & 1;
     const uint32_t cmpl_base = 1u << pb;
     const int thr_shift = 31 - pb;
@@ -220,7 +205,6 @@ __device__ inline uint32_t rans2_encode_block(const uint8_t *__restrict__ in, ui
         //   * the renormalisation (spill test -> ring store -> shift) sits behind a wave-uniform branch that skewed streams
         //     take once in tens of steps, so the common step is: decode entry, compare, 64x64 high multiply, shift, mad;
         //   * ring flush and unit refill are checked once per 128 steps, outside the straight-line loop.
-        __shared__ __align__(16) uint8_t sring[2048 + 16];
         const uint8_t *inA = reinterpret_cast<const uint8_t *>((uintptr_t)in & ~(uintptr_t)15);
         const uint32_t p0 = (uint32_t)((uintptr_t)in & 15);  // ring position of symbol 0
         const uint4 *src = reinterpret_cast<const uint4 *>(inA) + lane;
@@ -335,6 +319,41 @@ __device__ inline uint32_t rans2_encode_block(const uint8_t *__restrict__ in, ui
         __syncthreads();
         for (uint32_t i = flushed + lane; i < cnt; i += 64) w[i] = ring[i & 511u];
     }
+    s_out = s; cnt_out = cnt;
+}
+
+// Encode one block.  `in` = symbol bytes (global), n = count, nominalN = 9 or 256, pb = 12 or 15,
+// out = 4-byte aligned global buffer with the capacity of common.hpp.  Returns the block size in bytes
+// (uniform across the wave).  Must be called by all 64 lanes of a single-wave workgroup.
+// LDS: hist[256], cum[257], tab[256].
+__device__ inline uint32_t rans2_encode_block(const uint8_t *__restrict__ in, uint32_t n, uint32_t nominalN, int pb,
+                                              uint8_t *__restrict__ out8, uint32_t *hist, uint32_t *cum, EncSym *tab,
+                                              uint64_t *stamp = nullptr) {
+    const uint32_t lane = threadIdx.x & 63;
+    uint32_t *out = reinterpret_cast<uint32_t *>(out8);
+    if (n == 0) {  // libxpng.c:313
+        if (lane == 0) out[0] = 4;
+        return 4;
+    }
+#define XPNG_STAMP(k) do { if (stamp && lane == 0) stamp[k] = __builtin_readcyclecounter(); } while (0)
+    XPNG_STAMP(0);
+    rans_histogram(in, n, hist);
+    XPNG_STAMP(1);
+    uint32_t top, distinct;
+    rans_alphabet(hist, nominalN, top, distinct);
+    const uint32_t N = top + 1, rawBits = (uint32_t)bit_width(top);
+    if (distinct == 1) {  // libxpng.c:318
+        if (lane == 0) { out[0] = 8u | (1u << 24); out[1] = n | ((uint32_t)in[0] << 24); }
+        return 8;
+    }
+    rans_tables(hist, cum, tab, N, n, pb);
+    XPNG_STAMP(2);
+    uint32_t *w = out + 3;
+    __shared__ uint32_t ring[ENC_RING_WORDS];
+    __shared__ __align__(16) uint8_t sring[ENC_SRING_BYTES];
+    uint64_t s;
+    uint32_t cnt;
+    rans2_encode_chain(in, n, pb, tab, w, ring, sring, s, cnt);  // the recurrence (libxpng.c:362-392)
     w += cnt;
     if (lane < 2) { w[2 * lane] = (uint32_t)s; w[2 * lane + 1] = (uint32_t)(s >> 32); }  // state0, state1 (libxpng.c:394)
     w += 4;

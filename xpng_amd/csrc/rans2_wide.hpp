@@ -7,8 +7,9 @@
 //   k_rans2_prep    wave per (tile, stream): histogram -> alphabet -> tables (rans_* helpers of rans2.hpp); empty and
 //                   one-symbol blocks are finished on the spot; otherwise the encoder table and the normalised
 //                   frequencies go to global memory
-//   k_rans2_chain2  lane = one rANS state; a wave carries the same stream class of 16 (alpha) or 32 (context) tiles, so the
-//                   chains of one wave have similar lengths; block-synchronous (see the kernel)
+//   k_rans2_chain_all  lane = one rANS state; a wave carries the same stream class (alpha, or context c) of 32 tiles, so the
+//                   chains of one wave have similar lengths; block-synchronous (rans2_chain2_body).  The alpha streams of the
+//                   launch's biggest tiles (the top class, top_class_cut.hpp) have a wavefront each instead (rans2_chain1_body)
 //   k_rans2_finish  wave per (tile, stream): states, header, frequency table, type-2 (raw) fallback
 #pragma once
 #include "common.hpp"
@@ -37,21 +38,23 @@ __host__ __device__ inline uint64_t watab_bytes(uint64_t streams) { return ((str
 //  over the kernels of a pipelined step is what the step time tracks, and 162 waves x 37 KB x 26 ms was the
 //  second largest item of that sum.)
 
-// streams [c_first, c_first + c_count) of every tile (the alpha streams, c = 9, are prepared and chained while the stream-
-// formation kernel is still producing the context streams: they only need the transform's alpha plane)
-// (j0: the launch covers work items j0 .. of the enumeration - the alpha streams of the biggest tiles may be coded elsewhere, see
-//  k_rans2_encode, tile_container.hpp)
+// streams [c_first, c_first + c_count) of every tile: ONE launch over all ten (nine for RGB) behind the routing kernel, on the
+// caller's stream (through round 4 the alpha streams, which only need the transform's alpha plane, were prepared and chained on
+// a side stream while the routing kernel was still producing the context streams)
+// (n1: the alpha streams of work items [0, n1) - the top class, top_class_cut.hpp - are chained a wavefront each by the narrow role of
+//  k_rans2_chain_all, which takes a stream's table whole into LDS: theirs is left in the plain per-tile layout, at the head of the
+//  tile's share of wtab, and the interleaved groups of the wide alpha role count from work item n1)
 __global__ __launch_bounds__(64) void k_rans2_prep(const TileDesc *__restrict__ tiles, TileSel sel, uint32_t c_first, uint32_t c_count,
                                                    const uint8_t *__restrict__ planes, uint64_t plane_stride,
                                                    uint8_t *__restrict__ scratch, const uint32_t *__restrict__ ctx_n,
                                                    uint32_t *__restrict__ blk_sz, WPrep *__restrict__ prep,
-                                                   uint8_t *__restrict__ wtab, uint16_t *__restrict__ wF, uint32_t j0,
+                                                   uint8_t *__restrict__ wtab, uint16_t *__restrict__ wF, uint32_t n1,
                                                    uint8_t *__restrict__ watab) {
     bw_prio();
     __shared__ uint32_t hist[256];
     __shared__ uint32_t cum[260];
     __shared__ EncSym tab[256];
-    const uint32_t tile = vtile(sel, j0 + blockIdx.x / c_count), c = c_first + blockIdx.x % c_count, lane = threadIdx.x & 63;
+    const uint32_t tile = vtile(sel, blockIdx.x / c_count), c = c_first + blockIdx.x % c_count, lane = threadIdx.x & 63;
     const TileDesc t = tiles[tile];
     uint8_t *sc = scratch + t.sbase;
     const uint8_t *in;
@@ -79,8 +82,8 @@ __global__ __launch_bounds__(64) void k_rans2_prep(const TileDesc *__restrict__ 
     rans_tables(hist, cum, tab, N, n, pb);
     EncSym *gt = reinterpret_cast<EncSym *>(wtab + (uint64_t)tile * WTAB_TILE_BYTES + wtab_off(c));
     uint16_t *gF = wF + ((uint64_t)tile * 10 + c) * 256;
-    if (c == 9) {  // (alpha: the launch's interleaved layout; the stream's place in it is its work-item index, as the chain kernel counts it)
-        const uint32_t jr = blockIdx.x / c_count;
+    if (c == 9 && blockIdx.x / c_count >= n1) {  // (alpha: the launch's interleaved layout; the stream's place in it is its work-item index behind the top class, as the wide alpha role counts it)
+        const uint32_t jr = blockIdx.x / c_count - n1;
         gt = reinterpret_cast<EncSym *>(watab + (uint64_t)(jr >> 5) * WATAB_GROUP_BYTES + (jr & 31u) * 16u);
         for (uint32_t i = lane; i < N; i += 64) { gt[i * 32u] = tab[i]; gF[i] = (uint16_t)hist[i]; }
     } else {
@@ -301,18 +304,59 @@ __global__ __launch_bounds__(64) void k_rans2_chain2(const TileDesc *__restrict_
                                                      const uint8_t *__restrict__ watab) {
     rans2_chain2_body<BIG>(tiles, sel, total, planes, plane_stride, scratch, ctx_n, prep, wtab, j0, watab, blockIdx.x);
 }
-// Both classes of a batched RGBA encode in ONE launch: workgroups [0, agroups) are the alpha chains - the longest, so they are
-// dispatched first - and the context chains follow.  The two classes ran beside each other on two streams through round 4; as
-// two ranges of one grid they still run beside each other on the chip and hold one hardware queue for the longer of the two,
-// not two queues for the sum.  The role branch is uniform over the (single-wavefront) workgroup.
-constexpr size_t chain_all_lds_bytes() { return chain2_lds_bytes<true>() > chain2_lds_bytes<false>() ? chain2_lds_bytes<true>() : chain2_lds_bytes<false>(); }
+// The narrow alpha role: ONE wavefront, ONE stream - the alpha stream of work item j - between k_rans2_prep and k_rans2_finish like
+// a lane pair of the wide role: it takes the stream's encoder table (the plain 4 KB layout k_rans2_prep left at the head of the tile's
+// share of wtab; entries past the alphabet are never indexed) into LDS, runs the recurrence of the single-image encoder
+// (rans2_encode_chain, rans2.hpp: scalar cursors, symbol ring, ring of spilled words - about 176 cycles a step against 270-400 of a
+// lane pair) and leaves what rans2_chain2_body<true> leaves: the words behind the block's three header words, the two final states
+// and the word count in the stream's WPrep.  Dynamic LDS: the table and the two rings, nothing of the whole-block encoder's
+// histograms (chain1_lds_bytes: less than a context workgroup of the same launch holds).
+constexpr size_t chain1_lds_bytes() { return 256 * sizeof(EncSym) + ENC_RING_WORDS * 4 + ENC_SRING_BYTES; }
+__device__ __attribute__((always_inline)) inline void rans2_chain1_body(const TileDesc *__restrict__ tiles, TileSel sel,
+                                                     const uint8_t *__restrict__ planes, uint64_t plane_stride,
+                                                     uint8_t *__restrict__ scratch, WPrep *__restrict__ prep,
+                                                     const uint8_t *__restrict__ wtab, const uint32_t j) {
+    extern __shared__ __align__(16) uint8_t chain1_lds[];
+    EncSym *const tab = reinterpret_cast<EncSym *>(chain1_lds);                                               // [256]
+    uint32_t *const ring = reinterpret_cast<uint32_t *>(chain1_lds + 256 * sizeof(EncSym));                    // [ENC_RING_WORDS]
+    uint8_t *const sring = chain1_lds + 256 * sizeof(EncSym) + ENC_RING_WORDS * 4;                             // [ENC_SRING_BYTES], 16-byte aligned
+    __builtin_amdgcn_s_setprio(XPNG_CHAIN_PRIO);
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t tile = vtile(sel, j);
+    WPrep *p = prep + (uint64_t)tile * 10 + 9;
+    if (sgpr(p->kind) != 1) return;  // (empty and one-symbol blocks: k_rans2_prep has finished them)
+    const TileDesc t = tiles[tile];
+    const uint4 *src = reinterpret_cast<const uint4 *>(wtab + (uint64_t)tile * WTAB_TILE_BYTES);
+    for (uint32_t i = lane; i < 256; i += 64) reinterpret_cast<uint4 *>(tab)[i] = src[i];
+    __syncthreads();
+    uint32_t *w = reinterpret_cast<uint32_t *>(scratch + t.sbase + off_blk(t.n, nullptr, 9)) + 3;  // (the alpha block's place does not depend on the context lengths)
+    uint64_t s;
+    uint32_t cnt;
+    rans2_encode_chain(planes + 4 * plane_stride + t.pbase + 1, t.n - 1, 15, tab, w, ring, sring, s, cnt);
+    if (lane < 2) p->st[lane] = s;
+    if (lane == 0) p->cnt = cnt;
+}
+
+// Both classes of a batched RGBA encode in ONE launch: the alpha chains - the longest, so they are dispatched first - and the context
+// chains behind them.  The two classes ran beside each other on two streams through round 4; as ranges of one grid they still run
+// beside each other on the chip and hold one hardware queue for the longer of the two, not two queues for the sum.
+// The alpha class is two roles: workgroups [0, n1) carry the alpha stream of one work item each (rans2_chain1_body: the top class of
+// the size-sorted launch, top_class_cut.hpp - a launch lasts as long as its longest chain, and the biggest tiles' chains on a
+// wavefront of their own end when wide chains of two thirds their length end), workgroups [n1, n1 + agroups) 32 each of the work
+// items from n1 on.  The role branch is uniform over the (single-wavefront) workgroup; every role is independent of every other.
+constexpr size_t chain_all_lds_bytes() {
+    size_t m = chain2_lds_bytes<true>() > chain2_lds_bytes<false>() ? chain2_lds_bytes<true>() : chain2_lds_bytes<false>();
+    return chain1_lds_bytes() > m ? chain1_lds_bytes() : m;
+}
+static_assert(chain1_lds_bytes() == 8208 && chain_all_lds_bytes() == 9728, "dynamic LDS of k_rans2_chain_all: the context role's, as before the narrow alpha role");
 __global__ __launch_bounds__(64) void k_rans2_chain_all(const TileDesc *__restrict__ tiles, TileSel sel, uint32_t total,
                                                         const uint8_t *__restrict__ planes, uint64_t plane_stride,
                                                         uint8_t *__restrict__ scratch, const uint32_t *__restrict__ ctx_n,
                                                         WPrep *__restrict__ prep, const uint8_t *__restrict__ wtab,
-                                                        const uint8_t *__restrict__ watab, uint32_t agroups) {
-    if (blockIdx.x < agroups) rans2_chain2_body<true>(tiles, sel, total, planes, plane_stride, scratch, ctx_n, prep, wtab, 0, watab, blockIdx.x);
-    else rans2_chain2_body<false>(tiles, sel, total, planes, plane_stride, scratch, ctx_n, prep, wtab, 0, watab, blockIdx.x - agroups);
+                                                        const uint8_t *__restrict__ watab, uint32_t n1, uint32_t agroups, uint32_t aj0) {
+    if (blockIdx.x < n1) rans2_chain1_body(tiles, sel, planes, plane_stride, scratch, prep, wtab, blockIdx.x);
+    else if (blockIdx.x < n1 + agroups) rans2_chain2_body<true>(tiles, sel, total, planes, plane_stride, scratch, ctx_n, prep, wtab, aj0, watab, blockIdx.x - n1);  // (aj0 = n1, except in a probe build with the narrow role knocked out)
+    else rans2_chain2_body<false>(tiles, sel, total, planes, plane_stride, scratch, ctx_n, prep, wtab, 0, watab, blockIdx.x - n1 - agroups);
 }
 
 __global__ __launch_bounds__(64) void k_rans2_finish(const TileDesc *__restrict__ tiles, TileSel sel, uint32_t spt,

@@ -14,14 +14,14 @@ namespace xpng {
 // Stream c < 9: context stream c, alphabet 9, PROB_BITS 12.  Stream 9 (RGBA): alpha symbols = plane `a`
 // from index 1, alphabet 256, PROB_BITS 15.      grid = work items * c_count, block = 64: streams [c_first, c_first + c_count)
 // of the first grid / c_count work items of the enumeration.
-// Two uses.  (1) A few tiles (one image): every stream of every tile, the whole entropy stage of the encode.  (2) Beside the wide
-// form of a batch [r4]: ONE stream class - alpha, c_first = 9 - of the first work items of the size-sorted enumeration, i.e. of the
-// biggest tiles.  A wide chain kernel lasts as long as its longest chain and a lane-per-state step takes ~400 cycles against ~176
-// here: with the alpha streams of the biggest size class (>= 3/4 of the largest tile: 17 of a 4096^2 image's 81) a wavefront each,
-// the wide launch of the rest ends with the 444 x 444 tiles' chains - two thirds of the longest.  The block is final when this
-// kernel is done (header, states, table, raw fallback): prep[] (when given) says so and k_rans2_finish leaves it alone.
-// (ONE kernel for both uses: with two callers the compiler stops inlining rans2_encode_block and its hand-scheduled loop becomes a
-//  function call - the single-image encode went from 11.5 to 14.7 ms when a second kernel called it.)
+// One use: a few tiles (one image) - every stream of every tile, the whole entropy stage of the encode.  The block is final when this
+// kernel is done (header, states, table, raw fallback).  (Round 4 also ran it beside the wide form of a batch, on a third stream, for
+// the alpha streams of the biggest size class - 17 of a 4096^2 image's 81 tiles - and lost: DESIGN.md 6.2.  `prep` is what is left
+// of that: a launch that passes the WPrep table marks its blocks final there; every launch of this tree passes nullptr.  What the
+// batch form has now is the recurrence alone, rans2_encode_chain, as a role of k_rans2_chain_all for the top class: rans2_wide.hpp.)
+// (With two callers the compiler stopped inlining rans2_encode_block and its hand-scheduled loop became a function call - the
+//  single-image encode went from 11.5 to 14.7 ms when a second kernel called it: the loop is an always_inline function of its own
+//  since, and this kernel's code is what it was - profiles/device_code_top_class.txt.)
 __global__ __launch_bounds__(64) void k_rans2_encode(const TileDesc *__restrict__ tiles, TileSel sel, uint32_t c_first, uint32_t c_count,
                                                      const uint8_t *__restrict__ planes, uint64_t plane_stride,
                                                      uint8_t *__restrict__ scratch, const uint32_t *__restrict__ ctx_n,

@@ -28,6 +28,7 @@
 #include "rans1_wide.hpp"
 #include "rans1_wide_dec.hpp"
 #include "tile_container.hpp"
+#include "top_class_cut.hpp"
 #include "region.hpp"
 #include "mixed.hpp"
 #include "mixed_float.hpp"
@@ -153,6 +154,7 @@ struct xpnghip_ctx {
     // decode keeps its own pair of tables: a caller that alternates encode and decode on one context (a pipeline) would
     // otherwise re-upload, and synchronise its stream, on every call
     uint32_t *d_order = nullptr;          // tile indices of [r0, r1) by decreasing pixel count (TileSel::order)
+    std::vector<uint32_t> order_n;        // ... and their pixel counts in that order (what top_class_cut reads)
     // ONE side stream per context, created by the first call that forks (dec_launch): the alpha branch of a narrow level-1 RGBA decode
     // and the big-alphabet chains of a level-2 decode run on it (DecodeWs::side borrows it).  The batched level-1 forms and every
     // encode stay on the caller's stream: every stream alive takes a share of the runtime's hardware queues
@@ -325,6 +327,7 @@ static int ctx_create_range_impl(xpnghip_ctx **out, int device, uint64_t w, uint
         for (uint64_t i = c->r0; i < c->r1; i++) ord.push_back((uint32_t)i);
         std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return c->tiles[a].n > c->tiles[b].n; });
         if (hipMemcpy(c->d_order, ord.data(), ord.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { xpnghip_ctx_destroy(c); return fail("context setup failed"); }
+        for (uint32_t i : ord) c->order_n.push_back(c->tiles[i].n);
     }
     c->stamps = c->d_dbg && probe_env("XPNG_STAMPS") != nullptr;  // (probe builds only)
 #ifdef XPNG_PROBES
@@ -545,13 +548,20 @@ static int launch_encode_m1(xpnghip_ctx *c, const EncSpan &e, hipStream_t s) {
         // every tile, and ONE chain launch whose grid holds the alpha class (RGBA) in front of the context classes
         // (k_rans2_chain_all, rans2_wide.hpp: why).  (Through round 4 the alpha streams were prepared and chained on a side stream
         // behind the transform, beside the routing kernel and the context chains.)
-        // (Size classes of the alpha chains - the biggest tiles' alpha streams a wavefront each on a third stream - LOST: DESIGN.md 6,
-        //  profiles/r04_experiments.txt.)
+        // (Size classes of the alpha chains on a THIRD STREAM - 17 of 81 tiles' alpha streams a wavefront each, whole blocks by
+        //  k_rans2_encode - lost in round 4: DESIGN.md 6, profiles/r04_experiments.txt.  The top class below is a range of the same
+        //  grid: no stream, no event, the largest tile class only.)
         // (probe builds: a knocked-out preparation narrows the launch to the other class; a knocked-out chain class gets no workgroups)
+        // The top class (top_class_cut.hpp): the alpha streams of the biggest tiles of a size-sorted launch - work items [0, n1) -
+        // get a wavefront each in front of the wide alpha groups, which carry the work items from n1 on; k_rans2_prep leaves their
+        // tables in the layout that role reads.  (probe builds: chain_a1 knocks the narrow role out, chain_a the wide one.)
+        uint32_t n1 = PXSZ == 4 && e.order && !c->mixed && !probe_env("XPNG_NO_TOP_CLASS") ? top_class_cut(c->order_n.data(), (uint32_t)c->order_n.size(), nimg) * nimg : 0u;
+        if (n1 >= total) n1 = 0;
         const uint32_t pa = PXSZ == 4 && !dbg_skip("prep_a") ? 1u : 0u, pc = dbg_skip("prep_c") ? 0u : 9u;
-        if (pa + pc) k_rans2_prep<<<total * (pa + pc), 64, 0, s>>>(c->d_tiles, sel, pc ? 0 : 9, pa + pc, planesA, c->plane_stride, c->d_scratch, c->d_ctx_n, c->d_blk_sz, c->d_wprep, c->d_wtab, c->d_wF, 0, watab);
-        const uint32_t agroups = PXSZ == 4 && !dbg_skip("chain_a") ? (total + 31) / 32 : 0u, cgroups = dbg_skip("chain_c") ? 0u : ((total + 31) / 32) * 9;
-        if (agroups + cgroups) k_rans2_chain_all<<<agroups + cgroups, 64, chain_all_lds_bytes() + probe_pad("XPNG_PAD_CHAIN"), s>>>(c->d_tiles, sel, total, planesA, c->plane_stride, c->d_scratch, c->d_ctx_n, c->d_wprep, c->d_wtab, watab, agroups);
+        if (pa + pc) k_rans2_prep<<<total * (pa + pc), 64, 0, s>>>(c->d_tiles, sel, pc ? 0 : 9, pa + pc, planesA, c->plane_stride, c->d_scratch, c->d_ctx_n, c->d_blk_sz, c->d_wprep, c->d_wtab, c->d_wF, n1, watab);
+        const uint32_t n1groups = dbg_skip("chain_a1") ? 0u : n1;
+        const uint32_t agroups = PXSZ == 4 && !dbg_skip("chain_a") ? (total - n1 + 31) / 32 : 0u, cgroups = dbg_skip("chain_c") ? 0u : ((total + 31) / 32) * 9;
+        if (n1groups + agroups + cgroups) k_rans2_chain_all<<<n1groups + agroups + cgroups, 64, chain_all_lds_bytes() + probe_pad("XPNG_PAD_CHAIN"), s>>>(c->d_tiles, sel, total, planesA, c->plane_stride, c->d_scratch, c->d_ctx_n, c->d_wprep, c->d_wtab, watab, n1groups, agroups, n1);
         if (!dbg_skip("finish")) k_rans2_finish<<<total * c->spt, 64, 0, s>>>(c->d_tiles, sel, c->spt, planesA, c->plane_stride, c->d_scratch, c->d_ctx_n, c->d_blk_sz, c->d_wprep, c->d_wF);
     }
     k_tile_sizes<<<(total + 255) / 256, 256, 0, s>>>(c->d_tiles, sel, total, PXSZ, c->spt, c->d_sums, c->d_k_n, c->d_blk_sz, c->d_tile_sz, c->d_tile_hdr);
