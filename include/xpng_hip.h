@@ -612,6 +612,79 @@ int xpnghip_decode_varsize_device_batch_views_blur(xpnghip_ctx *ctx, int mode, c
                                                    const float *scale, const float *bias, uint32_t filter, const float *colours,
                                                    const xpnghip_view_blur *blurs, void *stream);
 
+/* ---- an affine map per view in the copy-out of a views call ----------------------------------
+ * RandomRotation, RandomAffine, the rotate / shear / translate operations of RandAugment, AutoAugment and TrivialAugment, and the
+ * rotations of detection and segmentation pipelines with nearest-neighbour sampling for their label maps.  Every geometric
+ * operation above is an axis-aligned rectangle with an optional mirror; here a view has an inverse 2 x 3 matrix instead, which
+ * carries the crop, the size change, the mirror, the rotation and the shear at once, and one fill per call for what lies outside.
+ * THE RULE.  `affine` is 6 floats, row-major 2 x 3, from continuous OUTPUT coordinates to continuous SOURCE coordinates of the
+ * whole image; pixel (j, i) has its centre at (j + 0.5, i + 0.5).  For output pixel (ox, oy), X = (float)ox + 0.5f and
+ * Y = (float)oy + 0.5f:
+ *     sx = fmaf(m[0], X, fmaf(m[1], Y, m[2])) - 0.5f        this nesting; the subtraction is one fp32 operation
+ *     sy = fmaf(m[3], X, fmaf(m[4], Y, m[5])) - 0.5f
+ * THE FOOTPRINT F of a view, computed on the host in double from the fp32 entries: the source coordinates of the four corner output
+ * pixels (ox in {0, out_w-1}, oy in {0, out_h-1}; the map is affine, so the extremes are there),
+ *     F = [floor(min sx) - 1, floor(max sx) + 2] x [floor(min sy) - 1, floor(max sy) + 2]   intersected with the image; it may be empty.
+ * A TAP q(j, i, c) is the image's byte as fp32 where (j, i) lies inside F, and fill[k] everywhere else, k the colour R, G, B or A
+ * of that channel.  `fill` is 4 floats in byte units, each finite and within 0 .. 255; NULL means zeros.  The test is made on the
+ * integer tap, so no tap leaves F by construction; and F contains every tap that exact arithmetic would place inside the image,
+ * because the entry bounds below keep the fp32 error of sx and sy below 0.1 against F's margin of one whole pixel.  The alpha an
+ * RGB context lacks is still v = 255 exactly, with no read.
+ *     filter XPNGHIP_FILTER_BILINEAR (0)    x0 = floorf(sx)  lx = sx - x0    y0 = floorf(sy)  ly = sy - y0
+ *         t = fmaf(lx, q(x0+1, y0)   - q(x0, y0),   q(x0, y0))
+ *         u = fmaf(lx, q(x0+1, y0+1) - q(x0, y0+1), q(x0, y0+1))
+ *         v = fmaf(ly, u - t, t)
+ *       which is torchvision's tensor affine() with `fill`, i.e. grid_sample(padding_mode="zeros", align_corners=False) blended
+ *       with a mask;
+ *     filter XPNGHIP_FILTER_NEAREST (3)     v = q((int)rintf(sx), (int)rintf(sy)), ties to even: grid_sample's rule.
+ * The fourth filter word is accepted ONLY by the functions of this section, and they accept 0 and 3 only. */
+#define XPNGHIP_FILTER_NEAREST 3u
+/* Behind v everything is the views-colour rule, unchanged: the optional 3 x 4 matrix and its clamp, y = fmaf(v_or_t, scale[c],
+ * bias[c]), out = (T)y, the BGR exchange, alpha last, the layouts and the dtypes.
+ * ENTRY BOUNDS.  Every entry finite, and |m[0]| * out_w, |m[1]| * out_h, |m[2]| (and the same of the second row) each at most
+ * 2^18 = 262144.  Every source coordinate of the view and every intermediate of the rule then stays below 2^20 in magnitude -
+ * inside the 2^22 at which a view must be refused -, an fp32 operation there errs by at most 2^-5, and three of them by less than
+ * 0.1 of a pixel.  Anything else is refused before anything is written; the text names the entry (and, in the device call, the view).
+ * Consequences: (a) the matrix {1, 0, x, 0, 1, y} with integer x, y and the view inside the image is a pure crop, bit for bit the
+ * slice of the float call, under both filters: sx is an integer, lx = 0 and fmaf(0, d, q) = q; (b) an exact quarter turn - entries
+ * 0 and +-1, constants integers or half-integers that put sx, sy on integers - is bit for bit np.rot90 of the crop, and the mirror
+ * matrix {-1, 0, x + w, 0, 1, y} gives the bits of the flip; (c) no tap leaves F; (d) a view whose F is empty is all fill, then
+ * the matrix and the constants, and it selects no tile.
+ * Not offered: antialiasing under a shrinking map (torchvision has none either); bicubic under a warp; blur or solarise in the same
+ * call; perspective maps; uint8 outputs; a fill per view.
+ * host-only, needs no device: the footprint of one view over a w x h image as rect = {x, y, w, h} ({0, 0, 0, 0}: empty).  Returns 1,
+ * with the text, for a bad image size, output size or matrix. */
+int xpnghip_affine_footprint(uint64_t w, uint64_t h, const float *affine, uint32_t out_w, uint32_t out_h, uint64_t *rect);
+/* host-only, needs no device, and it is the rule.  No rect and no flip: the matrix carries both.  filter is 0 or 3; fill and colour
+ * may be NULL.  Refuses, in this order and with nothing written: the filter; everything xpnghip_resample_colour_host refuses of its
+ * other arguments, with the same texts; the matrix; the fill; the colour matrix. */
+int xpnghip_resample_affine_host(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const float *affine, uint32_t out_w,
+                                 uint32_t out_h, uint32_t layout, uint32_t dtype, const float *scale, const float *bias,
+                                 uint32_t filter, const float *fill, const float *colour, void *out);
+/* host-only, needs no device: the launch list of an affine views call, the sibling of xpnghip_view_tiles.  affines is nviews * 6
+ * floats, out_sizes nviews pairs.  A tile is listed if and only if it intersects the footprint of at least one view of its image
+ * (region_select's test on the footprints; an empty footprint selects nothing); the order is xpnghip_view_tiles'.  Returns the
+ * count, or -1 on a bad argument or when `cap` entries are too few.  The device call uses the same function. */
+int64_t xpnghip_affine_view_tiles(const uint64_t *dims, uint32_t nimg, uint32_t nviews, const uint32_t *view_image,
+                                  const float *affines, const uint32_t *out_sizes, uint32_t *tiles, uint64_t cap);
+/* The views-colour call with `affines` (nviews * 6 floats on the host, required) and `fill` (4 floats on the host, or NULL) in
+ * place of rects and flips.  View v of image i receives, bit for bit, what xpnghip_resample_affine_host writes for raster_i with its
+ * matrix, the call's fill and, where colours is given, its colour matrix.  The checks, their order and their texts are the
+ * views-colour call's, with the rectangles' and the flips' replaced by the fill's (once per call, in front of the views) and the
+ * matrices' (per view, where the rectangle's stood); the filter must be 0 or 3.  Nothing is written when a call is refused.
+ * SELECTION: xpnghip_affine_view_tiles.  RECORDS: one 64-byte record per view (the staging slot, the buffer, the six floats, out_w,
+ * out_h and the footprint) in a table of its own in the context's workspace - counted by xpnghip_ctx_workspace_bytes, grown only
+ * when a call has more views than any affine call before it - uploaded with the selected list and, where given, the colour table
+ * under the views call's single synchronisation.  The views call's own record table is neither used nor allocated.  The fill
+ * travels in the kernel's arguments.  One kernel, xpng_amd/csrc/mixed_views_affine.hpp, writes every view.  A call whose views ALL
+ * have an empty footprint decodes nothing - xpnghip_ctx_last_decode_tiles is 0 and the status is clear - and writes the fill. */
+int xpnghip_decode_varsize_device_batch_views_affine(xpnghip_ctx *ctx, int mode, const void *const *d_blobs, const uint64_t *blobs_len,
+                                                     uint32_t nimg, const uint64_t *tile_off, uint32_t nviews,
+                                                     const uint32_t *view_image, void *const *d_outs, const uint32_t *out_sizes,
+                                                     const float *affines /* nviews * 6 */, const float *fill, uint32_t layout,
+                                                     uint32_t dtype, const float *scale, const float *bias, uint32_t filter,
+                                                     const float *colours, void *stream);
+
 /* ---- staged batch from device tensors: the inverse of the float call --------------------------
  * A model writes floats, not the file's bytes.  The call below is xpnghip_images_begin with the upload replaced by one staging
  * kernel that reads the caller's DEVICE buffers - planar or interleaved, RGB or BGR, uint8, f16, bf16 or f32 - and writes the

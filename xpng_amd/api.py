@@ -41,6 +41,8 @@ HIP_SYMBOLS = [
     "xpnghip_resample_colour_host", "xpnghip_decode_varsize_device_batch_views_colour",
     "xpnghip_resample_cubic_host", "xpnghip_decode_varsize_device_batch_views_cubic",
     "xpnghip_blur_weights", "xpnghip_resample_blur_host", "xpnghip_decode_varsize_device_batch_views_blur",
+    "xpnghip_affine_footprint", "xpnghip_resample_affine_host", "xpnghip_affine_view_tiles",
+    "xpnghip_decode_varsize_device_batch_views_affine",
 ]
 HOST_SYMBOLS = ["xpng_store", "xpng_load", "xpng_from_jpg", "xpng_store_T", "xpng_load_T", "xpng_from_jpg_T",
                 "store_7", "load_7"]
@@ -227,6 +229,17 @@ def _bind_hip(path):
         L.xpnghip_decode_varsize_device_batch_views_blur.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64), C.c_uint32, C.POINTER(u64), C.c_uint32,
                                                                      u32p, C.POINTER(vp), u32p, C.POINTER(u64), u8p, C.c_uint32, C.c_uint32, f32p,
                                                                      f32p, C.c_uint32, f32p, C.POINTER(ViewBlur), vp]
+        L.xpnghip_affine_footprint.restype = C.c_int
+        L.xpnghip_affine_footprint.argtypes = [u64, u64, f32p, C.c_uint32, C.c_uint32, C.POINTER(u64)]
+        L.xpnghip_resample_affine_host.restype = C.c_int
+        L.xpnghip_resample_affine_host.argtypes = [C.c_int, vp, u64, u64, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32p, f32p, C.c_uint32,
+                                                   f32p, f32p, vp]
+        L.xpnghip_affine_view_tiles.restype = C.c_int64
+        L.xpnghip_affine_view_tiles.argtypes = [C.POINTER(u64), C.c_uint32, C.c_uint32, u32p, f32p, u32p, u32p, u64]
+        L.xpnghip_decode_varsize_device_batch_views_affine.restype = C.c_int
+        L.xpnghip_decode_varsize_device_batch_views_affine.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64), C.c_uint32, C.POINTER(u64), C.c_uint32,
+                                                                       u32p, C.POINTER(vp), u32p, f32p, f32p, C.c_uint32, C.c_uint32, f32p, f32p,
+                                                                       C.c_uint32, f32p, vp]
         L.xpnghip_view_tiles.restype = C.c_int64
         L.xpnghip_view_tiles.argtypes = [C.POINTER(u64), C.c_uint32, C.c_uint32, u32p, C.POINTER(u64), u32p, u64]
         L.xpnghip_ctx_last_decode_tiles.restype = u64
@@ -809,6 +822,114 @@ def view_tiles(dims, view_image, rects) -> list:
     return list(arr[:n])
 
 
+FILTER_NEAREST = 3  # XPNGHIP_FILTER_NEAREST: the fourth filter word, which the affine entry points alone take (beside FILTER_BILINEAR)
+
+
+def _affine6(name, m):
+    """one inverse affine matrix - 6 numbers or a (2, 3) array, output coordinates to source coordinates - as 6 floats"""
+    try:
+        a = np.asarray(m, dtype=np.float64)
+    except (TypeError, ValueError):
+        a = None
+    if a is None or a.shape not in ((6,), (2, 3)):
+        raise XpngError(f"{name}: an affine matrix is 6 numbers or a (2, 3) array, not {m!r}")
+    return [float(np.float32(v)) for v in a.reshape(6)]
+
+
+def _fill4(name, fill):
+    """None (stays None: zeros), one number for every channel, or up to four numbers R, G, B, A (missing ones 0) as 4 floats"""
+    if fill is None:
+        return None
+    try:
+        v = [float(fill)] * 4 if not hasattr(fill, "__len__") else [float(x) for x in fill]
+    except (TypeError, ValueError):
+        v = None
+    if v is None or not 1 <= len(v) <= 4:
+        raise XpngError(f"{name}: fill is None, a number or up to four numbers R, G, B, A in byte units, not {fill!r}")
+    return (C.c_float * 4)(*(v + [0.0] * (4 - len(v))))
+
+
+def _size_pairs(name, sizes, n):
+    """one (OH, OW) for every view or one pair per view as the C array of pairs {out_w, out_h}"""
+    try:
+        sizes = list(sizes)
+        if len(sizes) == 2 and not hasattr(sizes[0], "__len__"):
+            sizes = [sizes] * n
+        if len(sizes) != n:
+            raise XpngError(f"{name}: sizes has {len(sizes)} entries for {n} views")
+        return (C.c_uint32 * max(2 * n, 1))(*[int(v) & 0xFFFFFFFF for (oh, ow) in sizes for v in (ow, oh)])
+    except (TypeError, ValueError):
+        raise XpngError(f"{name}: sizes must be (OH, OW) or one (OH, OW) per view, not {sizes!r}") from None
+
+
+def affine_footprint(dim, matrix, size):
+    """The footprint of one affine view (xpnghip_affine_footprint; host-only, needs no device): dim = (w, h) of the image, matrix
+    the inverse 2 x 3 map, size = (OH, OW).  Returns (x, y, w, h), the rectangle of the image outside which every tap is the fill -
+    the source coordinates of the four corner output pixels, widened by one pixel and by the second tap, clipped to the image -
+    or (0, 0, 0, 0) when it is empty.  Raises XpngError on a matrix outside the entry bounds (include/xpng_hip.h)."""
+    m = (C.c_float * 6)(*_affine6("affine_footprint", matrix))
+    try:
+        oh, ow = (int(v) for v in size)
+        w, h = (int(v) for v in dim)
+    except (TypeError, ValueError):
+        raise XpngError(f"affine_footprint: dim must be (w, h) and size (OH, OW), not {dim!r}, {size!r}") from None
+    r = (C.c_uint64 * 4)()
+    if hip_lib().xpnghip_affine_footprint(w & 0xFFFFFFFFFFFFFFFF, h & 0xFFFFFFFFFFFFFFFF, m, ow & 0xFFFFFFFF, oh & 0xFFFFFFFF, r):
+        raise XpngError("xpnghip_affine_footprint: " + _err())
+    return tuple(int(v) for v in r)
+
+
+def affine_view_tiles(dims, view_image, matrices, sizes) -> list:
+    """The launch list of MixedContext.decode_batch_views_affine (xpnghip_affine_view_tiles; host-only, needs no device): view_tiles
+    with the footprint of every view (affine_footprint) in place of its rectangle; a view with an empty footprint selects nothing.
+    matrices[v] is the inverse 2 x 3 map of view v, sizes one (OH, OW) for every view or one pair per view."""
+    dims = [(int(w), int(h)) for (w, h) in dims]
+    matrices = list(matrices)
+    nviews = len(matrices)
+    vi = _view_images("affine_view_tiles", None if view_image is None else list(view_image), nviews)
+    if view_image is not None and len(list(view_image)) != nviews:
+        raise XpngError(f"affine_view_tiles: view_image has {len(list(view_image))} entries for {nviews} matrices")
+    am = (C.c_float * max(6 * nviews, 1))(*[x for v, m in enumerate(matrices) for x in _affine6(f"affine_view_tiles: matrices[{v}]", m)])
+    so = _size_pairs("affine_view_tiles", sizes, nviews)
+    ok = 0 < len(dims) <= 4096 and all(0 < v <= 1 << 24 for d in dims for v in d)
+    cap = sum(_tile_count(w, h) for (w, h) in dims) if ok else 1
+    flat, arr = (C.c_uint64 * max(2 * len(dims), 1))(*[v & 0xFFFFFFFFFFFFFFFF for d in dims for v in d]), (C.c_uint32 * max(cap, 1))()
+    n = hip_lib().xpnghip_affine_view_tiles(flat, len(dims), nviews, vi, am, so, arr, cap)
+    if n < 0:
+        raise XpngError(f"affine_view_tiles: bad arguments ({len(dims)} images, {nviews} views: an image index outside the batch, a matrix outside "
+                        "the entry bounds, an output size outside 1 .. 16384, or a side outside 1 .. 16777216)")
+    return list(arr[:n])
+
+
+def resample_affine_host(raster, size, matrix, layout: int, dtype: int, scale=None, bias=None, filter: int = FILTER_BILINEAR, fill=None,
+                         colour=None) -> bytes:
+    """The rule of MixedContext.decode_batch_views_affine on the host (xpnghip_resample_affine_host; needs no device): `raster` is
+    an (h, w, 3|4) uint8 array in the file's form, size = (OH, OW), matrix the inverse 2 x 3 map from output to source coordinates
+    (pixel centres at + 0.5; tensors.affine_matrix builds one).  filter is FILTER_BILINEAR - four taps, torchvision's affine() on a
+    tensor - or FILTER_NEAREST (ties to even).  A tap outside the view's footprint or the image is `fill`: None (zeros), a number,
+    or R, G, B, A in byte units.  colour is None or a colour matrix as resample_colour_host takes it.  There is no rect and no
+    flip: the matrix carries both.  Returns the C * OH * OW elements of `dtype` in `layout` as raw bytes, bit for bit what the
+    device call writes for these pixels."""
+    r = np.ascontiguousarray(raster, dtype=np.uint8)
+    if r.ndim != 3 or r.shape[2] not in (3, 4):
+        raise XpngError("resample_affine_host: the raster must be (h, w, 3) or (h, w, 4) uint8")
+    try:
+        oh, ow = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise XpngError(f"resample_affine_host: size must be (OH, OW), not {size!r}") from None
+    px = r.shape[2]
+    sc, bi, ch = _scale_bias(layout, px, scale, bias)
+    am = (C.c_float * 6)(*_affine6("resample_affine_host", matrix))
+    fl = _fill4("resample_affine_host", fill)
+    cm = None if colour is None else (C.c_float * 12)(*_colour12("resample_affine_host", colour))
+    ok = ch > 0 and 1 <= oh <= 16384 and 1 <= ow <= 16384          # (anything else the library refuses, naming the value)
+    buf = np.empty(ch * oh * ow if ok else 1, dtype=np.uint32)     # 4-byte aligned, room for the widest element
+    if hip_lib().xpnghip_resample_affine_host(px, r.ctypes.data, r.shape[1], r.shape[0], am, ow & 0xFFFFFFFF, oh & 0xFFFFFFFF, layout, dtype, sc, bi,
+                                              int(filter) & 0xFFFFFFFF, fl, cm, buf.ctypes.data):
+        raise XpngError("xpnghip_resample_affine_host: " + _err())
+    return buf.tobytes()[:ch * oh * ow * dtype_bytes(dtype)]
+
+
 def quantize_host(src, npx: int, channels: int, layout: int, dtype: int, scale=None, bias=None) -> np.ndarray:
     """The quantisation rule of StagedImages.from_device on the host (xpnghip_quantize_host; needs no device): `src` is a tight
     buffer of channels * npx elements of `dtype` (0 = uint8, DTYPE_F16, DTYPE_BF16, DTYPE_F32) in `layout` (LAYOUT_PLANAR and
@@ -1211,17 +1332,7 @@ class MixedContext(_Handle):
         vi = _view_images(name, None if view_image is None else list(view_image), n)
         if view_image is not None and len(list(view_image)) != n:
             raise XpngError(f"{name}: view_image has {len(list(view_image))} entries for {n} output buffers")
-        so = None
-        if sizes is not None:
-            try:
-                sizes = list(sizes)
-                if len(sizes) == 2 and not hasattr(sizes[0], "__len__"):
-                    sizes = [sizes] * n
-                if len(sizes) != n:
-                    raise XpngError(f"{name}: sizes has {len(sizes)} entries for {n} views")
-                so = (C.c_uint32 * max(2 * n, 1))(*[int(v) & 0xFFFFFFFF for (oh, ow) in sizes for v in (ow, oh)])
-            except (TypeError, ValueError):
-                raise XpngError(f"{name}: sizes must be (OH, OW) or one (OH, OW) per view, not {sizes!r}") from None
+        so = None if sizes is None else _size_pairs(name, sizes, n)
         sc, bi, _ = _scale_bias(layout, self.pxsz, scale, bias)
         ra = _rect_array(name, rects, n)
         fl = _flip_array(name, flips, n, "views")
@@ -1273,6 +1384,36 @@ class MixedContext(_Handle):
         xpnghip_decode_varsize_device_batch_views_blur (the rule is in include/xpng_hip.h)."""
         self._views("decode_batch_views_blur", mode, d_blobs, lens, view_image, d_outs, layout, dtype, sizes, scale, bias, rects, flips, tile_offs,
                     stream, colours, filter, blurs)
+
+    def decode_batch_views_affine(self, mode, d_blobs, lens, view_image, d_outs, layout, dtype, sizes, matrices, scale=None, bias=None,
+                                  filter: int = FILTER_BILINEAR, fill=None, tile_offs=None, stream=0, colours=None):
+        """decode_batch_views under an affine map per view: matrices[v] is the inverse 2 x 3 map of view v, from its output
+        coordinates to source coordinates of its whole image (tensors.affine_matrix builds one from a rectangle, a size, an angle,
+        a translation, a scale, a shear and a flip), in place of rects and flips.  filter is FILTER_BILINEAR or FILTER_NEAREST;
+        a tap outside the view's footprint is `fill` (None, a number, or R, G, B, A in byte units; one for the call).  Only the
+        tiles that some view's footprint touches are decoded (affine_view_tiles), and view v equals resample_affine_host's bytes.
+        sizes, view_image and colours are decode_batch_views': xpnghip_decode_varsize_device_batch_views_affine (the rule is in
+        include/xpng_hip.h)."""
+        name = "decode_batch_views_affine"
+        n = len(d_outs)
+        matrices = list(matrices)
+        if len(matrices) != n:
+            raise XpngError(f"{name}: matrices has {len(matrices)} entries for {n} views")
+        am = (C.c_float * max(6 * n, 1))(*[x for v, m in enumerate(matrices) for x in _affine6(f"{name}: matrices[{v}]", m)])
+        cm = None
+        if colours is not None:
+            colours = list(colours)
+            if len(colours) != n:
+                raise XpngError(f"{name}: colours has {len(colours)} entries for {n} views")
+            if any(m is not None for m in colours):
+                cm = (C.c_float * (12 * n))(*[x for v, m in enumerate(colours) for x in (COLOUR_IDENTITY if m is None else _colour12(f"{name}: colours[{v}]", m))])
+        vi = _view_images(name, None if view_image is None else list(view_image), n)
+        if view_image is not None and len(list(view_image)) != n:
+            raise XpngError(f"{name}: view_image has {len(list(view_image))} entries for {n} output buffers")
+        so = None if sizes is None else _size_pairs(name, sizes, n)
+        sc, bi, _ = _scale_bias(layout, self.pxsz, scale, bias)
+        self._decode("xpnghip_decode_varsize_device_batch_views_affine", mode, d_blobs, lens, d_outs, tile_offs, stream, so, am, _fill4(name, fill), layout,
+                     dtype, sc, bi, int(filter) & 0xFFFFFFFF, cm, before=(n, vi))
 
     def last_decode_tiles(self) -> int:
         """tile work items of the context's most recent decode launch (xpnghip_ctx_last_decode_tiles): n_tiles after the other

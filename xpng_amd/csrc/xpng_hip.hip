@@ -38,6 +38,7 @@
 #include "mixed_views_colour.hpp"
 #include "mixed_views_cubic.hpp"
 #include "mixed_views_blur.hpp"
+#include "mixed_views_affine.hpp"
 #include "stage_from.hpp"
 
 using namespace xpng;
@@ -231,6 +232,10 @@ struct xpnghip_ctx {
     uint64_t cap_m_bscratch = 0;       // bytes d_m_bscratch holds
     BlurRec *d_m_blur = nullptr;
     uint64_t cap_m_blur = 0;           // records d_m_blur has room for
+    // ... and, for an affine views call only (mixed_views_affine.hpp), one 64-byte record per view in place of d_m_views: grown,
+    // dropped and uploaded as d_m_views is; no other call allocates it
+    AffineRec *d_m_affine = nullptr;
+    uint64_t cap_m_affine = 0;         // records d_m_affine has room for
     uint64_t last_tiles = 0;           // tile work items of the most recent decode launch (xpnghip_ctx_last_decode_tiles)
 };
 
@@ -1493,6 +1498,128 @@ extern "C" int xpnghip_resample_blur_host(int pxsz, const uint8_t *raster, uint6
                                           const float *colour, const xpnghip_view_blur *blur, void *out) {
     XPNG_GUARDED(resample_blur_host_impl(pxsz, raster, w, h, rect, flip, out_w, out_h, layout, dtype, scale, bias, filter, colour, blur, out))
 }
+// ---- an affine map per view (mixed_views_affine.hpp) -----------------------------------------------------------
+// the filter words of the affine entry points: bilinear or nearest, nothing else
+static bool affine_filter_ok(uint32_t filter, std::string &why) {
+    if (filter == XPNGHIP_FILTER_BILINEAR || filter == XPNGHIP_FILTER_NEAREST) return true;
+    why = "bad filter " + std::to_string(filter) + " (an affine call takes XPNGHIP_FILTER_BILINEAR = 0 or XPNGHIP_FILTER_NEAREST = 3)";
+    return false;
+}
+static bool affine_fill_ok(const float *fill, std::string &why) {
+    for (int e = 0; fill && e < 4; e++) {
+        if (std::isfinite(fill[e]) && fill[e] >= 0.0f && fill[e] <= 255.0f) continue;
+        why = "bad fill: entry " + std::to_string(e) + " is " + blur_num(fill[e]) + " (R, G, B, A in byte units: each must be finite and lie in 0 .. 255)";
+        return false;
+    }
+    return true;
+}
+// The matrix of a view against its output size, and its footprint {x, y, w, h} in pixels of the W x H image ({0, 0, 0, 0}: empty).
+// The entry bounds: |m| times the extent it multiplies - out_w in the first column, out_h in the second, 1 in the third - is at
+// most 2^18, so every coordinate of the view and every intermediate of the rule stays below 2^20 in magnitude.
+// The corners in double from the fp32 entries; the map is affine, so the extremes are there.  `who` names the view in a device call
+static bool affine_footprint(uint64_t W, uint64_t H, const float *m, uint32_t ow, uint32_t oh, const std::string &who, uint64_t *rect, std::string &why) {
+    for (int e = 0; e < 6; e++) {
+        const uint32_t n = e % 3 == 0 ? ow : e % 3 == 1 ? oh : 1u;
+        if (std::isfinite(m[e]) && fabs((double)m[e]) * n <= 262144.0) continue;
+        why = "bad affine matrix" + who + ": entry [" + std::to_string(e / 3) + "][" + std::to_string(e % 3) + "] is " + blur_num(m[e]) +
+              " (every entry must be finite, and its magnitude times " + (e % 3 == 0 ? "out_w" : e % 3 == 1 ? "out_h" : "1") + " = " + std::to_string(n) + " at most 262144)";
+        return false;
+    }
+    double lo[2] = {0, 0}, hi[2] = {0, 0};
+    for (int a = 0; a < 2; a++)
+        for (int q = 0; q < 4; q++) {
+            const double X = (q & 1 ? (double)(ow - 1) : 0.0) + 0.5, Y = (q & 2 ? (double)(oh - 1) : 0.0) + 0.5;
+            const double s = (double)m[3 * a] * X + (double)m[3 * a + 1] * Y + (double)m[3 * a + 2] - 0.5;
+            if (!q || s < lo[a]) lo[a] = s;
+            if (!q || s > hi[a]) hi[a] = s;
+        }
+    const int64_t x0 = std::max<int64_t>((int64_t)floor(lo[0]) - 1, 0), x1 = std::min<int64_t>((int64_t)floor(hi[0]) + 2, (int64_t)W - 1);
+    const int64_t y0 = std::max<int64_t>((int64_t)floor(lo[1]) - 1, 0), y1 = std::min<int64_t>((int64_t)floor(hi[1]) + 2, (int64_t)H - 1);
+    const bool empty = x0 > x1 || y0 > y1;
+    rect[0] = empty ? 0 : (uint64_t)x0; rect[1] = empty ? 0 : (uint64_t)y0;
+    rect[2] = empty ? 0 : (uint64_t)(x1 - x0 + 1); rect[3] = empty ? 0 : (uint64_t)(y1 - y0 + 1);
+    return true;
+}
+extern "C" int xpnghip_affine_footprint(uint64_t w, uint64_t h, const float *affine, uint32_t out_w, uint32_t out_h, uint64_t *rect) {
+    std::string why;
+    if (!affine || !rect) return fail("xpnghip_affine_footprint: null matrix or rectangle");
+    if (!w || !h || w > (1u << 24) || h > (1u << 24)) return fail("bad image size " + std::to_string(w) + " x " + std::to_string(h) + " (each side must be 1 .. 16777216)");
+    if (!resize_size_ok(out_w, out_h, why)) return fail(why);
+    uint64_t r[4];
+    if (!affine_footprint(w, h, affine, out_w, out_h, "", r, why)) return fail(why);
+    memcpy(rect, r, sizeof r);
+    return 0;
+}
+// The twin of k_mixed_views_affine on the host: the same operations in the same order, every multiplication inside an explicit
+// fmaf(), contraction off on top of that.  It IS the rule of the affine views call.
+static int resample_affine_host_impl(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const float *affine, uint32_t out_w, uint32_t out_h,
+                                     uint32_t layout, uint32_t dtype, const float *scale, const float *bias, uint32_t filter, const float *fill,
+                                     const float *colour, void *out) {
+#pragma clang fp contract(off)
+    std::string why;
+    if (!affine_filter_ok(filter, why)) return fail(why);
+    int C;
+    FloatConsts k;
+    ResizeRec z0;
+    if (resize_host_args("xpnghip_resample_affine_host", pxsz, raster, w, h, nullptr, 0, out_w, out_h, layout, dtype, scale, bias, out, C, k, z0)) return 1;
+    if (!affine) return fail("xpnghip_resample_affine_host: null matrix");
+    uint64_t F[4];
+    if (!affine_footprint(w, h, affine, out_w, out_h, "", F, why)) return fail(why);
+    if (!affine_fill_ok(fill, why)) return fail(why);
+    if (colour && !colour_matrix_ok(colour, "", why)) return fail(why);
+    const float zero[4] = {0.0f, 0.0f, 0.0f, 0.0f}, *fl = fill ? fill : zero, *m = affine;
+    const bool planar = layout & XPNGHIP_LAYOUT_PLANAR, bgr = layout & XPNGHIP_LAYOUT_BGR;
+    const int NS = pxsz == 4 && C == 4 ? 4 : 3;
+    const int64_t fx0 = (int64_t)F[0], fy0 = (int64_t)F[1], fx1 = fx0 + (int64_t)F[2], fy1 = fy0 + (int64_t)F[3];
+    auto q = [&](int64_t j, int64_t i, int sc) {
+        if (j < fx0 || j >= fx1 || i < fy0 || i >= fy1) return fl[sc];
+        return (float)raster[((uint64_t)i * w + (uint64_t)j) * pxsz + sc];
+    };
+    for (uint32_t oy = 0; oy < out_h; oy++)
+        for (uint32_t ox = 0; ox < out_w; ox++) {
+            const float X = (float)ox + 0.5f, Y = (float)oy + 0.5f;
+            const float ax = fmaf(m[1], Y, m[2]), ay = fmaf(m[4], Y, m[5]);
+            const float bx = fmaf(m[0], X, ax), by = fmaf(m[3], X, ay);
+            const float sx = bx - 0.5f, sy = by - 0.5f;
+            float v[4] = {0.0f, 0.0f, 0.0f, 255.0f};  // R, G, B of the file and its alpha (255: the alpha an RGB raster does not store)
+            if (filter == XPNGHIP_FILTER_NEAREST) {
+                const int64_t j = (int64_t)rintf(sx), i = (int64_t)rintf(sy);  // (ties to even: the default rounding mode)
+                for (int sc = 0; sc < NS; sc++) v[sc] = q(j, i, sc);
+            } else {
+                const float x0 = floorf(sx), y0 = floorf(sy);
+                const float lx = sx - x0, ly = sy - y0;
+                const int64_t j = (int64_t)x0, i = (int64_t)y0;
+                for (int sc = 0; sc < NS; sc++) {
+                    const float q00 = q(j, i, sc), q10 = q(j + 1, i, sc), q01 = q(j, i + 1, sc), q11 = q(j + 1, i + 1, sc);
+                    const float d0 = q10 - q00, d1 = q11 - q01;
+                    const float t = fmaf(lx, d0, q00), u = fmaf(lx, d1, q01);
+                    const float d = u - t;
+                    v[sc] = fmaf(ly, d, t);
+                }
+            }
+            float t[3] = {v[0], v[1], v[2]};
+            for (int r = 0; colour && r < 3; r++) {
+                const float *cm = colour + 4 * r;
+                const float a = fmaf(cm[2], v[2], cm[3]);
+                const float b = fmaf(cm[1], v[1], a);
+                const float x = fmaf(cm[0], v[0], b);
+                t[r] = x < 0.0f ? 0.0f : x > 255.0f ? 255.0f : x;
+            }
+            for (int c = 0; c < C; c++) {
+                const float u = c == 3 ? v[3] : t[bgr ? 2 - c : c];
+                const float y = fmaf(u, k.scale[c], k.bias[c]);
+                const uint64_t e = planar ? ((uint64_t)c * out_h + oy) * out_w + ox : ((uint64_t)oy * out_w + ox) * C + c;
+                if (dtype == XPNGHIP_DTYPE_F32) reinterpret_cast<float *>(out)[e] = y;
+                else reinterpret_cast<uint16_t *>(out)[e] = dtype == XPNGHIP_DTYPE_F16 ? f16_bits_rne(y) : bf16_bits_rne(y);
+            }
+        }
+    return 0;
+}
+extern "C" int xpnghip_resample_affine_host(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const float *affine, uint32_t out_w, uint32_t out_h,
+                                            uint32_t layout, uint32_t dtype, const float *scale, const float *bias, uint32_t filter, const float *fill,
+                                            const float *colour, void *out) {
+    XPNG_GUARDED(resample_affine_host_impl(pxsz, raster, w, h, affine, out_w, out_h, layout, dtype, scale, bias, filter, fill, colour, out))
+}
 // ---- staging from tensors (stage_from.hpp) ---------------------------------------------------------------------
 // the layout word of a call whose channel count is per image: the PLANAR and BGR bits and nothing else
 static bool stage_layout_ok(uint32_t layout, std::string &why) {
@@ -1778,6 +1905,7 @@ static void view_select(const std::vector<TileDesc> &tiles, const std::vector<ui
     for (uint32_t v = 0; v < nviews; v++) {
         const uint32_t i = view_image ? view_image[v] : v;
         const uint64_t whole[4] = {0, 0, dims[2ull * i], dims[2ull * i + 1]};
+        if (rects && !(rects[4ull * v + 2] && rects[4ull * v + 3])) continue;  // (an affine view's empty footprint selects nothing; a rectangle of the other calls is never empty: view_args_ok)
         one.assign(tiles.begin() + first[i], tiles.begin() + first[i + 1]);
         region_select(one, rects ? rects + 4ull * v : whole, sel);
         for (uint32_t t : sel) keep[first[i] + t] = 1;
@@ -1785,13 +1913,25 @@ static void view_select(const std::vector<TileDesc> &tiles, const std::vector<ui
     out.clear();
     for (uint32_t t : sorted) if (keep[t]) out.push_back(t);
 }
-extern "C" int64_t xpnghip_view_tiles(const uint64_t *dims, uint32_t nimg, uint32_t nviews, const uint32_t *view_image, const uint64_t *rects,
-                                      uint32_t *tiles, uint64_t cap) {
+// the launch list over images of `dims`; `affines` (with out_sizes) replaces the rectangles by the footprints of the views
+static int64_t view_tiles_impl(const uint64_t *dims, uint32_t nimg, uint32_t nviews, const uint32_t *view_image, const uint64_t *rects,
+                               const float *affines, const uint32_t *out_sizes, uint32_t *tiles, uint64_t cap) {
     try {
         if (!dims || nimg < 1 || nimg > 4096) return -1;
         for (uint32_t i = 0; i < 2 * nimg; i++) if (!dims[i] || dims[i] > (1u << 24)) return -1;
         std::string why;
         if (!view_args_ok(dims, nimg, nviews, view_image, rects, why)) return -1;
+        std::vector<uint64_t> foot;
+        if (affines) {
+            if (!out_sizes) return -1;
+            foot.resize(4ull * nviews);
+            for (uint32_t v = 0; v < nviews; v++) {
+                const uint32_t i = view_image ? view_image[v] : v;
+                if (!resize_size_ok(out_sizes[2ull * v], out_sizes[2ull * v + 1], why)) return -1;
+                if (!affine_footprint(dims[2ull * i], dims[2ull * i + 1], affines + 6ull * v, out_sizes[2ull * v], out_sizes[2ull * v + 1], "", &foot[4ull * v], why)) return -1;
+            }
+            rects = foot.data();
+        }
         // the concatenated table and its size-sorted list, as xpnghip_ctx_create_mixed builds them
         std::vector<TileDesc> all, one;
         std::vector<uint32_t> first((size_t)nimg + 1);
@@ -1811,21 +1951,45 @@ extern "C" int64_t xpnghip_view_tiles(const uint64_t *dims, uint32_t nimg, uint3
         return (int64_t)list.size();
     } catch (...) { return -1; }
 }
+extern "C" int64_t xpnghip_view_tiles(const uint64_t *dims, uint32_t nimg, uint32_t nviews, const uint32_t *view_image, const uint64_t *rects,
+                                      uint32_t *tiles, uint64_t cap) {
+    return view_tiles_impl(dims, nimg, nviews, view_image, rects, nullptr, nullptr, tiles, cap);
+}
+extern "C" int64_t xpnghip_affine_view_tiles(const uint64_t *dims, uint32_t nimg, uint32_t nviews, const uint32_t *view_image, const float *affines,
+                                             const uint32_t *out_sizes, uint32_t *tiles, uint64_t cap) {
+    if (!affines) return -1;
+    return view_tiles_impl(dims, nimg, nviews, view_image, nullptr, affines, out_sizes, tiles, cap);
+}
 extern "C" uint64_t xpnghip_ctx_last_decode_tiles(const xpnghip_ctx *c) { return c ? c->last_tiles : 0; }
 
+// what the affine form of a views call has in place of rectangles and flips: nviews * 6 floats and the fill (NULL: zeros)
+struct AffineCall {
+    const float *affines, *fill;
+};
 static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg, const uint64_t *tile_off,
                              uint32_t nviews, const uint32_t *view_image, void *const *d_outs, const uint32_t *out_sizes, const uint64_t *rects,
                              const uint8_t *flips, uint32_t layout, uint32_t dtype, const float *scale, const float *bias, uint32_t filter,
-                             const float *colours, void *stream, bool cubic = false, const xpnghip_view_blur *blurs = nullptr) {
+                             const float *colours, void *stream, bool cubic = false, const xpnghip_view_blur *blurs = nullptr,
+                             const AffineCall *af = nullptr) {
     // every argument is checked before anything reaches the device: a rejected call writes nothing
     int C, es;
     FloatConsts fk{};
     const FloatCall fc{dtype, scale, bias};
     if (mixed_decode_args(c, mode, d_blobs, blobs_len, nimg, d_outs, &layout, &fc, C, es, fk)) return 1;  // (everything the float call refuses)
     std::string why;
-    if (!cubic && !resample_filter_ok(filter, why)) return fail(why);  // (the cubic call has no filter word)
+    if (af ? !affine_filter_ok(filter, why) : !cubic && !resample_filter_ok(filter, why)) return fail(why);  // (the cubic call has no filter word)
     if (!out_sizes) return fail("out_sizes is NULL: a views call needs the pair {out_w, out_h} of every view");
+    if (af && !af->affines) return fail("affines is NULL: an affine views call needs the six floats of every view");
     if (!view_args_ok(c->m_dims.data(), nimg, nviews, view_image, rects, why)) return fail(why);
+    // an affine call has no rectangles and no flips: its matrices and its fill are checked in their place, and the footprints of
+    // its views are the rectangles of the selection
+    std::vector<AffineRec> arecs(af ? nviews : 0);
+    std::vector<uint64_t> foot(af ? 4ull * nviews : 0);
+    AffineFill afill{};
+    if (af) {
+        if (!affine_fill_ok(af->fill, why)) return fail(why);
+        for (int e = 0; af->fill && e < 4; e++) afill.v[e] = af->fill[e];
+    }
     const uint64_t px = (uint64_t)c->pxsz, bpr = rup(c->m_max_w * px, 16);
     std::vector<uint64_t> slot((size_t)nimg + 1, 0);  // (mixed_stage_slots' layout: the refusals below come before anything is allocated)
     for (uint32_t i = 0; i < nimg; i++) slot[i + 1] = slot[i] + rup(c->m_dims[2ull * i + 1] * bpr, 256);
@@ -1836,12 +2000,22 @@ static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
         const std::string who = " (view " + std::to_string(v) + ", image " + std::to_string(i) + ")";
         ResizeRec z;
         if (!resize_size_ok(ow, oh, why)) return fail(why + who);
-        if (!resize_record(c->m_dims[2ull * i], c->m_dims[2ull * i + 1], rects ? rects + 4ull * v : nullptr, flips ? flips[v] : 0u, ow, oh, z, why)) return fail(why + who);
+        if (af) {
+            if (!affine_footprint(c->m_dims[2ull * i], c->m_dims[2ull * i + 1], af->affines + 6ull * v, ow, oh, " of view " + std::to_string(v), &foot[4ull * v], why)) return fail(why);
+        } else if (!resize_record(c->m_dims[2ull * i], c->m_dims[2ull * i + 1], rects ? rects + 4ull * v : nullptr, flips ? flips[v] : 0u, ow, oh, z, why)) return fail(why + who);
         if (!d_outs[v]) return fail("null output buffer of view " + std::to_string(v));
         if ((uintptr_t)d_outs[v] & (uintptr_t)(es - 1)) {
             char b[32];
             snprintf(b, sizeof b, "%p", d_outs[v]);
             return fail("output buffer " + std::string(b) + " of view " + std::to_string(v) + " is not aligned to its " + std::to_string(es) + "-byte elements");
+        }
+        if (af) {
+            max_oh = std::max(max_oh, oh);
+            const float *m = af->affines + 6ull * v;
+            const uint64_t *f = &foot[4ull * v];
+            arecs[v] = AffineRec{slot[i], (uint8_t *)d_outs[v], {m[0], m[1], m[2], m[3], m[4], m[5]}, ow, oh,
+                                 (int32_t)f[0], (int32_t)f[1], (int32_t)(f[0] + f[2]), (int32_t)(f[1] + f[3])};
+            continue;
         }
         const ResampleRec q = resample_record(z);  // (the four ratios exactly as the resized and the resampled calls compute them)
         recs[v] = ViewRec{slot[i], (uint8_t *)d_outs[v], q.rx, q.ry, q.rw, q.rh, ow, oh, q.kx, q.ky, q.ikx, q.iky, q.flip, 0};
@@ -1892,11 +2066,19 @@ static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
         }
     }
     std::vector<uint32_t> list;
-    view_select(c->tiles, c->m_first, c->m_list, c->m_dims.data(), nviews, view_image, rects, list);
+    view_select(c->tiles, c->m_first, c->m_list, c->m_dims.data(), nviews, view_image, af ? foot.data() : rects, list);
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(c);
     if (mixed_stage_slots(c, bpr, slot)) return 1;
-    if (c->cap_m_views < nviews) {
+    if (af && c->cap_m_affine < nviews) {  // (the affine call's own record table: it never touches d_m_views)
+        if (c->d_m_affine) {
+            for (hipStream_t q : {s, c->stream, c->side}) if (q) HIPCHK(hipStreamSynchronize(q));
+            c->ws.drop((void **)&c->d_m_affine); c->cap_m_affine = 0;
+        }
+        WS_GET(c->d_m_affine, (uint64_t)nviews * sizeof(AffineRec));
+        c->cap_m_affine = nviews;
+    }
+    if (!af && c->cap_m_views < nviews) {
         if (c->d_m_views) {  // (an earlier call's copy-out may still read the old table: the context's work is on these streams)
             for (hipStream_t q : {s, c->stream, c->side}) if (q) HIPCHK(hipStreamSynchronize(q));
             c->ws.drop((void **)&c->d_m_views); c->cap_m_views = 0;
@@ -1934,19 +2116,43 @@ static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
     }
     // the resized call's protocol: both tables are in pageable host memory that ends with this call, so the stream is synchronised
     // once behind the two copies - queued before the decode's own kernels, so the wait never covers this call's work
-    HIPCHK(hipMemcpyAsync(c->d_m_views, recs.data(), (uint64_t)nviews * sizeof(ViewRec), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_m_vlist, list.data(), (uint64_t)list.size() * 4, hipMemcpyHostToDevice, s));
+    if (af) HIPCHK(hipMemcpyAsync(c->d_m_affine, arecs.data(), (uint64_t)nviews * sizeof(AffineRec), hipMemcpyHostToDevice, s));
+    else HIPCHK(hipMemcpyAsync(c->d_m_views, recs.data(), (uint64_t)nviews * sizeof(ViewRec), hipMemcpyHostToDevice, s));
+    if (!list.empty()) HIPCHK(hipMemcpyAsync(c->d_m_vlist, list.data(), (uint64_t)list.size() * 4, hipMemcpyHostToDevice, s));
     if (colours) HIPCHK(hipMemcpyAsync(c->d_m_vcolour, colours, (uint64_t)nviews * sizeof(ViewColour), hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
-    std::vector<void *> base(nimg);
-    for (uint32_t i = 0; i < nimg; i++) base[i] = c->d_m_stage + slot[i];
-    if (dec_prepare(c, mode, d_blobs, blobs_len, nimg, base.data(), s)) return 1;
-    XPNG_REQUIRE(c->d_m_first, c->d_m_stage, c->d_m_views, c->d_m_vlist);
-    const int rc = dec_launch(c, mode, nimg, c->m_max_w, tile_off, s, 0, (uint32_t)c->tiles.size(), &list, c->d_m_vlist, bpr);
-    if (rc) return rc;
+    XPNG_REQUIRE(c->d_m_first, c->d_m_stage, af ? (const void *)c->d_m_affine : (const void *)c->d_m_views, c->d_m_vlist);
+    if (list.empty()) {
+        // an affine call whose views all lie outside their images (every other views call selects a tile: its rectangles are not
+        // empty): nothing is decoded, the status is clear and the copy-out below writes the fill
+        XPNG_REQUIRE(c->d_status);
+        HIPCHK(hipMemsetAsync(c->d_status, 0, 4, s));
+        c->last_tiles = 0;
+    } else {
+        std::vector<void *> base(nimg);
+        for (uint32_t i = 0; i < nimg; i++) base[i] = c->d_m_stage + slot[i];
+        if (dec_prepare(c, mode, d_blobs, blobs_len, nimg, base.data(), s)) return 1;
+        const int rc = dec_launch(c, mode, nimg, c->m_max_w, tile_off, s, 0, (uint32_t)c->tiles.size(), &list, c->d_m_vlist, bpr);
+        if (rc) return rc;
+    }
     const uint32_t bgr = layout & XPNGHIP_LAYOUT_BGR;
     const dim3 grid((max_oh + MC_ROWS - 1) / MC_ROWS, nplain);
     if (colours) XPNG_REQUIRE(c->d_m_vcolour);
+    if (af) {  // one kernel for every view: a matrix carries the crop, the size and the mirror
+        const dim3 agrid((max_oh + AF_ROWS - 1) / AF_ROWS, nviews);
+        const ViewColour *vm = colours ? c->d_m_vcolour : nullptr;
+        with_3or4(c->pxsz, [&](auto PXc) { with_3or4(C, [&](auto Cc) { with_planar(layout, [&](auto PL) { with_float(dtype, [&](auto t) {
+            constexpr int PXv = decltype(PXc)::value, Cv = decltype(Cc)::value;
+            constexpr bool PLv = decltype(PL)::value;
+#ifdef XPNG_PROBES
+            // the lane-mapping study (tools/views_affine_timing.py): the siblings' mapping, one output row per wave pass
+            if (probe_env("XPNG_AFFINE_ROW_MAP")) { k_mixed_views_affine<PXv, Cv, PLv, decltype(t), 1><<<agrid, 256, 0, s>>>(c->d_m_affine, vm, c->d_m_stage, bpr, bgr, filter, afill, fk); return; }
+#endif
+            k_mixed_views_affine<PXv, Cv, PLv, decltype(t)><<<agrid, 256, 0, s>>>(c->d_m_affine, vm, c->d_m_stage, bpr, bgr, filter, afill, fk);
+        }); }); }); });
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
     if (nplain)
     with_3or4(c->pxsz, [&](auto PXc) { with_3or4(C, [&](auto Cc) { with_planar(layout, [&](auto PL) { with_float(dtype, [&](auto t) {
         constexpr int PXv = decltype(PXc)::value, Cv = decltype(Cc)::value;
@@ -2009,6 +2215,15 @@ extern "C" int xpnghip_decode_varsize_device_batch_views_blur(xpnghip_ctx *c, in
     if (!blur_filter_ok(filter, why)) return fail(why);
     const bool cubic = filter == XPNGHIP_FILTER_CUBIC_AA;
     XPNG_GUARDED(decode_views_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, nviews, view_image, d_outs, out_sizes, rects, flips, layout, dtype, scale, bias, cubic ? 0 : filter, colours, stream, cubic, blurs))
+}
+// the views-colour call with a matrix per view in place of its rectangle and flip, and one fill (mixed_views_affine.hpp)
+extern "C" int xpnghip_decode_varsize_device_batch_views_affine(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
+                                                                const uint64_t *tile_off, uint32_t nviews, const uint32_t *view_image, void *const *d_outs,
+                                                                const uint32_t *out_sizes, const float *affines, const float *fill, uint32_t layout,
+                                                                uint32_t dtype, const float *scale, const float *bias, uint32_t filter, const float *colours,
+                                                                void *stream) {
+    const AffineCall af{affines, fill};
+    XPNG_GUARDED(decode_views_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, nviews, view_image, d_outs, out_sizes, nullptr, nullptr, layout, dtype, scale, bias, filter, colours, stream, false, nullptr, &af))
 }
 
 // ---- mixed-size batch encode (mixed.hpp) ---------------------------------------------------------

@@ -10,7 +10,8 @@ MixedContext.decode_batch_resampled when that resize is to antialias).
 `load_views` gives any number of crops per file from ONE decode of it, and decodes only the tiles they touch
 (MixedContext.decode_batch_views); with colour= every view also gets a colour matrix of its own in the same pass (colour_matrix,
 random_colour_jitter), and with blur= and solarise= a Gaussian blur and a solarise of its own in a second kernel of that call
-(MixedContext.decode_batch_views_blur; random_gaussian_blur, random_solarise).
+(MixedContext.decode_batch_views_blur; random_gaussian_blur, random_solarise); with affine= every view is rotated, sheared, scaled
+and translated in the copy-out instead (MixedContext.decode_batch_views_affine; affine_matrix, random_affine).
 api.py stays free of torch; this module is the only one of the package that imports it at load time."""
 from __future__ import annotations
 
@@ -352,7 +353,7 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
 
 def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool = False, device=None, dtype=torch.float16, mean=None,
                std=None, antialias: bool = True, stack: bool = False, out=None, colour=None, interpolation: str = "bilinear", blur=None,
-               solarise=None):
+               solarise=None, affine=None, fill=None):
     """Any number of views per file, each decoded once: views is a list of (path_index, rect_or_None, flip) - rect = (x, y, w, h)
     inside file path_index, None for the whole image; flip True mirrors left to right - and view v comes back as a tensor
     (C, OH_v, OW_v) for layout "chw" or (OH_v, OW_v, C) for "hwc", in view order.  size is one (OH, OW) for every view or one pair
@@ -399,7 +400,18 @@ def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool
     list given - with both interpolations - every device call is ONE MixedContext.decode_batch_views_blur: views that ask for
     neither are written as before, the others take a second kernel over fp32 planes in the context's workspace; view v equals,
     bit for bit, api.resample_blur_host, which also answers level-7 and single-colour files.  With both None the function runs
-    exactly the calls it ran without the arguments."""
+    exactly the calls it ran without the arguments.
+
+    affine gives views a rotation, a shear, a scale and a translation - RandomRotation, RandomAffine, the geometric operations of
+    RandAugment - in the same pass.  It is None or one entry per view, each None or an inverse 2 x 3 matrix from the view's output
+    coordinates to source coordinates of its whole image, as affine_matrix and random_affine return them.  A view that has a matrix
+    must have rect None and flip False - the matrix carries both; a None entry takes affine_matrix(rect or the whole image, size,
+    flip=flip).  The call needs antialias=False and interpolation "bilinear" (four taps, torchvision's affine() on tensors) or
+    "nearest" (for label maps; accepted only here).  What a tap finds outside the image is fill: None (zeros), a number, or R, G,
+    B, A in byte units, one for the call.  Every device call is then ONE MixedContext.decode_batch_views_affine, which decodes only
+    the tiles that a view's warped footprint touches, and view v equals, bit for bit, api.resample_affine_host with its matrix,
+    which also answers level-7 and single-colour files.  blur= or solarise= together with affine= is an error.  With affine None
+    the function runs exactly the calls it ran without the argument."""
     if layout not in ("chw", "hwc"):
         raise XpngError(f"load_views: layout must be 'chw' or 'hwc', not {layout!r}")
     if channels not in (None, 3, 4):
@@ -472,6 +484,28 @@ def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool
                 if not 0.0 <= t <= 255.0:
                     raise XpngError(f"load_views: solarise[{v}] is {t!r}, not None or a threshold in 0 .. 255")
             blurs.append(None if b is None and t is None else (sigma, radius, t))
+    mats, afilt = None, api.FILTER_BILINEAR
+    if affine is not None:
+        mats = list(affine)
+        if len(mats) != V:
+            raise XpngError(f"load_views: affine has {len(mats)} entries for {V} views: one matrix (or None) per view")
+        if antialias or interpolation not in ("bilinear", "nearest"):
+            raise XpngError("load_views: affine= needs antialias=False and interpolation 'bilinear' or 'nearest': a warp is sampled with four taps "
+                            f"or one, not {interpolation!r} with antialias={antialias!r}")
+        if blurs is not None:
+            raise XpngError("load_views: blur= or solarise= together with affine= is not offered")
+        for v, m in enumerate(mats):
+            if m is not None and (views[v][1] is not None or views[v][2]):
+                raise XpngError(f"load_views: view {v} has a matrix, so its rectangle must be None and its flip False: the matrix carries both")
+        mats = [None if m is None else api._affine6(f"load_views: affine[{v}]", m) for v, m in enumerate(mats)]
+        fill = api._fill4("load_views", fill)
+        fill = None if fill is None else list(fill)
+        afilt = api.FILTER_NEAREST if interpolation == "nearest" else api.FILTER_BILINEAR
+        interpolation = "bilinear"
+    elif interpolation == "nearest":
+        raise XpngError("load_views: interpolation='nearest' is offered with affine= only")
+    elif fill is not None:
+        raise XpngError("load_views: fill= is the value outside an affine view: it needs affine=")
     dev = torch.device("cuda" if device is None else device)
     if dev.type == "cuda" and not torch.cuda.is_available():
         raise XpngError("load_views: no GPU is visible (device='cpu' answers level-7 and single-colour files without one)")
@@ -485,6 +519,18 @@ def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool
         _, w, h, _ = heads[i]
         if r is not None and not (r[2] > 0 and r[3] > 0 and 0 <= r[0] <= w - r[2] and 0 <= r[1] <= h - r[3]):
             raise XpngError(f"load_views: the rectangle {r} of view {v} is empty or leaves the {w} x {h} image {os.fspath(paths[i])!r}")
+    if mats is not None:                                               # a view without a matrix: its crop, its resize and its flip as one
+        mats = [m if m is not None else affine_matrix(views[v][1] or (0, 0, heads[views[v][0]][1], heads[views[v][0]][2]), sizes[v], flip=views[v][2]).reshape(6).tolist()
+                for v, m in enumerate(mats)]
+        # what the library would refuse of a matrix or of the fill is refused here, before any view is written
+        for v, m in enumerate(mats):
+            try:
+                api.affine_footprint(heads[views[v][0]][1:3], m, sizes[v])
+            except XpngError as e:
+                raise XpngError(f"load_views: view {v}: {e}") from None
+        for k, x in enumerate(fill or ()):
+            if not 0.0 <= x <= 255.0:                                  # (NaN included)
+                raise XpngError(f"load_views: bad fill: entry {k} is {x!r} (R, G, B, A in byte units: each must be finite and lie in 0 .. 255)")
     chans = [channels or heads[i][3] for (i, _, _) in views]
     cache = {}
     for C in set(chans):
@@ -529,7 +575,9 @@ def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool
             if vi != i:
                 continue
             word = api.layout(planar=layout == "chw", bgr=bgr, channels=chans[v])
-            if blurs is not None:
+            if mats is not None:
+                raw = api.resample_affine_host(ras, sizes[v], mats[v], word, dt, *cache[chans[v]], filter=afilt, fill=fill, colour=cols[v])
+            elif blurs is not None:
                 raw = api.resample_blur_host(ras, sizes[v], word, dt, *cache[chans[v]], rect=r, flip=f, filter=api.FILTER_CUBIC_AA if cubic else filt,
                                              colour=cols[v], blur=blurs[v])
             elif cubic:
@@ -567,7 +615,9 @@ def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool
                     kw = dict(rects=[views[v][1] or (0, 0, heads[views[v][0]][1], heads[views[v][0]][2]) for v in mine],
                               flips=[views[v][2] for v in mine],
                               colours=[cols[v] for v in mine] if cols[mine[0]] is not None else None)
-                    if blurs is not None:
+                    if mats is not None:
+                        ctx.decode_batch_views_affine(*args[:8], [mats[v] for v in mine], *cache[C], filter=afilt, fill=fill, colours=kw["colours"])
+                    elif blurs is not None:
                         ctx.decode_batch_views_blur(*args, filter=api.FILTER_CUBIC_AA if cubic else filt, blurs=[blurs[v] for v in mine], **kw)
                     elif cubic:
                         ctx.decode_batch_views_cubic(*args, **kw)
@@ -695,6 +745,115 @@ def random_solarise(n, threshold=128, p=0.2, generator=None):
         raise XpngError(f"random_solarise: p must be within 0 .. 1, not {p!r}")
     u = torch.rand((n,), dtype=torch.float64, generator=generator).tolist()
     return [float(threshold) if coin < p else None for coin in u]
+
+
+def _size_pair(name, size):
+    try:
+        oh, ow = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise XpngError(f"{name}: size must be (OH, OW), not {size!r}") from None
+    if not (1 <= oh <= 16384 and 1 <= ow <= 16384):
+        raise XpngError(f"{name}: size {(oh, ow)} is outside 1 .. 16384")
+    return oh, ow
+
+
+def affine_matrix(rect, size, angle=0.0, translate=(0, 0), scale=1.0, shear=(0.0, 0.0), flip=False):
+    """The (2, 3) float32 INVERSE matrix of a view, as load_views(affine=...) and MixedContext.decode_batch_views_affine take it:
+    from continuous output coordinates (x to the right, y down, pixel (j, i) centred at (j + 0.5, i + 0.5)) to continuous source
+    coordinates of the whole image.  The view shows rect = (x, y, w, h) of the image resized to size = (OH, OW) - mirrored left to
+    right first where flip is true - and then rotated, sheared, scaled and translated about the OUTPUT's centre, with the
+    parameter meanings of torchvision's RandomAffine / F.affine: angle in degrees, clockwise; translate = (tx, ty) in output pixels;
+    scale > 0; shear = (sx, sy) in degrees (a number is (sx, 0)).
+
+    Composed in float64 and rounded once.  The order, from an output pixel back to the source:
+      1. P = (X - OW / 2, Y - OH / 2)                               coordinates about the output's centre
+      2. P' = A^-1 P, A^-1 = (R(angle) Sh(shear) S(scale))^-1 (P - translate)  torchvision's _get_inverse_affine_matrix with centre 0
+      3. Q = P' + (OW / 2, OH / 2)                                  back into the frame of the resized rectangle
+      4. sx = x + Qx * w / OW  (flip: x + w - Qx * w / OW),  sy = y + Qy * h / OH     the crop and the resize
+    All defaults give exactly the crop-resize matrix [[w / OW, 0, x], [0, h / OH, y]], and an angle that is a multiple of 90 without
+    shear takes cos and sin as exactly 0 and +-1, so a quarter turn of a square view of its own size is exact on the bits.  Where this differs from torchvision: there
+    the image is cropped and resized (RandomResizedCrop) in a pass of its own, which interpolates once more and cuts the corners
+    that the rotation then turns into the frame to `fill`; here step 4 is part of the one map, so a rotated view shows the source
+    pixels around its rectangle where the image has them, and `fill` only outside the image.  The flip comes before the warp."""
+    oh, ow = _size_pair("affine_matrix", size)
+    try:
+        x, y, w, h = (float(v) for v in rect)
+        tx, ty = (float(v) for v in translate)
+        shx, shy = (float(shear), 0.0) if not hasattr(shear, "__len__") else (float(v) for v in shear)
+        rot, sc = math.radians(float(angle)), float(scale)
+    except (TypeError, ValueError):
+        raise XpngError(f"affine_matrix: rect is (x, y, w, h), translate (tx, ty), shear a number or (sx, sy); got {rect!r}, {translate!r}, {shear!r}") from None
+    if not (w > 0 and h > 0 and sc > 0.0 and math.isfinite(sc)):
+        raise XpngError(f"affine_matrix: the rectangle must not be empty and scale must be positive, not {rect!r}, {scale!r}")
+    shx, shy = math.radians(shx), math.radians(shy)
+    a = math.cos(rot - shy) / math.cos(shy)
+    b = -math.cos(rot - shy) * math.tan(shx) / math.cos(shy) - math.sin(rot)
+    c = math.sin(rot - shy) / math.cos(shy)
+    d = -math.sin(rot - shy) * math.tan(shx) / math.cos(shy) + math.cos(rot)
+    inv = np.array([[d / sc, -b / sc, 0.0], [-c / sc, a / sc, 0.0], [0.0, 0.0, 1.0]])
+    if shx == 0.0 and shy == 0.0 and float(angle) % 90.0 == 0.0:      # whole quarter turns exactly: cos and sin are 0 and +-1, not 6e-17
+        co, si = ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))[int(float(angle) // 90.0) % 4]
+        inv = np.array([[co / sc, si / sc, 0.0], [-si / sc, co / sc, 0.0], [0.0, 0.0, 1.0]]) + 0.0   # (+ 0.0: no -0.0)
+    move = lambda px, py: np.array([[1.0, 0.0, px], [0.0, 1.0, py], [0.0, 0.0, 1.0]])
+    crop = np.array([[-w / ow if flip else w / ow, 0.0, x + w if flip else x], [0.0, h / oh, y], [0.0, 0.0, 1.0]])
+    M = crop @ move(ow / 2.0, oh / 2.0) @ inv @ move(-tx, -ty) @ move(-ow / 2.0, -oh / 2.0)
+    return M[:2].astype(np.float32)
+
+
+def random_affine(n, rects, size, degrees, translate=None, scale=None, shear=None, generator=None):
+    """n matrices for load_views(affine=...), one per view, with parameters drawn as torchvision's RandomAffine.get_params draws
+    them: the angle uniform in degrees = (lo, hi) (a number d is (-d, d)); with translate = (a, b), tx and ty uniform in
+    +-a * OW and +-b * OH, rounded to whole output pixels; with scale = (lo, hi) the scale uniform in it; with shear = (lo, hi) or
+    (xlo, xhi, ylo, yhi) (a number s is (-s, s)) the shears uniform in them.  rects is one (x, y, w, h) per view - what
+    random_resized_crops returns, or the whole images - and size one (OH, OW) for every view or one pair per view; view k is
+    affine_matrix(rects[k], size_k, angle, (tx, ty), scale, (sx, sy)).  A pure host function; with a seeded torch.Generator the list
+    is reproducible."""
+    n = int(n)
+    rects = list(rects)
+    if n < 0 or len(rects) != n:
+        raise XpngError(f"random_affine: n is {n} and rects has {len(rects)} entries")
+    sizes = list(size)
+    if len(sizes) == 2 and not hasattr(sizes[0], "__len__"):
+        sizes = [sizes] * n
+    if len(sizes) != n:
+        raise XpngError(f"random_affine: {len(sizes)} sizes for {n} views: one (OH, OW), or one per view")
+
+    def span(name, x, k):
+        if x is None:
+            return None
+        try:
+            v = [-float(x), float(x)] if not hasattr(x, "__len__") else [float(t) for t in x]
+        except (TypeError, ValueError):
+            v = []
+        if len(v) not in k or any(lo > hi for lo, hi in zip(v[::2], v[1::2])):
+            raise XpngError(f"random_affine: {name} must be a number or (low, high) with low <= high, not {x!r}")
+        return v
+
+    deg, sc, sh = span("degrees", degrees, (2,)), span("scale", scale, (2,)), span("shear", shear, (2, 4))
+    if deg is None:
+        raise XpngError("random_affine: degrees is required (0 for no rotation)")
+    if sc is not None and not sc[0] > 0.0:
+        raise XpngError(f"random_affine: scale must be positive, not {scale!r}")
+    if translate is not None:
+        try:
+            ta, tb = (float(t) for t in translate)
+        except (TypeError, ValueError):
+            ta = -1.0
+        if not (0.0 <= ta <= 1.0 and 0.0 <= tb <= 1.0):
+            raise XpngError(f"random_affine: translate must be two fractions within 0 .. 1, not {translate!r}")
+    u = torch.rand((n, 6), dtype=torch.float64, generator=generator).tolist()   # one draw whatever the outcomes: entry k depends on row k alone
+    out = []
+    for k, (ua, ux, uy, us, uhx, uhy) in enumerate(u):
+        oh, ow = _size_pair("random_affine", sizes[k])
+        angle = deg[0] + (deg[1] - deg[0]) * ua
+        tx = ty = 0
+        if translate is not None:
+            tx, ty = int(round((2.0 * ux - 1.0) * ta * ow)), int(round((2.0 * uy - 1.0) * tb * oh))
+        s = 1.0 if sc is None else sc[0] + (sc[1] - sc[0]) * us
+        shx = 0.0 if sh is None else sh[0] + (sh[1] - sh[0]) * uhx
+        shy = 0.0 if sh is None or len(sh) == 2 else sh[2] + (sh[3] - sh[2]) * uhy
+        out.append(affine_matrix(rects[k], (oh, ow), angle, (tx, ty), s, (shx, shy)))
+    return out
 
 
 def _inverse_scale_bias(mean, std, present):
