@@ -313,8 +313,12 @@ def test_corrupt_files_are_rejected_not_executed(gpu, po, tmp_path):
 
 def test_batch_kernels_forced_on_small_inputs(gpu, manifest, po, tmp_path, monkeypatch):
     """Large batches switch the entropy stage to its "wide" kernels (many streams per wavefront: rans2_wide.hpp,
-    rans2_wide_dec.hpp, k_dec_walk_wide) and to 256-thread workgroups.  XPNG_WIDE_RANS=1 forces that path for any input, so
-    the goldens, the edge cases and the corrupt-file behaviour are checked on it too."""
+    rans2_wide_dec.hpp, k_dec_walk_wide) and to 256-thread workgroups.  XPNG_WIDE_RANS=1 forces the wide kernels for any input,
+    so the goldens, the edge cases and the corrupt-file behaviour are checked on them too.  Of the 256-thread workgroups it
+    brings only those that follow the same selector (wide_form: k_dec_resid among them).  k_m1_streams, k_m2_streams and
+    k_m2_dec_resid follow small_blocks(), which looks at the size of the launch alone: here they keep their 1024-thread form,
+    a pairing with the wide chains that no production call launches.  tests/test_iteration_edges.py reaches their 256-thread
+    form by the size of the launch."""
     monkeypatch.setenv("XPNG_WIDE_RANS", "1")
     checked = 0
     for name, ent in small_entries(manifest):

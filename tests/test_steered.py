@@ -212,6 +212,12 @@ def test_census_reaches_every_branch_the_encoder_can_write(survey):
 #                   recon_wavefront otherwise (30000 x 4: rows too long; 7 x 9000: nine bands of 1024 rows with seams);
 #                   wide entropy path (XPNG_WIDE_RANS=1 or more than 2048 chains) and tiles up to 2048 px: k_dec_recon_band<PXSZ,
 #                   DecTile / M2DecTile> (recon_band_core).
+#   routing         by small_blocks(items) = items > 2048 (common.hpp), a selector of its own that no environment variable of the release
+#                   library moves: up to 2048 (tile, stream) items k_m1_streams<PXSZ, 1024> (launch_encode_m1), k_m2_streams<1024>
+#                   (launch_encode_m2) and k_m2_dec_resid<1024> (decode_m2_launch), 4096 pixels per loop iteration; beyond,
+#                   k_m1_streams<PXSZ, 256>, k_m2_streams<256> and k_m2_dec_resid<256>, 1024 pixels per iteration.  XPNG_WIDE_RANS=1 on the
+#                   single images here keeps the 1024-thread form beside the wide chains; only the batches below that select the wide
+#                   kernels by their size run the 256-thread form (tests/test_iteration_edges.py crafts tiles for it).
 _ORACLE = {}
 
 
