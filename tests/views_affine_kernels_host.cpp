@@ -1,7 +1,7 @@
 // Host run of k_mixed_views_affine (xpng_amd/csrc/mixed_views_affine.hpp): every thread of every block, one after another, over both
 // pixel sizes, all 12 layouts and the three element types (24 instances) and both filters, with the shims for the device operations
-// of tests/kernel_host.hpp (the kernel reuses the named operations of mixed_float.hpp and ViewColour and colour_row of
-// mixed_views_colour.hpp, whose texts are compiled in front of it).  Both lane mappings are run: the patch of four rows per wave
+// of tests/kernel_host.hpp (the kernel reuses the named operations of mixed_float.hpp, the end of a pixel and the row writer of
+// mixed_views_pixel.hpp and ViewColour of mixed_views_colour.hpp, whose texts are compiled in front of it).  Both lane mappings are run: the patch of four rows per wave
 // that the product launches and the one row per wave of the timing study.
 // A launch holds several images and MORE views than images: views of different heights (the grid is the tallest view's, so blocks of
 // short views must return), rotations by generic angles, a shear with a scale, an exact quarter turn, a mirror, an integer
@@ -34,7 +34,8 @@ static void chk_read(const uint8_t *p, uint32_t n, uint32_t align) {
 }
 
 #include FLOAT_TEXT     // FloatConsts, the element types, pick4, narrow2, store1, float_chunk: mixed_float.hpp
-#include COLOUR_TEXT    // ViewColour, colour_row: mixed_views_colour.hpp
+#include PIXEL_TEXT     // colour_row, pixel_finish, pixel_store, row_narrow, row_wide: mixed_views_pixel.hpp
+#include COLOUR_TEXT    // ViewColour: mixed_views_colour.hpp
 #include KERNEL_TEXT    // AffineRec, AffineFill and the kernel, cut out of xpng_amd/csrc/mixed_views_affine.hpp by the test
 
 template <class T> static uint32_t elem_bits(float y) {

@@ -1,6 +1,6 @@
 // Host run of k_mixed_views_blur (xpng_amd/csrc/mixed_views_blur.hpp): every thread of every block, over both channel counts, both
 // layouts, both colour orders and the three element types (all 12 instances, each with and without the BGR exchange), with the shims
-// for the device operations of tests/kernel_host.hpp (the kernel reuses fma_f32, pick4 and store1 of mixed_float.hpp, whose text is
+// for the device operations of tests/kernel_host.hpp (the kernel reuses fma_f32, pick4 and store1 of mixed_float.hpp and pixel_store of mixed_views_pixel.hpp, whose text is
 // compiled in front of it).
 // The kernel has barriers, so a block's 256 threads cannot simply run one after another: every thread is a fiber (ucontext) with a
 // stack of its own, the barrier hands control back to the block's scheduler, and the scheduler resumes the threads round after
@@ -79,6 +79,7 @@ template <class F> static void launch_fibers(uint32_t gx, uint32_t gy, F f) {
 
 #define __shared__ static
 #include FLOAT_TEXT   // FloatConsts, the element types, pick4, narrow2, store1: mixed_float.hpp
+#include PIXEL_TEXT   // pixel_store (and the row writers, which this kernel does not use): mixed_views_pixel.hpp
 #include KERNEL_TEXT  // BlurRec, blur_refl and the kernel, cut out of xpng_amd/csrc/mixed_views_blur.hpp by the test
 
 template <class T> static uint32_t elem_bits(float y) {

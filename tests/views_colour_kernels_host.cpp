@@ -1,7 +1,8 @@
 // Host run of k_mixed_views_colour (xpng_amd/csrc/mixed_views_colour.hpp): every thread of every block, one after another, over both
 // pixel sizes, all 12 layouts and the three element types (24 instances) and both filters, with the shims for the device operations
 // of tests/kernel_host.hpp (the kernel reuses the named operations of mixed_float.hpp, resize_tap of mixed_resize.hpp, the window
-// and the weight of mixed_resample.hpp and ViewRec of mixed_views.hpp, whose texts are compiled in front of it).
+// and the weight of mixed_resample.hpp, ViewRec of mixed_views.hpp and the end of a pixel and the row writer of
+// mixed_views_pixel.hpp, whose texts are compiled in front of it).
 // A launch holds several images and MORE views than images, as tests/views_kernels_host.cpp's: views of different sizes (the grid
 // is the tallest view's, so blocks of short views must return), several views of one image, an image without a view, ratios on both
 // sides of 1 on each axis, both flips, rectangles at the image's edges - and a different matrix per view: the identity, a
@@ -35,6 +36,7 @@ static void chk_read(const uint8_t *p, uint32_t n, uint32_t align) {
 #include RESIZE_TEXT    // resize_tap: mixed_resize.hpp
 #include RESAMPLE_TEXT  // resample_win, resample_weight, resample_div: mixed_resample.hpp
 #include VIEWS_TEXT     // ViewRec: mixed_views.hpp
+#include PIXEL_TEXT     // colour_row, pixel_finish, pixel_store, row_narrow, row_wide: mixed_views_pixel.hpp
 #include KERNEL_TEXT    // ViewColour and the kernel, cut out of xpng_amd/csrc/mixed_views_colour.hpp by the test
 
 template <class T> static uint32_t elem_bits(float y) {

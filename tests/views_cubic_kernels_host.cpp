@@ -1,8 +1,8 @@
 // Host run of k_mixed_views_cubic (xpng_amd/csrc/mixed_views_cubic.hpp): every thread of every block, one after another, over both
 // pixel sizes, all 12 layouts and the three element types (24 instances), with a matrix per view and with none (a null table), with
 // the shims for the device operations of tests/kernel_host.hpp (the kernel reuses the named operations of mixed_float.hpp, the
-// window record and the division of mixed_resample.hpp, ViewRec of mixed_views.hpp and ViewColour and colour_row of
-// mixed_views_colour.hpp, whose texts are compiled in front of it).
+// window record and the division of mixed_resample.hpp, ViewRec of mixed_views.hpp, the end of a pixel and the row writer of
+// mixed_views_pixel.hpp and ViewColour of mixed_views_colour.hpp, whose texts are compiled in front of it).
 // The launches are the view programs of tests/views_kernels_host.cpp in the form tests/views_colour_kernels_host.cpp runs them:
 // several images and MORE views than images, views of different sizes (the grid is the tallest view's, so blocks of short views
 // must return), several views of one image, an image without a view, ratios on both sides of 1 on each axis, both flips,
@@ -36,7 +36,8 @@ static void chk_read(const uint8_t *p, uint32_t n, uint32_t align) {
 #include FLOAT_TEXT     // FloatConsts, the element types, pick4, narrow2, store1, float_chunk: mixed_float.hpp
 #include RESAMPLE_TEXT  // ResampleWin, resample_div: mixed_resample.hpp
 #include VIEWS_TEXT     // ViewRec: mixed_views.hpp
-#include COLOUR_TEXT    // ViewColour, colour_row: mixed_views_colour.hpp
+#include PIXEL_TEXT     // colour_row, pixel_finish, pixel_store, row_narrow, row_wide: mixed_views_pixel.hpp
+#include COLOUR_TEXT    // ViewColour: mixed_views_colour.hpp
 #include KERNEL_TEXT    // cubic_win, cubic_weight and the kernel, cut out of xpng_amd/csrc/mixed_views_cubic.hpp by the test
 
 template <class T> static uint32_t elem_bits(float y) {

@@ -677,6 +677,18 @@ def _colour12(name, m):
     return [float(v) for v in a.reshape(12)]
 
 
+def _colour_table(name, colours, n):
+    """the `colours` of a views call of n views as its table of 12 * n floats; None where colours is None or every entry is"""
+    if colours is None:
+        return None
+    colours = list(colours)
+    if len(colours) != n:
+        raise XpngError(f"{name}: colours has {len(colours)} entries for {n} views")
+    if all(m is None for m in colours):
+        return None
+    return (C.c_float * (12 * n))(*[x for v, m in enumerate(colours) for x in (COLOUR_IDENTITY if m is None else _colour12(f"{name}: colours[{v}]", m))])
+
+
 def resample_colour_host(raster, size, layout: int, dtype: int, scale=None, bias=None, rect=None, flip=False, filter: int = FILTER_TRIANGLE_AA,
                          colour=None) -> bytes:
     """The rule of MixedContext.decode_batch_views with a colour matrix on the host (xpnghip_resample_colour_host; needs no
@@ -1310,6 +1322,15 @@ class MixedContext(_Handle):
         self._decode("xpnghip_decode_varsize_device_batch_resampled", mode, d_blobs, lens, d_outs, tile_offs, stream, layout, dtype, sc, bi, ra, fl, ow, oh,
                      int(filter) & 0xFFFFFFFF)
 
+    def _view_args(self, name, view_image, sizes, layout, scale, bias, n):
+        """what every views call of n views marshals alike: view_image, the size pairs and the constants"""
+        vi = _view_images(name, None if view_image is None else list(view_image), n)
+        if view_image is not None and len(list(view_image)) != n:
+            raise XpngError(f"{name}: view_image has {len(list(view_image))} entries for {n} output buffers")
+        so = None if sizes is None else _size_pairs(name, sizes, n)
+        sc, bi, _ = _scale_bias(layout, self.pxsz, scale, bias)
+        return vi, so, sc, bi
+
     def _views(self, name, mode, d_blobs, lens, view_image, d_outs, layout, dtype, sizes, scale, bias, rects, flips, tile_offs, stream, colours, filter,
                blurs=None):
         """the marshalling of the views calls; filter _CUBIC: the cubic call, which has no filter word and always takes `colours`;
@@ -1321,19 +1342,8 @@ class MixedContext(_Handle):
             if len(blurs) != n:
                 raise XpngError(f"{name}: blurs has {len(blurs)} entries for {n} views")
             br = (ViewBlur * max(n, 1))(*[_blur_record(f"{name}: blurs[{v}]", b) for v, b in enumerate(blurs)])
-        cm = None
-        if colours is not None:
-            colours = list(colours)
-            if len(colours) != n:
-                raise XpngError(f"{name}: colours has {len(colours)} entries for {n} views")
-            if any(m is not None for m in colours):
-                flat = [x for v, m in enumerate(colours) for x in (COLOUR_IDENTITY if m is None else _colour12(f"{name}: colours[{v}]", m))]
-                cm = (C.c_float * (12 * n))(*flat)
-        vi = _view_images(name, None if view_image is None else list(view_image), n)
-        if view_image is not None and len(list(view_image)) != n:
-            raise XpngError(f"{name}: view_image has {len(list(view_image))} entries for {n} output buffers")
-        so = None if sizes is None else _size_pairs(name, sizes, n)
-        sc, bi, _ = _scale_bias(layout, self.pxsz, scale, bias)
+        cm = _colour_table(name, colours, n)
+        vi, so, sc, bi = self._view_args(name, view_image, sizes, layout, scale, bias, n)
         ra = _rect_array(name, rects, n)
         fl = _flip_array(name, flips, n, "views")
         if name == "decode_batch_views_blur":
@@ -1400,18 +1410,8 @@ class MixedContext(_Handle):
         if len(matrices) != n:
             raise XpngError(f"{name}: matrices has {len(matrices)} entries for {n} views")
         am = (C.c_float * max(6 * n, 1))(*[x for v, m in enumerate(matrices) for x in _affine6(f"{name}: matrices[{v}]", m)])
-        cm = None
-        if colours is not None:
-            colours = list(colours)
-            if len(colours) != n:
-                raise XpngError(f"{name}: colours has {len(colours)} entries for {n} views")
-            if any(m is not None for m in colours):
-                cm = (C.c_float * (12 * n))(*[x for v, m in enumerate(colours) for x in (COLOUR_IDENTITY if m is None else _colour12(f"{name}: colours[{v}]", m))])
-        vi = _view_images(name, None if view_image is None else list(view_image), n)
-        if view_image is not None and len(list(view_image)) != n:
-            raise XpngError(f"{name}: view_image has {len(list(view_image))} entries for {n} output buffers")
-        so = None if sizes is None else _size_pairs(name, sizes, n)
-        sc, bi, _ = _scale_bias(layout, self.pxsz, scale, bias)
+        cm = _colour_table(name, colours, n)
+        vi, so, sc, bi = self._view_args(name, view_image, sizes, layout, scale, bias, n)
         self._decode("xpnghip_decode_varsize_device_batch_views_affine", mode, d_blobs, lens, d_outs, tile_offs, stream, so, am, _fill4(name, fill), layout,
                      dtype, sc, bi, int(filter) & 0xFFFFFFFF, cm, before=(n, vi))
 

@@ -42,8 +42,8 @@ struct AffineFill {
 constexpr uint32_t AF_NEAREST = 3;  // XPNGHIP_FILTER_NEAREST
 constexpr uint32_t AF_ROWS = 16;    // output rows per workgroup
 
-// grid (ceil(max oh / AF_ROWS), nviews), 256 threads; the template axes, the early return of a short view's blocks, the head, the
-// aligned 16-byte stores, the tail and the two planar forms are k_mixed_views_colour's, and exactly C * oh * ow * sizeof(T) bytes of
+// grid (ceil(max oh / AF_ROWS), nviews), 256 threads; the template axes and the early return of a short view's blocks are
+// k_mixed_views_colour's, the stores are the wide row writer's (mixed_views_pixel.hpp), and exactly C * oh * ow * sizeof(T) bytes of
 // the view's buf are written.  The unit is the pixel: its coordinates, its taps and their inside-F tests are computed once and
 // every source byte is read once per output pixel.  vm == nullptr: no colour matrix.
 // PR is the lane mapping: a wave covers PR neighbouring output rows with 64 / PR lanes each in one pass.  Under a rotation a wave
@@ -53,7 +53,7 @@ constexpr uint32_t AF_ROWS = 16;    // output rows per workgroup
 template <int PX, int C, bool PLANAR, class T, int PR = 4>
 __global__ __launch_bounds__(256) void k_mixed_views_affine(const AffineRec *__restrict__ vr, const ViewColour *__restrict__ vm, const uint8_t *__restrict__ stage,
                                                             uint64_t stage_bpr, uint32_t bgr, uint32_t filter, AffineFill fill, FloatConsts k) {
-    constexpr uint32_t ES = sizeof(T), E = 16 / ES;
+    constexpr uint32_t ES = sizeof(T);
     constexpr uint32_t NS = PX == 4 && C == 4 ? 4 : 3;  // source bytes of a pixel that are read: the colours, and a stored alpha that is asked for
     constexpr uint32_t LR = 64 / PR;                    // lanes of a wave on one output row
     static_assert(PR == 1 || PR == 2 || PR == 4, "a head and a tail of up to 7 elements need at least 8 lanes on a row");
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void k_mixed_views_affine(const AffineRec *__r
     const uint32_t row_el = PLANAR ? OW : OW * C;  // elements of one row of the caller's buffer
     const uint8_t *img = stage + z.stage;          // the image's first pixel
     const uint32_t fw = (uint32_t)(z.fx1 - z.fx0), fh = (uint32_t)(z.fy1 - z.fy0);
-    const bool same = !PLANAR || (((uint64_t)OH * OW * ES) & 15u) == 0;  // every plane's row oy starts at one offset modulo 16
+    const uint64_t plane = (uint64_t)OH * OW * ES;  // bytes from a plane's row oy to the next plane's
     for (uint32_t it = wv * PR + lr; it < rows; it += 4 * PR) {
         const uint32_t oy = oy0 + it;
         const float Y = (float)oy + 0.5f;
@@ -108,84 +108,9 @@ __global__ __launch_bounds__(256) void k_mixed_views_affine(const AffineRec *__r
                     v[b] = fma_f32(ly, u - t, t);
                 }
             }
-            float tr = v[0], tg = v[1], tb = v[2];
-            if (vm) { tr = colour_row(m, v[0], v[1], v[2]); tg = colour_row(m + 4, v[0], v[1], v[2]); tb = colour_row(m + 8, v[0], v[1], v[2]); }
-            o[0] = bgr ? tb : tr; o[1] = tg; o[2] = bgr ? tr : tb;
-            o[3] = NS == 4 ? v[NS - 1] : 255.0f;  // a stored alpha, or the alpha an RGB file does not store
+            pixel_finish(v, m, vm != nullptr, bgr, o);
         };
-        if constexpr (PLANAR) {
-            uint8_t *d = z.buf + (uint64_t)oy * row_el * ES;  // row oy of plane 0
-            const uint64_t plane = (uint64_t)OH * OW * ES;
-            auto single = [&](uint32_t j) {
-                float o[4];
-                pixel(j, o);
-#pragma unroll
-                for (uint32_t c = 0; c < (uint32_t)C; c++) store1<T>(d + c * plane, j, fma_f32(o[c], pick4(k.scale, c), pick4(k.bias, c)));
-            };
-            if (!same) {  // a pixel per lane: the stores of a row's lanes are neighbouring elements of each plane's row
-                for (uint32_t j = lc; j < row_el; j += LR) single(j);
-                continue;
-            }
-            uint32_t head = ((16u - (uint32_t)((uintptr_t)d & 15)) & 15u) / ES;
-            if (head > row_el) head = row_el;
-            const uint32_t nq = (row_el - head) / E, tail0 = head + E * nq;
-            if (lc < head) single(lc);
-            if (tail0 + lc < row_el) single(tail0 + lc);
-            uint8_t *d16 = d + (uint64_t)head * ES;  // 16-byte aligned, in every plane
-            for (uint32_t q = lc; q < nq; q += LR) {
-                const uint32_t j = head + E * q;
-                float o[8][4];
-#pragma unroll
-                for (uint32_t i = 0; i < E; i++) pixel(j + i, o[i]);
-#pragma unroll
-                for (uint32_t c = 0; c < (uint32_t)C; c++) {
-                    float v[8] = {}, sa[4] = {}, ba[4] = {};
-                    sa[0] = pick4(k.scale, c); ba[0] = pick4(k.bias, c);
-#pragma unroll
-                    for (uint32_t i = 0; i < E; i++) v[i] = o[i][c];
-                    out_st128(d16 + c * plane + 16ull * q, float_chunk<T, 1>(v, sa, ba));
-                }
-            }
-        } else {
-            constexpr uint32_t NP = (C - 1 + E - 1) / C + 1;  // pixels a store can touch
-            uint8_t *d = z.buf + (uint64_t)oy * row_el * ES;
-            uint32_t head = ((16u - (uint32_t)((uintptr_t)d & 15)) & 15u) / ES;
-            if (head > row_el) head = row_el;
-            const uint32_t nq = (row_el - head) / E, tail0 = head + E * nq;
-            auto single = [&](uint32_t j) {
-                const uint32_t ox = j / C, c = j - ox * C;
-                float o[4];
-                pixel(ox, o);
-                store1<T>(d, j, fma_f32(pick4(o, c), pick4(k.scale, c), pick4(k.bias, c)));
-            };
-            if (lc < head) single(lc);
-            if (tail0 + lc < row_el) single(tail0 + lc);
-            uint8_t *d16 = d + (uint64_t)head * ES;  // 16-byte aligned
-            for (uint32_t q = lc; q < nq; q += LR) {
-                const uint32_t j = head + E * q, p = j / C, rr = j - p * C;  // the store starts at channel rr of pixel p
-                float f[NP * C] = {}, sa[4] = {}, ba[4] = {};  // the pixels' values in the caller's order, pixel after pixel
-#pragma unroll
-                for (uint32_t i = 0; i < (uint32_t)C; i++) {
-                    const uint32_t c = rr + i < (uint32_t)C ? rr + i : rr + i - C;
-                    sa[i] = pick4(k.scale, c); ba[i] = pick4(k.bias, c);
-                }
-#pragma unroll
-                for (uint32_t dq = 0; dq < NP; dq++) {
-                    if (dq * C >= rr + E) continue;  // (the store ends in front of this pixel; it may lie behind the row)
-                    float o[4];
-                    pixel(p + dq, o);
-#pragma unroll
-                    for (uint32_t c = 0; c < (uint32_t)C; c++) f[dq * C + c] = o[c];
-                }
-                float v[8] = {};
-#pragma unroll
-                for (uint32_t i = 0; i < E; i++) {
-                    if constexpr (C == 3) v[i] = rr == 0 ? f[i] : rr == 1 ? f[i + 1] : f[i + 2];
-                    else v[i] = rr == 0 ? f[i] : rr == 1 ? f[i + 1] : rr == 2 ? f[i + 2] : f[i + 3];
-                }
-                out_st128(d16 + 16ull * q, float_chunk<T, C>(v, sa, ba));
-            }
-        }
+        row_wide<C, PLANAR, T>(z.buf + (uint64_t)oy * row_el * ES, OW, plane, lc, LR, k, pixel);
     }
 }
 

@@ -52,10 +52,10 @@ __device__ __forceinline__ uint32_t blur_refl(int32_t i, uint32_t n) {
 // C planes -, PLANAR and T the caller's layout and element.  Per colour plane: the tile and its halo of R on every side go from the
 // scratch into s_in, each wave taking whole rows with the reflection resolved at the load; the horizontal operation of every row of
 // s_in goes into s_mid; the vertical operation runs over s_mid.  A lane owns column `lane` of rows wv, wv + 4, .. of the tile and
-// keeps its pixels' three colours in registers until the last plane is through, then stores the C elements of each pixel: a wave's
-// stores are 64 neighbouring elements of a plane's row, or 64 * C neighbouring elements of an interleaved row.  Exactly
-// C * oh * ow * sizeof(T) bytes of the view's buf are written and no read leaves the view's slice.  R == 0 (solarise alone) skips
-// the LDS and the barriers; R is uniform for the block.
+// keeps its pixels' three colours in registers until the last plane is through, then stores the C elements of each pixel
+// (pixel_store, mixed_views_pixel.hpp): a wave's stores are 64 neighbouring elements of a plane's row, or 64 * C neighbouring
+// elements of an interleaved row.  Exactly C * oh * ow * sizeof(T) bytes of the view's buf are written and no read leaves the
+// view's slice.  R == 0 (solarise alone) skips the LDS and the barriers; R is uniform for the block.
 template <int C, bool PLANAR, class T>
 __global__ __launch_bounds__(256) void k_mixed_views_blur(const BlurRec *__restrict__ br, const float *__restrict__ scratch, uint32_t bgr, FloatConsts k) {
     constexpr uint32_t ES = sizeof(T), NIT = BLUR_TH / 4;
@@ -125,12 +125,7 @@ __global__ __launch_bounds__(256) void k_mixed_views_blur(const BlurRec *__restr
         if (bgr) { const float t = o[0]; o[0] = o[2]; o[2] = t; }
         o[3] = 0.0f;
         if constexpr (C == 4) o[3] = scratch_ld(src + 3 * plane + e + lane);  // stored, or the 255 the first pass wrote
-#pragma unroll
-        for (uint32_t c = 0; c < (uint32_t)C; c++) {
-            const float yv = fma_f32(o[c], pick4(k.scale, c), pick4(k.bias, c));
-            if constexpr (PLANAR) store1<T>(z.buf + (c * plane + e) * ES, lane, yv);
-            else store1<T>(z.buf + e * C * ES, lane * C + c, yv);
-        }
+        pixel_store<C, PLANAR, T>(z.buf + e * (PLANAR ? 1 : C) * ES, plane * ES, lane, o, k);
     }
 }
 

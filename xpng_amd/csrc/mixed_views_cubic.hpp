@@ -62,7 +62,7 @@ constexpr uint32_t CUBIC_ROWS = 4;
 // C * oh * ow * sizeof(T) bytes of the view's buf are written.  What is not taken from that kernel is the 16-byte store: there a
 // lane resamples the two to eight pixels one store covers, one after another, and a 224-wide planar f16 row keeps 28 of a wave's 64
 // lanes busy; here a pixel costs hundreds of taps and its C stores nothing beside them, so a lane takes ONE pixel and stores its
-// elements one by one (that kernel's form for planes that are no multiple of 16 bytes), and no pixel is resampled twice.
+// elements one by one (the narrow row writer of mixed_views_pixel.hpp), and no pixel is resampled twice.
 // vm may be null - no matrices in this call, uniform for the launch - and then no matrix is read.  The source side is a
 // loop per output pixel over the rows of its y window, CUBIC_ROWS at a time, and the taps of its x window: reads of single bytes (PX
 // 3) or of one whole pixel as an aligned dword (PX 4: the staging slots and rows are 16-byte aligned) inside the view's rectangle,
@@ -87,6 +87,7 @@ __global__ __launch_bounds__(256) void k_mixed_views_cubic(const ViewRec *__rest
     const uint32_t row_el = PLANAR ? OW : OW * C;  // elements of one row of the caller's buffer
     const float isx = z.kx > 1.0f ? z.ikx : 1.0f, isy = z.ky > 1.0f ? z.iky : 1.0f;
     const uint8_t *rect0 = stage + z.stage + (uint64_t)z.ry * stage_bpr + (uint64_t)z.rx * PX;  // the rectangle's first pixel
+    const uint64_t plane = (uint64_t)OH * OW * ES;  // bytes from a plane's row oy to the next plane's
     for (uint32_t it = wv; it < rows; it += 4) {
         const uint32_t oy = oy0 + it;
         const ResampleWin wy = cubic_win(oy, z.ky, z.rh);
@@ -135,27 +136,9 @@ __global__ __launch_bounds__(256) void k_mixed_views_cubic(const ViewRec *__rest
                 const float x = resample_div(A[i], W);
                 v[i] = x < 0.0f ? 0.0f : x > 255.0f ? 255.0f : x;
             }
-            float tr = v[0], tg = v[1], tb = v[2];
-            if (mat) {
-                tr = colour_row(m, v[0], v[1], v[2]); tg = colour_row(m + 4, v[0], v[1], v[2]); tb = colour_row(m + 8, v[0], v[1], v[2]);
-            }
-            o[0] = bgr ? tb : tr; o[1] = tg; o[2] = bgr ? tr : tb;
-            o[3] = NS == 4 ? v[NS - 1] : 255.0f;  // a stored alpha, or the alpha an RGB file does not store
+            pixel_finish(v, m, mat, bgr, o);
         };
-        // a PIXEL per lane, its C elements stored one by one: a wave's stores are 64 neighbouring elements of each plane's row, or
-        // 64 * C neighbouring elements of the interleaved row
-        uint8_t *d = z.buf + (uint64_t)oy * row_el * ES;  // row oy (of plane 0)
-        const uint64_t plane = (uint64_t)OH * OW * ES;
-        for (uint32_t ox = lane; ox < OW; ox += 64) {
-            float o[4];
-            pixel(ox, o);
-#pragma unroll
-            for (uint32_t c = 0; c < (uint32_t)C; c++) {
-                const float y = fma_f32(o[c], pick4(k.scale, c), pick4(k.bias, c));
-                if constexpr (PLANAR) store1<T>(d + c * plane, ox, y);
-                else store1<T>(d, ox * C + c, y);
-            }
-        }
+        row_narrow<C, PLANAR, T>(z.buf + (uint64_t)oy * row_el * ES, OW, plane, lane, 64, k, pixel);
     }
 }
 

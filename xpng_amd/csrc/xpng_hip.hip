@@ -1162,6 +1162,38 @@ template <class Q> static float resample_axis_apply(const ResampleAxis &a, float
     if (!(W > 0.0f)) *bad = true;
     return A / W;
 }
+// What the twins of the views kernels share behind a pixel's resampled values (mixed_views_pixel.hpp), contraction off as in the
+// twins themselves.  The three rows of a view's colour matrix and the clamp: t[k] from v = R, G, B
+static void colour_rows_host(const float *colour, const float *v, float *t) {
+#pragma clang fp contract(off)
+    for (int q = 0; q < 3; q++) {
+        const float *m = colour + 4 * q;
+        const float a = fmaf(m[2], v[2], m[3]);
+        const float b = fmaf(m[1], v[1], a);
+        const float x = fmaf(m[0], v[0], b);
+        t[q] = x < 0.0f ? 0.0f : x > 255.0f ? 255.0f : x;
+    }
+}
+// the element of a buffer of `dtype`
+static void host_put(void *out, uint32_t dtype, uint64_t e, float y) {
+    if (dtype == XPNGHIP_DTYPE_F32) reinterpret_cast<float *>(out)[e] = y;
+    else reinterpret_cast<uint16_t *>(out)[e] = dtype == XPNGHIP_DTYPE_F16 ? f16_bits_rne(y) : bf16_bits_rne(y);
+}
+// a twin's output: C channels of w x h elements of `dtype`, planar or interleaved (a twin that collects its values first, so that
+// a failing call writes nothing, points this at fp32 values and narrows them behind its checks)
+struct HostOut {
+    void *out;
+    uint32_t dtype;
+    bool planar;
+    int C;
+    uint32_t w, h;
+};
+// value v of channel position c of output pixel (ox, oy): the constants, the element's index, the element
+static void host_element(const HostOut &o, const FloatConsts &k, uint32_t ox, uint32_t oy, int c, float v) {
+#pragma clang fp contract(off)
+    const float y = fmaf(v, k.scale[c], k.bias[c]);
+    host_put(o.out, o.dtype, o.planar ? ((uint64_t)c * o.h + oy) * o.w + ox : ((uint64_t)oy * o.w + ox) * o.C + c, y);
+}
 static int resample_host_impl(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip, uint32_t out_w, uint32_t out_h,
                               uint32_t layout, uint32_t dtype, const float *scale, const float *bias, uint32_t filter, void *out) {
 #pragma clang fp contract(off)
@@ -1180,6 +1212,7 @@ static int resample_host_impl(int pxsz, const uint8_t *raster, uint64_t w, uint6
     for (uint32_t oy = 0; oy < out_h; oy++) ay[oy] = resample_axis_host(oy, z.ky, z.rh);
     // the values first, the elements after them: a call that fails writes nothing
     std::vector<float> ys((uint64_t)C * out_h * out_w);
+    const HostOut yo{ys.data(), XPNGHIP_DTYPE_F32, planar, C, out_w, out_h};
     bool bad = false;
     for (uint32_t oy = 0; oy < out_h; oy++)
         for (uint32_t ox = 0; ox < out_w; ox++)
@@ -1193,13 +1226,10 @@ static int resample_host_impl(int pxsz, const uint8_t *raster, uint64_t w, uint6
                     };
                     v = resample_axis_apply(ay[oy], z.iky, H, &bad);
                 }
-                ys[planar ? ((uint64_t)c * out_h + oy) * out_w + ox : ((uint64_t)oy * out_w + ox) * C + c] = fmaf(v, k.scale[c], k.bias[c]);
+                host_element(yo, k, ox, oy, c, v);
             }
     if (bad) return fail("internal error: a window of the triangle filter has no weight");  // (W > 0 always: DESIGN.md 19)
-    for (uint64_t e = 0; e < ys.size(); e++) {
-        if (dtype == XPNGHIP_DTYPE_F32) reinterpret_cast<float *>(out)[e] = ys[e];
-        else reinterpret_cast<uint16_t *>(out)[e] = dtype == XPNGHIP_DTYPE_F16 ? f16_bits_rne(ys[e]) : bf16_bits_rne(ys[e]);
-    }
+    for (uint64_t e = 0; e < ys.size(); e++) host_put(out, dtype, e, ys[e]);
     return 0;
 }
 extern "C" int xpnghip_resample_host(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip, uint32_t out_w, uint32_t out_h,
@@ -1245,6 +1275,7 @@ static int resample_colour_host_impl(int pxsz, const uint8_t *raster, uint64_t w
     for (uint32_t oy = 0; oy < out_h; oy++) ay[oy] = axis(oy, z.ky, z.rh);
     // the values first, the elements after them: a call that fails writes nothing
     std::vector<float> ys((uint64_t)C * out_h * out_w);
+    const HostOut yo{ys.data(), XPNGHIP_DTYPE_F32, planar, C, out_w, out_h};
     bool bad = false;
     for (uint32_t oy = 0; oy < out_h; oy++)
         for (uint32_t ox = 0; ox < out_w; ox++) {
@@ -1257,23 +1288,11 @@ static int resample_colour_host_impl(int pxsz, const uint8_t *raster, uint64_t w
                 v[sc] = resample_axis_apply(ay[oy], z.iky, H, &bad);
             }
             float t[3];
-            for (int q = 0; q < 3; q++) {
-                const float *m = colour + 4 * q;
-                const float a = fmaf(m[2], v[2], m[3]);
-                const float b = fmaf(m[1], v[1], a);
-                const float x = fmaf(m[0], v[0], b);
-                t[q] = x < 0.0f ? 0.0f : x > 255.0f ? 255.0f : x;
-            }
-            for (int c = 0; c < C; c++) {
-                const float u = c == 3 ? v[3] : t[bgr ? 2 - c : c];
-                ys[planar ? ((uint64_t)c * out_h + oy) * out_w + ox : ((uint64_t)oy * out_w + ox) * C + c] = fmaf(u, k.scale[c], k.bias[c]);
-            }
+            colour_rows_host(colour, v, t);
+            for (int c = 0; c < C; c++) host_element(yo, k, ox, oy, c, c == 3 ? v[3] : t[bgr ? 2 - c : c]);
         }
     if (bad) return fail("internal error: a window of the triangle filter has no weight");  // (W > 0 always: DESIGN.md 19)
-    for (uint64_t e = 0; e < ys.size(); e++) {
-        if (dtype == XPNGHIP_DTYPE_F32) reinterpret_cast<float *>(out)[e] = ys[e];
-        else reinterpret_cast<uint16_t *>(out)[e] = dtype == XPNGHIP_DTYPE_F16 ? f16_bits_rne(ys[e]) : bf16_bits_rne(ys[e]);
-    }
+    for (uint64_t e = 0; e < ys.size(); e++) host_put(out, dtype, e, ys[e]);
     return 0;
 }
 extern "C" int xpnghip_resample_colour_host(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip, uint32_t out_w,
@@ -1335,6 +1354,7 @@ static int resample_cubic_host_impl(int pxsz, const uint8_t *raster, uint64_t w,
     for (uint32_t oy = 0; oy < out_h; oy++) ay[oy] = cubic_axis_host(oy, z.ky, z.rh);
     // the values first, the elements after them: a call that fails writes nothing
     std::vector<float> ys((uint64_t)C * out_h * out_w);
+    const HostOut yo{ys.data(), XPNGHIP_DTYPE_F32, planar, C, out_w, out_h};
     bool bad = false;
     for (uint32_t oy = 0; oy < out_h; oy++)
         for (uint32_t ox = 0; ox < out_w; ox++) {
@@ -1348,23 +1368,11 @@ static int resample_cubic_host_impl(int pxsz, const uint8_t *raster, uint64_t w,
                 v[sc] = x < 0.0f ? 0.0f : x > 255.0f ? 255.0f : x;  // a cubic overshoots: the clamp a uint8 pipeline applies
             }
             float t[3] = {v[0], v[1], v[2]};
-            for (int q = 0; colour && q < 3; q++) {
-                const float *m = colour + 4 * q;
-                const float a = fmaf(m[2], v[2], m[3]);
-                const float b = fmaf(m[1], v[1], a);
-                const float x = fmaf(m[0], v[0], b);
-                t[q] = x < 0.0f ? 0.0f : x > 255.0f ? 255.0f : x;
-            }
-            for (int c = 0; c < C; c++) {
-                const float u = c == 3 ? v[3] : t[bgr ? 2 - c : c];
-                ys[planar ? ((uint64_t)c * out_h + oy) * out_w + ox : ((uint64_t)oy * out_w + ox) * C + c] = fmaf(u, k.scale[c], k.bias[c]);
-            }
+            if (colour) colour_rows_host(colour, v, t);
+            for (int c = 0; c < C; c++) host_element(yo, k, ox, oy, c, c == 3 ? v[3] : t[bgr ? 2 - c : c]);
         }
     if (bad) return fail("internal error: a window of the cubic filter has no weight");  // (W > 0 always: DESIGN.md 22)
-    for (uint64_t e = 0; e < ys.size(); e++) {
-        if (dtype == XPNGHIP_DTYPE_F32) reinterpret_cast<float *>(out)[e] = ys[e];
-        else reinterpret_cast<uint16_t *>(out)[e] = dtype == XPNGHIP_DTYPE_F16 ? f16_bits_rne(ys[e]) : bf16_bits_rne(ys[e]);
-    }
+    for (uint64_t e = 0; e < ys.size(); e++) host_put(out, dtype, e, ys[e]);
     return 0;
 }
 extern "C" int xpnghip_resample_cubic_host(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip, uint32_t out_w,
@@ -1481,15 +1489,13 @@ static int resample_blur_host_impl(int pxsz, const uint8_t *raster, uint64_t w, 
         }
     }
     const bool planar = layout & XPNGHIP_LAYOUT_PLANAR, bgr = layout & XPNGHIP_LAYOUT_BGR, sol = b.solarise < 256.0f;
+    const HostOut ho{out, dtype, planar, C, out_w, out_h};
     for (uint32_t oy = 0; oy < out_h; oy++)
         for (uint32_t ox = 0; ox < out_w; ox++)
             for (int c = 0; c < C; c++) {
                 float v = T[(uint64_t)(c == 3 ? 3 : bgr ? 2 - c : c) * plane + (uint64_t)oy * out_w + ox];
                 if (c < 3 && sol && v >= b.solarise) v = 255.0f - v;
-                const float y = fmaf(v, k.scale[c], k.bias[c]);
-                const uint64_t e = planar ? ((uint64_t)c * out_h + oy) * out_w + ox : ((uint64_t)oy * out_w + ox) * C + c;
-                if (dtype == XPNGHIP_DTYPE_F32) reinterpret_cast<float *>(out)[e] = y;
-                else reinterpret_cast<uint16_t *>(out)[e] = dtype == XPNGHIP_DTYPE_F16 ? f16_bits_rne(y) : bf16_bits_rne(y);
+                host_element(ho, k, ox, oy, c, v);
             }
     return 0;
 }
@@ -1570,6 +1576,7 @@ static int resample_affine_host_impl(int pxsz, const uint8_t *raster, uint64_t w
     const float zero[4] = {0.0f, 0.0f, 0.0f, 0.0f}, *fl = fill ? fill : zero, *m = affine;
     const bool planar = layout & XPNGHIP_LAYOUT_PLANAR, bgr = layout & XPNGHIP_LAYOUT_BGR;
     const int NS = pxsz == 4 && C == 4 ? 4 : 3;
+    const HostOut ho{out, dtype, planar, C, out_w, out_h};
     const int64_t fx0 = (int64_t)F[0], fy0 = (int64_t)F[1], fx1 = fx0 + (int64_t)F[2], fy1 = fy0 + (int64_t)F[3];
     auto q = [&](int64_t j, int64_t i, int sc) {
         if (j < fx0 || j >= fx1 || i < fy0 || i >= fy1) return fl[sc];
@@ -1598,20 +1605,8 @@ static int resample_affine_host_impl(int pxsz, const uint8_t *raster, uint64_t w
                 }
             }
             float t[3] = {v[0], v[1], v[2]};
-            for (int r = 0; colour && r < 3; r++) {
-                const float *cm = colour + 4 * r;
-                const float a = fmaf(cm[2], v[2], cm[3]);
-                const float b = fmaf(cm[1], v[1], a);
-                const float x = fmaf(cm[0], v[0], b);
-                t[r] = x < 0.0f ? 0.0f : x > 255.0f ? 255.0f : x;
-            }
-            for (int c = 0; c < C; c++) {
-                const float u = c == 3 ? v[3] : t[bgr ? 2 - c : c];
-                const float y = fmaf(u, k.scale[c], k.bias[c]);
-                const uint64_t e = planar ? ((uint64_t)c * out_h + oy) * out_w + ox : ((uint64_t)oy * out_w + ox) * C + c;
-                if (dtype == XPNGHIP_DTYPE_F32) reinterpret_cast<float *>(out)[e] = y;
-                else reinterpret_cast<uint16_t *>(out)[e] = dtype == XPNGHIP_DTYPE_F16 ? f16_bits_rne(y) : bf16_bits_rne(y);
-            }
+            if (colour) colour_rows_host(colour, v, t);
+            for (int c = 0; c < C; c++) host_element(ho, k, ox, oy, c, c == 3 ? v[3] : t[bgr ? 2 - c : c]);
         }
     return 0;
 }
@@ -1962,33 +1957,55 @@ extern "C" int64_t xpnghip_affine_view_tiles(const uint64_t *dims, uint32_t nimg
 }
 extern "C" uint64_t xpnghip_ctx_last_decode_tiles(const xpnghip_ctx *c) { return c ? c->last_tiles : 0; }
 
-// what the affine form of a views call has in place of rectangles and flips: nviews * 6 floats and the fill (NULL: zeros)
-struct AffineCall {
-    const float *affines, *fill;
+// A grow-on-demand table of the views calls: `cap` is what ptr has room for, `need` what this call asks for, both in the table's
+// own unit.  A table that is too small is dropped and allocated anew.  An earlier call's copy-out may still read the old one - the
+// context's work is on these streams - so they are synchronised first, and only when there is an old table.
+#define VIEWS_TABLE(ptr, cap, need, bytes)                                                                 \
+    do {                                                                                                  \
+        if ((cap) < (need)) {                                                                             \
+            if (ptr)                                                                                      \
+                for (hipStream_t q : {s, c->stream, c->side}) if (q) HIPCHK(hipStreamSynchronize(q));     \
+            c->ws.drop((void **)&(ptr)); (cap) = 0;                                                       \
+            WS_GET(ptr, bytes);                                                                           \
+            (cap) = (need);                                                                               \
+        }                                                                                                 \
+    } while (0)
+// What the five views entry points differ in, filled by field name: the rectangles and flips (NULL: whole images, no flip), the
+// filter word, the colour matrices (nviews * 12 floats; NULL: none), whether the call takes the cubic rule (it has no filter word
+// then), the blur records (NULL: none) and, where `affine` is set, nviews * 6 floats and the fill (NULL: zeros) in place of
+// rectangles and flips
+struct ViewsCall {
+    const uint64_t *rects = nullptr;
+    const uint8_t *flips = nullptr;
+    uint32_t filter = 0;
+    const float *colours = nullptr;
+    bool cubic = false;
+    const xpnghip_view_blur *blurs = nullptr;
+    bool affine = false;
+    const float *affines = nullptr, *fill = nullptr;
 };
 static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg, const uint64_t *tile_off,
-                             uint32_t nviews, const uint32_t *view_image, void *const *d_outs, const uint32_t *out_sizes, const uint64_t *rects,
-                             const uint8_t *flips, uint32_t layout, uint32_t dtype, const float *scale, const float *bias, uint32_t filter,
-                             const float *colours, void *stream, bool cubic = false, const xpnghip_view_blur *blurs = nullptr,
-                             const AffineCall *af = nullptr) {
+                             uint32_t nviews, const uint32_t *view_image, void *const *d_outs, const uint32_t *out_sizes, uint32_t layout,
+                             uint32_t dtype, const float *scale, const float *bias, void *stream, const ViewsCall &vc) {
     // every argument is checked before anything reaches the device: a rejected call writes nothing
     int C, es;
     FloatConsts fk{};
     const FloatCall fc{dtype, scale, bias};
     if (mixed_decode_args(c, mode, d_blobs, blobs_len, nimg, d_outs, &layout, &fc, C, es, fk)) return 1;  // (everything the float call refuses)
     std::string why;
-    if (af ? !affine_filter_ok(filter, why) : !cubic && !resample_filter_ok(filter, why)) return fail(why);  // (the cubic call has no filter word)
+    const float *colours = vc.colours;  // (re-pointed below at the partitioned copy of a call with second-pass views)
+    if (vc.affine ? !affine_filter_ok(vc.filter, why) : !vc.cubic && !resample_filter_ok(vc.filter, why)) return fail(why);  // (the cubic call has no filter word)
     if (!out_sizes) return fail("out_sizes is NULL: a views call needs the pair {out_w, out_h} of every view");
-    if (af && !af->affines) return fail("affines is NULL: an affine views call needs the six floats of every view");
-    if (!view_args_ok(c->m_dims.data(), nimg, nviews, view_image, rects, why)) return fail(why);
+    if (vc.affine && !vc.affines) return fail("affines is NULL: an affine views call needs the six floats of every view");
+    if (!view_args_ok(c->m_dims.data(), nimg, nviews, view_image, vc.rects, why)) return fail(why);
     // an affine call has no rectangles and no flips: its matrices and its fill are checked in their place, and the footprints of
     // its views are the rectangles of the selection
-    std::vector<AffineRec> arecs(af ? nviews : 0);
-    std::vector<uint64_t> foot(af ? 4ull * nviews : 0);
+    std::vector<AffineRec> arecs(vc.affine ? nviews : 0);
+    std::vector<uint64_t> foot(vc.affine ? 4ull * nviews : 0);
     AffineFill afill{};
-    if (af) {
-        if (!affine_fill_ok(af->fill, why)) return fail(why);
-        for (int e = 0; af->fill && e < 4; e++) afill.v[e] = af->fill[e];
+    if (vc.affine) {
+        if (!affine_fill_ok(vc.fill, why)) return fail(why);
+        for (int e = 0; vc.fill && e < 4; e++) afill.v[e] = vc.fill[e];
     }
     const uint64_t px = (uint64_t)c->pxsz, bpr = rup(c->m_max_w * px, 16);
     std::vector<uint64_t> slot((size_t)nimg + 1, 0);  // (mixed_stage_slots' layout: the refusals below come before anything is allocated)
@@ -2000,18 +2017,18 @@ static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
         const std::string who = " (view " + std::to_string(v) + ", image " + std::to_string(i) + ")";
         ResizeRec z;
         if (!resize_size_ok(ow, oh, why)) return fail(why + who);
-        if (af) {
-            if (!affine_footprint(c->m_dims[2ull * i], c->m_dims[2ull * i + 1], af->affines + 6ull * v, ow, oh, " of view " + std::to_string(v), &foot[4ull * v], why)) return fail(why);
-        } else if (!resize_record(c->m_dims[2ull * i], c->m_dims[2ull * i + 1], rects ? rects + 4ull * v : nullptr, flips ? flips[v] : 0u, ow, oh, z, why)) return fail(why + who);
+        if (vc.affine) {
+            if (!affine_footprint(c->m_dims[2ull * i], c->m_dims[2ull * i + 1], vc.affines + 6ull * v, ow, oh, " of view " + std::to_string(v), &foot[4ull * v], why)) return fail(why);
+        } else if (!resize_record(c->m_dims[2ull * i], c->m_dims[2ull * i + 1], vc.rects ? vc.rects + 4ull * v : nullptr, vc.flips ? vc.flips[v] : 0u, ow, oh, z, why)) return fail(why + who);
         if (!d_outs[v]) return fail("null output buffer of view " + std::to_string(v));
         if ((uintptr_t)d_outs[v] & (uintptr_t)(es - 1)) {
             char b[32];
             snprintf(b, sizeof b, "%p", d_outs[v]);
             return fail("output buffer " + std::string(b) + " of view " + std::to_string(v) + " is not aligned to its " + std::to_string(es) + "-byte elements");
         }
-        if (af) {
+        if (vc.affine) {
             max_oh = std::max(max_oh, oh);
-            const float *m = af->affines + 6ull * v;
+            const float *m = vc.affines + 6ull * v;
             const uint64_t *f = &foot[4ull * v];
             arecs[v] = AffineRec{slot[i], (uint8_t *)d_outs[v], {m[0], m[1], m[2], m[3], m[4], m[5]}, ow, oh,
                                  (int32_t)f[0], (int32_t)f[1], (int32_t)(f[0] + f[2]), (int32_t)(f[1] + f[3])};
@@ -2035,12 +2052,12 @@ static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
     std::vector<BlurRec> brecs;
     std::vector<ViewColour> pcol;
     uint64_t scratch_floats = 0;
-    if (blurs) {
+    if (vc.blurs) {
         for (uint32_t v = 0; v < nviews; v++)
-            if (!blur_record_ok(blurs[v], recs[v].ow, recs[v].oh, " of view " + std::to_string(v), why)) return fail(why);
-        std::stable_partition(order.begin(), order.end(), [&](uint32_t v) { return blur_off(blurs[v]); });
+            if (!blur_record_ok(vc.blurs[v], recs[v].ow, recs[v].oh, " of view " + std::to_string(v), why)) return fail(why);
+        std::stable_partition(order.begin(), order.end(), [&](uint32_t v) { return blur_off(vc.blurs[v]); });
         nplain = 0;
-        while (nplain < nviews && blur_off(blurs[order[nplain]])) nplain++;
+        while (nplain < nviews && blur_off(vc.blurs[order[nplain]])) nplain++;
     }
     if (nplain < nviews) {
         std::vector<ViewRec> part(nviews);
@@ -2057,7 +2074,7 @@ static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
         for (uint32_t i = nplain; i < nviews; i++) {
             ViewRec &r = recs[i];
             BlurRec &b = brecs[i - nplain];
-            const xpnghip_view_blur &q = blurs[order[i]];
+            const xpnghip_view_blur &q = vc.blurs[order[i]];
             b = BlurRec{scratch_floats, r.buf, r.ow, r.oh, q.radius, q.solarise, {}};
             blur_weights(q.sigma, q.radius, b.w);
             scratch_floats += rup((uint64_t)C * r.oh * r.ow * 4, 256) / 4;  // (the slice's own planes, rounded up to 256 bytes)
@@ -2066,62 +2083,30 @@ static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
         }
     }
     std::vector<uint32_t> list;
-    view_select(c->tiles, c->m_first, c->m_list, c->m_dims.data(), nviews, view_image, af ? foot.data() : rects, list);
+    view_select(c->tiles, c->m_first, c->m_list, c->m_dims.data(), nviews, view_image, vc.affine ? foot.data() : vc.rects, list);
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(c);
     if (mixed_stage_slots(c, bpr, slot)) return 1;
-    if (af && c->cap_m_affine < nviews) {  // (the affine call's own record table: it never touches d_m_views)
-        if (c->d_m_affine) {
-            for (hipStream_t q : {s, c->stream, c->side}) if (q) HIPCHK(hipStreamSynchronize(q));
-            c->ws.drop((void **)&c->d_m_affine); c->cap_m_affine = 0;
-        }
-        WS_GET(c->d_m_affine, (uint64_t)nviews * sizeof(AffineRec));
-        c->cap_m_affine = nviews;
-    }
-    if (!af && c->cap_m_views < nviews) {
-        if (c->d_m_views) {  // (an earlier call's copy-out may still read the old table: the context's work is on these streams)
-            for (hipStream_t q : {s, c->stream, c->side}) if (q) HIPCHK(hipStreamSynchronize(q));
-            c->ws.drop((void **)&c->d_m_views); c->cap_m_views = 0;
-        }
-        WS_GET(c->d_m_views, (uint64_t)nviews * sizeof(ViewRec));
-        c->cap_m_views = nviews;
-    }
+    // (the affine call has a record table of its own and never touches d_m_views)
+    if (vc.affine) VIEWS_TABLE(c->d_m_affine, c->cap_m_affine, nviews, (uint64_t)nviews * sizeof(AffineRec));
+    else VIEWS_TABLE(c->d_m_views, c->cap_m_views, nviews, (uint64_t)nviews * sizeof(ViewRec));
     WS_GET(c->d_m_vlist, (uint64_t)c->tiles.size() * 4);
-    if (colours && c->cap_m_vcolour < nviews) {
-        if (c->d_m_vcolour) {
-            for (hipStream_t q : {s, c->stream, c->side}) if (q) HIPCHK(hipStreamSynchronize(q));
-            c->ws.drop((void **)&c->d_m_vcolour); c->cap_m_vcolour = 0;
-        }
-        WS_GET(c->d_m_vcolour, (uint64_t)nviews * sizeof(ViewColour));
-        c->cap_m_vcolour = nviews;
-    }
+    if (colours) VIEWS_TABLE(c->d_m_vcolour, c->cap_m_vcolour, nviews, (uint64_t)nviews * sizeof(ViewColour));
     if (!brecs.empty()) {
-        if (c->cap_m_bscratch < scratch_floats * 4 || c->cap_m_blur < brecs.size()) {
-            if (c->d_m_bscratch || c->d_m_blur)
-                for (hipStream_t q : {s, c->stream, c->side}) if (q) HIPCHK(hipStreamSynchronize(q));
-            if (c->cap_m_bscratch < scratch_floats * 4) {
-                c->ws.drop((void **)&c->d_m_bscratch); c->cap_m_bscratch = 0;
-                WS_GET(c->d_m_bscratch, scratch_floats * 4);
-                c->cap_m_bscratch = scratch_floats * 4;
-            }
-            if (c->cap_m_blur < brecs.size()) {
-                c->ws.drop((void **)&c->d_m_blur); c->cap_m_blur = 0;
-                WS_GET(c->d_m_blur, (uint64_t)brecs.size() * sizeof(BlurRec));
-                c->cap_m_blur = brecs.size();
-            }
-        }
+        VIEWS_TABLE(c->d_m_bscratch, c->cap_m_bscratch, scratch_floats * 4, scratch_floats * 4);
+        VIEWS_TABLE(c->d_m_blur, c->cap_m_blur, brecs.size(), (uint64_t)brecs.size() * sizeof(BlurRec));
         // the first pass of these views writes their slices of the scratch
         for (uint32_t i = nplain; i < nviews; i++) recs[i].buf = (uint8_t *)(c->d_m_bscratch + brecs[i - nplain].src);
         HIPCHK(hipMemcpyAsync(c->d_m_blur, brecs.data(), (uint64_t)brecs.size() * sizeof(BlurRec), hipMemcpyHostToDevice, s));
     }
     // the resized call's protocol: both tables are in pageable host memory that ends with this call, so the stream is synchronised
     // once behind the two copies - queued before the decode's own kernels, so the wait never covers this call's work
-    if (af) HIPCHK(hipMemcpyAsync(c->d_m_affine, arecs.data(), (uint64_t)nviews * sizeof(AffineRec), hipMemcpyHostToDevice, s));
+    if (vc.affine) HIPCHK(hipMemcpyAsync(c->d_m_affine, arecs.data(), (uint64_t)nviews * sizeof(AffineRec), hipMemcpyHostToDevice, s));
     else HIPCHK(hipMemcpyAsync(c->d_m_views, recs.data(), (uint64_t)nviews * sizeof(ViewRec), hipMemcpyHostToDevice, s));
     if (!list.empty()) HIPCHK(hipMemcpyAsync(c->d_m_vlist, list.data(), (uint64_t)list.size() * 4, hipMemcpyHostToDevice, s));
     if (colours) HIPCHK(hipMemcpyAsync(c->d_m_vcolour, colours, (uint64_t)nviews * sizeof(ViewColour), hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
-    XPNG_REQUIRE(c->d_m_first, c->d_m_stage, af ? (const void *)c->d_m_affine : (const void *)c->d_m_views, c->d_m_vlist);
+    XPNG_REQUIRE(c->d_m_first, c->d_m_stage, vc.affine ? (const void *)c->d_m_affine : (const void *)c->d_m_views, c->d_m_vlist);
     if (list.empty()) {
         // an affine call whose views all lie outside their images (every other views call selects a tile: its rectangles are not
         // empty): nothing is decoded, the status is clear and the copy-out below writes the fill
@@ -2138,29 +2123,33 @@ static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
     const uint32_t bgr = layout & XPNGHIP_LAYOUT_BGR;
     const dim3 grid((max_oh + MC_ROWS - 1) / MC_ROWS, nplain);
     if (colours) XPNG_REQUIRE(c->d_m_vcolour);
-    if (af) {  // one kernel for every view: a matrix carries the crop, the size and the mirror
+    const ViewColour *vm = colours ? c->d_m_vcolour : nullptr;
+    if (vc.affine) {  // one kernel for every view: a matrix carries the crop, the size and the mirror
         const dim3 agrid((max_oh + AF_ROWS - 1) / AF_ROWS, nviews);
-        const ViewColour *vm = colours ? c->d_m_vcolour : nullptr;
         with_3or4(c->pxsz, [&](auto PXc) { with_3or4(C, [&](auto Cc) { with_planar(layout, [&](auto PL) { with_float(dtype, [&](auto t) {
             constexpr int PXv = decltype(PXc)::value, Cv = decltype(Cc)::value;
             constexpr bool PLv = decltype(PL)::value;
 #ifdef XPNG_PROBES
             // the lane-mapping study (tools/views_affine_timing.py): the siblings' mapping, one output row per wave pass
-            if (probe_env("XPNG_AFFINE_ROW_MAP")) { k_mixed_views_affine<PXv, Cv, PLv, decltype(t), 1><<<agrid, 256, 0, s>>>(c->d_m_affine, vm, c->d_m_stage, bpr, bgr, filter, afill, fk); return; }
+            if (probe_env("XPNG_AFFINE_ROW_MAP")) { k_mixed_views_affine<PXv, Cv, PLv, decltype(t), 1><<<agrid, 256, 0, s>>>(c->d_m_affine, vm, c->d_m_stage, bpr, bgr, vc.filter, afill, fk); return; }
 #endif
-            k_mixed_views_affine<PXv, Cv, PLv, decltype(t)><<<agrid, 256, 0, s>>>(c->d_m_affine, vm, c->d_m_stage, bpr, bgr, filter, afill, fk);
+            k_mixed_views_affine<PXv, Cv, PLv, decltype(t)><<<agrid, 256, 0, s>>>(c->d_m_affine, vm, c->d_m_stage, bpr, bgr, vc.filter, afill, fk);
         }); }); }); });
         HIPCHK(hipGetLastError());
         return 0;
     }
-    if (nplain)
-    with_3or4(c->pxsz, [&](auto PXc) { with_3or4(C, [&](auto Cc) { with_planar(layout, [&](auto PL) { with_float(dtype, [&](auto t) {
-        constexpr int PXv = decltype(PXc)::value, Cv = decltype(Cc)::value;
-        constexpr bool PLv = decltype(PL)::value;
-        if (cubic) k_mixed_views_cubic<PXv, Cv, PLv, decltype(t)><<<grid, 256, 0, s>>>(c->d_m_views, colours ? c->d_m_vcolour : nullptr, c->d_m_stage, bpr, bgr, fk);
-        else if (colours) k_mixed_views_colour<PXv, Cv, PLv, decltype(t)><<<grid, 256, 0, s>>>(c->d_m_views, c->d_m_vcolour, c->d_m_stage, bpr, bgr, filter, fk);
-        else k_mixed_views_as_float<PXv, Cv, PLv, decltype(t)><<<grid, 256, 0, s>>>(c->d_m_views, c->d_m_stage, bpr, bgr, filter, fk);
-    }); }); }); });
+    // the copy-out kernel of this call's filter over the records vr (their matrices mats, or none) into buffers of layout PL and
+    // element t, as with_planar and with_float hand them over
+    auto copy_out = [&](dim3 g, const ViewRec *vr, const ViewColour *mats, auto PL, auto t, uint32_t bgr_, const FloatConsts &k) {
+        with_3or4(c->pxsz, [&](auto PXc) { with_3or4(C, [&](auto Cc) {
+            constexpr int PXv = decltype(PXc)::value, Cv = decltype(Cc)::value;
+            constexpr bool PLv = decltype(PL)::value;
+            if (vc.cubic) k_mixed_views_cubic<PXv, Cv, PLv, decltype(t)><<<g, 256, 0, s>>>(vr, mats, c->d_m_stage, bpr, bgr_, k);
+            else if (mats) k_mixed_views_colour<PXv, Cv, PLv, decltype(t)><<<g, 256, 0, s>>>(vr, mats, c->d_m_stage, bpr, bgr_, vc.filter, k);
+            else k_mixed_views_as_float<PXv, Cv, PLv, decltype(t)><<<g, 256, 0, s>>>(vr, c->d_m_stage, bpr, bgr_, vc.filter, k);
+        }); });
+    };
+    if (nplain) with_planar(layout, [&](auto PL) { with_float(dtype, [&](auto t) { copy_out(grid, c->d_m_views, vm, PL, t, bgr, fk); }); });
     HIPCHK(hipGetLastError());
     if (brecs.empty()) return 0;
     // the two passes of the views that blur or solarise: the copy-out kernel of the filter as <PX, C, planar, float> with no BGR
@@ -2169,14 +2158,7 @@ static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
     const uint32_t n2 = nviews - nplain;
     const dim3 grid1((max_oh2 + MC_ROWS - 1) / MC_ROWS, n2), grid2(max_tiles2, n2);
     const FloatConsts ident{{1.0f, 1.0f, 1.0f, 1.0f}, {0.0f, 0.0f, 0.0f, 0.0f}};
-    const ViewRec *vr2 = c->d_m_views + nplain;
-    const ViewColour *vm2 = colours ? c->d_m_vcolour + nplain : nullptr;
-    with_3or4(c->pxsz, [&](auto PXc) { with_3or4(C, [&](auto Cc) {
-        constexpr int PXv = decltype(PXc)::value, Cv = decltype(Cc)::value;
-        if (cubic) k_mixed_views_cubic<PXv, Cv, true, float><<<grid1, 256, 0, s>>>(vr2, vm2, c->d_m_stage, bpr, 0u, ident);
-        else if (colours) k_mixed_views_colour<PXv, Cv, true, float><<<grid1, 256, 0, s>>>(vr2, vm2, c->d_m_stage, bpr, 0u, filter, ident);
-        else k_mixed_views_as_float<PXv, Cv, true, float><<<grid1, 256, 0, s>>>(vr2, c->d_m_stage, bpr, 0u, filter, ident);
-    }); });
+    copy_out(grid1, c->d_m_views + nplain, vm ? vm + nplain : nullptr, std::true_type{}, float{}, 0u, ident);
     HIPCHK(hipGetLastError());
     with_3or4(C, [&](auto Cc) { with_planar(layout, [&](auto PL) { with_float(dtype, [&](auto t) {
         k_mixed_views_blur<decltype(Cc)::value, decltype(PL)::value, decltype(t)><<<grid2, 256, 0, s>>>(c->d_m_blur, c->d_m_bscratch, bgr, fk);
@@ -2188,21 +2170,27 @@ extern "C" int xpnghip_decode_varsize_device_batch_views(xpnghip_ctx *c, int mod
                                                          const uint64_t *tile_off, uint32_t nviews, const uint32_t *view_image, void *const *d_outs,
                                                          const uint32_t *out_sizes, const uint64_t *rects, const uint8_t *flips, uint32_t layout,
                                                          uint32_t dtype, const float *scale, const float *bias, uint32_t filter, void *stream) {
-    XPNG_GUARDED(decode_views_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, nviews, view_image, d_outs, out_sizes, rects, flips, layout, dtype, scale, bias, filter, nullptr, stream))
+    ViewsCall vc;
+    vc.rects = rects; vc.flips = flips; vc.filter = filter;
+    XPNG_GUARDED(decode_views_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, nviews, view_image, d_outs, out_sizes, layout, dtype, scale, bias, stream, vc))
 }
 extern "C" int xpnghip_decode_varsize_device_batch_views_colour(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
                                                                 const uint64_t *tile_off, uint32_t nviews, const uint32_t *view_image, void *const *d_outs,
                                                                 const uint32_t *out_sizes, const uint64_t *rects, const uint8_t *flips, uint32_t layout,
                                                                 uint32_t dtype, const float *scale, const float *bias, uint32_t filter, const float *colours,
                                                                 void *stream) {
-    XPNG_GUARDED(decode_views_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, nviews, view_image, d_outs, out_sizes, rects, flips, layout, dtype, scale, bias, filter, colours, stream))
+    ViewsCall vc;
+    vc.rects = rects; vc.flips = flips; vc.filter = filter; vc.colours = colours;
+    XPNG_GUARDED(decode_views_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, nviews, view_image, d_outs, out_sizes, layout, dtype, scale, bias, stream, vc))
 }
 // the views-colour call without a filter word: always the cubic rule (mixed_views_cubic.hpp)
 extern "C" int xpnghip_decode_varsize_device_batch_views_cubic(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
                                                                const uint64_t *tile_off, uint32_t nviews, const uint32_t *view_image, void *const *d_outs,
                                                                const uint32_t *out_sizes, const uint64_t *rects, const uint8_t *flips, uint32_t layout,
                                                                uint32_t dtype, const float *scale, const float *bias, const float *colours, void *stream) {
-    XPNG_GUARDED(decode_views_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, nviews, view_image, d_outs, out_sizes, rects, flips, layout, dtype, scale, bias, 0, colours, stream, true))
+    ViewsCall vc;
+    vc.rects = rects; vc.flips = flips; vc.colours = colours; vc.cubic = true;
+    XPNG_GUARDED(decode_views_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, nviews, view_image, d_outs, out_sizes, layout, dtype, scale, bias, stream, vc))
 }
 // the views-colour call plus one blur record per view (mixed_views_blur.hpp); filter 2 is the cubic rule, blurs == NULL the
 // underlying call itself
@@ -2213,8 +2201,11 @@ extern "C" int xpnghip_decode_varsize_device_batch_views_blur(xpnghip_ctx *c, in
                                                               const xpnghip_view_blur *blurs, void *stream) {
     std::string why;
     if (!blur_filter_ok(filter, why)) return fail(why);
-    const bool cubic = filter == XPNGHIP_FILTER_CUBIC_AA;
-    XPNG_GUARDED(decode_views_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, nviews, view_image, d_outs, out_sizes, rects, flips, layout, dtype, scale, bias, cubic ? 0 : filter, colours, stream, cubic, blurs))
+    ViewsCall vc;
+    vc.rects = rects; vc.flips = flips; vc.colours = colours; vc.blurs = blurs;
+    vc.cubic = filter == XPNGHIP_FILTER_CUBIC_AA;
+    vc.filter = vc.cubic ? 0 : filter;
+    XPNG_GUARDED(decode_views_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, nviews, view_image, d_outs, out_sizes, layout, dtype, scale, bias, stream, vc))
 }
 // the views-colour call with a matrix per view in place of its rectangle and flip, and one fill (mixed_views_affine.hpp)
 extern "C" int xpnghip_decode_varsize_device_batch_views_affine(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
@@ -2222,8 +2213,9 @@ extern "C" int xpnghip_decode_varsize_device_batch_views_affine(xpnghip_ctx *c, 
                                                                 const uint32_t *out_sizes, const float *affines, const float *fill, uint32_t layout,
                                                                 uint32_t dtype, const float *scale, const float *bias, uint32_t filter, const float *colours,
                                                                 void *stream) {
-    const AffineCall af{affines, fill};
-    XPNG_GUARDED(decode_views_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, nviews, view_image, d_outs, out_sizes, nullptr, nullptr, layout, dtype, scale, bias, filter, colours, stream, false, nullptr, &af))
+    ViewsCall vc;
+    vc.filter = filter; vc.colours = colours; vc.affine = true; vc.affines = affines; vc.fill = fill;
+    XPNG_GUARDED(decode_views_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, nviews, view_image, d_outs, out_sizes, layout, dtype, scale, bias, stream, vc))
 }
 
 // ---- mixed-size batch encode (mixed.hpp) ---------------------------------------------------------
