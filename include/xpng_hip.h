@@ -685,6 +685,78 @@ int xpnghip_decode_varsize_device_batch_views_affine(xpnghip_ctx *ctx, int mode,
                                                      uint32_t dtype, const float *scale, const float *bias, uint32_t filter,
                                                      const float *colours, void *stream);
 
+/* ---- autocontrast, equalise, posterise, solarise and invert per view -------------------------
+ * The tone operations of AutoAugment, RandAugment and TrivialAugment, in any order, behind the blur call or the affine call.
+ * Autocontrast and equalise need a statistic over the whole finished plane, so a view with a step takes a second pass.  One
+ * 20-byte TONE RECORD per view, up to four steps executed in order: */
+typedef struct { uint8_t op[4]; float arg[4]; } xpnghip_view_tone;   /* 20 bytes */
+#define XPNGHIP_TONE_NONE 0u          /* arg 0 */
+#define XPNGHIP_TONE_AUTOCONTRAST 1u  /* arg 0 */
+#define XPNGHIP_TONE_EQUALISE 2u      /* arg 0 */
+#define XPNGHIP_TONE_POSTERISE 3u     /* arg = bits, an integer 0 .. 8 */
+#define XPNGHIP_TONE_SOLARISE 4u      /* arg = threshold, 0 .. 255 */
+#define XPNGHIP_TONE_INVERT 5u        /* arg 0 */
+/* Steps are contiguous from index 0: after the first NONE every later op is NONE.
+ * THE RULE.  The steps run on the three colour planes - alpha, or the 255 an RGB context lacks, passes through untouched - on
+ * exactly the values q the underlying call would hand to scale / bias: after resampling, colour matrix, blur and its clamp and the
+ * blur record's own solarise; before the constants, the BGR exchange and the narrowing.  Per colour plane, N = out_h * out_w:
+ *     entry          b = q > 0.0f ? (q > 255.0f ? 255.0f : q) : 0.0f
+ *                    (a clamp that also maps -0.0f to +0.0f: every later value is a non-negative float in 0 .. 255)
+ *     autocontrast   lo, hi = the minimum and maximum of the plane as the earlier steps left it.  hi == lo: unchanged.  Otherwise
+ *                    s = 255.0f / (hi - lo), an fp32 subtraction and a correctly rounded fp32 division; where s is infinite
+ *                    (hi - lo below about 7.5e-37) the plane is unchanged too; t = (b - lo) * s, an fp32
+ *                    subtraction and an fp32 multiplication, never fused; b = t > 255.0f ? 255.0f : t
+ *                    (torchvision's autocontrast on a float tensor, in byte units)
+ *     equalise       n = (uint32_t)rintf(b), ties to even, 0 .. 255; h[n] the count of n over the plane; last = the highest non-empty
+ *                    bin; step = (N - h[last]) / 255 in integers.  step == 0: unchanged (fractional values stay fractional).
+ *                    Otherwise b = (float)min(255, (step / 2 + h[0] + .. + h[n - 1]) / step), integer division
+ *                    (on integer-valued planes PIL's ImageOps.equalize and torchvision's equalize, value for value)
+ *     posterise k    m = 2^(8 - k); b = b - fmodf(b, m), exact in fp32.  k = 8 floors a fractional value, k = 0 gives 0
+ *                    (on integer values b & mask: ImageOps.posterize)
+ *     solarise thr   b = b >= thr ? 255.0f - b : b
+ *     invert         b = 255.0f - b
+ * A step's statistics are taken over the plane as all earlier steps left it.  Minimum, maximum and integer counts do not depend on
+ * the order in which a plane is reduced, so the device calls below equal the host functions bit for bit.
+ * Refused, before anything is written or reaches the device, with a text that names the view (in the device calls) and the step:
+ * an op above 5; a non-NONE op after a NONE; a non-zero arg on an op that takes none; posterise bits that are not an integer in
+ * 0 .. 8; a threshold that is not finite or lies outside 0 .. 255; everything the underlying call refuses.
+ * Not offered: sharpness (a stencil: it belongs with the blur); torchvision's contrast about the image's own mean (a float mean
+ * depends on the order of summation); blur under a warp; more than four steps; uint8 outputs.
+ * host-only, need no device, and they are the rule: xpnghip_resample_blur_host's and xpnghip_resample_affine_host's arguments plus
+ * one tone record (NULL: no step, the underlying function's bits). */
+int xpnghip_resample_tone_host(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip,
+                               uint32_t out_w, uint32_t out_h, uint32_t layout, uint32_t dtype, const float *scale,
+                               const float *bias, uint32_t filter, const float *colour, const xpnghip_view_blur *blur,
+                               const xpnghip_view_tone *tone, void *out);
+int xpnghip_resample_affine_tone_host(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const float *affine, uint32_t out_w,
+                                      uint32_t out_h, uint32_t layout, uint32_t dtype, const float *scale, const float *bias,
+                                      uint32_t filter, const float *fill, const float *colour, const xpnghip_view_tone *tone,
+                                      void *out);
+/* The blur call and the affine call with `tones` (nviews records on the host, or NULL) in front of `stream`.  View v receives, bit
+ * for bit, what the host function above writes with its record.  tones == NULL, or records that are all NONE, IS the underlying
+ * call: same kernels, same bytes, nothing more allocated or uploaded.  In the blur form blurs and colours may be NULL and filter is
+ * 0, 1 or 2; in the affine form filter is 0 or 3, the fill pixels take part in the statistics, and blur under a warp stays not
+ * offered.  A view with a step is a second-pass view: the copy-out kernel of the call writes its fp32 planes into the scratch of the
+ * blur call (a second slice of the same size where the view also blurs); per step index one statistics launch (only where some
+ * view's step there is autocontrast or equalise) and one apply launch rewrite the planes in place
+ * (xpng_amd/csrc/mixed_views_tone.hpp); the blur call's second kernel, with a record that is all off, writes the caller's buffer.
+ * The workspace gains one 48-byte record per tone view and one statistics slot of 3096 bytes per (tone view, statistics step),
+ * zeroed on the stream by every call, both counted by xpnghip_ctx_workspace_bytes and grown only when a call needs more than any
+ * call before it. */
+int xpnghip_decode_varsize_device_batch_views_tone(xpnghip_ctx *ctx, int mode, const void *const *d_blobs, const uint64_t *blobs_len,
+                                                   uint32_t nimg, const uint64_t *tile_off, uint32_t nviews,
+                                                   const uint32_t *view_image, void *const *d_outs, const uint32_t *out_sizes,
+                                                   const uint64_t *rects, const uint8_t *flips, uint32_t layout, uint32_t dtype,
+                                                   const float *scale, const float *bias, uint32_t filter, const float *colours,
+                                                   const xpnghip_view_blur *blurs, const xpnghip_view_tone *tones, void *stream);
+int xpnghip_decode_varsize_device_batch_views_affine_tone(xpnghip_ctx *ctx, int mode, const void *const *d_blobs,
+                                                          const uint64_t *blobs_len, uint32_t nimg, const uint64_t *tile_off,
+                                                          uint32_t nviews, const uint32_t *view_image, void *const *d_outs,
+                                                          const uint32_t *out_sizes, const float *affines /* nviews * 6 */,
+                                                          const float *fill, uint32_t layout, uint32_t dtype, const float *scale,
+                                                          const float *bias, uint32_t filter, const float *colours,
+                                                          const xpnghip_view_tone *tones, void *stream);
+
 /* ---- staged batch from device tensors: the inverse of the float call --------------------------
  * A model writes floats, not the file's bytes.  The call below is xpnghip_images_begin with the upload replaced by one staging
  * kernel that reads the caller's DEVICE buffers - planar or interleaved, RGB or BGR, uint8, f16, bf16 or f32 - and writes the

@@ -43,6 +43,8 @@ HIP_SYMBOLS = [
     "xpnghip_blur_weights", "xpnghip_resample_blur_host", "xpnghip_decode_varsize_device_batch_views_blur",
     "xpnghip_affine_footprint", "xpnghip_resample_affine_host", "xpnghip_affine_view_tiles",
     "xpnghip_decode_varsize_device_batch_views_affine",
+    "xpnghip_resample_tone_host", "xpnghip_resample_affine_tone_host",
+    "xpnghip_decode_varsize_device_batch_views_tone", "xpnghip_decode_varsize_device_batch_views_affine_tone",
 ]
 HOST_SYMBOLS = ["xpng_store", "xpng_load", "xpng_from_jpg", "xpng_store_T", "xpng_load_T", "xpng_from_jpg_T",
                 "store_7", "load_7"]
@@ -80,6 +82,10 @@ _probes = None
 
 class ViewBlur(C.Structure):  # include/xpng_hip.h xpnghip_view_blur
     _fields_ = [("sigma", C.c_float), ("radius", C.c_uint32), ("solarise", C.c_float), ("reserved", C.c_uint32)]
+
+
+class ViewTone(C.Structure):  # include/xpng_hip.h xpnghip_view_tone
+    _fields_ = [("op", C.c_uint8 * 4), ("arg", C.c_float * 4)]
 
 
 def _bind_hip(path):
@@ -240,6 +246,20 @@ def _bind_hip(path):
         L.xpnghip_decode_varsize_device_batch_views_affine.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64), C.c_uint32, C.POINTER(u64), C.c_uint32,
                                                                        u32p, C.POINTER(vp), u32p, f32p, f32p, C.c_uint32, C.c_uint32, f32p, f32p,
                                                                        C.c_uint32, f32p, vp]
+        L.xpnghip_resample_tone_host.restype = C.c_int
+        L.xpnghip_resample_tone_host.argtypes = [C.c_int, vp, u64, u64, C.POINTER(u64), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                 f32p, f32p, C.c_uint32, f32p, C.POINTER(ViewBlur), C.POINTER(ViewTone), vp]
+        L.xpnghip_resample_affine_tone_host.restype = C.c_int
+        L.xpnghip_resample_affine_tone_host.argtypes = [C.c_int, vp, u64, u64, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32p, f32p,
+                                                        C.c_uint32, f32p, f32p, C.POINTER(ViewTone), vp]
+        L.xpnghip_decode_varsize_device_batch_views_tone.restype = C.c_int
+        L.xpnghip_decode_varsize_device_batch_views_tone.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64), C.c_uint32, C.POINTER(u64), C.c_uint32,
+                                                                     u32p, C.POINTER(vp), u32p, C.POINTER(u64), u8p, C.c_uint32, C.c_uint32, f32p,
+                                                                     f32p, C.c_uint32, f32p, C.POINTER(ViewBlur), C.POINTER(ViewTone), vp]
+        L.xpnghip_decode_varsize_device_batch_views_affine_tone.restype = C.c_int
+        L.xpnghip_decode_varsize_device_batch_views_affine_tone.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64), C.c_uint32, C.POINTER(u64),
+                                                                            C.c_uint32, u32p, C.POINTER(vp), u32p, f32p, f32p, C.c_uint32, C.c_uint32,
+                                                                            f32p, f32p, C.c_uint32, f32p, C.POINTER(ViewTone), vp]
         L.xpnghip_view_tiles.restype = C.c_int64
         L.xpnghip_view_tiles.argtypes = [C.POINTER(u64), C.c_uint32, C.c_uint32, u32p, C.POINTER(u64), u32p, u64]
         L.xpnghip_ctx_last_decode_tiles.restype = u64
@@ -942,6 +962,81 @@ def resample_affine_host(raster, size, matrix, layout: int, dtype: int, scale=No
     return buf.tobytes()[:ch * oh * ow * dtype_bytes(dtype)]
 
 
+# the ops of a tone record (include/xpng_hip.h XPNGHIP_TONE_*)
+TONE_NONE, TONE_AUTOCONTRAST, TONE_EQUALISE, TONE_POSTERISE, TONE_SOLARISE, TONE_INVERT = 0, 1, 2, 3, 4, 5
+
+
+def _tone_record(name, t):
+    """None or up to four (op, arg) pairs - a bare op stands for (op, 0) - as a ViewTone; the library checks the values"""
+    if isinstance(t, ViewTone):
+        return t
+    rec = ViewTone()
+    try:
+        steps = [] if t is None else list(t)
+        if len(steps) > 4:
+            raise XpngError(f"{name}: a tone entry has at most four steps, not {len(steps)}")
+        for i, st in enumerate(steps):
+            op, arg = st if hasattr(st, "__len__") else (st, 0.0)
+            rec.op[i], rec.arg[i] = int(op) & 0xFF if 0 <= int(op) <= 255 else 255, float(arg)
+    except (TypeError, ValueError):
+        raise XpngError(f"{name}: a tone entry is None or up to four (op, arg) pairs, not {t!r}") from None
+    return rec
+
+
+def resample_tone_host(raster, size, layout: int, dtype: int, scale=None, bias=None, rect=None, flip=False, filter: int = FILTER_TRIANGLE_AA,
+                       colour=None, blur=None, tone=None) -> bytes:
+    """The rule of MixedContext.decode_batch_views_tone on the host (xpnghip_resample_tone_host; needs no device):
+    resample_blur_host's arguments plus tone = None or up to four (op, arg) steps, executed in order on the three colour planes of
+    the values resample_blur_host would hand to the constants: TONE_AUTOCONTRAST, TONE_EQUALISE, (TONE_POSTERISE, bits),
+    (TONE_SOLARISE, threshold), TONE_INVERT.  tone None gives resample_blur_host's bytes.  Returns the C * OH * OW elements of
+    `dtype` in `layout` as raw bytes, bit for bit what the device call writes for these pixels."""
+    r = np.ascontiguousarray(raster, dtype=np.uint8)
+    if r.ndim != 3 or r.shape[2] not in (3, 4):
+        raise XpngError("resample_tone_host: the raster must be (h, w, 3) or (h, w, 4) uint8")
+    try:
+        oh, ow = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise XpngError(f"resample_tone_host: size must be (OH, OW), not {size!r}") from None
+    px = r.shape[2]
+    sc, bi, ch = _scale_bias(layout, px, scale, bias)
+    ra = _rect_array("resample_tone_host", None if rect is None else [rect], 1)
+    cm = None if colour is None else (C.c_float * 12)(*_colour12("resample_tone_host", colour))
+    rec = _blur_record("resample_tone_host", blur)
+    tr = _tone_record("resample_tone_host", tone)
+    ok = ch > 0 and 1 <= oh <= 16384 and 1 <= ow <= 16384          # (anything else the library refuses, naming the value)
+    buf = np.empty(ch * oh * ow if ok else 1, dtype=np.uint32)     # 4-byte aligned, room for the widest element
+    if hip_lib().xpnghip_resample_tone_host(px, r.ctypes.data, r.shape[1], r.shape[0], ra, int(flip), ow & 0xFFFFFFFF, oh & 0xFFFFFFFF, layout, dtype,
+                                            sc, bi, int(filter) & 0xFFFFFFFF, cm, C.byref(rec), C.byref(tr), buf.ctypes.data):
+        raise XpngError("xpnghip_resample_tone_host: " + _err())
+    return buf.tobytes()[:ch * oh * ow * dtype_bytes(dtype)]
+
+
+def resample_affine_tone_host(raster, size, matrix, layout: int, dtype: int, scale=None, bias=None, filter: int = FILTER_BILINEAR, fill=None,
+                              colour=None, tone=None) -> bytes:
+    """The rule of MixedContext.decode_batch_views_affine_tone on the host (xpnghip_resample_affine_tone_host; needs no device):
+    resample_affine_host's arguments plus tone as resample_tone_host takes it.  The fill pixels take part in the statistics of
+    autocontrast and equalise.  tone None gives resample_affine_host's bytes."""
+    r = np.ascontiguousarray(raster, dtype=np.uint8)
+    if r.ndim != 3 or r.shape[2] not in (3, 4):
+        raise XpngError("resample_affine_tone_host: the raster must be (h, w, 3) or (h, w, 4) uint8")
+    try:
+        oh, ow = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise XpngError(f"resample_affine_tone_host: size must be (OH, OW), not {size!r}") from None
+    px = r.shape[2]
+    sc, bi, ch = _scale_bias(layout, px, scale, bias)
+    am = (C.c_float * 6)(*_affine6("resample_affine_tone_host", matrix))
+    fl = _fill4("resample_affine_tone_host", fill)
+    cm = None if colour is None else (C.c_float * 12)(*_colour12("resample_affine_tone_host", colour))
+    tr = _tone_record("resample_affine_tone_host", tone)
+    ok = ch > 0 and 1 <= oh <= 16384 and 1 <= ow <= 16384          # (anything else the library refuses, naming the value)
+    buf = np.empty(ch * oh * ow if ok else 1, dtype=np.uint32)     # 4-byte aligned, room for the widest element
+    if hip_lib().xpnghip_resample_affine_tone_host(px, r.ctypes.data, r.shape[1], r.shape[0], am, ow & 0xFFFFFFFF, oh & 0xFFFFFFFF, layout, dtype, sc,
+                                                   bi, int(filter) & 0xFFFFFFFF, fl, cm, C.byref(tr), buf.ctypes.data):
+        raise XpngError("xpnghip_resample_affine_tone_host: " + _err())
+    return buf.tobytes()[:ch * oh * ow * dtype_bytes(dtype)]
+
+
 def quantize_host(src, npx: int, channels: int, layout: int, dtype: int, scale=None, bias=None) -> np.ndarray:
     """The quantisation rule of StagedImages.from_device on the host (xpnghip_quantize_host; needs no device): `src` is a tight
     buffer of channels * npx elements of `dtype` (0 = uint8, DTYPE_F16, DTYPE_BF16, DTYPE_F32) in `layout` (LAYOUT_PLANAR and
@@ -1414,6 +1509,55 @@ class MixedContext(_Handle):
         vi, so, sc, bi = self._view_args(name, view_image, sizes, layout, scale, bias, n)
         self._decode("xpnghip_decode_varsize_device_batch_views_affine", mode, d_blobs, lens, d_outs, tile_offs, stream, so, am, _fill4(name, fill), layout,
                      dtype, sc, bi, int(filter) & 0xFFFFFFFF, cm, before=(n, vi))
+
+    def _tone_table(self, name, tones, n):
+        """tones (None stays None) as the C array of n records"""
+        if tones is None:
+            return None
+        tones = list(tones)
+        if len(tones) != n:
+            raise XpngError(f"{name}: tones has {len(tones)} entries for {n} views")
+        return (ViewTone * max(n, 1))(*[_tone_record(f"{name}: tones[{v}]", t) for v, t in enumerate(tones)])
+
+    def decode_batch_views_tone(self, mode, d_blobs, lens, view_image, d_outs, layout, dtype, sizes, scale=None, bias=None, rects=None, flips=None,
+                                filter: int = FILTER_TRIANGLE_AA, tile_offs=None, stream=0, colours=None, blurs=None, tones=None):
+        """decode_batch_views_blur plus tone steps per view: tones is None or one entry per view, each None or a list of up to four
+        (op, arg) pairs as resample_tone_host takes them, and view v equals that function's bytes.  A view with a step takes the
+        second pass over fp32 planes in the context's workspace, where its statistics are reduced and its steps applied in place.
+        tones None, or every entry None, is decode_batch_views_blur itself:
+        xpnghip_decode_varsize_device_batch_views_tone (the rule is in include/xpng_hip.h)."""
+        name = "decode_batch_views_tone"
+        n = len(d_outs)
+        br = None
+        if blurs is not None:
+            blurs = list(blurs)
+            if len(blurs) != n:
+                raise XpngError(f"{name}: blurs has {len(blurs)} entries for {n} views")
+            br = (ViewBlur * max(n, 1))(*[_blur_record(f"{name}: blurs[{v}]", b) for v, b in enumerate(blurs)])
+        tr = self._tone_table(name, tones, n)
+        cm = _colour_table(name, colours, n)
+        vi, so, sc, bi = self._view_args(name, view_image, sizes, layout, scale, bias, n)
+        ra = _rect_array(name, rects, n)
+        fl = _flip_array(name, flips, n, "views")
+        self._decode("xpnghip_decode_varsize_device_batch_views_tone", mode, d_blobs, lens, d_outs, tile_offs, stream, so, ra, fl, layout, dtype,
+                     sc, bi, int(filter) & 0xFFFFFFFF, cm, br, tr, before=(n, vi))
+
+    def decode_batch_views_affine_tone(self, mode, d_blobs, lens, view_image, d_outs, layout, dtype, sizes, matrices, scale=None, bias=None,
+                                       filter: int = FILTER_BILINEAR, fill=None, tile_offs=None, stream=0, colours=None, tones=None):
+        """decode_batch_views_affine plus tone steps per view, as decode_batch_views_tone takes them; the fill pixels take part in
+        the statistics.  View v equals resample_affine_tone_host's bytes; tones None is decode_batch_views_affine itself:
+        xpnghip_decode_varsize_device_batch_views_affine_tone (the rule is in include/xpng_hip.h)."""
+        name = "decode_batch_views_affine_tone"
+        n = len(d_outs)
+        matrices = list(matrices)
+        if len(matrices) != n:
+            raise XpngError(f"{name}: matrices has {len(matrices)} entries for {n} views")
+        am = (C.c_float * max(6 * n, 1))(*[x for v, m in enumerate(matrices) for x in _affine6(f"{name}: matrices[{v}]", m)])
+        tr = self._tone_table(name, tones, n)
+        cm = _colour_table(name, colours, n)
+        vi, so, sc, bi = self._view_args(name, view_image, sizes, layout, scale, bias, n)
+        self._decode("xpnghip_decode_varsize_device_batch_views_affine_tone", mode, d_blobs, lens, d_outs, tile_offs, stream, so, am,
+                     _fill4(name, fill), layout, dtype, sc, bi, int(filter) & 0xFFFFFFFF, cm, tr, before=(n, vi))
 
     def last_decode_tiles(self) -> int:
         """tile work items of the context's most recent decode launch (xpnghip_ctx_last_decode_tiles): n_tiles after the other

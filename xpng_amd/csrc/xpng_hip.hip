@@ -39,6 +39,7 @@
 #include "mixed_views_cubic.hpp"
 #include "mixed_views_blur.hpp"
 #include "mixed_views_affine.hpp"
+#include "mixed_views_tone.hpp"
 #include "stage_from.hpp"
 
 using namespace xpng;
@@ -236,6 +237,12 @@ struct xpnghip_ctx {
     // dropped and uploaded as d_m_views is; no other call allocates it
     AffineRec *d_m_affine = nullptr;
     uint64_t cap_m_affine = 0;         // records d_m_affine has room for
+    // ... and, for a call with tone steps only (mixed_views_tone.hpp), one 48-byte record per view with a step and one statistics slot
+    // per (such view, autocontrast or equalise step): grown and dropped as d_m_views is; the slots are zeroed on the stream by every call
+    ToneRec *d_m_tone = nullptr;
+    uint64_t cap_m_tone = 0;           // records d_m_tone has room for
+    uint32_t *d_m_tstat = nullptr;
+    uint64_t cap_m_tstat = 0;          // slots d_m_tstat has room for
     uint64_t last_tiles = 0;           // tile work items of the most recent decode launch (xpnghip_ctx_last_decode_tiles)
 };
 
@@ -1615,6 +1622,137 @@ extern "C" int xpnghip_resample_affine_host(int pxsz, const uint8_t *raster, uin
                                             const float *colour, void *out) {
     XPNG_GUARDED(resample_affine_host_impl(pxsz, raster, w, h, affine, out_w, out_h, layout, dtype, scale, bias, filter, fill, colour, out))
 }
+// ---- tone steps behind the blur call or the affine call (mixed_views_tone.hpp) ----------------------------------
+static const char *const TONE_NAMES[6] = {"none", "autocontrast", "equalise", "posterise", "solarise", "invert"};
+// a whole record.  `who` names the view in a device call
+static bool tone_record_ok(const xpnghip_view_tone &t, const std::string &who, std::string &why) {
+    bool ended = false;
+    for (int i = 0; i < 4; i++) {
+        const uint32_t op = t.op[i];
+        const float a = t.arg[i];
+        const std::string at = "bad tone" + who + ", step " + std::to_string(i) + ": ";
+        if (op > XPNGHIP_TONE_INVERT) { why = at + "op is " + std::to_string(op) + ", not 0 .. 5"; return false; }
+        if (op != XPNGHIP_TONE_NONE && ended) { why = at + TONE_NAMES[op] + " follows a step that is NONE (steps are contiguous from index 0)"; return false; }
+        if (op == XPNGHIP_TONE_NONE) ended = true;
+        if (op == XPNGHIP_TONE_POSTERISE) {
+            if (!(a >= 0.0f && a <= 8.0f && a == floorf(a))) { why = at + "posterise bits are " + blur_num(a) + ", not an integer in 0 .. 8"; return false; }
+        } else if (op == XPNGHIP_TONE_SOLARISE) {
+            if (!(a >= 0.0f && a <= 255.0f)) { why = at + "solarise threshold is " + blur_num(a) + " (it must be finite and lie in 0 .. 255)"; return false; }
+        } else if (!(a == 0.0f)) {
+            why = at + "arg is " + blur_num(a) + " on " + TONE_NAMES[op] + ", which takes none (it must be 0)";
+            return false;
+        }
+    }
+    return true;
+}
+static bool tone_off(const xpnghip_view_tone &t) { return t.op[0] == XPNGHIP_TONE_NONE; }  // (of a checked record)
+// The steps of a checked record on the three colour planes of T (planes of N floats back to back), in the header's words: it IS
+// the rule of the tone calls.  Contraction off; the product of autocontrast is an operation of its own.
+static void tone_planes_host(float *T, uint64_t N, const xpnghip_view_tone &t) {
+#pragma clang fp contract(off)
+    for (int q = 0; q < 3; q++) {
+        float *p = T + (uint64_t)q * N;
+        for (uint64_t i = 0; i < N; i++) p[i] = p[i] > 0.0f ? (p[i] > 255.0f ? 255.0f : p[i]) : 0.0f;
+        for (int si = 0; si < 4 && t.op[si] != XPNGHIP_TONE_NONE; si++) {
+            const float a = t.arg[si];
+            switch (t.op[si]) {
+            case XPNGHIP_TONE_AUTOCONTRAST: {
+                float lo = p[0], hi = p[0];
+                for (uint64_t i = 1; i < N; i++) { lo = p[i] < lo ? p[i] : lo; hi = p[i] > hi ? p[i] : hi; }
+                if (hi == lo) break;
+                const float d = hi - lo;
+                const float s = 255.0f / d;
+                if (std::isinf(s)) break;  // (d below about 7.5e-37: s is infinite and the plane stays as it is)
+                for (uint64_t i = 0; i < N; i++) {
+                    const float e = p[i] - lo;
+                    const float x = e * s;
+                    p[i] = x > 255.0f ? 255.0f : x;
+                }
+                break;
+            }
+            case XPNGHIP_TONE_EQUALISE: {
+                uint64_t hst[256] = {};
+                for (uint64_t i = 0; i < N; i++) hst[(uint32_t)rintf(p[i])]++;
+                int last = 255;
+                while (!hst[last]) last--;
+                const uint64_t step = (N - hst[last]) / 255;
+                if (!step) break;
+                float lut[256];
+                uint64_t sum = step / 2;
+                for (int n = 0; n < 256; n++) { lut[n] = (float)std::min<uint64_t>(255, sum / step); sum += hst[n]; }
+                for (uint64_t i = 0; i < N; i++) p[i] = lut[(uint32_t)rintf(p[i])];
+                break;
+            }
+            case XPNGHIP_TONE_POSTERISE: {
+                const float m = (float)(1u << (8u - (uint32_t)a));
+                for (uint64_t i = 0; i < N; i++) p[i] = p[i] - fmodf(p[i], m);
+                break;
+            }
+            case XPNGHIP_TONE_SOLARISE:
+                for (uint64_t i = 0; i < N; i++) p[i] = p[i] >= a ? 255.0f - p[i] : p[i];
+                break;
+            default:  // invert
+                for (uint64_t i = 0; i < N; i++) p[i] = 255.0f - p[i];
+            }
+        }
+    }
+}
+// what the two host rules share: `under` writes the underlying call's values as C fp32 planes (identity constants, no BGR exchange)
+// - its own checks included -, the steps run on them, and the caller's constants, colour order, layout and dtype come last
+template <class F> static int tone_host_tail(int C, const FloatConsts &k, uint32_t out_w, uint32_t out_h, uint32_t layout, uint32_t dtype, const xpnghip_view_tone &tone,
+                                              void *out, F under) {
+    const uint64_t plane = (uint64_t)out_h * out_w;
+    std::vector<float> T((uint64_t)C * plane);
+    const float one[4] = {1.0f, 1.0f, 1.0f, 1.0f}, zero[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (under(XPNGHIP_LAYOUT_PLANAR | ((uint32_t)C << 8), one, zero, T.data())) return 1;
+    tone_planes_host(T.data(), plane, tone);
+    const bool planar = layout & XPNGHIP_LAYOUT_PLANAR, bgr = layout & XPNGHIP_LAYOUT_BGR;
+    const HostOut ho{out, dtype, planar, C, out_w, out_h};
+    for (uint32_t oy = 0; oy < out_h; oy++)
+        for (uint32_t ox = 0; ox < out_w; ox++)
+            for (int c = 0; c < C; c++) host_element(ho, k, ox, oy, c, T[(uint64_t)(c == 3 ? 3 : bgr ? 2 - c : c) * plane + (uint64_t)oy * out_w + ox]);
+    return 0;
+}
+static int resample_tone_host_impl(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip, uint32_t out_w, uint32_t out_h,
+                                   uint32_t layout, uint32_t dtype, const float *scale, const float *bias, uint32_t filter, const float *colour,
+                                   const xpnghip_view_blur *blur, const xpnghip_view_tone *tone, void *out) {
+    std::string why;
+    if (tone && !tone_record_ok(*tone, "", why)) return fail(why);
+    if (!tone || tone_off(*tone)) return resample_blur_host_impl(pxsz, raster, w, h, rect, flip, out_w, out_h, layout, dtype, scale, bias, filter, colour, blur, out);
+    if (!blur_filter_ok(filter, why)) return fail(why);
+    int C;
+    FloatConsts k;
+    ResizeRec z0;
+    if (resize_host_args("xpnghip_resample_tone_host", pxsz, raster, w, h, rect, flip, out_w, out_h, layout, dtype, scale, bias, out, C, k, z0)) return 1;
+    return tone_host_tail(C, k, out_w, out_h, layout, dtype, *tone, out, [&](uint32_t tl, const float *one, const float *zero, float *T) {
+        return resample_blur_host_impl(pxsz, raster, w, h, rect, flip, out_w, out_h, tl, XPNGHIP_DTYPE_F32, one, zero, filter, colour, blur, T);
+    });
+}
+extern "C" int xpnghip_resample_tone_host(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const uint64_t *rect, int flip, uint32_t out_w,
+                                          uint32_t out_h, uint32_t layout, uint32_t dtype, const float *scale, const float *bias, uint32_t filter,
+                                          const float *colour, const xpnghip_view_blur *blur, const xpnghip_view_tone *tone, void *out) {
+    XPNG_GUARDED(resample_tone_host_impl(pxsz, raster, w, h, rect, flip, out_w, out_h, layout, dtype, scale, bias, filter, colour, blur, tone, out))
+}
+static int resample_affine_tone_host_impl(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const float *affine, uint32_t out_w, uint32_t out_h,
+                                          uint32_t layout, uint32_t dtype, const float *scale, const float *bias, uint32_t filter, const float *fill,
+                                          const float *colour, const xpnghip_view_tone *tone, void *out) {
+    std::string why;
+    if (tone && !tone_record_ok(*tone, "", why)) return fail(why);
+    if (!tone || tone_off(*tone)) return resample_affine_host_impl(pxsz, raster, w, h, affine, out_w, out_h, layout, dtype, scale, bias, filter, fill, colour, out);
+    if (!affine_filter_ok(filter, why)) return fail(why);
+    int C;
+    FloatConsts k;
+    ResizeRec z0;
+    if (resize_host_args("xpnghip_resample_affine_tone_host", pxsz, raster, w, h, nullptr, 0, out_w, out_h, layout, dtype, scale, bias, out, C, k, z0)) return 1;
+    return tone_host_tail(C, k, out_w, out_h, layout, dtype, *tone, out, [&](uint32_t tl, const float *one, const float *zero, float *T) {
+        return resample_affine_host_impl(pxsz, raster, w, h, affine, out_w, out_h, tl, XPNGHIP_DTYPE_F32, one, zero, filter, fill, colour, T);
+    });
+}
+extern "C" int xpnghip_resample_affine_tone_host(int pxsz, const uint8_t *raster, uint64_t w, uint64_t h, const float *affine, uint32_t out_w, uint32_t out_h,
+                                                 uint32_t layout, uint32_t dtype, const float *scale, const float *bias, uint32_t filter, const float *fill,
+                                                 const float *colour, const xpnghip_view_tone *tone, void *out) {
+    XPNG_GUARDED(resample_affine_tone_host_impl(pxsz, raster, w, h, affine, out_w, out_h, layout, dtype, scale, bias, filter, fill, colour, tone, out))
+}
 // ---- staging from tensors (stage_from.hpp) ---------------------------------------------------------------------
 // the layout word of a call whose channel count is per image: the PLANAR and BGR bits and nothing else
 static bool stage_layout_ok(uint32_t layout, std::string &why) {
@@ -1970,10 +2108,10 @@ extern "C" uint64_t xpnghip_ctx_last_decode_tiles(const xpnghip_ctx *c) { return
             (cap) = (need);                                                                               \
         }                                                                                                 \
     } while (0)
-// What the five views entry points differ in, filled by field name: the rectangles and flips (NULL: whole images, no flip), the
+// What the seven views entry points differ in, filled by field name: the rectangles and flips (NULL: whole images, no flip), the
 // filter word, the colour matrices (nviews * 12 floats; NULL: none), whether the call takes the cubic rule (it has no filter word
 // then), the blur records (NULL: none) and, where `affine` is set, nviews * 6 floats and the fill (NULL: zeros) in place of
-// rectangles and flips
+// rectangles and flips; the tone records (NULL: none) of the two tone calls
 struct ViewsCall {
     const uint64_t *rects = nullptr;
     const uint8_t *flips = nullptr;
@@ -1983,6 +2121,7 @@ struct ViewsCall {
     const xpnghip_view_blur *blurs = nullptr;
     bool affine = false;
     const float *affines = nullptr, *fill = nullptr;
+    const xpnghip_view_tone *tones = nullptr;
 };
 static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg, const uint64_t *tile_off,
                              uint32_t nviews, const uint32_t *view_image, void *const *d_outs, const uint32_t *out_sizes, uint32_t layout,
@@ -2048,38 +2187,74 @@ static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
     // copy-out launch gets its part by pointer offset.  Without such a view nothing below differs from the underlying call
     std::vector<uint32_t> order(nviews);
     for (uint32_t v = 0; v < nviews; v++) order[v] = v;
-    uint32_t nplain = nviews, max_oh2 = 0, max_tiles2 = 0;
-    std::vector<BlurRec> brecs;
+    // A view with a tone step (mixed_views_tone.hpp) is a second-pass view too: its first pass goes into the scratch as well; where it
+    // also blurs, k_mixed_views_blur writes fp32 planes into a SECOND slice (a blur cannot work in place: the `mid` records, behind
+    // the others in the blur table); the steps rewrite the last slice in place, and the view's record of the last launch is all off
+    uint32_t nplain = nviews, max_oh2 = 0, max_tiles2 = 0, max_tiles_mid = 0, max_chunks = 0, nslots = 0;
+    std::vector<BlurRec> brecs, mid;
+    std::vector<uint64_t> first_dst, mid_dst;  // where a second-pass view's first pass and a mid record's planes go, in floats of the scratch
+    std::vector<ToneRec> trecs;
     std::vector<ViewColour> pcol;
     uint64_t scratch_floats = 0;
-    if (vc.blurs) {
-        for (uint32_t v = 0; v < nviews; v++)
+    const xpnghip_view_blur blur_none{0.0f, 0u, 256.0f, 0u};
+    auto blurred = [&](uint32_t v) { return vc.blurs && !blur_off(vc.blurs[v]); };
+    auto toned = [&](uint32_t v) { return vc.tones && !tone_off(vc.tones[v]); };
+    auto is_plain = [&](uint32_t v) { return !blurred(v) && !toned(v); };
+    if (vc.blurs || vc.tones) {
+        for (uint32_t v = 0; vc.blurs && v < nviews; v++)
             if (!blur_record_ok(vc.blurs[v], recs[v].ow, recs[v].oh, " of view " + std::to_string(v), why)) return fail(why);
-        std::stable_partition(order.begin(), order.end(), [&](uint32_t v) { return blur_off(vc.blurs[v]); });
+        for (uint32_t v = 0; vc.tones && v < nviews; v++)
+            if (!tone_record_ok(vc.tones[v], " of view " + std::to_string(v), why)) return fail(why);
+        std::stable_partition(order.begin(), order.end(), is_plain);
         nplain = 0;
-        while (nplain < nviews && blur_off(vc.blurs[order[nplain]])) nplain++;
+        while (nplain < nviews && is_plain(order[nplain])) nplain++;
     }
     if (nplain < nviews) {
-        std::vector<ViewRec> part(nviews);
-        for (uint32_t i = 0; i < nviews; i++) part[i] = recs[order[i]];
-        recs.swap(part);
+        if (vc.affine) {
+            std::vector<AffineRec> part(nviews);
+            for (uint32_t i = 0; i < nviews; i++) part[i] = arecs[order[i]];
+            arecs.swap(part);
+        } else {
+            std::vector<ViewRec> part(nviews);
+            for (uint32_t i = 0; i < nviews; i++) part[i] = recs[order[i]];
+            recs.swap(part);
+        }
         if (colours) {
             pcol.resize(nviews);
             for (uint32_t i = 0; i < nviews; i++) memcpy(pcol[i].m, colours + 12ull * order[i], sizeof(ViewColour));
             colours = pcol[0].m;
         }
         max_oh = 0;
-        for (uint32_t i = 0; i < nplain; i++) max_oh = std::max(max_oh, recs[i].oh);
+        for (uint32_t i = 0; i < nplain; i++) max_oh = std::max(max_oh, out_sizes[2ull * order[i] + 1]);
         brecs.resize(nviews - nplain);
         for (uint32_t i = nplain; i < nviews; i++) {
-            ViewRec &r = recs[i];
+            const uint32_t v = order[i], ow = out_sizes[2ull * v], oh = out_sizes[2ull * v + 1];
             BlurRec &b = brecs[i - nplain];
-            const xpnghip_view_blur &q = vc.blurs[order[i]];
-            b = BlurRec{scratch_floats, r.buf, r.ow, r.oh, q.radius, q.solarise, {}};
+            const xpnghip_view_blur &q = blurred(v) ? vc.blurs[v] : blur_none;
+            const uint64_t slice = rup((uint64_t)C * oh * ow * 4, 256) / 4;  // (the slice's own planes, rounded up to 256 bytes)
+            const uint32_t tiles = ((ow + BLUR_TW - 1) / BLUR_TW) * ((oh + BLUR_TH - 1) / BLUR_TH);
+            b = BlurRec{scratch_floats, (uint8_t *)d_outs[v], ow, oh, q.radius, q.solarise, {}};
             blur_weights(q.sigma, q.radius, b.w);
-            scratch_floats += rup((uint64_t)C * r.oh * r.ow * 4, 256) / 4;  // (the slice's own planes, rounded up to 256 bytes)
-            max_oh2 = std::max(max_oh2, r.oh);
-            max_tiles2 = std::max(max_tiles2, ((r.ow + BLUR_TW - 1) / BLUR_TW) * ((r.oh + BLUR_TH - 1) / BLUR_TH));
+            first_dst.push_back(scratch_floats);
+            scratch_floats += slice;
+            max_oh2 = std::max(max_oh2, oh);
+            max_tiles2 = std::max(max_tiles2, tiles);
+            if (!toned(v)) continue;
+            if (blurred(v)) {  // the blur moves to a mid record, the last launch's record reads the second slice
+                mid.push_back(b);
+                mid_dst.push_back(scratch_floats);
+                max_tiles_mid = std::max(max_tiles_mid, tiles);
+                b = BlurRec{scratch_floats, (uint8_t *)d_outs[v], ow, oh, 0u, 256.0f, {1.0f}};
+                scratch_floats += slice;
+            }
+            const xpnghip_view_tone &t = vc.tones[v];
+            ToneRec tr{b.src, oh * ow, {t.op[0], t.op[1], t.op[2], t.op[3]}, {}, {}};
+            for (int si = 0; si < 4; si++) {
+                tr.arg[si] = t.op[si] == XPNGHIP_TONE_POSTERISE ? (float)(1u << (8u - (uint32_t)t.arg[si])) : t.arg[si];
+                if (t.op[si] == XPNGHIP_TONE_AUTOCONTRAST || t.op[si] == XPNGHIP_TONE_EQUALISE) tr.slot[si] = nslots++;
+            }
+            trecs.push_back(tr);
+            max_chunks = std::max(max_chunks, (3u * oh * ow + TONE_CHUNK - 1) / TONE_CHUNK);
         }
     }
     std::vector<uint32_t> list;
@@ -2094,10 +2269,26 @@ static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
     if (colours) VIEWS_TABLE(c->d_m_vcolour, c->cap_m_vcolour, nviews, (uint64_t)nviews * sizeof(ViewColour));
     if (!brecs.empty()) {
         VIEWS_TABLE(c->d_m_bscratch, c->cap_m_bscratch, scratch_floats * 4, scratch_floats * 4);
-        VIEWS_TABLE(c->d_m_blur, c->cap_m_blur, brecs.size(), (uint64_t)brecs.size() * sizeof(BlurRec));
+        VIEWS_TABLE(c->d_m_blur, c->cap_m_blur, brecs.size() + mid.size(), (uint64_t)(brecs.size() + mid.size()) * sizeof(BlurRec));
         // the first pass of these views writes their slices of the scratch
-        for (uint32_t i = nplain; i < nviews; i++) recs[i].buf = (uint8_t *)(c->d_m_bscratch + brecs[i - nplain].src);
+        for (uint32_t i = nplain; i < nviews; i++) {
+            uint8_t *dst = (uint8_t *)(c->d_m_bscratch + first_dst[i - nplain]);
+            if (vc.affine) arecs[i].buf = dst;
+            else recs[i].buf = dst;
+        }
         HIPCHK(hipMemcpyAsync(c->d_m_blur, brecs.data(), (uint64_t)brecs.size() * sizeof(BlurRec), hipMemcpyHostToDevice, s));
+    }
+    if (!mid.empty()) {  // (behind the records of the last launch, in the same table)
+        for (size_t i = 0; i < mid.size(); i++) mid[i].buf = (uint8_t *)(c->d_m_bscratch + mid_dst[i]);
+        HIPCHK(hipMemcpyAsync(c->d_m_blur + brecs.size(), mid.data(), (uint64_t)mid.size() * sizeof(BlurRec), hipMemcpyHostToDevice, s));
+    }
+    if (!trecs.empty()) {
+        VIEWS_TABLE(c->d_m_tone, c->cap_m_tone, trecs.size(), (uint64_t)trecs.size() * sizeof(ToneRec));
+        HIPCHK(hipMemcpyAsync(c->d_m_tone, trecs.data(), (uint64_t)trecs.size() * sizeof(ToneRec), hipMemcpyHostToDevice, s));
+        if (nslots) {  // every slot starts from zero in every call: counts, hi and the complement of lo all grow
+            VIEWS_TABLE(c->d_m_tstat, c->cap_m_tstat, nslots, (uint64_t)nslots * TONE_SLOT_WORDS * 4);
+            HIPCHK(hipMemsetAsync(c->d_m_tstat, 0, (uint64_t)nslots * TONE_SLOT_WORDS * 4, s));
+        }
     }
     // the resized call's protocol: both tables are in pageable host memory that ends with this call, so the stream is synchronised
     // once behind the two copies - queued before the decode's own kernels, so the wait never covers this call's work
@@ -2124,9 +2315,11 @@ static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
     const dim3 grid((max_oh + MC_ROWS - 1) / MC_ROWS, nplain);
     if (colours) XPNG_REQUIRE(c->d_m_vcolour);
     const ViewColour *vm = colours ? c->d_m_vcolour : nullptr;
+    const uint32_t n2 = nviews - nplain;
+    const FloatConsts ident{{1.0f, 1.0f, 1.0f, 1.0f}, {0.0f, 0.0f, 0.0f, 0.0f}};
     if (vc.affine) {  // one kernel for every view: a matrix carries the crop, the size and the mirror
-        const dim3 agrid((max_oh + AF_ROWS - 1) / AF_ROWS, nviews);
-        with_3or4(c->pxsz, [&](auto PXc) { with_3or4(C, [&](auto Cc) { with_planar(layout, [&](auto PL) { with_float(dtype, [&](auto t) {
+        const dim3 agrid((max_oh + AF_ROWS - 1) / AF_ROWS, nplain);
+        if (nplain) with_3or4(c->pxsz, [&](auto PXc) { with_3or4(C, [&](auto Cc) { with_planar(layout, [&](auto PL) { with_float(dtype, [&](auto t) {
             constexpr int PXv = decltype(PXc)::value, Cv = decltype(Cc)::value;
             constexpr bool PLv = decltype(PL)::value;
 #ifdef XPNG_PROBES
@@ -2136,7 +2329,13 @@ static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
             k_mixed_views_affine<PXv, Cv, PLv, decltype(t)><<<agrid, 256, 0, s>>>(c->d_m_affine, vm, c->d_m_stage, bpr, bgr, vc.filter, afill, fk);
         }); }); }); });
         HIPCHK(hipGetLastError());
-        return 0;
+        if (!n2) return 0;
+        // the views with tone steps: the same kernel as <PX, C, planar, float> with no BGR exchange and identity constants into the scratch
+        const dim3 agrid1((max_oh2 + AF_ROWS - 1) / AF_ROWS, n2);
+        with_3or4(c->pxsz, [&](auto PXc) { with_3or4(C, [&](auto Cc) {
+            k_mixed_views_affine<decltype(PXc)::value, decltype(Cc)::value, true, float><<<agrid1, 256, 0, s>>>(c->d_m_affine + nplain, vm ? vm + nplain : nullptr, c->d_m_stage, bpr, 0u, vc.filter, afill, ident);
+        }); });
+        HIPCHK(hipGetLastError());
     }
     // the copy-out kernel of this call's filter over the records vr (their matrices mats, or none) into buffers of layout PL and
     // element t, as with_planar and with_float hand them over
@@ -2149,17 +2348,42 @@ static int decode_views_impl(xpnghip_ctx *c, int mode, const void *const *d_blob
             else k_mixed_views_as_float<PXv, Cv, PLv, decltype(t)><<<g, 256, 0, s>>>(vr, c->d_m_stage, bpr, bgr_, vc.filter, k);
         }); });
     };
-    if (nplain) with_planar(layout, [&](auto PL) { with_float(dtype, [&](auto t) { copy_out(grid, c->d_m_views, vm, PL, t, bgr, fk); }); });
+    if (!vc.affine && nplain) with_planar(layout, [&](auto PL) { with_float(dtype, [&](auto t) { copy_out(grid, c->d_m_views, vm, PL, t, bgr, fk); }); });
     HIPCHK(hipGetLastError());
     if (brecs.empty()) return 0;
     // the two passes of the views that blur or solarise: the copy-out kernel of the filter as <PX, C, planar, float> with no BGR
     // exchange and identity constants into the scratch, then k_mixed_views_blur into the caller's layout and dtype
     XPNG_REQUIRE(c->d_m_bscratch, c->d_m_blur);
-    const uint32_t n2 = nviews - nplain;
     const dim3 grid1((max_oh2 + MC_ROWS - 1) / MC_ROWS, n2), grid2(max_tiles2, n2);
-    const FloatConsts ident{{1.0f, 1.0f, 1.0f, 1.0f}, {0.0f, 0.0f, 0.0f, 0.0f}};
-    copy_out(grid1, c->d_m_views + nplain, vm ? vm + nplain : nullptr, std::true_type{}, float{}, 0u, ident);
+    if (!vc.affine) copy_out(grid1, c->d_m_views + nplain, vm ? vm + nplain : nullptr, std::true_type{}, float{}, 0u, ident);
     HIPCHK(hipGetLastError());
+    if (!trecs.empty()) {
+        // the views with tone steps (mixed_views_tone.hpp): where such a view blurs, its blur as fp32 planes into its second slice;
+        // then per step index that some view uses a statistics launch - only where some view's step there is autocontrast or
+        // equalise - and an apply launch, in place
+        XPNG_REQUIRE(c->d_m_tone);
+        if (!mid.empty()) {
+            with_3or4(C, [&](auto Cc) {
+                k_mixed_views_blur<decltype(Cc)::value, true, float><<<dim3(max_tiles_mid, (uint32_t)mid.size()), 256, 0, s>>>(c->d_m_blur + brecs.size(), c->d_m_bscratch, 0u, ident);
+            });
+            HIPCHK(hipGetLastError());
+        }
+        const dim3 tgrid(max_chunks, (uint32_t)trecs.size());
+        for (uint32_t si = 0; si < 4; si++) {
+            bool any = false, stat = false;
+            for (const ToneRec &t : trecs) {
+                any |= t.op[si] != TONE_NONE;
+                stat |= t.op[si] == TONE_AUTOCONTRAST || t.op[si] == TONE_EQUALISE;
+            }
+            if (!any) break;  // (steps are contiguous: nobody has a later one)
+            if (stat) {
+                XPNG_REQUIRE(c->d_m_tstat);
+                k_mixed_views_tone_stats<<<tgrid, 256, 0, s>>>(c->d_m_tone, c->d_m_bscratch, c->d_m_tstat, si);
+            }
+            k_mixed_views_tone_apply<<<tgrid, 256, 0, s>>>(c->d_m_tone, c->d_m_bscratch, c->d_m_tstat, si);
+            HIPCHK(hipGetLastError());
+        }
+    }
     with_3or4(C, [&](auto Cc) { with_planar(layout, [&](auto PL) { with_float(dtype, [&](auto t) {
         k_mixed_views_blur<decltype(Cc)::value, decltype(PL)::value, decltype(t)><<<grid2, 256, 0, s>>>(c->d_m_blur, c->d_m_bscratch, bgr, fk);
     }); }); });
@@ -2215,6 +2439,29 @@ extern "C" int xpnghip_decode_varsize_device_batch_views_affine(xpnghip_ctx *c, 
                                                                 void *stream) {
     ViewsCall vc;
     vc.filter = filter; vc.colours = colours; vc.affine = true; vc.affines = affines; vc.fill = fill;
+    XPNG_GUARDED(decode_views_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, nviews, view_image, d_outs, out_sizes, layout, dtype, scale, bias, stream, vc))
+}
+// the blur call and the affine call plus one tone record per view (mixed_views_tone.hpp); tones == NULL is the underlying call itself
+extern "C" int xpnghip_decode_varsize_device_batch_views_tone(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
+                                                              const uint64_t *tile_off, uint32_t nviews, const uint32_t *view_image, void *const *d_outs,
+                                                              const uint32_t *out_sizes, const uint64_t *rects, const uint8_t *flips, uint32_t layout,
+                                                              uint32_t dtype, const float *scale, const float *bias, uint32_t filter, const float *colours,
+                                                              const xpnghip_view_blur *blurs, const xpnghip_view_tone *tones, void *stream) {
+    std::string why;
+    if (!blur_filter_ok(filter, why)) return fail(why);
+    ViewsCall vc;
+    vc.rects = rects; vc.flips = flips; vc.colours = colours; vc.blurs = blurs; vc.tones = tones;
+    vc.cubic = filter == XPNGHIP_FILTER_CUBIC_AA;
+    vc.filter = vc.cubic ? 0 : filter;
+    XPNG_GUARDED(decode_views_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, nviews, view_image, d_outs, out_sizes, layout, dtype, scale, bias, stream, vc))
+}
+extern "C" int xpnghip_decode_varsize_device_batch_views_affine_tone(xpnghip_ctx *c, int mode, const void *const *d_blobs, const uint64_t *blobs_len, uint32_t nimg,
+                                                                     const uint64_t *tile_off, uint32_t nviews, const uint32_t *view_image, void *const *d_outs,
+                                                                     const uint32_t *out_sizes, const float *affines, const float *fill, uint32_t layout,
+                                                                     uint32_t dtype, const float *scale, const float *bias, uint32_t filter, const float *colours,
+                                                                     const xpnghip_view_tone *tones, void *stream) {
+    ViewsCall vc;
+    vc.filter = filter; vc.colours = colours; vc.affine = true; vc.affines = affines; vc.fill = fill; vc.tones = tones;
     XPNG_GUARDED(decode_views_impl(c, mode, d_blobs, blobs_len, nimg, tile_off, nviews, view_image, d_outs, out_sizes, layout, dtype, scale, bias, stream, vc))
 }
 

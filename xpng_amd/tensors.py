@@ -11,7 +11,9 @@ MixedContext.decode_batch_resampled when that resize is to antialias).
 (MixedContext.decode_batch_views); with colour= every view also gets a colour matrix of its own in the same pass (colour_matrix,
 random_colour_jitter), and with blur= and solarise= a Gaussian blur and a solarise of its own in a second kernel of that call
 (MixedContext.decode_batch_views_blur; random_gaussian_blur, random_solarise); with affine= every view is rotated, sheared, scaled
-and translated in the copy-out instead (MixedContext.decode_batch_views_affine; affine_matrix, random_affine).
+and translated in the copy-out instead (MixedContext.decode_batch_views_affine; affine_matrix, random_affine); with tone= a view is
+autocontrasted, equalised, posterised, solarised and inverted, up to four steps in any order, behind either
+(MixedContext.decode_batch_views_tone, decode_batch_views_affine_tone; random_tone).
 api.py stays free of torch; this module is the only one of the package that imports it at load time."""
 from __future__ import annotations
 
@@ -353,7 +355,7 @@ def load_files(paths, layout: str = "chw", channels=None, bgr: bool = False, dev
 
 def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool = False, device=None, dtype=torch.float16, mean=None,
                std=None, antialias: bool = True, stack: bool = False, out=None, colour=None, interpolation: str = "bilinear", blur=None,
-               solarise=None, affine=None, fill=None):
+               solarise=None, affine=None, fill=None, tone=None):
     """Any number of views per file, each decoded once: views is a list of (path_index, rect_or_None, flip) - rect = (x, y, w, h)
     inside file path_index, None for the whole image; flip True mirrors left to right - and view v comes back as a tensor
     (C, OH_v, OW_v) for layout "chw" or (OH_v, OW_v, C) for "hwc", in view order.  size is one (OH, OW) for every view or one pair
@@ -411,7 +413,19 @@ def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool
     B, A in byte units, one for the call.  Every device call is then ONE MixedContext.decode_batch_views_affine, which decodes only
     the tiles that a view's warped footprint touches, and view v equals, bit for bit, api.resample_affine_host with its matrix,
     which also answers level-7 and single-colour files.  blur= or solarise= together with affine= is an error.  With affine None
-    the function runs exactly the calls it ran without the argument."""
+    the function runs exactly the calls it ran without the argument.
+
+    tone gives views the tone operations of AutoAugment, RandAugment and TrivialAugment, in any order.  It is None or one entry per
+    view, each None or a sequence of up to four steps executed in order: "autocontrast", "equalise", ("posterise", bits) with bits
+    an integer 0 .. 8, ("solarise", threshold) with a threshold in 0 .. 255, and "invert" (the rule is in include/xpng_hip.h; on
+    whole byte values equalise, posterise, solarise and invert are PIL's ImageOps, autocontrast is torchvision's on a float tensor).
+    The steps run on the three colour planes of the finished view - behind the resampling, the colour matrix, the blur and the
+    solarise= list, which stays the blur record's - and before the normalisation; autocontrast and equalise take their statistics
+    over the whole view, fill pixels of a warp included.  tone= works with every interpolation, with colour=, blur= and solarise=,
+    and with affine=.  Every device call is then ONE MixedContext.decode_batch_views_tone, or with affine= ONE
+    decode_batch_views_affine_tone, and view v equals, bit for bit, api.resample_tone_host or api.resample_affine_tone_host, which
+    also answer level-7 and single-colour files.  random_tone draws such lists.  With tone None the function runs exactly the
+    calls it ran without the argument."""
     if layout not in ("chw", "hwc"):
         raise XpngError(f"load_views: layout must be 'chw' or 'hwc', not {layout!r}")
     if channels not in (None, 3, 4):
@@ -484,6 +498,12 @@ def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool
                 if not 0.0 <= t <= 255.0:
                     raise XpngError(f"load_views: solarise[{v}] is {t!r}, not None or a threshold in 0 .. 255")
             blurs.append(None if b is None and t is None else (sigma, radius, t))
+    tones = None
+    if tone is not None:
+        tones = list(tone)
+        if len(tones) != V:
+            raise XpngError(f"load_views: tone has {len(tones)} entries for {V} views: one list of steps (or None) per view")
+        tones = [_tone_steps(f"load_views: tone[{v}]", t) for v, t in enumerate(tones)]
     mats, afilt = None, api.FILTER_BILINEAR
     if affine is not None:
         mats = list(affine)
@@ -575,7 +595,13 @@ def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool
             if vi != i:
                 continue
             word = api.layout(planar=layout == "chw", bgr=bgr, channels=chans[v])
-            if mats is not None:
+            if tones is not None and mats is not None:
+                raw = api.resample_affine_tone_host(ras, sizes[v], mats[v], word, dt, *cache[chans[v]], filter=afilt, fill=fill, colour=cols[v],
+                                                    tone=tones[v])
+            elif tones is not None:
+                raw = api.resample_tone_host(ras, sizes[v], word, dt, *cache[chans[v]], rect=r, flip=f, filter=api.FILTER_CUBIC_AA if cubic else filt,
+                                             colour=cols[v], blur=None if blurs is None else blurs[v], tone=tones[v])
+            elif mats is not None:
                 raw = api.resample_affine_host(ras, sizes[v], mats[v], word, dt, *cache[chans[v]], filter=afilt, fill=fill, colour=cols[v])
             elif blurs is not None:
                 raw = api.resample_blur_host(ras, sizes[v], word, dt, *cache[chans[v]], rect=r, flip=f, filter=api.FILTER_CUBIC_AA if cubic else filt,
@@ -615,7 +641,13 @@ def load_views(paths, views, size, layout: str = "chw", channels=None, bgr: bool
                     kw = dict(rects=[views[v][1] or (0, 0, heads[views[v][0]][1], heads[views[v][0]][2]) for v in mine],
                               flips=[views[v][2] for v in mine],
                               colours=[cols[v] for v in mine] if cols[mine[0]] is not None else None)
-                    if mats is not None:
+                    if tones is not None and mats is not None:
+                        ctx.decode_batch_views_affine_tone(*args[:8], [mats[v] for v in mine], *cache[C], filter=afilt, fill=fill, colours=kw["colours"],
+                                                           tones=[tones[v] for v in mine])
+                    elif tones is not None:
+                        ctx.decode_batch_views_tone(*args, filter=api.FILTER_CUBIC_AA if cubic else filt,
+                                                    blurs=None if blurs is None else [blurs[v] for v in mine], tones=[tones[v] for v in mine], **kw)
+                    elif mats is not None:
                         ctx.decode_batch_views_affine(*args[:8], [mats[v] for v in mine], *cache[C], filter=afilt, fill=fill, colours=kw["colours"])
                     elif blurs is not None:
                         ctx.decode_batch_views_blur(*args, filter=api.FILTER_CUBIC_AA if cubic else filt, blurs=[blurs[v] for v in mine], **kw)
@@ -745,6 +777,75 @@ def random_solarise(n, threshold=128, p=0.2, generator=None):
         raise XpngError(f"random_solarise: p must be within 0 .. 1, not {p!r}")
     u = torch.rand((n,), dtype=torch.float64, generator=generator).tolist()
     return [float(threshold) if coin < p else None for coin in u]
+
+
+_TONE_OPS = {"autocontrast": api.TONE_AUTOCONTRAST, "equalise": api.TONE_EQUALISE, "posterise": api.TONE_POSTERISE,
+             "solarise": api.TONE_SOLARISE, "invert": api.TONE_INVERT}
+
+
+def _tone_steps(name, entry):
+    """one entry of load_views(tone=...) - None or up to four steps - as the list of (op, arg) pairs of api.resample_tone_host, checked"""
+    if entry is None:
+        return None
+    if isinstance(entry, str):
+        raise XpngError(f"{name} is {entry!r}: an entry is None or a sequence of steps, not one step")
+    try:
+        steps = list(entry)
+    except TypeError:
+        raise XpngError(f"{name} is {entry!r}, not None or a sequence of up to four steps") from None
+    if len(steps) > 4:
+        raise XpngError(f"{name} has {len(steps)} steps: at most four")
+    out = []
+    for k, st in enumerate(steps):
+        op, arg = (st, None) if isinstance(st, str) else (tuple(st) + (None, None))[:2] if hasattr(st, "__len__") and 1 <= len(st) <= 2 else (None, None)
+        if op not in _TONE_OPS:
+            raise XpngError(f"{name}, step {k} is {st!r}: a step is 'autocontrast', 'equalise', ('posterise', bits), ('solarise', threshold) or 'invert'")
+        if op in ("posterise", "solarise"):
+            try:
+                arg = float(arg)
+            except (TypeError, ValueError):
+                raise XpngError(f"{name}, step {k}: {op!r} needs a number, as ({op!r}, value), not {st!r}") from None
+            if op == "posterise" and not (0.0 <= arg <= 8.0 and arg == int(arg)):
+                raise XpngError(f"{name}, step {k}: posterise bits are {arg!r}, not an integer in 0 .. 8")
+            if op == "solarise" and not 0.0 <= arg <= 255.0:
+                raise XpngError(f"{name}, step {k}: the solarise threshold is {arg!r}, not within 0 .. 255")
+        elif arg is not None:
+            raise XpngError(f"{name}, step {k}: {op!r} takes no argument, not {st!r}")
+        out.append((_TONE_OPS[op], 0.0 if arg is None else arg))
+    return out or None
+
+
+def random_tone(n, num_ops=2, ops=("autocontrast", "equalise", "posterise", "solarise"), magnitude=9, num_magnitude_bins=31, p=1.0,
+                generator=None):
+    """n entries for load_views(tone=...), one per view, drawn as RandAugment draws its operations: num_ops steps (0 .. 4), each
+    uniform out of `ops` (names out of "autocontrast", "equalise", "posterise", "solarise", "invert") and kept with probability p.
+    The magnitude is RandAugment's table: posterise keeps 8 - round(magnitude * 4 / (num_magnitude_bins - 1)) bits, solarise takes
+    the threshold 255 * (1 - magnitude / (num_magnitude_bins - 1)).  A pure host function: one torch.rand draw of shape
+    (n, num_ops, 2), so entry k depends on row k alone; with a seeded torch.Generator the list is reproducible."""
+    n, num_ops, bins = int(n), int(num_ops), int(num_magnitude_bins)
+    if n < 0:
+        raise XpngError(f"random_tone: n is {n}")
+    if not 0 <= num_ops <= 4:
+        raise XpngError(f"random_tone: num_ops must be 0 .. 4, not {num_ops!r}")
+    ops = list(ops)
+    if not ops or any(o not in _TONE_OPS for o in ops):
+        raise XpngError(f"random_tone: ops must be names out of {sorted(_TONE_OPS)}, not {ops!r}")
+    if bins < 2 or not 0 <= float(magnitude) <= bins - 1:
+        raise XpngError(f"random_tone: magnitude must be within 0 .. num_magnitude_bins - 1 = {bins - 1}, not {magnitude!r}")
+    if not 0.0 <= float(p) <= 1.0:
+        raise XpngError(f"random_tone: p must be within 0 .. 1, not {p!r}")
+    bits = 8 - int(round(float(magnitude) * 4.0 / (bins - 1)))
+    thr = 255.0 * (1.0 - float(magnitude) / (bins - 1))
+    u = torch.rand((n, num_ops, 2), dtype=torch.float64, generator=generator).tolist()   # one draw whatever the outcomes
+    out = []
+    for row in u:
+        steps = []
+        for (pick, coin) in row:
+            op = ops[min(int(pick * len(ops)), len(ops) - 1)]
+            if coin < p:
+                steps.append((op, bits) if op == "posterise" else (op, thr) if op == "solarise" else op)
+        out.append(steps or None)
+    return out
 
 
 def _size_pair(name, size):
